@@ -18,6 +18,11 @@ under torch.distributed.run (one rank per GPU, RCCL gradient all-reduce).  Rank 
   `whole_step` = images/s x 26.140262 GFLOP / 2516.6 TF, the section-8(d) figure for the whole train step;
 * `cpu_baseline`: the CPU oracle (torch-CPU fp32 restatement of the reference, kind "port") timed on this
   host's cores on a bounded sample (batch 8 train steps), rank 0, N = 1 only.
+
+A plain run of the train step sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `whole_step`, the
+last step's loss items).  `--full` adds what needs runs of its own: the per-kernel window (`roofline`, `kernel_classes`), the
+eval-forward timing (`forward_eval`) and `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (see dump_outputs); the inputs and the initial weights are seeded, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -124,6 +129,27 @@ def cpu_baseline(seconds_budget: float = 25.0):
     dt = (time.time() - t0) / n
     return {"value": round(bs / dt, 3), "unit": "images/sec", "cores": torch.get_num_threads(), "kind": "port",
             "sample": f"{n} YOLOv8-n 640x640 train steps at batch {bs} (fwd+loss+bwd+Adam), torch-CPU fp32 oracle, {dt * 1e3:.0f} ms/step"}
+
+
+DUMP_CAP_BYTES = 60 * 2 ** 20           # --dump-outputs: below 64 MB in all, .npy headers included
+DUMP_SMALL_BYTES = 2 ** 20              # arrays up to this size are always written whole
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array of ``arrays`` ({name: numpy array}) as out_dir/<name>.npy, float32 (float64 stays float64).  When they hold more
+    than DUMP_CAP_BYTES in all, every array above DUMP_SMALL_BYTES keeps the same share of its elements: a fixed, seeded sample (sorted
+    flat indices), identical from run to run for the same sizes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= DUMP_SMALL_BYTES)
+    keep = 1.0 if total <= DUMP_CAP_BYTES else (DUMP_CAP_BYTES - small) / (total - small)
+    for name, a in arrays.items():
+        if keep < 1.0 and a.nbytes > DUMP_SMALL_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * keep), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 CENTERNET_GFLOP_PER_IMG = 62.24          # DLA-34, nc 80, 512x512 forward (SURVEY section 8(d))
@@ -870,7 +896,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--nms-load", type=int, default=0, help="yolov7 / ssd: plant this many above-threshold candidates per image (clusters of four overlapping boxes) "
                                                             "into the head output after every forward, so that the suppression kernels have work at random init")
-    ap.add_argument("--profile-steps", type=int, default=10, help="steps of the per-kernel HIP-event window after the timed region")
+    ap.add_argument("--profile-steps", type=int, default=10, help="--full: steps of the per-kernel HIP-event window after the timed region (a plain run has no such window)")
     ap.add_argument("--workload", default="yolov8_train", choices=["yolov8_train", "yolov8_eval", "centernet", "centernet_train", "deeplab", "deeplab_train", "yolov7", "yolov7_train", "ssd", "ssd_train"],
                     help="centernet: BASELINE.json configs[3] -- CenterNet DLA-34 (nc 80) 512x512 inference + heat-map decode, batch 64 per GPU")
     ap.add_argument("--exchange", default="torch", choices=["torch", "c"], help="N > 1: gradient exchange through torch.distributed (default) or "
@@ -878,7 +904,15 @@ def main():
     ap.add_argument("--fusion", type=int, default=0, help="yolov8_eval: 1 runs the eval forward with the cross-layer fusion groups (Bottleneck pairs, Detect levels as one launch each; measured 1-6 %% slower: TUNING build only, CVX_LIB=build/libcvx_tuning.so)")
     ap.add_argument("--stream", default="default", choices=["default", "own"], help="own: launch on a torch.cuda.Stream of the bench's own instead of "
                     "the legacy default stream (A/B switch for the hardware-queue budget, DESIGN.md section 6)")
+    ap.add_argument("--full", action="store_true", help="yolov8_train: also the per-kernel window after the timed steps (roofline, kernel_classes), "
+                    "the eval-forward timing (forward_eval) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="yolov8_train: write what the last timed step computed (loss items, updated parameters, "
+                    "BatchNorm running statistics, Adam's first moment) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "yolov8_train":
+        ap.error("--dump-outputs is implemented for --workload yolov8_train only")
     if args.stream == "own":
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
         torch.cuda.set_stream(torch.cuda.Stream())
@@ -951,59 +985,51 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     eng = model._last_engine                                  # exists after the first step (also with --warmup 0)
-    # Per-kernel timing: HIP events recorded on the engine's launch streams around every kernel class.  The ~1000 event
-    # records per step cost ~20 % of wall time, so they run on their own steps directly after the timed region (same
-    # process, same buffers, same clocks) instead of inside it; `value` is never measured with them on.
-    prof_steps = max(1, args.profile_steps)
-    step(x, batch)
-    sync()
-    eng.profile(True)
-    for _ in range(prof_steps):
+    loss_items = [float(v) for v in items.cpu()]
+    if args.dump_outputs and rank == 0:                       # before anything else runs a step: the state the last timed step left
+        opt_state = step.optimizer.state_dict()["state"]
+        sd = model.state_dict()
+        dump_outputs(args.dump_outputs, {
+            "loss_items": items.cpu().numpy(),
+            "params": torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]).cpu().numpy(),
+            "bn_running_stats": torch.cat([v.reshape(-1).float() for k, v in sd.items() if k.endswith(("running_mean", "running_var"))]).cpu().numpy(),
+            "adam_exp_avg": torch.cat([opt_state[i]["exp_avg"].reshape(-1).float() for i in sorted(opt_state)]).cpu().numpy()})
+    if args.full:
+        # Per-kernel timing: HIP events recorded on the engine's launch streams around every kernel class.  The ~1000 event
+        # records per step cost ~20 % of wall time, so they run on their own steps directly after the timed region (same
+        # process, same buffers, same clocks) instead of inside it; `value` is never measured with them on.
+        prof_steps = max(1, args.profile_steps)
         step(x, batch)
-    sync()
-    prof = eng.profile_read()
-    eng.profile(False)
-    # inference forward (BN folded into the conv epilogues, no BN passes): the north_star quotes its MFMA fraction
-    model.eval()
-    with torch.no_grad():
-        for _ in range(3):
-            model._run_forward(x, False)
         sync()
-        t1 = time.perf_counter()
-        n_eval = 20
-        for _ in range(n_eval):
-            model._run_forward(x, False)
+        eng.profile(True)
+        for _ in range(prof_steps):
+            step(x, batch)
         sync()
-    eval_ms = (time.perf_counter() - t1) / n_eval * 1e3
-    model.train()
+        prof = eng.profile_read()
+        eng.profile(False)
+        # inference forward (BN folded into the conv epilogues, no BN passes): the north_star quotes its MFMA fraction
+        model.eval()
+        with torch.no_grad():
+            for _ in range(3):
+                model._run_forward(x, False)
+            sync()
+            t1 = time.perf_counter()
+            n_eval = 20
+            for _ in range(n_eval):
+                model._run_forward(x, False)
+            sync()
+        eval_ms = (time.perf_counter() - t1) / n_eval * 1e3
+        model.train()
     elapsed_rank0 = elapsed
     if use_dist:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    loss_items = [float(v) for v in items.cpu()]
 
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         fwd_gf, train_gf = GFLOP.get(args.model, (float('nan'), float('nan')))
         value = B * world * args.steps / elapsed
-        conv = {k: prof[k] for k in ("conv_fwd", "conv_dgrad")}
-        conv_ms = sum(v["ms"] for v in conv.values())
-        conv_fl = sum(v["flops"] for v in conv.values())
-        conv_launches = sum(v["launches"] for v in conv.values())
-        achieved = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        conv_by = sum(v["bytes"] for v in conv.values())
-        conv_gbs = conv_by / (conv_ms * 1e-3) / 1e9 if conv_ms > 0 else 0.0
-        traffic, traffic_note = measured_traffic(args.model, B)
-        mfma_busy, mfma_note = measured_mfma_busy()
-        classes = {}
-        for k, v in prof.items():
-            if v["launches"] == 0:
-                continue
-            sec = v["ms"] * 1e-3
-            classes[k] = {"ms_per_step": round(v["ms"] / prof_steps, 4), "launches_per_step": v["launches"] // prof_steps,
-                          "tflops": round(v["flops"] / sec / 1e12, 2) if v["flops"] else None,
-                          "algorithmic_gbs": round(v["bytes"] / sec / 1e9, 1)}
         out = {
             "metric": f"images/sec 640x640 YOLOv8-{args.model} train step", "value": round(value, 2), "unit": "images/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "weak",
@@ -1016,29 +1042,47 @@ def main():
                        "exchange": ("none (1 rank)" if not use_dist else ("C ABI: cvx_engine_backward_exchange (RCCL through dlopen)" if comm is not None
                                                                           else "torch.distributed all_reduce per bucket (ProcessGroupNCCL)")),
                        "ms_per_step_rank0": round(elapsed_rank0 / args.steps * 1e3, 4),
-                       "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default")},
-            "roofline": {"bound": "mfma",
-                         "kernel": "implicit-GEMM convolution, forward + data-gradient launches: conv_halo_kernel + conv_tile_kernel + conv_pw_kernel + "
-                                   "conv_gemm_kernel + conv_igemm_dma_kernel (+ the fp32 stem passes)",
-                         "achieved": round(achieved, 3), "peak": MFMA_FP16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / MFMA_FP16_PEAK_TFLOPS, 5), "traffic": traffic, "traffic_source": traffic_note,
-                         "mfma_busy_frac": mfma_busy, "mfma_busy_source": mfma_note,
-                         "algorithmic_flops_per_launch": round(conv_fl / max(conv_launches, 1)),
-                         "algorithmic_bytes_per_launch": round(conv_by / max(conv_launches, 1)),
-                         "avg_launch_us": round(conv_ms * 1e3 / max(conv_launches, 1), 3), "launches_per_step": conv_launches // prof_steps,
-                         "hbm_view": {"achieved_gbs": round(conv_gbs, 1), "peak_gbs": HBM_PEAK_GBS, "frac": round(conv_gbs / HBM_PEAK_GBS, 5)}},
-            "whole_step": {"train_tflops": round(value / world * train_gf / 1e3, 3),
-                           "frac_of_mfma_peak": round(value / world * train_gf / 1e3 / MFMA_FP16_PEAK_TFLOPS, 5),
-                           "gflop_per_image": train_gf},
-            "forward_eval": {"ms_per_batch": round(eval_ms, 4), "images_per_sec": round(B / eval_ms * 1e3, 1),
-                             "tflops": round(B * fwd_gf / eval_ms, 2),
-                             "frac_of_mfma_peak": round(B * fwd_gf / eval_ms / MFMA_FP16_PEAK_TFLOPS, 5),
-                             "note": "per GPU; eval-mode forward of the same batch, folded BN + SiLU in the conv epilogues; weights constant between these forwards: fp16 weight images kept (cvx_engine_keep_shadows)"},
-            "kernel_classes": classes,
-            "loss_items_last_step": loss_items,
-            "engine_workspace_gib": round(eng.workspace_bytes() / 2 ** 30, 3),
-        }
-        if world == 1 and not args.no_cpu_baseline:
+                       "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default")}}
+        if args.full:
+            conv = {k: prof[k] for k in ("conv_fwd", "conv_dgrad")}
+            conv_ms = sum(v["ms"] for v in conv.values())
+            conv_fl = sum(v["flops"] for v in conv.values())
+            conv_launches = sum(v["launches"] for v in conv.values())
+            achieved = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            conv_by = sum(v["bytes"] for v in conv.values())
+            conv_gbs = conv_by / (conv_ms * 1e-3) / 1e9 if conv_ms > 0 else 0.0
+            traffic, traffic_note = measured_traffic(args.model, B)
+            mfma_busy, mfma_note = measured_mfma_busy()
+            classes = {}
+            for k, v in prof.items():
+                if v["launches"] == 0:
+                    continue
+                sec = v["ms"] * 1e-3
+                classes[k] = {"ms_per_step": round(v["ms"] / prof_steps, 4), "launches_per_step": v["launches"] // prof_steps,
+                              "tflops": round(v["flops"] / sec / 1e12, 2) if v["flops"] else None,
+                              "algorithmic_gbs": round(v["bytes"] / sec / 1e9, 1)}
+            out["roofline"] = {"bound": "mfma",
+                               "kernel": "implicit-GEMM convolution, forward + data-gradient launches: conv_halo_kernel + conv_tile_kernel + conv_pw_kernel + "
+                                         "conv_gemm_kernel + conv_igemm_dma_kernel (+ the fp32 stem passes)",
+                               "achieved": round(achieved, 3), "peak": MFMA_FP16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / MFMA_FP16_PEAK_TFLOPS, 5), "traffic": traffic, "traffic_source": traffic_note,
+                               "mfma_busy_frac": mfma_busy, "mfma_busy_source": mfma_note,
+                               "algorithmic_flops_per_launch": round(conv_fl / max(conv_launches, 1)),
+                               "algorithmic_bytes_per_launch": round(conv_by / max(conv_launches, 1)),
+                               "avg_launch_us": round(conv_ms * 1e3 / max(conv_launches, 1), 3), "launches_per_step": conv_launches // prof_steps,
+                               "hbm_view": {"achieved_gbs": round(conv_gbs, 1), "peak_gbs": HBM_PEAK_GBS, "frac": round(conv_gbs / HBM_PEAK_GBS, 5)}}
+        out["whole_step"] = {"train_tflops": round(value / world * train_gf / 1e3, 3),
+                             "frac_of_mfma_peak": round(value / world * train_gf / 1e3 / MFMA_FP16_PEAK_TFLOPS, 5),
+                             "gflop_per_image": train_gf}
+        if args.full:
+            out["forward_eval"] = {"ms_per_batch": round(eval_ms, 4), "images_per_sec": round(B / eval_ms * 1e3, 1),
+                                   "tflops": round(B * fwd_gf / eval_ms, 2),
+                                   "frac_of_mfma_peak": round(B * fwd_gf / eval_ms / MFMA_FP16_PEAK_TFLOPS, 5),
+                                   "note": "per GPU; eval-mode forward of the same batch, folded BN + SiLU in the conv epilogues; weights constant between these forwards: fp16 weight images kept (cvx_engine_keep_shadows)"}
+            out["kernel_classes"] = classes
+        out["loss_items_last_step"] = loss_items
+        out["engine_workspace_gib"] = round(eng.workspace_bytes() / 2 ** 30, 3)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

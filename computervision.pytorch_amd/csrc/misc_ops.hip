@@ -1022,7 +1022,7 @@ __device__ __forceinline__ h8 pool5_col(const h8* rm, const unsigned* ri, int h,
 }
 
 constexpr int SPPF_FWD_BYTES_PER_PIXEL = 16 + 16 + 4;  // stage map | row maxima | row argmax nibbles
-constexpr int SPPF_BWD_BYTES_PER_PIXEL = 16 + 32;      // stage gradient (fp16) | fp32 accumulators of the stage's input gradient
+constexpr int SPPF_BWD_BYTES_PER_PIXEL = 16 + 32;      // stage output gradient (fp16) | its input gradient (fp16) | argmax bytes (8), 8 spare
 
 __global__ __launch_bounds__(256) void sppf_pool3_fwd_kernel(ViewDesc in, ViewDesc o1, ViewDesc o2, ViewDesc o3, int H, int W, int CG, uint8_t* i1,
                                                              uint8_t* i2, uint8_t* i3) {
@@ -1056,15 +1056,16 @@ __global__ __launch_bounds__(256) void sppf_pool3_fwd_kernel(ViewDesc in, ViewDe
 }
 
 // The backward chain of the same three pools in one launch: g(y2) += route3(g(y3)), g(y1) += route2(g(y2)), g(x) (+)= route1(g(y1)), each stage
-// rounded to fp16 like the tensors the three launches passed to each other.  Every output pixel sends its gradient to the ONE input pixel its
-// argmax byte names (an fp32 LDS atomic per channel) instead of every input pixel searching the 25 outputs that could have picked it; the
-// fp32 sums are the same up to the order of the additions.
+// rounded to fp16 like the tensors the three launches passed to each other.  Every input pixel gathers the gradient of the (at most 25) output
+// pixels whose argmax byte names it, in a fixed tap order, from the stage's output gradient and argmax bytes staged in LDS: the fp32 sums are
+// added in the same order on every run (a scatter with LDS atomics added them in whatever order the waves reached them).
 __global__ __launch_bounds__(256) void sppf_pool3_bwd_kernel(ViewDesc g3, ViewDesc g2, ViewDesc g1, ViewDesc g0, int H, int W, int CG, const uint8_t* i1,
                                                              const uint8_t* i2, const uint8_t* i3, int acc_mask) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sppf_lds[];
   const int HW = H * W;
   h8* gcur = reinterpret_cast<h8*>(sppf_lds);              // gradient of the stage's output
-  float* acc = reinterpret_cast<float*>(gcur + HW);        // [HW][8] gradient of its input, being summed
+  h8* gnext = gcur + HW;                                   // gradient of its input: the next stage's output gradient
+  unsigned long long* pks = reinterpret_cast<unsigned long long*>(gnext + HW);   // [HW] the stage's argmax bytes, 8 channels per pixel
   const int b = blockIdx.x / CG, cg = blockIdx.x - b * CG;
   for (int p = threadIdx.x; p < HW; p += 256) gcur[p] = *reinterpret_cast<const h8*>(g3.p + voff(g3, b, p) + cg * 8);
 #pragma unroll
@@ -1072,37 +1073,44 @@ __global__ __launch_bounds__(256) void sppf_pool3_bwd_kernel(ViewDesc g3, ViewDe
     const uint8_t* idx = s == 2 ? i3 : s == 1 ? i2 : i1;
     const ViewDesc& gin = s == 2 ? g2 : s == 1 ? g1 : g0;
     const bool accumulate = ((acc_mask >> s) & 1) != 0;  // the stage's input gradient already holds the concat consumer's share
-    for (int t = threadIdx.x; t < HW * 8; t += 256) acc[t] = 0.f;
+    for (int p = threadIdx.x; p < HW; p += 256) pks[p] = *reinterpret_cast<const unsigned long long*>(idx + (((long long)b * HW + p) * CG + cg) * 8);
     __syncthreads();
-    for (int p = threadIdx.x; p < HW; p += 256) {
-      const int h = p / W, w = p - h * W;
-      const unsigned long long pk = *reinterpret_cast<const unsigned long long*>(idx + (((long long)b * HW + p) * CG + cg) * 8);
-      const h8 g = gcur[p];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int tap = (int)((pk >> (8 * k)) & 0xff);
-        const int dy = tap / 5, dx = tap - dy * 5;
-        atomicAdd(&acc[((h + dy - 2) * W + (w + dx - 2)) * 8 + k], (float)g[k]);
-      }
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < HW; p += 256) {
-      half_t* q = gin.p + voff(gin, b, p) + cg * 8;
+    for (int q = threadIdx.x; q < HW; q += 256) {
+      const int hq = q / W, wq = q - hq * W;
       float a[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] = acc[p * 8 + k];
+      for (int k = 0; k < 8; ++k) a[k] = 0.f;
+      for (int dy = 0; dy < 5; ++dy) {                     // output pixel p = q - (dy - 2, dx - 2) sends to q when its tap is dy * 5 + dx
+        const int h = hq - dy + 2;
+        if (h < 0 || h >= H) continue;
+        for (int dx = 0; dx < 5; ++dx) {
+          const int w = wq - dx + 2;
+          if (w < 0 || w >= W) continue;
+          const int p = h * W + w;
+          const unsigned long long pk = pks[p];
+          const h8 g = gcur[p];
+          const unsigned tap = (unsigned)(dy * 5 + dx);
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (((pk >> (8 * k)) & 0xff) == tap) a[k] += (float)g[k];
+        }
+      }
+      half_t* dst = gin.p + voff(gin, b, q) + cg * 8;
       if (accumulate) {
-        const h8 old = *reinterpret_cast<const h8*>(q);
+        const h8 old = *reinterpret_cast<const h8*>(dst);
 #pragma unroll
         for (int k = 0; k < 8; ++k) a[k] += (float)old[k];
       }
       h8 o;
 #pragma unroll
       for (int k = 0; k < 8; ++k) o[k] = (half_t)a[k];
-      gcur[p] = o;                         // the next stage's output gradient
-      *reinterpret_cast<h8*>(q) = o;       // every stage's total goes back to its slice, like the three launches left them
+      gnext[q] = o;                         // the next stage's output gradient
+      *reinterpret_cast<h8*>(dst) = o;      // every stage's total goes back to its slice, like the three launches left them
     }
     __syncthreads();
+    h8* t = gcur;
+    gcur = gnext;
+    gnext = t;
   }
 }
 

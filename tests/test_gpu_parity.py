@@ -607,6 +607,66 @@ def test_maxpool5_and_upsample2_units(dev, B, H, W, C):
     assert rel(gin2.float().permute(0, 3, 1, 2), xr2.grad + 1.0) < 5e-4
 
 
+@pytest.mark.parametrize("B,H,W,image", [(2, 640, 640, "synth"), (2, 160, 224, "synth"), (2, 640, 640, "flat")])
+def test_sppf_fused_backward_against_fp64_and_run_to_run(dev, B, H, W, image):
+    """The fused backward of SPPF's three chained 5x5 pools (modules.py:314-318; one launch, sppf_pool3_bwd_kernel) on the engine's own
+    operands after a training backward: cv2's data gradient (fp64 from its dy and fp16 weights) lands in the four slices of the concat
+    buffer, then g(y2) += pool'(g(y3)), g(y1) += pool'(g(y2)), g(x) += pool'(g(y1)), every stage rounded to fp16 -- each stage against
+    torch's max_pool2d backward in fp64 on the engine's stage gradient (so the acc_mask accumulation is covered).  "flat": a constant
+    image, so away from the zero-padded borders neighbouring activations are equal and the pools' windows are full of ties (resolved
+    like torch's first-max scan).
+    Then the same backward twice more on the same state: the gradient arena and the concat buffer's gradient are bit-identical."""
+    from computervision.pytorch_amd.train import V8DetectionLoss
+    from configs import Yolo8DetConfig
+    x = synth.images(B, H, W, seed=5) if image == "synth" else torch.full((B, 3, H, W), 0.5)
+    x, batch = x.to(dev), {k: v.to(dev) for k, v in synth.targets(B, seed=6).items()}
+    m = new_model(dev).train()
+    crit = V8DetectionLoss(Yolo8DetConfig(), m)
+    eng = m.engine_for(H, W)
+    gr = eng.graph
+    ops = {o["name"]: (i, o) for i, o in enumerate(gr.ops)}
+    grads, sppf_grads = [], []
+    for _ in range(3):
+        m.flat_grads.zero_()
+        loss, _ = crit(m(x), batch)
+        loss.backward()
+        torch.cuda.synchronize()
+        grads.append(m.flat_grads.clone())
+        i2, o2 = ops["9.cv2"]
+        buf = o2["in"][0]
+        sppf_grads.append(eng.read_buffer(buf, B, grad=True).clone())
+    assert all(torch.equal(grads[0], g) for g in grads[1:]), "gradient arena differs between identical backward passes"
+    assert all(torch.equal(sppf_grads[0], g) for g in sppf_grads[1:]), "SPPF concat gradient differs between identical backward passes"
+    ch = ops["9.pool0"][1]["in"][2]
+    h, w = ops["9.pool0"][1]["ih"], ops["9.pool0"][1]["iw"]
+    assert gr.ops.index(ops["9.pool2"][1]) == ops["9.pool0"][0] + 2
+    act = eng.read_buffer(buf, B).double().cpu()[..., :4 * ch]                  # (B, h, w, 4 ch): x | y1 | y2 | y3, fp16 values
+    got = sppf_grads[0].double().cpu()[..., :4 * ch]
+    nchw = lambda a: a.permute(0, 3, 1, 2).contiguous()                         # noqa: E731
+    sl = lambda a, j: nchw(a[..., j * ch:(j + 1) * ch])                           # noqa: E731
+    for j in range(3):                                                          # the forward chain, exactly
+        assert torch.equal(F.max_pool2d(sl(act, j), 5, 1, 2), sl(act, j + 1)), j
+    if image == "flat":                                                         # zero padding aside, neighbours hold equal values: ties
+        x0 = sl(act, 0)
+        tie = float((x0[..., 1:, :] == x0[..., :-1, :]).double().mean())
+        assert tie > 0.25, tie
+    cs = m.layout.convs["9.cv2"]
+    C, cin = o2["out"][2], cs.cin
+    assert cin == 4 * ch and cs.k == 1
+    wq = m.flat_params[cs.w_off:cs.w_off + C * cin].reshape(C, cin).float().half().double().cpu()
+    dy = eng.read_layer(i2, B, "dy").double().cpu().reshape(B, h, w, C)
+    share = torch.einsum("bhwo,oc->bhwc", dy, wq)                               # cv2's data gradient into the four slices
+    assert float(share.abs().max()) > 0
+    for j in range(4):
+        want = sl(share, j)
+        if j < 3:                                                               # + the next pool's backward of the engine's own g(y_{j+1})
+            yin = sl(act, j).requires_grad_(True)
+            want = want + torch.autograd.grad(F.max_pool2d(yin, 5, 1, 2), yin, sl(got, j + 1))[0]
+        rms = float(want.pow(2).mean().sqrt())
+        e = rel(sl(got, j), want)
+        assert e < 2e-3 + 6e-8 / max(rms, 1e-30), (j, e, rms)                   # one fp16 rounding per stage, as _check_backward_per_layer
+
+
 @pytest.mark.parametrize("B,H,W,C", [(2, 75, 75, 16), (1, 38, 51, 8), (3, 7, 5, 64), (1, 1, 9, 24)])
 def test_inference_pool_resize_norm_units(dev, B, H, W, C):
     """The pooling / resampling / normalisation kernels of the DLA, ResNet + DeepLab and VGG + SSD graphs against torch on odd
@@ -2699,9 +2759,14 @@ def test_ssd_training_forward_backward_matches_the_reference_fixture(dev, gold):
         assert rel(o.detach().cpu(), r) < max(1.25 * rel(e, r), 1e-2), (rel(o.detach().cpu(), r), rel(e, r))
     eg = {k: p.grad.cpu() for k, p in m.named_parameters() if k in ref_grads}
     gmax = max(float(v.norm()) for v in ref_grads.values())
-    live = [k for k in ref_grads if float(ref_grads[k].norm()) >= 1e-6 * gmax]
-    dead = [k for k in ref_grads if k not in live]
-    assert len(dead) == 13 and all(float(eg[k].abs().max()) == 0.0 for k in dead)       # the 13 VGG convolution biases behind a BatchNorm
+    # the 13 VGG convolution biases behind a BatchNorm, named from the plan: in torch their gradient is round-off whose size depends on the
+    # CPU's summation order (thread count), so a fixed fraction of gmax does not separate them from the smallest live gradients everywhere
+    behind_bn = {f"backbone.layers.{it[0]}.bias": f"backbone.layers.{it[7]}.bias" for it in S.vgg_plan() if it[1] == "conv" and it[7] is not None}
+    dead = [k for k in ref_grads if k in behind_bn]
+    live = [k for k in ref_grads if k not in behind_bn]
+    assert len(dead) == 13 and all(float(eg[k].abs().max()) == 0.0 for k in dead)
+    assert all(float(ref_grads[k].norm()) < 1e-3 * float(ref_grads[behind_bn[k]].norm()) for k in dead)   # round-off next to the BN shift's gradient
+    assert all(float(ref_grads[k].norm()) >= 1e-6 * gmax for k in live)
 
     def total(a, b):
         return (sum(float((a[k].double() - b[k].double()).pow(2).sum()) for k in live) / sum(float(b[k].double().pow(2).sum()) for k in live)) ** 0.5

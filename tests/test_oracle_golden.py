@@ -11,6 +11,23 @@ from oracle import yolov8_ref as O
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
+# The fixtures were written on one host's CPU (an Intel Xeon with AVX-512, where the fp32 oracle reproduces them bit for bit).  On another
+# CPU the fp32 convolutions and reductions take other kernels (oneDNN picks them per instruction set and cache sizes) and sum in another
+# order, so the oracle's fp32 results move by round-off that grows with the depth of the computation.  On an AMD EPYC 9575F (Zen 5,
+# AVX-512, 16 threads, same torch) the parent bounds failed in test_train_two_steps (g_stem: 20 of 432 elements, max |diff| 3.1e-5),
+# test_forward_640_subsample (1 of 2376, 1.2e-5 against atol 1e-5), test_centernet_oracle_init_forward_decode (a float64 checksum off
+# in its last bit) and test_yolov7_oracle_init_forward_decode_nms (out0: 225 of 5250, max |diff| 8.6e-4).  Measured there as a fraction
+# of the compared tensor's largest magnitude: forward outputs and first-step gradients <= 1.1e-5 (640 levels 1.5e-6, stem gradient
+# 9.9e-6, YOLOv7 outputs 1.1e-5), weights after two Adam steps 4.3e-5 (Adam divides by sqrt(v)), the YOLOv7 decode 7.2e-5 (exp of the
+# size logits).  Those comparisons add ~4x that, scaled by the fixture tensor's largest magnitude, to their own atol.
+HOST_FWD = 5e-5
+HOST_DEEP = 2e-4
+
+
+def assert_close_across_hosts(actual, desired, rtol, atol, host):
+    desired = np.asarray(desired)
+    np.testing.assert_allclose(actual, desired, rtol=rtol, atol=atol + host * float(np.abs(desired).max()))
+
 
 def test_init_matches_reference_checksums():
     sd = O.init_state_dict("n", 80, seed=0)
@@ -52,18 +69,18 @@ def test_train_two_steps(gold):
     for step in range(2):
         loss, items, grads, _ = O.train_step(sd, x, batch, state)
         np.testing.assert_allclose(float(loss), g["loss"][step], rtol=1e-5)
-        np.testing.assert_allclose(items.numpy(), g["items"][step], rtol=1e-5, atol=1e-6)
+        assert_close_across_hosts(items.numpy(), g["items"][step], rtol=1e-5, atol=1e-6, host=HOST_FWD)
         norms = np.array([float(grads[k].norm()) for k in keys])
-        np.testing.assert_allclose(norms, g["grad_norms"][step], rtol=2e-4, atol=1e-7)
+        assert_close_across_hosts(norms, g["grad_norms"][step], rtol=2e-4, atol=1e-7, host=HOST_FWD)
         if step == 0:
-            np.testing.assert_allclose(grads["model.0.conv.weight"].numpy(), g["g_stem"], rtol=1e-4, atol=1e-6)
-            np.testing.assert_allclose(grads["model.2.m.0.cv1.conv.weight"].numpy(), g["g_c2f"], rtol=1e-4, atol=1e-6)
-            np.testing.assert_allclose(grads["model.22.cv3.0.2.bias"].numpy(), g["g_headb"], rtol=1e-4, atol=1e-6)
-            np.testing.assert_allclose(grads["model.9.cv2.bn.weight"].numpy(), g["g_bn"], rtol=1e-4, atol=1e-6)
-    np.testing.assert_allclose(sd["model.0.conv.weight"].numpy(), g["w_stem_after2"], rtol=1e-4, atol=1e-6)
-    np.testing.assert_allclose(sd["model.22.cv2.1.2.weight"].numpy(), g["w_head_after2"], rtol=1e-4, atol=1e-6)
-    np.testing.assert_allclose(sd["model.4.m.1.cv2.bn.weight"].numpy(), g["bn_after2"], rtol=1e-4, atol=1e-6)
-    np.testing.assert_allclose(sd["model.4.m.1.cv2.bn.running_var"].numpy(), g["rv_after2"], rtol=1e-4, atol=1e-6)
+            assert_close_across_hosts(grads["model.0.conv.weight"].numpy(), g["g_stem"], rtol=1e-4, atol=1e-6, host=HOST_FWD)
+            assert_close_across_hosts(grads["model.2.m.0.cv1.conv.weight"].numpy(), g["g_c2f"], rtol=1e-4, atol=1e-6, host=HOST_FWD)
+            assert_close_across_hosts(grads["model.22.cv3.0.2.bias"].numpy(), g["g_headb"], rtol=1e-4, atol=1e-6, host=HOST_FWD)
+            assert_close_across_hosts(grads["model.9.cv2.bn.weight"].numpy(), g["g_bn"], rtol=1e-4, atol=1e-6, host=HOST_FWD)
+    assert_close_across_hosts(sd["model.0.conv.weight"].numpy(), g["w_stem_after2"], rtol=1e-4, atol=1e-6, host=HOST_DEEP)
+    assert_close_across_hosts(sd["model.22.cv2.1.2.weight"].numpy(), g["w_head_after2"], rtol=1e-4, atol=1e-6, host=HOST_DEEP)
+    assert_close_across_hosts(sd["model.4.m.1.cv2.bn.weight"].numpy(), g["bn_after2"], rtol=1e-4, atol=1e-6, host=HOST_DEEP)
+    assert_close_across_hosts(sd["model.4.m.1.cv2.bn.running_var"].numpy(), g["rv_after2"], rtol=1e-4, atol=1e-6, host=HOST_DEEP)
 
 
 def test_assigner_fixture(gold):
@@ -91,7 +108,7 @@ def test_forward_640_subsample(gold):
         outs = O.forward(sd, synth.images(1, 640, 640, seed=1), "n", 80, training=True)
     assert [tuple(o.shape) for o in outs] == [(1, 144, 80, 80), (1, 144, 40, 40), (1, 144, 20, 20)]
     for i, o in enumerate(outs):
-        np.testing.assert_allclose(o.flatten()[::97].numpy(), g[f"lvl{i}"], rtol=1e-5, atol=1e-5)
+        assert_close_across_hosts(o.flatten()[::97].numpy(), g[f"lvl{i}"], rtol=1e-5, atol=1e-5, host=HOST_FWD)
         np.testing.assert_allclose(float(o.norm()), g["norms"][i], rtol=1e-5)
 
 
@@ -189,8 +206,8 @@ def test_centernet_oracle_init_forward_decode(gold):
     sums = json.load(open(os.path.join(GOLD, "centernet_seed0_init_sums.json")))
     assert list(sums.keys()) == list(sd.keys()) and len(sd) == 326
     for k, (s, a) in sums.items():
-        v = sd[k].double()
-        assert float(v.sum()) == s and float(v.abs().sum()) == a, k
+        v = sd[k].double()                                             # the float64 sums' own order differs by host: last-bit agreement
+        np.testing.assert_allclose([float(v.sum()), float(v.abs().sum())], [s, a], rtol=1e-12, atol=1e-12, err_msg=k)
     g = gold("centernet_fwd_128.npz")
     x = torch.from_numpy(g["x"])
     tr = C.forward(sd, x, 80, training=True)                       # also moves the BN running statistics, as the fixture run did
@@ -475,11 +492,11 @@ def test_yolov7_oracle_init_forward_decode_nms(gold):
     sd = _yolov7_fixture_state(g)
     with torch.no_grad():
         outs = Y.forward(sd, torch.from_numpy(g["x"]))
-    np.testing.assert_allclose(outs[0].numpy(), g["out0"], rtol=1e-4, atol=1e-4)
-    np.testing.assert_allclose(outs[1].numpy(), g["out1"], rtol=1e-4, atol=1e-4)
-    np.testing.assert_allclose(outs[2].flatten()[::5].numpy(), g["out2_sub"], rtol=1e-4, atol=1e-4)
+    assert_close_across_hosts(outs[0].numpy(), g["out0"], rtol=1e-4, atol=1e-4, host=HOST_FWD)
+    assert_close_across_hosts(outs[1].numpy(), g["out1"], rtol=1e-4, atol=1e-4, host=HOST_FWD)
+    assert_close_across_hosts(outs[2].flatten()[::5].numpy(), g["out2_sub"], rtol=1e-4, atol=1e-4, host=HOST_FWD)
     dec = Y.decode(outs, 20, (160, 224))
-    np.testing.assert_allclose(dec.flatten()[::7].numpy(), g["dec_sub"], rtol=1e-4, atol=1e-5)
+    assert_close_across_hosts(dec.flatten()[::7].numpy(), g["dec_sub"], rtol=1e-4, atol=1e-5, host=HOST_DEEP)
     res = Y.nms(dec, 20, float(g["conf"]), float(g["nms_thr"]))
     for b in range(2):
         rows, keep = res[b]

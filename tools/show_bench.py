@@ -1,4 +1,4 @@
-"""Pretty-print a bench.py JSON line: python tools/show_bench.py file.json [...]"""
+"""Pretty-print a `bench.py --full` JSON line (train step): python tools/show_bench.py file.json [...]"""
 import json
 import sys
 

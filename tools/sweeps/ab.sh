@@ -7,7 +7,7 @@ for rep in $(seq $REPS); do
   for cfg in "$@"; do
     label=${cfg%%:*}
     envs=${cfg#*:}
-    env $(echo $envs | tr ',' ' ') python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    env $(echo $envs | tr ',' ' ') python bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d.get('kernel_classes',{})

@@ -3,7 +3,7 @@ REPS=${REPS:-2}
 STEPS=${STEPS:-30}
 for rep in $(seq $REPS); do
   for lib in "$@"; do
-    CVX_LIB=$(pwd)/$lib python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    CVX_LIB=$(pwd)/$lib python bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d.get('kernel_classes',{})
