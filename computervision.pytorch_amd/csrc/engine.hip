@@ -856,12 +856,19 @@ int plan_batch(cvx_engine* e, int B, bool training) {
         e->slab_tail_blocks = (int)sblocks.size();
         e->slab_tail_op = (int)i;
       }
+      // A layer that folds its own weight gradient (the stem, on the main stream) gets NO reducer workgroups: slab_blk0 == slab_blk1.  A
+      // workgroup of the table-driven reducer does `grads[dst] += sum * inv_scale` on the reduction stream, a read-modify-write of the very
+      // words the stem's fold adds to, and nothing orders the two streams there.
       c.slab_blk0 = (int)sblocks.size();
-      for (long long s0 = 0; s0 < total; s0 += 256 / sd.lanes) sblocks.push_back(BlockRef{(int)sdescs.size(), (int)s0});
+      if (sd.nsplit > 0)
+        for (long long s0 = 0; s0 < total; s0 += 256 / sd.lanes) sblocks.push_back(BlockRef{(int)sdescs.size(), (int)s0});
       c.slab_blk1 = (int)sblocks.size();
       sdescs.push_back(sd);
     }
   }
+  for (const BlockRef& br : sblocks)
+    CVX_CHECK(br.desc >= 0 && br.desc < (int)sdescs.size() && sdescs[br.desc].nsplit > 0,
+              "slab block table: a reducer workgroup points at a layer without slabs of its own (nsplit == 0)");
   e->ytmp = nullptr;
   if (training && ytmp_elems > 0) {
     CVX_TRY(dev_alloc(e, e->batch_allocs, e->batch_bytes, &p, ytmp_elems * 4));

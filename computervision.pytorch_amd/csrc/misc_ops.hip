@@ -1248,6 +1248,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* slabs, f
   __shared__ float sred[256];
   const BlockRef br = blocks[blockIdx.x];
   const SlabDesc d = descs[br.desc];
+  if (d.nsplit == 0) return;  // (whole workgroup) nothing to add: no read-modify-write of gradients another stream may be folding into
   const long long total = (long long)d.rows * d.Cin;
   const long long slab_elems = (long long)d.rows * d.Cin_pad;
   const int LR = d.lanes, COLS = 256 / LR;
