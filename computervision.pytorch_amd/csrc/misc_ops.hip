@@ -1329,6 +1329,101 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, float* g, float* m,
   }
 }
 
+// The weight average (ModelEMA.update of the reference): e <- rn(rn(e * d) + rn(omd * p)), three correctly rounded fp32 operations in this
+// order, which is what torch's `v *= d; v += (1 - d) * p` computes.  Contraction is switched off for exactly these three: this toolchain's
+// __fmul_rn / __fadd_rn are plain `*` and `+` that the backend does fuse into an FMA (it did, in the 16-byte path).
+__device__ __forceinline__ float ema_mix(float e, float p, float d, float omd) {
+#pragma clang fp contract(off)
+  const float a = e * d;
+  const float b = omd * p;
+  return a + b;
+}
+
+// adam_kernel (device-resident step state) with the average in the same pass: `e` moves toward the value of p this thread is about to store --
+// toward the unchanged p on a skipped step -- in the same 16-byte vector.  The parameter is in registers already, so the average costs its own
+// read and write and no launch.  p, m and v must come out bit for bit as adam_kernel leaves them (the fused and the two-launch step are
+// interchangeable), and which products the compiler contracts into FMAs is its heuristic's choice -- a copy of adam_kernel's expressions fused
+// differently here.  So the contraction is written out: adam_step4 / adam_step1 spell the FMAs adam_kernel compiles to for gfx950 in its
+// 16-byte path and in its scalar tail (they differ: the tail keeps v and the denominator as multiply + add), with contraction off around them.
+// tests/test_ema_gpu.py compares the two paths on the device.
+__device__ __forceinline__ void adam_step4(float& p, float& m, float& v, float g, float b1, float b2, float eps, float lr_over_bc1,
+                                           float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  const float g1 = (1.f - b1) * g, g2 = (1.f - b2) * g;
+  m = __builtin_fmaf(b1, m, g1);
+  v = __builtin_fmaf(b2, v, g2 * g);
+  const float num = lr_over_bc1 * m;
+  p = p - num / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+}
+__device__ __forceinline__ void adam_step1(float& p, float& m, float& v, float g, float b1, float b2, float eps, float lr_over_bc1,
+                                           float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  const float g1 = (1.f - b1) * g, g2 = (1.f - b2) * g;
+  m = __builtin_fmaf(b1, m, g1);
+  const float bv = b2 * v, gg = g2 * g;
+  v = bv + gg;
+  const float num = lr_over_bc1 * m, den = sqrtf(v) * inv_sqrt_bc2;
+  p = p - num / (den + eps);
+}
+
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps,
+                                                       const int* found_inf, int zero_grad, const float* state, float gscale, float* e, float d,
+                                                       float omd) {
+  const bool skip = found_inf && *found_inf != 0;
+  const float lr_over_bc1 = state[2], inv_sqrt_bc2 = state[3];
+  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (i + 4 <= n) {
+    f4 pp = *reinterpret_cast<f4*>(p + i), ee = *reinterpret_cast<f4*>(e + i);
+    if (!skip) {
+      f4 gg = *reinterpret_cast<f4*>(g + i), mm = *reinterpret_cast<f4*>(m + i), vv = *reinterpret_cast<f4*>(v + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float pk = pp[k], mk = mm[k], vk = vv[k];
+        adam_step4(pk, mk, vk, gg[k] * gscale, b1, b2, eps, lr_over_bc1, inv_sqrt_bc2);
+        pp[k] = pk;
+        mm[k] = mk;
+        vv[k] = vk;
+      }
+      *reinterpret_cast<f4*>(p + i) = pp;
+      *reinterpret_cast<f4*>(m + i) = mm;
+      *reinterpret_cast<f4*>(v + i) = vv;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ee[k] = ema_mix(ee[k], pp[k], d, omd);
+    *reinterpret_cast<f4*>(e + i) = ee;
+    if (zero_grad) *reinterpret_cast<f4*>(g + i) = f4{0.f, 0.f, 0.f, 0.f};
+  } else {
+    for (; i < n; ++i) {
+      float pp = p[i];
+      if (!skip) {
+        float mm = m[i], vv = v[i];
+        adam_step1(pp, mm, vv, g[i] * gscale, b1, b2, eps, lr_over_bc1, inv_sqrt_bc2);
+        m[i] = mm;
+        v[i] = vv;
+        p[i] = pp;
+      }
+      e[i] = ema_mix(e[i], pp, d, omd);
+      if (zero_grad) g[i] = 0.f;
+    }
+  }
+}
+
+// The average as a pass of its own (BatchNorm statistics; parameters when no optimiser step is fused with it): 16-byte vectors, scalar tail.
+__global__ __launch_bounds__(256) void ema_update_kernel(float* e, const float* p, long long n, float d, float omd) {
+  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (i + 4 <= n) {
+    f4 ee = *reinterpret_cast<f4*>(e + i);
+    const f4 pp = *reinterpret_cast<const f4*>(p + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ee[k] = ema_mix(ee[k], pp[k], d, omd);
+    *reinterpret_cast<f4*>(e + i) = ee;
+  } else {
+    for (; i < n; ++i) e[i] = ema_mix(e[i], p[i], d, omd);
+  }
+}
+
 __global__ __launch_bounds__(256) void check_finite_kernel(const float* g, long long n, int* found_inf) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
@@ -1574,6 +1669,14 @@ int cvx_adam_dev(float* p, float* g, float* m, float* v, long long n, float b1, 
                  int zero_grad, float grad_scale, hipStream_t st) {
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, state, b1, b2, found_inf);
   return launch1d(adam_kernel, (n + 3) / 4, st, p, g, m, v, n, 0.f, b1, b2, eps, 0.f, found_inf, zero_grad, (const float*)state, grad_scale);
+}
+int cvx_adam_ema_dev(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps, float* state, const int* found_inf,
+                     int zero_grad, float grad_scale, float* e, float d, float omd, hipStream_t st) {
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, state, b1, b2, found_inf);
+  return launch1d(adam_ema_kernel, (n + 3) / 4, st, p, g, m, v, n, b1, b2, eps, found_inf, zero_grad, (const float*)state, grad_scale, e, d, omd);
+}
+int cvx_ema_update_launch(float* e, const float* p, long long n, float d, float omd, hipStream_t st) {
+  return launch1d(ema_update_kernel, (n + 3) / 4, st, e, p, n, d, omd);
 }
 int cvx_check_finite_launch(const float* g, long long n, int* found_inf, hipStream_t st) {
   if (n <= 0) return 0;

@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .ema import clone_model
 from .engine import Engine
 from .graph import Graph, TensorSlot
 
@@ -271,6 +272,8 @@ class DeepLabV3PlusR101(nn.Module):
         self._attach_views()
         self._init_like_reference()
         self.last_rows = None
+
+    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
 
     def _build_tree(self):
         for key in self.layout.slots:

@@ -1,4 +1,4 @@
-"""CenterNet (DLA-34) on the MI355X engine -- INFERENCE path (BASELINE.json configs[3]).
+"""CenterNet (DLA-34) on the MI355X engine: inference AND training (BASELINE.json configs[3]).
 
 Mirrors ``core/models/centernet_model.py:9-379`` of the reference as an engine graph:
 
@@ -14,8 +14,10 @@ Mirrors ``core/models/centernet_model.py:9-379`` of the reference as an engine g
   centernet_model.py:141-146) and is not executed; ``base.final`` (the unused ImageNet classifier) is kept as parameters only.
 
 All parameters live in one flat fp32 arena, BN statistics in a second one; ``state_dict`` has the reference's 326 keys
-and shapes in its order and is bit-identical to ``CenterNet(cfg)`` under the same global seed.  Training mode is not
-built this round: ``model.train()`` forward raises.
+and shapes in its order and is bit-identical to ``CenterNet(cfg)`` under the same global seed.
+
+Training (``model.train()``): the same graph with batch-statistics BatchNorm and the backward of every op; ``CenterNetLoss``
+(csrc/loss_centernet.hip) and ``CenterNetTrainStep`` below are the reference's ``train_loop`` (centernet_train.py:104-121) as C-ABI calls.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .ema import clone_model
 from .engine import Engine
 from .graph import Graph, TensorSlot
 
@@ -331,6 +334,8 @@ class CenterNetDLA34(nn.Module):
         self.last_raw = None
 
     # ---- module tree with the reference's names (state_dict keys / order) --------------------------
+    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
+
     def _build_tree(self):
         for key in self.layout.slots:
             mod = self

@@ -273,6 +273,35 @@ def adam_step_dev(params, grads, exp_avg, exp_avg_sq, betas, eps, state, found_i
             "cvx_adam_step_dev")
 
 
+def ema_update(ema_arena: torch.Tensor, src: torch.Tensor, d: float, one_minus_d: float):
+    """ema <- rn(rn(ema * d) + rn(one_minus_d * src)) on the current stream (cvx_ema_update; d and 1 - d formed in double by the caller)."""
+    lib = L.load()
+    _need_gpu(ema_arena, "ema")
+    _need_gpu(src, "src")
+    if ema_arena.numel() != src.numel():
+        raise L.CvxError(f"the average holds {ema_arena.numel()} values, the arena it follows {src.numel()}")
+    if ema_arena.numel() == 0:
+        return
+    _note_param_write(ema_arena)      # the clone's engines keep fp16 weight images while the weights stand: this write ends that
+    L.check(lib.cvx_ema_update(L.ptr(ema_arena), L.ptr(src), ema_arena.numel(), float(d), float(one_minus_d), L.stream_ptr(src.device)),
+            "cvx_ema_update")
+
+
+def adam_ema_step_dev(params, grads, exp_avg, exp_avg_sq, betas, eps, state, ema_arena, d, one_minus_d, found_inf=None, zero_grad=True,
+                      grad_scale=1.0):
+    """adam_step_dev with the weight average in the same pass (cvx_adam_ema_step_dev)."""
+    lib = L.load()
+    _need_gpu(params, "params")
+    _need_gpu(ema_arena, "ema")
+    if ema_arena.numel() != params.numel():
+        raise L.CvxError(f"the average holds {ema_arena.numel()} values, the parameter arena {params.numel()}")
+    _note_param_write(params)
+    _note_param_write(ema_arena)
+    L.check(lib.cvx_adam_ema_step_dev(L.ptr(params), L.ptr(grads), L.ptr(exp_avg), L.ptr(exp_avg_sq), params.numel(), betas[0], betas[1], eps,
+                                      L.ptr(state), L.ptr(found_inf), 1 if zero_grad else 0, float(grad_scale), L.ptr(ema_arena), float(d),
+                                      float(one_minus_d), L.stream_ptr(params.device)), "cvx_adam_ema_step_dev")
+
+
 def check_finite(grads: torch.Tensor, found_inf: torch.Tensor):
     lib = L.load()
     L.check(lib.cvx_check_finite(L.ptr(grads), grads.numel(), L.ptr(found_inf), L.stream_ptr(grads.device)), "cvx_check_finite")

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .ema import clone_model
 from .engine import Engine, decode
 from .graph import REG_MAX, STRIDES, ParamLayout, build_yolov8_graph
 
@@ -173,6 +174,8 @@ class Yolo8(nn.Module):
         self._grads_attached = False
         self._attach_views()
         self._init_like_reference()
+
+    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
 
     # ---- arenas <-> module tree -------------------------------------------------------------------
     def _named_slots(self):

@@ -1,4 +1,4 @@
-"""SSD300 (VGG16-BN) on the MI355X engine -- INFERENCE path.
+"""SSD300 (VGG16-BN) on the MI355X engine: inference AND training.
 
 Mirrors ``core/models/ssd_model.py:6-191`` of the reference as an engine graph:
 
@@ -11,7 +11,10 @@ Mirrors ``core/models/ssd_model.py:6-191`` of the reference as an engine graph:
   (B, 8732, 4) and (B, 8732, 21) -- flattened in NCHW order per level, as the reference does (no permute, :177-183).
 
 ``state_dict``: the reference's 136 keys / shapes / order, bit-identical to ``SSD(cfg)`` under the same global seed (torch's
-default initialisation in the reference's construction order: loc_i / conf_i alternately).  Training (MultiBoxLossV2) is not built.
+default initialisation in the reference's construction order: loc_i / conf_i alternately).
+
+Training (``model.train()``): the same graph with batch-statistics BatchNorm and the backward of every op; ``MultiBoxLoss``
+(csrc/loss_multibox.hip: the reference's MultiBoxLossV2) and ``SsdTrainStep`` below are the reference's ``train_loop`` as C-ABI calls.
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .ema import clone_model
 from .engine import Engine
 from .graph import Graph, TensorSlot
 
@@ -216,6 +220,8 @@ class SSD300VGG(nn.Module):
         self._attach_views()
         self._init_like_reference()
         self.last_rows = None
+
+    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
 
     def _build_tree(self):
         for key in self.layout.slots:

@@ -18,7 +18,7 @@ import ctypes as C
 import os
 
 from . import _lib as L
-from .engine import V8LossOp, _note_param_write, adam_step, adam_step_dev, check_finite
+from .engine import V8LossOp, _note_param_write, adam_ema_step_dev, adam_step, adam_step_dev, check_finite, ema_update
 from .graph import STRIDES
 from .model import PredList, Yolo8
 
@@ -99,6 +99,16 @@ class FlatAdam(torch.optim.Optimizer):
         self._state = None          # device [lr, step, lr/(1-b1^t), 1/sqrt(1-b2^t)]: the step advances on the device
         self._lr_on_device = None
         self.found_inf: Optional[torch.Tensor] = None
+        self._ema = None            # attach_ema: a ModelEMA whose average moves with every step()
+        self.ema_fused = True       # False: the average as launches of its own after the Adam kernel (tools/ema_cost.py times both)
+
+    def attach_ema(self, ema):
+        """Every ``step()`` from now on also moves ``ema`` (a ``ModelEMA`` of this optimiser's model; None detaches it): the parameter average
+        inside the Adam kernel (``cvx_adam_ema_step_dev``), the BatchNorm statistics with one ``cvx_ema_update`` launch, ``ema.updates`` + 1 --
+        what ``ema.update(model)`` after ``optimizer.step()`` does in the reference's loop shape, a step skipped by ``found_inf`` included."""
+        if ema is not None:
+            ema.check(self.model)
+        self._ema = ema
 
     def _ensure_state(self):
         p = self.model.flat_params
@@ -122,8 +132,19 @@ class FlatAdam(torch.optim.Optimizer):
             self.sync_lr()               # a scheduler (or GradScaler.step -> optimizer.step) may have changed param_groups["lr"]
         g = self.param_groups[0]
         self._step += 1                  # host mirror only; the authoritative count lives in the device state
-        adam_step_dev(self.model.flat_params, self.model.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, self.found_inf,
-                      zero_grad, grad_scale)
+        ema = self._ema
+        if ema is None or not self.ema_fused:
+            adam_step_dev(self.model.flat_params, self.model.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, self.found_inf,
+                          zero_grad, grad_scale)
+            if ema is not None:
+                ema.update(self.model)
+            return
+        ema.check(self.model)
+        ema.updates += 1
+        d, omd = ema.factors()
+        adam_ema_step_dev(self.model.flat_params, self.model.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, ema.ema.flat_params,
+                          d, omd, self.found_inf, zero_grad, grad_scale)
+        ema_update(ema.ema.flat_stats, self.model.flat_stats, d, omd)
 
     def zero_grad(self, set_to_none: bool = True):
         self.model.flat_grads.zero_()

@@ -1,4 +1,4 @@
-"""YOLOv7-l on the MI355X engine -- INFERENCE path.
+"""YOLOv7-l on the MI355X engine: inference AND training.
 
 Mirrors ``core/models/yolov7_model.py:14-525`` (phi = 'l') of the reference as an engine graph:
 
@@ -15,7 +15,10 @@ Mirrors ``core/models/yolov7_model.py:14-525`` (phi = 'l') of the reference as a
   (coarsest first); ``forward`` returns them as the reference's NCHW tensors, ``cvx_yolo7_decode`` reads the rows in place.
 
 ``state_dict``: the reference's 558 keys / shapes / order, bit-identical to ``Yolo7(cfg)`` (``cfg.train.pretrained = False``)
-under the same global seed.  Training (Yolo7Loss with its SimOTA matching) is not built: ``model.train()`` forward raises.
+under the same global seed.
+
+Training (``model.train()``): the same graph with batch-statistics BatchNorm and the backward of every op; ``Yolo7Loss`` (csrc/loss_yolov7.hip,
+SimOTA matching included) and ``Yolo7TrainStep`` below are the reference's ``train_loop`` (yolo7_train.py:79-97) as C-ABI calls.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .ema import clone_model
 from .engine import Engine
 from .graph import Graph, TensorSlot
 
@@ -290,6 +294,8 @@ class Yolo7L(nn.Module):
         self._attach_views()
         self._init_like_reference()
         self.last_rows = None
+
+    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
 
     def _build_tree(self):
         for key in self.layout.slots:

@@ -9,7 +9,10 @@ train_loop, evaluate_loop`` and ``train()`` with the reference's schedule and ch
   trains at constant LR there too);
 * a checkpoint ``{"model", "optimizer", "scheduler", "warm_up"}`` every ``save_interval`` epochs and at the last epoch, a
   bare ``state_dict`` at the end (reference base.py:277-292, core/utils/ckpt.py:38-51); ``cfg.train.resume_training`` +
-  ``last_epoch`` resume from one (base.py:180-191).
+  ``last_epoch`` resume from one (base.py:180-191);
+* ``cfg.train.ema = True`` (read with ``getattr``: no config declares it) keeps the reference's ``ModelEMA`` (lr_scheduler.py:55-84) of the
+  model: updated inside every fused step, evaluated by ``evaluate_loop`` (``self.eval_model``), saved as the checkpoint's ``"ema"`` entry
+  and, at the end, as ``{tag}_final_ema.pth``.
 
 Dataset readers and TensorBoard are outside the hot path; ``load_data`` may be
 overridden or a dataloader injected, and defaults to seeded synthetic batches so the loop is runnable anywhere.
@@ -113,6 +116,21 @@ class BaseTrainer:
         self.set_optimizer()
         self.set_lr_scheduler()
         self.set_criterion()
+        self.set_ema()
+
+    @property
+    def eval_model(self):
+        """What ``evaluate_loop`` runs: the averaged clone when ``cfg.train.ema`` is on, the model otherwise."""
+        return self.model if self.ema is None else self.ema.ema
+
+    def set_ema(self):
+        """Opt-in weight average (the reference's ModelEMA, core/trainer/lr_scheduler.py:55-84): ``cfg.train.ema`` (default off),
+        ``ema_decay``, ``ema_tau``.  Attached to the optimiser, so every fused step moves it inside its Adam pass."""
+        self.ema = None
+        if getattr(self.cfg.train, "ema", False):
+            from computervision.pytorch_amd.ema import ModelEMA
+            self.ema = ModelEMA(self.model, decay=float(getattr(self.cfg.train, "ema_decay", 0.9999)), tau=float(getattr(self.cfg.train, "ema_tau", 2000)))
+            self.optimizer.attach_ema(self.ema)
 
     # hooks ---------------------------------------------------------------------------------------
     def set_model_algorithm(self):
@@ -149,11 +167,13 @@ class BaseTrainer:
         rank continues from (and a resumed job starts from) one consistent model."""
         from computervision.pytorch_amd.train import broadcast_bn_statistics
         broadcast_bn_statistics(self.model)
+        if self.ema is not None:             # the averaged parameters agree across ranks, the averaged per-rank statistics do not
+            broadcast_bn_statistics(self.ema.ema)
         if not self._is_rank0():
             return
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         if full:
-            CheckPoint.save(self.model, path, optimizer=self.optimizer, scheduler=self.lr_scheduler, warm_up=self.warmup_scheduler)
+            CheckPoint.save(self.model, path, optimizer=self.optimizer, scheduler=self.lr_scheduler, warm_up=self.warmup_scheduler, ema=self.ema)
         else:
             CheckPoint.save(self.model, path)
 
@@ -162,7 +182,7 @@ class BaseTrainer:
         metrics = [MeanMetric() for _ in self.metric_names]
         if CheckPoint.check(self.resume_training_weights):                     # reference base.py:180-191
             CheckPoint.load(self.resume_training_weights, self.device, self.model, pure=False, optimizer=self.optimizer,
-                            scheduler=self.lr_scheduler, warm_up=self.warmup_scheduler)
+                            scheduler=self.lr_scheduler, warm_up=self.warmup_scheduler, ema=self.ema)
             self.logger.info("resumed from %s at epoch %d", self.resume_training_weights, self.last_epoch)
         it = 0
         tag = f"{self.model_name}_{str(self.dataset_name).lower()}"
@@ -190,3 +210,5 @@ class BaseTrainer:
                 self.save_checkpoint(os.path.join(self.save_path, f"{tag}_epoch-{epoch}.pth"), full=True)
         if self.save_interval:
             self.save_checkpoint(os.path.join(self.save_path, f"{tag}_final.pth"), full=False)
+            if self.ema is not None and self._is_rank0():          # the weights to evaluate and ship: a bare state_dict of the average
+                CheckPoint.save(self.ema.ema, os.path.join(self.save_path, f"{tag}_final_ema.pth"))

@@ -98,11 +98,12 @@ class CenterNetTrainer(BaseTrainer):
         return [self._step(images, targets)[0]]
 
     def evaluate_loop(self) -> Dict:
-        self.model.eval()
+        model = self.eval_model                        # the weight average when cfg.train.ema is on
+        model.eval()
         total, n = 0.0, 0
         with torch.no_grad():
             for images, targets in self.val_dataloader:
-                preds = self.model(images.to(self.device))
+                preds = model(images.to(self.device))
                 total += float(self.criterion(preds, [t.to(self.device) for t in targets]))
                 n += 1
         return {"val_loss": total / max(n, 1)}

@@ -122,13 +122,14 @@ class DeeplabV3PlusTrainer(BaseTrainer):
         return [self._step(images, targets)]
 
     def evaluate_loop(self) -> Dict:
-        self.model.eval()
+        model = self.eval_model                        # the weight average when cfg.train.ema is on
+        model.eval()
         self.metrics.reset()
         total, n = 0.0, 0
         with torch.no_grad():
             for images, targets in self.val_dataloader:
                 images, targets = images.to(self.device), targets.to(self.device)
-                preds = self.model(images)
+                preds = model(images)
                 total += float(self.criterion(preds, targets))
                 self.metrics.add_batch(torch.argmax(preds, dim=1), targets)
                 n += 1

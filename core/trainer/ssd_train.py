@@ -90,11 +90,12 @@ class SsdTrainer(BaseTrainer):
         return [items[0], items[1], items[2]]
 
     def evaluate_loop(self) -> Dict:
-        self.model.eval()
+        model = self.eval_model                        # the weight average when cfg.train.ema is on
+        model.eval()
         total, n = 0.0, 0
         with torch.no_grad():
             for images, targets in self.val_dataloader:
-                preds = self.model(images.to(self.device))
+                preds = model(images.to(self.device))
                 total += float(self.criterion(y_true=targets.to(self.device), y_pred=preds)[0])
                 n += 1
         return {"val_loss": total / max(n, 1)}

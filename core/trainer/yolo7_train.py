@@ -88,12 +88,13 @@ class Yolo7Trainer(BaseTrainer):
         return [items[0], items[1], items[2], items[3]]
 
     def evaluate_loop(self) -> Dict:
-        self.model.eval()
+        model = self.eval_model                        # the weight average when cfg.train.ema is on
+        model.eval()
         total, n = 0.0, 0
         with torch.no_grad():
             for images, targets in self.val_dataloader:
                 images = images.to(self.device)
-                preds = self.model(images)
+                preds = model(images)
                 total += float(self.criterion(preds, targets.to(self.device), images)[0])
                 n += 1
         return {"val_loss": total / max(n, 1)}

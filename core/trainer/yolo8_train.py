@@ -90,11 +90,12 @@ class Yolo8Trainer(BaseTrainer):
         return [items.sum() * images.shape[0]]          # the reference's scalar: sum(box,cls,dfl) * batch
 
     def evaluate_loop(self) -> Dict:
-        self.model.eval()
+        model = self.eval_model                        # the weight average when cfg.train.ema is on
+        model.eval()
         total, n = 0.0, 0
         with torch.no_grad():
             for images, targets in self.val_dataloader:
-                preds = self.model(images.to(self.device))
+                preds = model(images.to(self.device))
                 loss, _ = self.criterion(preds, targets)
                 total += float(loss)
                 n += 1

@@ -1,5 +1,5 @@
 """Checkpoint files in the reference's format (core/utils/ckpt.py:7-75): ``torch.save`` of either a bare ``state_dict`` or
-``{"model", "optimizer", "scheduler", "warm_up"}``; the model's ``state_dict`` has the reference's keys and shapes and the
+``{"model", "optimizer", "scheduler", "warm_up"}`` (plus ``"ema"`` when a weight average is kept); the model's ``state_dict`` has the reference's keys and shapes and the
 optimizer entry is ``torch.optim.Adam``'s own layout (per-parameter ``state[i] = {step, exp_avg, exp_avg_sq}`` in
 ``model.parameters()`` order -- ``FlatAdam.state_dict`` slices its flat moment arenas accordingly), so full checkpoints are
 interchangeable in both directions: a reference ``.pth`` resumes here, and a file written here loads into the reference's
@@ -50,7 +50,9 @@ class CheckPoint:
         print(f"Failed to load {len(skipped)} keys, they are: {skipped[:20]}...")
 
     @staticmethod
-    def save(model, path, optimizer=None, scheduler=None, warm_up=None):
+    def save(model, path, optimizer=None, scheduler=None, warm_up=None, ema=None):
+        """``ema``: a ``ModelEMA``; a full checkpoint then carries ``"ema": {"model": <state_dict of the average>, "updates": int}`` beside
+        the reference's entries (its loader reads by key, so the file still loads there)."""
         sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}   # plain tensors: no arena views in the file
         if optimizer is None and scheduler is None:
             torch.save(sd, path)
@@ -62,15 +64,25 @@ class CheckPoint:
             obj["scheduler"] = scheduler.state_dict()
         if warm_up is not None:
             obj["warm_up"] = warm_up.state_dict()
+        if ema is not None:
+            obj["ema"] = ema.state_dict()
         torch.save(obj, path)
 
     @staticmethod
-    def load(path, device, model, pure=False, optimizer=None, scheduler=None, warm_up=None):
+    def load(path, device, model, pure=False, optimizer=None, scheduler=None, warm_up=None, ema=None):
+        """``ema``: a ``ModelEMA`` to restore; from a file without an ``"ema"`` entry it restarts from the loaded weights."""
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         if pure:
             model.load_state_dict(ckpt)
+            if ema is not None:
+                ema.restart_from(model)
             return
         model.load_state_dict(ckpt["model"])
+        if ema is not None:
+            if "ema" in ckpt:
+                ema.load_state_dict(ckpt["ema"])
+            else:
+                ema.restart_from(model)
         if optimizer is not None and "optimizer" in ckpt:
             optimizer.load_state_dict(ckpt["optimizer"])
         if scheduler is not None and "scheduler" in ckpt:

@@ -263,6 +263,20 @@ int cvx_check_finite(const float* grads, int64_t n, int32_t* found_inf, void* hi
 int cvx_adam_step_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1, float beta2, float eps,
                       float* state, const int32_t* found_inf, int32_t zero_grad, float grad_scale, void* hip_stream);
 
+/* ---- weight average (ModelEMA) ---------------------------------------------------------------------
+ * cvx_ema_update: ema[i] <- rn(rn(ema[i] * d) + rn(one_minus_d * src[i])) over n floats: three correctly rounded fp32 operations in
+ *   this order, never contracted -- bit for bit what torch's `v *= d; v += (1 - d) * msd[k]` leaves.  The caller forms d and 1 - d in
+ *   double precision and casts them.  ema and src are 16-byte aligned and distinct.  Asynchronous on hip_stream.
+ *   Replaces: ModelEMA.update, core/trainer/lr_scheduler.py:55-80 (one launch per arena instead of two torch kernels per state_dict entry).
+ * cvx_adam_ema_step_dev: cvx_adam_step_dev with the average of the parameters in the same pass -- ema moves toward the parameter value
+ *   the step stores; on a step skipped by found_inf toward the unchanged parameters, as a loop that calls ema.update(model) after
+ *   every scaler.step does.  params, grads, exp_avg, exp_avg_sq come out bit for bit as cvx_adam_step_dev leaves them.
+ *   Replaces: optimizer.step + ModelEMA.update on the parameters, core/trainer/lr_scheduler.py:37-43 and :55-80. */
+int cvx_ema_update(float* ema, const float* src, int64_t n, float d, float one_minus_d, void* hip_stream);
+int cvx_adam_ema_step_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1, float beta2, float eps,
+                          float* state, const int32_t* found_inf, int32_t zero_grad, float grad_scale, float* ema, float d, float one_minus_d,
+                          void* hip_stream);
+
 /* ---- eval tail: DFL decode + sigmoid, then class-aware NMS ---------------------------------------
  * cvx_decode: pred (B,A,no) -> y (B, 4+nc, A) fp32 [cx,cy,w,h (pixels), class scores]
  *   Replaces: Detect eval branch, core/models/yolov8/modules.py:434-446.
