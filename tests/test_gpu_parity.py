@@ -2318,6 +2318,41 @@ def _print_worst(title, worst):
         print(f"[per-layer] {title}: {kind}: largest {e:.3e} (bound {bound:.3e}) at {tag} {sub}")
 
 
+def _conv_spec(lay, name):
+    """The arena offsets of a conv op by its name, as a dict, whatever the model family: YOLOv8 keeps ConvSpec objects, the other layouts
+    dicts, and CenterNet's fused first head convolution (three reference modules, one engine conv) lives in lay.head_first."""
+    cs = lay.head_first if name == "backbone.heads.0" else lay.convs[name]
+    return cs if isinstance(cs, dict) else dict(cout_eng=cs.cout_eng, cin=cs.cin, k=cs.k, w_off=cs.w_off, gamma_off=cs.gamma_off,
+                                                beta_off=cs.beta_off, bias_off=cs.bias_off, rmean_off=cs.rmean_off, rvar_off=cs.rvar_off)
+
+
+def _check_dropout(xin, out):
+    """The forward of nn.Dropout(0.1) on the engine's own input: the mask is not predictable (counter-based hash), its statistics and the
+    inverted scaling are.  Returns (keep, nz): the mask as far as it shows (an element whose input is 0 tells nothing), and [input != 0]."""
+    keep = (out != 0) | (xin == 0)
+    nz = xin != 0
+    frac = float((out[nz] == 0).double().mean())
+    assert 0.08 < frac < 0.12, frac                                                  # p = 0.1 of the non-zero elements dropped
+    assert rel(out, xin * keep / 0.9) < 1e-3                                         # inverted scaling, one fp16 rounding
+    return keep, nz
+
+
+def _overwritten_inputs(gr):
+    """Names of the ops whose input (or residual) view no longer holds what the op read once the forward pass has ended: the op itself or a
+    later one writes an overlapping channel range of the same activation buffer (an in-place op, a slice that is rewritten).  Such an op
+    cannot be replayed from the engine's buffers after the fact."""
+    lost = set()
+    for i, o in enumerate(gr.ops):
+        for v in (o["in"], o.get("res")):
+            if v is None or v[0] < 0:
+                continue
+            for later in gr.ops[i:]:
+                w = later["out"]
+                if w[0] == v[0] and w[0] != gr.pred_buf and v[1] < w[1] + w[2] and w[1] < v[1] + v[2]:
+                    lost.add(o["name"])
+    return lost
+
+
 def _check_backward_per_layer(m, B, dpred, min_layers, min_buffers, images=None, bn_eps=None, ops=None, min_bn=None, title="backward"):
     """Every op of the last backward pass of model `m` against fp64 on the ENGINE'S OWN operands (cvx_engine_debug_copy): for each
     Conv + BatchNorm block its xhat, its forward output / residual, the gradient g arriving at its output and the gradient dy it
@@ -2384,10 +2419,7 @@ def _check_backward_per_layer(m, B, dpred, min_layers, min_buffers, images=None,
         expect[b][..., off:off + c] += contrib               # consumers may read overlapping slices of a concat buffer (ELAN)
         covered[b][off:off + c] = True
 
-    def spec(name):
-        cs = lay.head_first if name == "backbone.heads.0" else lay.convs[name]
-        return cs if isinstance(cs, dict) else dict(cout_eng=cs.cout_eng, cin=cs.cin, k=cs.k, w_off=cs.w_off, gamma_off=cs.gamma_off,
-                                                    beta_off=cs.beta_off, bias_off=cs.bias_off)
+    spec = lambda name: _conv_spec(lay, name)               # noqa: E731
 
     n_w = n_bn = 0
     zero_w, zero_bn = [], []                                # layers no gradient reaches: held to exact zeros, counted, and named in the output
@@ -2562,12 +2594,7 @@ def _check_backward_per_layer(m, B, dpred, min_layers, min_buffers, images=None,
         elif typ == L.OP_RESIZE:
             y = F.interpolate(xin, size=(o["oh"], o["ow"]), mode="bilinear", align_corners=False)
         elif typ == L.OP_DROPOUT:
-            out = nchw(act(o["out"]))
-            keep = (out != 0) | (xin.detach() == 0)
-            nz = xin.detach() != 0
-            frac = float((out[nz] == 0).double().mean())
-            assert 0.08 < frac < 0.12, frac                                                  # p = 0.1 of the non-zero elements dropped
-            assert rel(out, xin.detach() * keep / 0.9) < 1e-3                                # inverted scaling, one fp16 rounding
+            keep, nz = _check_dropout(xin.detach(), nchw(act(o["out"])))
             y = xin * keep / 0.9
             unknown[o["in"][0]] = (o["in"][1], o["in"][2], nhwc(~nz))                         # the mask is not observable where the input is 0
         else:
@@ -2600,30 +2627,51 @@ def _check_backward_per_layer(m, B, dpred, min_layers, min_buffers, images=None,
     return n_w, n_bn, checked
 
 
-def _check_forward_per_layer(m, images, B, pred, stats_before, ops=None, title="forward"):
-    """Every op of the last TRAINING forward of a Yolo8 model `m`, in graph order, against fp64 on the engine's own operands: the op's
-    input activation as the engine holds it (read_buffer), the fp32 parameters rounded to fp16 as the engine's weight shadow is (the
-    stem: the fp32 master weights and the caller's fp32 images), and from them, on the CPU in fp64,
-    conv -> batch mean / biased variance -> xhat -> silu(gamma xhat + beta) (+ the residual, from the engine's own residual buffer);
-    ACT_BIAS: conv + bias; max pool 5 and nearest upsample exactly.
+def _check_forward_per_layer(m, images, B, pred, stats_before, ops=None, title="forward", fp32_stem=False, unobservable=()):
+    """Every op of the last TRAINING forward of model `m` (any of the five families), in graph order, against fp64 on the engine's own
+    operands: the op's input activation as the engine holds it (read_buffer), the fp32 parameters rounded to fp16 as the engine's weight
+    shadow is -- the fp32 masters where the kernel reads masters: gamma / beta / bias, the L2Normalize weight, the depthwise transposed
+    convolution --, and from them, on the CPU in fp64,
+      conv (every k / stride / pad / dilation of these graphs) -> batch mean / biased variance -> xhat -> act(gamma xhat + beta [+ residual])
+      [+ residual], act = SiLU / ReLU / none; the residual comes from the engine's own residual buffer and joins before or after the
+      activation per CVX_OPF_RES_PRE_ACT;
+      CVX_OPF_CONV_BIAS (SSD's VGG: Conv(bias) + BN): the bias shifts the batch mean that enters running_mean and nothing else;
+      ACT_BIAS_RELU / ACT_BIAS_LINEAR: act(conv + bias) into an fp16 buffer;  ACT_BIAS: conv + bias into the fp32 prediction rows `pred`
+      at the op's pixel offset and column range;
+      max pools (2x2 incl. ceil mode, 3x3 stride 2 / 1, 5x5), nearest upsampling, slice copies: exactly;
+      global average pool, bilinear resize (align_corners=False, the 1x1 -> h x w broadcast included), L2Normalize
+      (x / (||x|| + 1e-10) * weight), depthwise ConvTranspose2d(2f, f, f/2): the torch expressions of _check_backward_per_layer, forward only;
+      dropout: kept fraction and inverted scaling (_check_dropout);
+      the NHWC-8 fp16 image copy every first layer but YOLOv8's fp32 stem reads: images.half() in channels 0..2, exact zeros in 3..7.
 
-    A CVX_OPF_RAW_F16 layer follows the contract of include/cvx_engine.h: statistics from the fp32 accumulators, the kept tensor is
-    the raw output rounded to fp16, normalisation reads that.  The replay mirrors that one rounding point (y64.float().half() before
-    normalising, statistics from the unrounded y64).
+    `fp32_stem`: the first conv is YOLOv8's fp32 stem (stem.hip), replayed from the caller's fp32 `images` and the fp32 master weights; it
+    keeps no xhat.  `unobservable`: the names of the ops that cannot be replayed because their input view has been overwritten by the end
+    of the forward -- asserted to be exactly _overwritten_inputs(graph); with `ops` None every op is compared or is one of them.
+
+    Documented rounding points beyond the fp16 store, mirrored by the replay and by nothing else:
+    * a CVX_OPF_RAW_F16 layer (include/cvx_engine.h): statistics from the fp32 accumulators, the kept tensor is the raw output rounded to
+      fp16, normalisation reads that -> y64.float().half() before normalising, statistics from the unrounded y64;
+    * the kept xhat of a BatchNorm + ReLU layer (bn_act.hip, bn_act_apply_kernel: "the backward mask [out > 0] rides in the lowest mantissa
+      bit of the kept xhat"): the replay rounds its xhat to fp16 and replaces that bit by [its own fp16 output > 0]; separately the engine's
+      bit must equal [the engine's own output > 0] exactly, element for element.  (Without the mirror the bit alone is worth
+      sqrt(1/12 + 1/2) = 0.76 ulp rms against the 0.29 ulp of a rounding: above the one-rounding bound by construction.)
 
     Bounds = 5e-4 relative L2 (the one-rounding bound of the module docstring) per fp16 rounding between the operands and the compared
     tensor:
-    * output view of an ordinary Conv + BN + SiLU (the stem included): 1 rounding (the fp16 store) -> 5e-4;
+    * output view of a Conv + BN + activation (the stem included), of a bias + ReLU / linear conv, of avgpool / resize / L2Normalize /
+      depthwise transposed conv: 1 rounding (the fp16 store) -> 5e-4;
     * output view of a RAW_F16 layer: 2 (raw output, mirrored by the replay so that only elements whose fp32 and fp64 accumulators round
       to different fp16 values differ; then the fp16 store) -> 1e-3;
-    * xhat (fp16 as kept) of an ordinary layer: 1 -> 5e-4;  xhat32 of a RAW_F16 layer: 1 (the mirrored one) -> 5e-4;  not for the stem,
-      which keeps none;
-    * ACT_BIAS rows of the fp32 `pred` buffer (class columns padded to nc_pad included): no rounding -> 1e-5;
-    * max pool / upsample outputs: torch.equal;
-    * running statistics after the step against (1 - m) old + m batch_mean and the UNBIASED batch variance (momentum 0.03, eps 1e-3:
-      model.BN_MOMENTUM / BN_EPS), fp32 arithmetic -> 1e-5 per layer; `stats_before` = a copy of flat_stats made before the forward.
+    * xhat (fp16 as kept; ReLU layers with the mask bit mirrored) of an ordinary layer: 1 -> 5e-4;  xhat32 of a RAW_F16 layer: 1 (the
+      mirrored one) -> 5e-4;  not for the fp32 stem, which keeps none;
+    * ACT_BIAS rows of the fp32 `pred` buffer (columns padded to a multiple of 8 included): no rounding -> 1e-5;
+    * pools / upsampling / copies / the image copy: torch.equal;
+    * running statistics after the step against (1 - m) old + m batch_mean and the UNBIASED batch variance, eps and momentum from the model
+      module's own BN_EPS / BN_MOMENTUM, fp32 arithmetic -> 1e-5 per layer; `stats_before` = a copy of flat_stats made before the forward.
     Outputs and xhat are held to their bound on the whole tensor and on each image and the border frame separately (_localised)."""
-    from computervision.pytorch_amd.model import BN_EPS, BN_MOMENTUM
+    import sys
+    mod = sys.modules[type(m).__module__]
+    BN_EPS, BN_MOMENTUM = mod.BN_EPS, mod.BN_MOMENTUM
     eng, lay = m._last_engine, m.layout
     gr = eng.graph
     P = m.flat_params.double().cpu()
@@ -2637,65 +2685,137 @@ def _check_forward_per_layer(m, images, B, pred, stats_before, ops=None, title="
         h, w, cc, _ = gr.bufs[b]
         return eng.read_buffer(b, B).double().cpu().reshape(B, h, w, cc)[..., off:off + c]
 
-    worst, n = {}, dict(conv=0, bias=0, xhat=0, stats=0, exact=0)
+    lost = _overwritten_inputs(gr)
+    assert lost == set(unobservable), (sorted(lost), sorted(unobservable))
+    exact_ops = (L.OP_MAXPOOL2, L.OP_MAXPOOL3S2, L.OP_MAXPOOL3S1, L.OP_MAXPOOL5, L.OP_UPSAMPLE2, L.OP_COPY)
+    worst = {}
+    n = dict(conv=0, bias16=0, bias=0, exact=0, other=0, dropout=0, unobservable=0)      # one of these per op
+    n2 = dict(xhat=0, stats=0, image=0)                                                  # further comparisons of the BN convs / the first conv
     for i, o in enumerate(gr.ops):
         if ops is not None and not ops(o):
             continue
-        tag = f"op {o['name']}"
-        if o["type"] == L.OP_MAXPOOL5 or o["type"] == L.OP_UPSAMPLE2:
-            xin = nchw(act(o["in"]))
-            want = F.max_pool2d(xin, 5, 1, 2) if o["type"] == L.OP_MAXPOOL5 else F.interpolate(xin, scale_factor=2, mode="nearest")
-            assert torch.equal(act(o["out"]), nhwc(want)), tag
-            n["exact"] += 1
+        tag, typ = f"op {o['name']}", o["type"]
+        if o["name"] in lost:
+            n["unobservable"] += 1
             continue
-        assert o["type"] == L.OP_CONV, (tag, o["type"])
-        cs = lay.convs[o["name"]]
-        C, cin, k = o["out"][2], cs.cin, cs.k
-        w = P[cs.w_off:cs.w_off + C * k * k * cin].reshape(C, k, k, cin).permute(0, 3, 1, 2).contiguous()
-        stem = o["in"][0] == gr.image_buf
+        if typ != L.OP_CONV:
+            xin, got = nchw(act(o["in"])), act(o["out"])
+            if typ in exact_ops:
+                if typ == L.OP_MAXPOOL2:
+                    want = F.max_pool2d(xin, 2, 2, ceil_mode=(o["oh"] * 2 != o["ih"]))
+                elif typ == L.OP_MAXPOOL3S2:
+                    want = F.max_pool2d(xin, 3, 2, 1)
+                elif typ == L.OP_MAXPOOL3S1:
+                    want = F.max_pool2d(xin, 3, 1, 1)
+                elif typ == L.OP_MAXPOOL5:
+                    want = F.max_pool2d(xin, 5, 1, 2)
+                elif typ == L.OP_UPSAMPLE2:
+                    want = F.interpolate(xin, scale_factor=2, mode="nearest")
+                else:
+                    want = xin
+                assert tuple(want.shape[2:]) == (o["oh"], o["ow"]) and torch.equal(got, nhwc(want)), tag
+                n["exact"] += 1
+                continue
+            if typ == L.OP_DROPOUT:
+                _check_dropout(xin, nchw(got))
+                n["dropout"] += 1
+                continue
+            if typ == L.OP_AVGPOOL:
+                want, kind = F.adaptive_avg_pool2d(xin, 1), "average pool output"
+            elif typ == L.OP_RESIZE:
+                want, kind = F.interpolate(xin, size=(o["oh"], o["ow"]), mode="bilinear", align_corners=False), "resize output"
+            elif typ == L.OP_L2NORM:                           # x / (||x|| + 1e-10) * weight (ssd_model.py:113-128), fp32 master weight
+                Cn = o["in"][2]
+                want = P[o["gamma_off"]:o["gamma_off"] + Cn].view(1, -1, 1, 1) * (xin / (xin.pow(2).sum(1, keepdim=True).sqrt() + 1e-10))
+                kind = "L2Normalize output"
+            elif typ == L.OP_DWCONVT:                          # depthwise ConvTranspose2d(k = 2f, s = f, p = f/2), fp32 master weights [C][2f][2f]
+                f, Cd = o["stride"], o["in"][2]
+                wd = P[o["w_off"]:o["w_off"] + Cd * 4 * f * f].reshape(Cd, 1, 2 * f, 2 * f)
+                want, kind = F.conv_transpose2d(xin, wd, None, stride=f, padding=f // 2, groups=Cd), "depthwise transposed conv output"
+            else:
+                raise AssertionError(f"op type {typ} without a forward check")
+            _localised(tag + " output", got, nhwc(want), 5e-4, 0.0, worst, kind)
+            n["other"] += 1
+            continue
+        cs = _conv_spec(lay, o["name"])
+        C, cin, k = o["out"][2], cs["cin"], cs["k"]
+        flags = o.get("flags", 0)
+        w = P[cs["w_off"]:cs["w_off"] + C * k * k * cin].reshape(C, k, k, cin).permute(0, 3, 1, 2).contiguous()
+        first = o["in"][0] == gr.image_buf
+        stem = first and fp32_stem
         if stem:
             xin = images.detach().double().cpu()
         else:
+            if first:                                        # the NHWC-8 fp16 copy of the caller's fp32 images (image_to_nhwc8_kernel)
+                img = eng.read_buffer(gr.image_buf, B).cpu()
+                assert tuple(img.shape) == (B, o["ih"], o["iw"], 8), img.shape
+                assert torch.equal(img[..., :3], images.detach().cpu().float().half().permute(0, 2, 3, 1)), tag + ": image copy"
+                assert torch.equal(img[..., 3:], torch.zeros_like(img[..., 3:])), tag + ": image copy, padding channels"
+                n2["image"] += 1
             xin, w = nchw(act(o["in"])[..., :cin]), w.float().half().double()
         y = nhwc(F.conv2d(xin, w, None, o["stride"], o["pad"], o["dil"]))
+        assert tuple(y.shape) == (B, o["oh"], o["ow"], C), (tag, y.shape)
         del xin
         if o["act"] == L.ACT_BIAS:
             a0 = o["out"][3]
             got = pred[:, a0:a0 + o["oh"] * o["ow"], o["out"][1]:o["out"][1] + C].reshape(B, o["oh"], o["ow"], C)
-            _localised(tag + " pred rows", got, y + P[cs.bias_off:cs.bias_off + C], 1e-5, 0.0, worst, "fp32 head output")
+            _localised(tag + " pred rows", got, y + P[cs["bias_off"]:cs["bias_off"] + C], 1e-5, 0.0, worst, "fp32 head output")
             n["bias"] += 1
             continue
-        assert o["act"] == L.ACT_BN_SILU, (tag, o["act"])
-        raw = bool(o.get("flags", 0) & L.OPF_RAW_F16)
+        if o["act"] in (L.ACT_BIAS_RELU, L.ACT_BIAS_LINEAR):
+            assert "res" not in o, tag
+            want = y + P[cs["bias_off"]:cs["bias_off"] + C]
+            if o["act"] == L.ACT_BIAS_RELU:
+                want = want.clamp_min(0)
+            _localised(tag + " output", act(o["out"]), want, 5e-4, 0.0, worst, "output of bias (+ ReLU) convs")
+            n["bias16"] += 1
+            continue
+        assert o["act"] in (L.ACT_BN_SILU, L.ACT_BN_RELU, L.ACT_BN_LINEAR), (tag, o["act"])
+        raw = bool(flags & L.OPF_RAW_F16)
         cnt = y.numel() // C
         mean, var = y.reshape(-1, C).mean(0), y.reshape(-1, C).var(0, unbiased=False)
-        for what, off, want in (("running_mean", cs.rmean_off, (1 - BN_MOMENTUM) * S0[cs.rmean_off:cs.rmean_off + C] + BN_MOMENTUM * mean),
-                                ("running_var", cs.rvar_off, (1 - BN_MOMENTUM) * S0[cs.rvar_off:cs.rvar_off + C] + BN_MOMENTUM * var * cnt / (cnt - 1))):
+        cbias = P[cs["bias_off"]:cs["bias_off"] + C] if flags & L.OPF_CONV_BIAS else 0.0     # bn(conv + b): b moves the batch mean only
+        for what, off, want in (("running_mean", cs["rmean_off"], (1 - BN_MOMENTUM) * S0[cs["rmean_off"]:cs["rmean_off"] + C] + BN_MOMENTUM * (mean + cbias)),
+                                ("running_var", cs["rvar_off"], (1 - BN_MOMENTUM) * S0[cs["rvar_off"]:cs["rvar_off"] + C] + BN_MOMENTUM * var * cnt / (cnt - 1))):
             e = rel(S1[off:off + C], want)
             _note(worst, what, e, 1e-5, tag)
             assert e < 1e-5, (tag, what, e)
-        n["stats"] += 1
+        n2["stats"] += 1
         if raw:
             y = y.float().half().double()                    # the one documented rounding point of a RAW_F16 layer
         xh = (y - mean) * (var + BN_EPS).rsqrt()
         del y
-        if not stem:
-            got_xh = eng.read_layer(i, B, "xhat32" if raw else "xhat").double().cpu().reshape(xh.shape)
-            _localised(tag + (" xhat32" if raw else " xhat"), got_xh, xh, 5e-4, 0.0, worst, "xhat32 of RAW_F16 layers" if raw else "xhat")
-            del got_xh
-            n["xhat"] += 1
-        z = xh * P[cs.gamma_off:cs.gamma_off + C] + P[cs.beta_off:cs.beta_off + C]
-        if "res" in o and (o.get("flags", 0) & L.OPF_RES_PRE_ACT):
+        z = xh * P[cs["gamma_off"]:cs["gamma_off"] + C] + P[cs["beta_off"]:cs["beta_off"] + C]
+        pre = bool(flags & L.OPF_RES_PRE_ACT)
+        if "res" in o and pre:
             z = z + act(o["res"])
-        want = z * torch.sigmoid(z)
-        if "res" in o and not (o.get("flags", 0) & L.OPF_RES_PRE_ACT):
+        want = z * torch.sigmoid(z) if o["act"] == L.ACT_BN_SILU else z.clamp_min(0) if o["act"] == L.ACT_BN_RELU else z
+        if "res" in o and not pre:
             want = want + act(o["res"])
-        _localised(tag + " output", act(o["out"]), want, 1e-3 if raw else 5e-4, 0.0, worst, "output of RAW_F16 layers" if raw else "output")
-        del xh, z, want
+        got = act(o["out"])
+        if not stem:
+            if o["act"] == L.ACT_BN_RELU and not raw:        # the ReLU mask in the lowest mantissa bit of the kept xhat: see the docstring
+                got16 = eng.read_layer(i, B, "xhat").cpu().reshape(xh.shape)
+                assert torch.equal((got16.view(torch.int16) & 1) == 1, got > 0), tag + ": ReLU mask bit of the kept xhat"
+                bits = (xh.float().half().view(torch.int16) & -2) | (want.float().half() > 0).to(torch.int16)
+                _localised(tag + " xhat", got16.double(), bits.view(torch.float16).double(), 5e-4, 0.0, worst, "xhat of ReLU layers (mask bit mirrored)")
+                del got16, bits
+            else:
+                got_xh = eng.read_layer(i, B, "xhat32" if raw else "xhat").double().cpu().reshape(xh.shape)
+                _localised(tag + (" xhat32" if raw else " xhat"), got_xh, xh, 5e-4, 0.0, worst, "xhat32 of RAW_F16 layers" if raw else "xhat")
+                del got_xh
+            n2["xhat"] += 1
+        _localised(tag + " output", got, want, 1e-3 if raw else 5e-4, 0.0, worst, "output of RAW_F16 layers" if raw else "output")
+        del xh, z, want, got
         n["conv"] += 1
+    if ops is None:                                          # coverage is a condition: every op is compared or named as unobservable
+        assert sum(n.values()) == len(gr.ops), (n, len(gr.ops))
     _print_worst(title, worst)
-    print(f"[per-layer] {title}: compared {n['conv']} Conv+BN+SiLU outputs ({n['xhat']} with xhat, {n['stats']} running statistics), "
-          f"{n['bias']} bias convs in pred, {n['exact']} pool / upsample outputs bit for bit")
+    print(f"[per-layer] {title}: compared {n['conv']} Conv+BN+activation outputs ({n2['xhat']} with xhat, {n2['stats']} running statistics), "
+          f"{n['bias16']} bias (+ ReLU) convs, {n['bias']} bias convs in pred, {n['exact']} pool / upsample / copy outputs bit for bit, "
+          f"{n['other']} average pool / resize / L2Normalize / transposed conv outputs, {n['dropout']} dropout, {n2['image']} image copies; "
+          f"{n['unobservable']} unobservable ({', '.join(sorted(lost)) or '-'})")
+    n.update(n2)
     return n
 
 
@@ -2768,7 +2888,7 @@ def test_yolov8_per_layer_forward_on_the_engines_own_operands(dev, scale, B, H, 
     layer -- the whole-network fixtures see a layer's border rows or its last ragged channel block only after up to 54 BatchNorms have
     renormalised them."""
     m, x, pred, _, stats_before = _yolov8_engine_step(dev, scale, B, H, W)
-    n = _check_forward_per_layer(m, x, B, pred, stats_before, ops=ops, title=f"yolov8-{scale} {B}x{H}x{W} forward")
+    n = _check_forward_per_layer(m, x, B, pred, stats_before, ops=ops, title=f"yolov8-{scale} {B}x{H}x{W} forward", fp32_stem=True)
     assert n["conv"] >= n_bn and n["stats"] >= n_bn and n["xhat"] >= n_bn - 1 and n["bias"] >= n_bias and n["exact"] >= n_exact, n
 
 
@@ -2786,6 +2906,34 @@ def test_deeplab_per_layer_backward_on_the_engines_own_operands(dev, gold):
     loss.backward()
     torch.cuda.synchronize()
     _check_backward_per_layer(m, x.shape[0], m.last_dpred, 100, 100)
+
+
+def test_deeplab_per_layer_forward_on_the_engines_own_operands(dev, gold):
+    """_check_forward_per_layer on the training forward of the DeepLabv3+ step of the backward twin (2 x 97 x 129, dropout active): all 118
+    ops.  112 Conv + BN (+ ReLU) blocks with xhat and running statistics (eps 1e-5, momentum 0.1, unbiased variance -- at the 7 x 9
+    stride-16 maps with B = 2 the biased one is 0.8 % off): the 7x7 stride-2 stem on the NHWC-8 image copy, the 33 Bottleneck outputs with
+    the identity inside the ReLU, the four activation-free downsample projections (two of them 1x1 stride 2), the dilated 3x3 of layer4
+    and of ASPP (rates 6 / 12 / 18 on a 7 x 9 map), the 1x1 conv on ASPPPooling's 1 x 1 map (two values per channel); the classifier's
+    biased 1x1 in the fp32 rows (nc_pad = 24 columns); the 3x3 stride-2 max pool bit for bit; global average pool, the 1x1 -> 7x9 and the
+    7x9 -> 25x33 bilinear resizes; dropout; the image copy.  No op of this graph is unobservable (nothing runs in place, no slice is
+    rewritten).
+    Largest values on the MI355X: outputs 2.13e-4, xhat 2.09e-4 (ReLU layers, mask bit mirrored: 2.15e-4), resize 1.99e-4, average pool
+    1.85e-4 (bounds 5e-4); fp32 rows 1.06e-7, running_mean 2.13e-7, running_var 4.04e-8 (bounds 1e-5).  1.3 s, the backward twin 2.0 s.
+    Scratch builds with one numerical change each (nothing of them is in the tree): the biased variance in the running-variance update
+    fails this test at op backbone.layer1.0.conv1 (running_var 5.09e-5 = momentum / 1650 values per channel) with every other DeepLab
+    test green; the Bottleneck residual added after the ReLU fails it at backbone.layer1.0.conv3 (output 0.97) and the bilinear source
+    coordinate without its half-pixel offset at classifier.aspp.up (output 0.48) -- those two also move the fixture step
+    (test_deeplab_training_step_matches_the_reference_fixture: loss off by 5.4e-3 resp. 2.5e-3 relative against its 2e-4)."""
+    g = gold("deeplab_train_97x129.npz")
+    m = _deeplab_train_model(dev, g, dropout_p=0.1)
+    m.seed = 5
+    x = torch.from_numpy(g["x"])
+    stats_before = m.flat_stats.clone()
+    m(x.to(dev))
+    torch.cuda.synchronize()
+    n = _check_forward_per_layer(m, x, x.shape[0], m.last_rows, stats_before, title="deeplab 2x97x129 forward", unobservable=())
+    assert len(m._last_engine.graph.ops) == 118
+    assert n == dict(conv=112, xhat=112, stats=112, bias16=0, bias=1, exact=1, other=3, dropout=1, image=1, unobservable=0), n
 
 
 def test_deeplab_step_with_gradient_exchange_and_loss_scaling(dev, gold):
@@ -2878,13 +3026,14 @@ def _yolov7_train_step(dev, g):
     m = Yolo7L(20)
     sd0 = {k: v.clone() for k, v in m.state_dict().items()}
     m = m.to(dev).train()
+    stats_before = m.flat_stats.clone()
     x = torch.from_numpy(g["x"])
     outs = m(x.to(dev))
     weights = Y7.projection_weights([o.shape for o in outs], int(g["proj_seed"]))
     loss = Y7.projection_loss(outs, [w.to(dev) for w in weights])
     loss.backward()
     torch.cuda.synchronize()
-    return m, sd0, x, outs, weights
+    return m, sd0, x, outs, weights, stats_before
 
 
 def test_yolov7_training_forward_backward_matches_the_reference_fixture(dev, gold):
@@ -2896,7 +3045,7 @@ def test_yolov7_training_forward_backward_matches_the_reference_fixture(dev, gol
     itself: test_yolov7_per_layer_backward_on_the_engines_own_operands."""
     from oracle import yolov7_ref as Y7
     g = gold("yolov7_train_160x224.npz")
-    m, sd0, x, outs, weights = _yolov7_train_step(dev, g)
+    m, sd0, x, outs, weights, _ = _yolov7_train_step(dev, g)
     _, ref_grads, ref_outs = Y7.loss_and_grads({k: v.clone() for k, v in sd0.items()}, x, weights)
     Y7.FP16_STORAGE[0] = True
     try:
@@ -2930,9 +3079,27 @@ def test_yolov7_per_layer_backward_on_the_engines_own_operands(dev, gold):
     with that buffer inside the SiLU: the residual branch takes dz), the three biased heads on their slices of the prediction rows,
     2x2 and 5x5 max pools, nearest upsampling, the concat buffers' accumulated gradients."""
     g = gold("yolov7_train_160x224.npz")
-    m, _, x, _, _ = _yolov7_train_step(dev, g)
+    m, _, x, _, _, _ = _yolov7_train_step(dev, g)
     n_w, n_bn, checked = _check_backward_per_layer(m, x.shape[0], m.last_dpred, 90, 50)
     assert n_w >= 95 and n_bn >= 92
+
+
+def test_yolov7_per_layer_forward_on_the_engines_own_operands(dev, gold):
+    """_check_forward_per_layer on the training forward of the YOLOv7 step (2 x 160 x 224): all 105 ops.  92 Conv + BN blocks with xhat
+    and running statistics (eps 1e-3, momentum 0.03): 86 plain SiLU blocks (3x3 and 1x1, seven of stride 2, 5 x 7 maps at stride 32), the
+    RepConv pairs (3x3 + BN without activation into a buffer, 1x1 + BN with that buffer inside the SiLU); the three biased heads on their
+    row ranges of the fp32 prediction rows; five 2x2 and three chained 5x5 max pools and the two nearest upsamplings bit for bit; the
+    image copy.  No op of this graph is unobservable.
+    Largest values on the MI355X: outputs 2.17e-4, xhat 2.13e-4 (bounds 5e-4); fp32 rows 2.08e-7, running_mean 1.67e-7, running_var
+    1.95e-8 (bounds 1e-5).  0.8 s, the backward twin 1.9 s.
+    Scratch builds: the biased running variance fails this test at op backbone.dark4.0.cv3.conv (running_var 3.09e-5) with the fixture
+    and the backward twin green; the last column tap of the first-layer kernel (conv_stem7.hip, which runs backbone.stem.0.conv) zeroed
+    fails it at that op (running_mean 0.91) -- the fixture sees that one too (outputs off by 1.24 against a yardstick of 0.074)."""
+    g = gold("yolov7_train_160x224.npz")
+    m, _, x, _, _, stats_before = _yolov7_train_step(dev, g)
+    n = _check_forward_per_layer(m, x, x.shape[0], m.last_rows, stats_before, title="yolov7 2x160x224 forward", unobservable=())
+    assert len(m._last_engine.graph.ops) == 105
+    assert n == dict(conv=92, xhat=92, stats=92, bias16=0, bias=3, exact=10, other=0, dropout=0, image=1, unobservable=0), n
 
 
 def test_yolov7_training_through_the_plugin_api(dev):
@@ -2970,13 +3137,14 @@ def _centernet_train_step(dev, g):
     m = CenterNetDLA34(nc)
     sd0 = {k: v.clone() for k, v in m.state_dict().items()}
     m = m.to(dev).train()
+    stats_before = m.flat_stats.clone()
     x = torch.from_numpy(g["x"])
     out = m(x.to(dev))
     weights = C.projection_weights(out.shape, int(g["proj_seed"]))
     loss = C.projection_loss(out, weights.to(dev))
     loss.backward()
     torch.cuda.synchronize()
-    return m, sd0, x, out, weights, nc
+    return m, sd0, x, out, weights, nc, stats_before
 
 
 def test_centernet_training_forward_backward_matches_the_reference_fixture(dev, gold):
@@ -2985,7 +3153,7 @@ def test_centernet_training_forward_backward_matches_the_reference_fixture(dev, 
     weights.  Yardstick as for DeepLab (ReLU network: mask flips under fp16 rounding): the oracle's fp16-operand emulation, run here."""
     from oracle import centernet_ref as C
     g = gold("centernet_train_128x160.npz")
-    m, sd0, x, out, weights, nc = _centernet_train_step(dev, g)
+    m, sd0, x, out, weights, nc, _ = _centernet_train_step(dev, g)
     _, ref_grads, ref_out = C.loss_and_grads({k: v.clone() for k, v in sd0.items()}, x, nc, weights)
     C.FP16_STORAGE[0] = True
     try:
@@ -3017,9 +3185,31 @@ def test_centernet_per_layer_backward_on_the_engines_own_operands(dev, gold):
     the Tree projections (BN without activation), 2x2 max pools, the concat copies, the depthwise transposed convolutions (data
     gradient, and their fp32 weight gradient 1e-5), the fused biased 3x3 head (dy = g * [out > 0] exactly) and the three 1x1 heads."""
     g = gold("centernet_train_128x160.npz")
-    m, _, x, _, _, _ = _centernet_train_step(dev, g)
+    m, _, x, _, _, _, _ = _centernet_train_step(dev, g)
     n_w, n_bn, checked = _check_backward_per_layer(m, x.shape[0], m.last_dpred, 49, 40)
     assert n_w >= 53
+
+
+def test_centernet_per_layer_forward_on_the_engines_own_operands(dev, gold):
+    """_check_forward_per_layer on the training forward of the CenterNet step (2 x 128 x 160): all 75 ops.  49 Conv + BN blocks with xhat
+    and running statistics (eps 1e-5, momentum 0.1): the 7x7 stride-1 stem on the NHWC-8 image copy, 33 ReLU blocks, the 12 BasicBlock
+    outputs with the residual inside the ReLU, the four activation-free Tree projections; the fused biased 3x3 head with ReLU (768
+    channels, fp16); the three 1x1 heads in their column ranges of the fp32 head tensor; six 2x2 max pools and ten concat copies bit for
+    bit; the six depthwise transposed convolutions of IDA-up (f = 2, 4, 8; fp32 master weights); the image copy.  No op of this graph is
+    unobservable (a BasicBlock reads one slice of the Root's concat buffer and writes another).
+    Largest values on the MI355X: outputs 2.13e-4, the fused head 2.07e-4, xhat 2.09e-4 (ReLU layers, mask bit mirrored: 4.26e-5),
+    transposed convolutions 2.11e-4 (bounds 5e-4); fp32 head tensor 1.05e-7, running_mean 1.22e-7, running_var 2.13e-8 (bounds 1e-5).
+    0.4 s, the backward twin 0.8 s.
+    Scratch builds: the biased running variance fails this test at op backbone.base.level_2.root.conv (running_var 1.20e-5) with the
+    fixture and the backward twin green; the BasicBlock residual added after the ReLU fails it at backbone.base.level_2.tree1.conv2
+    (output 0.66), the last column tap of the 7x7 first-layer kernel (conv_stem7.hip) zeroed at backbone.base.base_layer.0
+    (running_mean 0.41) -- the fixture sees those two as well (output off by 0.85 resp. 0.90 against a yardstick of 0.0097), the
+    backward twin, which takes the forward tensors as given, neither."""
+    g = gold("centernet_train_128x160.npz")
+    m, _, x, _, _, _, stats_before = _centernet_train_step(dev, g)
+    n = _check_forward_per_layer(m, x, x.shape[0], m.last_raw, stats_before, title="centernet 2x128x160 forward", unobservable=())
+    assert len(m._last_engine.graph.ops) == 75
+    assert n == dict(conv=49, xhat=49, stats=49, bias16=1, bias=3, exact=16, other=6, dropout=0, image=1, unobservable=0), n
 
 
 def test_centernet_training_through_the_plugin_api(dev):
@@ -3056,13 +3246,14 @@ def _ssd_train_step(dev, g):
     m = SSD300VGG(nc)
     sd0 = {k: v.clone() for k, v in m.state_dict().items()}
     m = m.to(dev).train()
+    stats_before = m.flat_stats.clone()
     x = torch.from_numpy(g["x"].astype(np.float32) / 255.0)
     outs = m(x.to(dev))
     weights = S.projection_weights([o.shape for o in outs], int(g["proj_seed"]))
     loss = S.projection_loss(outs, [w.to(dev) for w in weights])
     loss.backward()
     torch.cuda.synchronize()
-    return m, sd0, x, outs, weights, nc
+    return m, sd0, x, outs, weights, nc, stats_before
 
 
 def test_ssd_training_forward_backward_matches_the_reference_fixture(dev, gold):
@@ -3072,7 +3263,7 @@ def test_ssd_training_forward_backward_matches_the_reference_fixture(dev, gold):
     (exactly here, round-off in torch).  Yardstick: the oracle's fp16-operand emulation, run here."""
     from oracle import ssd_ref as S
     g = gold("ssd_train_300.npz")
-    m, sd0, x, outs, weights, nc = _ssd_train_step(dev, g)
+    m, sd0, x, outs, weights, nc, _ = _ssd_train_step(dev, g)
     _, ref_grads, ref_outs = S.loss_and_grads({k: v.clone() for k, v in sd0.items()}, x, nc, weights)
     S.FP16_STORAGE[0] = True
     try:
@@ -3113,9 +3304,27 @@ def test_ssd_per_layer_backward_on_the_engines_own_operands(dev, gold):
     activation-free extra layers, the twelve 3x3 heads on their column ranges of the prediction rows, 2x2 (one ceil-mode) and 3x3
     stride-1 max pools, L2Normalize (data gradient and its weight gradient)."""
     g = gold("ssd_train_300.npz")
-    m, _, x, _, _, _ = _ssd_train_step(dev, g)
+    m, _, x, _, _, _, _ = _ssd_train_step(dev, g)
     n_w, n_bn, checked = _check_backward_per_layer(m, x.shape[0], m.last_dpred, 13, 25)
     assert n_w >= 35
+
+
+def test_ssd_per_layer_forward_on_the_engines_own_operands(dev, gold):
+    """_check_forward_per_layer on the training forward of the SSD step (2 x 300 x 300): all 41 ops.  The 13 Conv(bias) + BN + ReLU blocks of
+    VGG16 with xhat and running statistics (eps 1e-5, momentum 0.1; the convolution's bias enters the running mean and nothing else);
+    conv6 (3x3, dilation 6) and conv7 with bias + ReLU and the eight activation-free biased extra layers (3x3 stride 2, 3x3 without
+    padding down to a 1 x 1 map) in fp16; the twelve 3x3 heads on their row and column ranges of the fp32 prediction rows (16 / 24 loc
+    columns, 88 / 128 conf columns); four 2x2 max pools (one in ceil mode: 75 -> 38) and the 3x3 stride-1 pool bit for bit; L2Normalize
+    with its fp32 weight; the image copy.  No op of this graph is unobservable.
+    Largest values on the MI355X: BN outputs 2.10e-4, bias (+ ReLU) outputs 2.09e-4, xhat (mask bit mirrored) 3.15e-5, L2Normalize
+    2.08e-4 (bounds 5e-4); fp32 rows 6.97e-7, running_mean 4.39e-8, running_var 2.01e-8 (bounds 1e-5).  2.4 s, the backward twin 6.9 s.
+    Scratch build: the biased running variance fails this test at op backbone.layers.34 (running_var 2.54e-5) with the fixture and the
+    backward twin green."""
+    g = gold("ssd_train_300.npz")
+    m, _, x, _, _, _, stats_before = _ssd_train_step(dev, g)
+    n = _check_forward_per_layer(m, x, x.shape[0], m.last_rows, stats_before, title="ssd 2x300x300 forward", unobservable=())
+    assert len(m._last_engine.graph.ops) == 41
+    assert n == dict(conv=13, xhat=13, stats=13, bias16=10, bias=12, exact=5, other=1, dropout=0, image=1, unobservable=0), n
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
