@@ -114,6 +114,8 @@ PROTOTYPES = {
     "cvx_bn_silu_bwd_nhwc": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _I32, _P]),
     "cvx_letterbox_geometry": (_I32, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_letterbox_u8_to_nchw": (_I32, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "cvx_aug_images": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _P]),
+    "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_engine_set_seed": (_I32, [_P, _U64]),
     "cvx_engine_keep_shadows": (_I32, [_P]),
     "cvx_engine_set_fusion": (_I32, [_P, _I32]),

@@ -1,0 +1,292 @@
+// Training-side input path of the two YOLO trainers on gfx950: the reference's per-image CPU augmentation
+// (core/data/detection_dataset.py:132-220 get_random_data, :222-345 mosaic_body / mosaic_for_voc, :405-449 merge_bboxes, :100-130 label
+// normalisation, core/data/collate.py:5-29) as two launches per batch.  The random draws stay on the host (augment.draw_params); what
+// arrives here is a table of jobs, one per source picture:
+//
+//   plain output  : 1 job,  canvas of 128, resized picture pasted at (dx, dy) with cv2_paste's clipping (image_process.py:132-158),
+//                   flip mirrors the CANVAS (:188-191), rect = the whole output;
+//   mosaic output : 4 jobs, each its own 128-canvas with a paste; flip mirrors the SOURCE before the resize (:227-231); the job's rect is
+//                   its quadrant of the output (:321-328; quad 0 top-left, 1 bottom-left, 2 bottom-right, 3 top-right).
+//
+// cvx_aug_images, per output pixel: bicubic tap (OpenCV's INTER_CUBIC in its uint8 fixed-point form, restated in tests/aug_restatement.py)
+// -> RGB2HSV (8-bit integer form) -> three LUT look-ups -> HSV2RGB (float form) -> to_tensor.  cvx_aug_boxes: box scaling, flip, clamps,
+// the w > 1 && h > 1 filter, merge_bboxes, normalisation to [image, cls, cx, cy, w, h], compacted in source order by a scan.
+//
+// Every fp32 step below is one rounded operation in the order written, so the whole file is compiled with contraction off; the host
+// restatement (numpy fp32) then agrees to the byte.
+#include "cvx_common.h"
+#include "../../include/cvx_engine.h"
+#include <limits.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int TW = 64, TH = 16, MAXJ = 4;   // tile of one workgroup: 4 waves, wave w takes rows w, w + 4, w + 8, w + 12 (64 px = 256 B per plane store)
+constexpr int OUTSIDE = INT_MIN;            // tap marker: this canvas row / column lies outside the pasted picture
+
+// One destination coordinate r of a resize n_src -> n_dst: first tap and the four Keys weights (A = -0.75) in Q11.
+__device__ __forceinline__ void cubic_tap(int r, int n_dst, int n_src, int* s, short* w) {
+  const float f = (float)(((double)r + 0.5) * (double)n_src / (double)n_dst - 0.5);
+  const float fl = floorf(f);
+  const float t = f - fl;
+  const float A = -0.75f;
+  const float t1 = t + 1.0f, u = 1.0f - t;
+  const float c0 = ((A * t1 - 5.0f * A) * t1 + 8.0f * A) * t1 - 4.0f * A;
+  const float c1 = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+  const float c2 = ((A + 2.0f) * u - (A + 3.0f)) * u * u + 1.0f;
+  const float c3 = 1.0f - c0 - c1 - c2;
+  *s = (int)fl - 1;
+  w[0] = (short)rintf(c0 * 2048.0f);
+  w[1] = (short)rintf(c1 * 2048.0f);
+  w[2] = (short)rintf(c2 * 2048.0f);
+  w[3] = (short)rintf(c3 * 2048.0f);
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ int sat_u8(float v) {   // saturate_cast<uchar>(float): round half to even, then clamp
+  const float r = rintf(v);
+  return r < 0.0f ? 0 : (r > 255.0f ? 255 : (int)r);
+}
+
+// cv2.cvtColor(RGB2HSV) on bytes -> LUTs -> cv2.cvtColor(HSV2RGB) on bytes (detection_dataset.py:195-205)
+__device__ __forceinline__ void colour(int& r, int& g, int& b, const int* sdiv, const int* hdiv, const uint8_t* lut) {
+  const int v = max(r, max(g, b)), mn = min(r, min(g, b));
+  const int diff = v - mn;
+  const int s = (diff * sdiv[v] + 2048) >> 12;
+  int num;
+  if (v == r) num = g - b;
+  else if (v == g) num = b - r + 2 * diff;
+  else num = r - g + 4 * diff;
+  int h = (num * hdiv[diff] + 2048) >> 12;
+  if (h < 0) h += 180;
+  const int hb = lut[clampi(h, 0, 255)], sb = lut[256 + clampi(s, 0, 255)], vb = lut[512 + v];
+  float hf = (float)hb * (6.0f / 180.0f);
+  const float sf = (float)sb / 255.0f, vf = (float)vb / 255.0f;
+  float fr = vf, fg = vf, fb = vf;
+  if (sb != 0) {
+    while (hf >= 6.0f) hf -= 6.0f;
+    int sector = (int)floorf(hf);
+    hf -= (float)sector;
+    if ((unsigned)sector >= 6u) {
+      sector = 0;
+      hf = 0.0f;
+    }
+    const float t0 = vf, t1 = vf * (1.0f - sf), t2 = vf * (1.0f - sf * hf), t3 = vf * (1.0f - sf * (1.0f - hf));
+    switch (sector) {   // OpenCV's sector table, (b, g, r) = tab[{1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0}]
+      case 0: fb = t1; fg = t3; fr = t0; break;
+      case 1: fb = t1; fg = t0; fr = t2; break;
+      case 2: fb = t3; fg = t0; fr = t1; break;
+      case 3: fb = t0; fg = t2; fr = t1; break;
+      case 4: fb = t0; fg = t1; fr = t3; break;
+      default: fb = t2; fg = t1; fr = t0; break;
+    }
+  }
+  r = sat_u8(fr * 255.0f);
+  g = sat_u8(fg * 255.0f);
+  b = sat_u8(fb * 255.0f);
+}
+
+__global__ __launch_bounds__(256) void aug_images_kernel(const cvx_aug_job* __restrict__ jobs, const int32_t* __restrict__ job_start,
+                                                         const uint8_t* __restrict__ luts, float* __restrict__ out, int H, int W) {
+  __shared__ cvx_aug_job sjob[MAXJ];
+  __shared__ int col_s[MAXJ][TW], row_s[MAXJ][TH];
+  __shared__ short col_w[MAXJ][TW][4], row_w[MAXJ][TH][4];
+  __shared__ int sdiv[256], hdiv[256];
+  __shared__ uint8_t lut[768];
+  const int tid = threadIdx.x, img = blockIdx.z;
+  const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
+  const int j0 = job_start[img];
+  const int nj = min(job_start[img + 1] - j0, MAXJ);
+  if (tid < nj) sjob[tid] = jobs[j0 + tid];
+  // OpenCV's division tables: rint((255 << 12) / i) and rint((180 << 12) / (6 i)); no quotient is a tie for i < 256, so the rounded
+  // integer division is the same number
+  sdiv[tid] = tid ? (2 * (255 << 12) + tid) / (2 * tid) : 0;
+  hdiv[tid] = tid ? (2 * (180 << 12) + 6 * tid) / (12 * tid) : 0;
+  for (int i = tid; i < 768; i += 256) lut[i] = luts[(size_t)img * 768 + i];
+  __syncthreads();
+  for (int e = tid; e < nj * (TW + TH); e += 256) {
+    const int s = e / (TW + TH), k = e - s * (TW + TH);
+    const cvx_aug_job& jb = sjob[s];
+    if (k < TW) {
+      int x = tx0 + k;
+      if (jb.quad < 0 && jb.flip) x = W - 1 - x;          // the canvas is mirrored after the paste
+      const int rx = x - jb.dx;
+      if (rx < 0 || rx >= jb.nw || x < 0) col_s[s][k] = OUTSIDE;
+      else cubic_tap(rx, jb.nw, jb.iw, &col_s[s][k], col_w[s][k]);
+    } else {
+      const int ry = ty0 + (k - TW) - jb.dy;
+      if (ry < 0 || ry >= jb.nh) row_s[s][k - TW] = OUTSIDE;
+      else cubic_tap(ry, jb.nh, jb.ih, &row_s[s][k - TW], row_w[s][k - TW]);
+    }
+  }
+  __syncthreads();
+  const int lx = tid & 63, x = tx0 + lx;
+  if (x >= W) return;
+  const size_t plane = (size_t)H * W;
+  for (int ly = tid >> 6; ly < TH; ly += 4) {
+    const int y = ty0 + ly;
+    if (y >= H) break;
+    int s = -1;
+    for (int q = 0; q < nj; ++q)
+      if (x >= sjob[q].x0 && x < sjob[q].x1 && y >= sjob[q].y0 && y < sjob[q].y1) s = q;
+    int r = 128, g = 128, b = 128;
+    if (s >= 0 && col_s[s][lx] != OUTSIDE && row_s[s][ly] != OUTSIDE) {
+      const cvx_aug_job& jb = sjob[s];
+      const int iw = jb.iw, ih = jb.ih, cs = col_s[s][lx], rs = row_s[s][ly];
+      const bool mirror = jb.quad >= 0 && jb.flip;           // mosaic: the source is mirrored before the resize
+      int off[4], wx[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = clampi(cs + k, 0, iw - 1);
+        off[k] = 3 * (mirror ? iw - 1 - c : c);
+        wx[k] = col_w[s][lx][k];
+      }
+      int ar = 0, ag = 0, ab = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint8_t* p = jb.src + (size_t)clampi(rs + j, 0, ih - 1) * iw * 3;
+        int hr = 0, hg = 0, hb = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          hr += wx[k] * p[off[k]];
+          hg += wx[k] * p[off[k] + 1];
+          hb += wx[k] * p[off[k] + 2];
+        }
+        const int wy = row_w[s][ly][j];
+        ar += wy * hr;
+        ag += wy * hg;
+        ab += wy * hb;
+      }
+      r = clampi((ar + (1 << 21)) >> 22, 0, 255);
+      g = clampi((ag + (1 << 21)) >> 22, 0, 255);
+      b = clampi((ab + (1 << 21)) >> 22, 0, 255);
+    }
+    colour(r, g, b, sdiv, hdiv, lut);
+    float* o = out + (size_t)img * 3 * plane + (size_t)y * W + x;
+    o[0] = (float)r / 255.0f;
+    o[plane] = (float)g / 255.0f;
+    o[2 * plane] = (float)b / 255.0f;
+  }
+}
+
+// One workgroup walks all boxes in chunks of 256; kept boxes take consecutive output rows in source order (ballot scan per wave, wave
+// totals through LDS) -- no atomics, so the order and the result never depend on timing.
+__global__ __launch_bounds__(256) void aug_boxes_kernel(const cvx_aug_job* __restrict__ jobs, const int32_t* __restrict__ job_box_start, int n_jobs,
+                                                        const float* __restrict__ boxes, int n_boxes, int H, int W, float* __restrict__ targets,
+                                                        int32_t* __restrict__ count) {
+  __shared__ int wave_tot[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float fW = (float)W, fH = (float)H;
+  int base = 0;
+  for (int c0 = 0; c0 < n_boxes; c0 += 256) {
+    const int i = c0 + tid;
+    bool keep = false;
+    float o0 = 0, o1 = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0;
+    if (i < n_boxes) {
+      int lo = 0, hi = n_jobs - 1;                          // the last job whose first box is <= i (jobs without boxes are skipped over)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (job_box_start[mid] <= i) lo = mid;
+        else hi = mid - 1;
+      }
+      const cvx_aug_job jb = jobs[lo];
+      const float* bx = boxes + (size_t)i * 5;
+      float x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
+      const float fiw = (float)jb.iw, fih = (float)jb.ih, fnw = (float)jb.nw, fnh = (float)jb.nh, fdx = (float)jb.dx, fdy = (float)jb.dy;
+      if (jb.quad >= 0 && jb.flip) {                        // mosaic_body :231, with iw = columns
+        const float a = fiw - x2, c = fiw - x1;
+        x1 = a;
+        x2 = c;
+      }
+      x1 = x1 * fnw / fiw + fdx;
+      x2 = x2 * fnw / fiw + fdx;
+      y1 = y1 * fnh / fih + fdy;
+      y2 = y2 * fnh / fih + fdy;
+      if (jb.quad < 0 && jb.flip) {                         // get_random_data :212
+        const float a = fW - x2, c = fW - x1;
+        x1 = a;
+        x2 = c;
+      }
+      if (x1 < 0.0f) x1 = 0.0f;
+      if (y1 < 0.0f) y1 = 0.0f;
+      if (x2 > fW) x2 = fW;
+      if (y2 > fH) y2 = fH;
+      keep = (x2 - x1 > 1.0f) && (y2 - y1 > 1.0f);
+      if (keep && jb.quad >= 0) {                           // merge_bboxes :405-449
+        const int q = jb.quad;
+        const float cutx = (float)(q <= 1 ? jb.x1 : jb.x0), cuty = (float)((q == 0 || q == 3) ? jb.y1 : jb.y0);
+        const bool sy = y2 >= cuty && y1 <= cuty, sx = x2 >= cutx && x1 <= cutx;
+        if (q == 0) {
+          if (y1 > cuty || x1 > cutx) keep = false;
+          if (sy) y2 = cuty;
+          if (sx) x2 = cutx;
+        } else if (q == 1) {
+          if (y2 < cuty || x1 > cutx) keep = false;
+          if (sy) y1 = cuty;
+          if (sx) x2 = cutx;
+        } else if (q == 2) {
+          if (y2 < cuty || x2 < cutx) keep = false;
+          if (sy) y1 = cuty;
+          if (sx) x1 = cutx;
+        } else {
+          if (y1 > cuty || x2 < cutx) keep = false;
+          if (sy) y2 = cuty;
+          if (sx) x1 = cutx;
+        }
+      }
+      x1 = x1 / fW;                                         // detection_dataset.py:110-119
+      x2 = x2 / fW;
+      y1 = y1 / fH;
+      y2 = y2 / fH;
+      const float bw = x2 - x1, bh = y2 - y1;
+      o0 = (float)jb.out;
+      o1 = bx[4];
+      o2 = x1 + bw / 2.0f;
+      o3 = y1 + bh / 2.0f;
+      o4 = bw;
+      o5 = bh;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_tot[wave] = __popcll(m);
+    __syncthreads();
+    int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += wave_tot[w];
+    if (keep) {
+      float* t = targets + (size_t)pos * 6;
+      t[0] = o0; t[1] = o1; t[2] = o2; t[3] = o3; t[4] = o4; t[5] = o5;
+    }
+    base += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    __syncthreads();
+  }
+  for (int i = base + tid; i < n_boxes; i += 256) {         // unused rows: image -1
+    float* t = targets + (size_t)i * 6;
+    t[0] = -1.0f; t[1] = 0.0f; t[2] = 0.0f; t[3] = 0.0f; t[4] = 0.0f; t[5] = 0.0f;
+  }
+  if (tid == 0) *count = base;
+}
+
+}  // namespace
+
+extern "C" int cvx_aug_images(const cvx_aug_job* jobs, const int32_t* job_start, const uint8_t* luts, int32_t batch, float* out_nchw, int32_t H,
+                              int32_t W, void* hip_stream) {
+  static_assert(sizeof(cvx_aug_job) == 64, "cvx_aug_job is 64 bytes on both sides of the ABI");
+  CVX_CHECK(jobs && job_start && luts && out_nchw, "null pointer");
+  CVX_CHECK(batch > 0 && batch <= 65535 && H > 0 && W > 0 && (long long)H * W * 3 < (1ll << 31), "bad shape");
+  const dim3 grid(cvx_cdiv(W, TW), cvx_cdiv(H, TH), batch);
+  CVX_CHECK(grid.y <= 65535, "output too tall");
+  hipLaunchKernelGGL(aug_images_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, jobs, job_start, luts, out_nchw, H, W);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int cvx_aug_boxes(const cvx_aug_job* jobs, const int32_t* job_box_start, int32_t n_jobs, const float* boxes, int32_t n_boxes, int32_t H,
+                             int32_t W, float* targets, int32_t* count, void* hip_stream) {
+  CVX_CHECK(jobs && job_box_start && count && n_jobs > 0 && n_boxes >= 0 && H > 0 && W > 0, "bad arguments");
+  CVX_CHECK(n_boxes == 0 || (boxes && targets), "boxes without a buffer");
+  hipLaunchKernelGGL(aug_boxes_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, jobs, job_box_start, n_jobs, boxes, n_boxes, H, W, targets,
+                     count);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}

@@ -550,6 +550,38 @@ int cvx_stem_backward_recompute_nchw(const float* images, int32_t batch, int32_t
                                      const float* gamma, const float* beta, const float* mean, const float* invstd, float inv_scale,
                                      float* dgamma, float* dbeta, float* dw, void* hip_stream);
 
+/* ---- device-side detection training augmentation (csrc/augment.hip) ------------------------------------------------------------------
+ * One job per source picture: 1 per plain output, 4 per mosaic output (quad 0 top-left, 1 bottom-left, 2 bottom-right, 3 top-right;
+ * quad = -1 marks a plain job).  src: uint8 HWC (ih, iw, 3) in device memory, resized to (nh, nw) with OpenCV's INTER_CUBIC in its
+ * uint8 fixed-point form and pasted at (dx, dy) on a canvas of 128 with cv2_paste's clipping (dx / dy may be negative, the picture may
+ * overhang).  flip: plain jobs mirror the CANVAS after the paste, mosaic jobs mirror the SOURCE before the resize.  out: index of the
+ * output image; [x0, x1) x [y0, y1): the part of that output this job fills (the whole image for a plain job, its quadrant for a
+ * mosaic job).  64 bytes. */
+typedef struct cvx_aug_job {
+  const uint8_t* src;
+  int32_t ih, iw, nh, nw, dx, dy, flip, out, x0, y0, x1, y1, quad, reserved;
+} cvx_aug_job;
+/* The image half, one launch for the whole batch, asynchronous on hip_stream.  job_start: (batch + 1) int32, jobs
+ * job_start[b] .. job_start[b+1] belong to output b (1 or 4 of them); luts: (batch, 3, 256) uint8, the hue / saturation / value tables;
+ * out_nchw: (batch, 3, H, W) fp32.  Per pixel: paste + bicubic tap -> RGB2HSV (OpenCV's 8-bit integer form) -> the three LUTs -> HSV2RGB
+ * (OpenCV's float form, bytes by round-half-even) -> byte / 255.  All tables are device memory.
+ * Replaces: DetectionDataset.get_random_data's image half (core/data/detection_dataset.py:180-205), mosaic_body's (:245-268) and the
+ * composition + colour transform of mosaic_for_voc / mosaic_for_coco (:321-341), cv2_paste (core/utils/image_process.py:132-158),
+ * TF.to_tensor (detection_dataset.py:101) and the torch.stack of yolo7_collate / yolo8_collate (core/data/collate.py:12,24). */
+int cvx_aug_images(const cvx_aug_job* jobs, const int32_t* job_start, const uint8_t* luts, int32_t batch, float* out_nchw, int32_t H, int32_t W,
+                   void* hip_stream);
+/* The box half, one launch, asynchronous.  boxes: (n_boxes, 5) fp32 rows (x1, y1, x2, y2, cls) in source pixels, job after job;
+ * job_box_start: (n_jobs + 1) int32, the rows of job j are job_box_start[j] .. job_box_start[j+1].  In fp32 and the reference's operation
+ * order (no fused multiply-add): x * nw / iw + dx, the flip, the clamps to the output, keep w > 1 && h > 1, for mosaic jobs merge_bboxes
+ * against the cuts (taken from the job's rect), then / W, / H and (cx, cy, w, h).  targets: (n_boxes, 6) fp32 rows
+ * [image, cls, cx, cy, w, h]; the kept boxes in source order (a scan, not atomics) fill rows 0 .. *count, the rest get image = -1;
+ * count: 1 int32 (device).  The reference's np.random.shuffle of the boxes is not reproduced, and a mosaic source's width is its
+ * column count (the reference reads rows first, :224).
+ * Replaces: the box halves of get_random_data (:207-218) and mosaic_body (:228-231,270-287), merge_bboxes (:405-449), the label
+ * normalisation of __getitem__ (:100-130) and the image-index column + concatenation of the collate functions (collate.py:8-13,20-23). */
+int cvx_aug_boxes(const cvx_aug_job* jobs, const int32_t* job_box_start, int32_t n_jobs, const float* boxes, int32_t n_boxes, int32_t H, int32_t W,
+                  float* targets, int32_t* count, void* hip_stream);
+
 /* ---- data-parallel gradient exchange over RCCL (csrc/comm.hip), SURVEY.md section 8(b) / 8(e) --------------------------------------
  * One process per GPU.  Rank 0 calls cvx_comm_unique_id (128 bytes, ncclGetUniqueId), ships them to every rank by any means, all ranks
  * call cvx_comm_create (ncclCommInitRank; RCCL is dlopen'ed on first use).  `comm` below is the ncclComm_t.
