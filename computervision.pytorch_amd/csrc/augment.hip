@@ -12,6 +12,14 @@
 // -> RGB2HSV (8-bit integer form) -> three LUT look-ups -> HSV2RGB (float form) -> to_tensor.  cvx_aug_boxes: box scaling, flip, clamps,
 // the w > 1 && h > 1 filter, merge_bboxes, normalisation to [image, cls, cx, cy, w, h], compacted in source order by a scan.
 //
+// Validation (DetectionDataset(train=False), get_random_data(random=False), :137-166) has no colour transform, and RGB -> HSV -> RGB is
+// lossy in 8 bits even with identity tables, so the image kernel is a template on COLOUR: cvx_aug_images launches <true>,
+// cvx_aug_images_plain <false> (paste + bicubic taps -> byte / 255).  A sibling entry point and not a bit in the job's reserved word: a
+// loader never mixes training and validation pictures in one batch, and a per-job bit would put a branch, and the live range of the
+// uncoloured bytes across it, into the colour instance that every existing caller runs; the template leaves that instance as it was.
+// cvx_aug_boxes_padded is the box half for consumers that take (batch, max_boxes, 5) labels plus per-image counts (cvx_ssd_encode_targets,
+// cvx_centernet_draw_targets): one workgroup per output image, the same box_row() arithmetic and the same scan as cvx_aug_boxes.
+//
 // Every fp32 step below is one rounded operation in the order written, so the whole file is compiled with contraction off; the host
 // restatement (numpy fp32) then agrees to the byte.
 #include "cvx_common.h"
@@ -88,6 +96,7 @@ __device__ __forceinline__ void colour(int& r, int& g, int& b, const int* sdiv, 
   b = sat_u8(fb * 255.0f);
 }
 
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void aug_images_kernel(const cvx_aug_job* __restrict__ jobs, const int32_t* __restrict__ job_start,
                                                          const uint8_t* __restrict__ luts, float* __restrict__ out, int H, int W) {
   __shared__ cvx_aug_job sjob[MAXJ];
@@ -102,9 +111,11 @@ __global__ __launch_bounds__(256) void aug_images_kernel(const cvx_aug_job* __re
   if (tid < nj) sjob[tid] = jobs[j0 + tid];
   // OpenCV's division tables: rint((255 << 12) / i) and rint((180 << 12) / (6 i)); no quotient is a tie for i < 256, so the rounded
   // integer division is the same number
-  sdiv[tid] = tid ? (2 * (255 << 12) + tid) / (2 * tid) : 0;
-  hdiv[tid] = tid ? (2 * (180 << 12) + 6 * tid) / (12 * tid) : 0;
-  for (int i = tid; i < 768; i += 256) lut[i] = luts[(size_t)img * 768 + i];
+  if constexpr (COLOUR) {
+    sdiv[tid] = tid ? (2 * (255 << 12) + tid) / (2 * tid) : 0;
+    hdiv[tid] = tid ? (2 * (180 << 12) + 6 * tid) / (12 * tid) : 0;
+    for (int i = tid; i < 768; i += 256) lut[i] = luts[(size_t)img * 768 + i];
+  }
   __syncthreads();
   for (int e = tid; e < nj * (TW + TH); e += 256) {
     const int s = e / (TW + TH), k = e - s * (TW + TH);
@@ -163,12 +174,95 @@ __global__ __launch_bounds__(256) void aug_images_kernel(const cvx_aug_job* __re
       g = clampi((ag + (1 << 21)) >> 22, 0, 255);
       b = clampi((ab + (1 << 21)) >> 22, 0, 255);
     }
-    colour(r, g, b, sdiv, hdiv, lut);
+    if constexpr (COLOUR) colour(r, g, b, sdiv, hdiv, lut);
     float* o = out + (size_t)img * 3 * plane + (size_t)y * W + x;
     o[0] = (float)r / 255.0f;
     o[plane] = (float)g / 255.0f;
     o[2 * plane] = (float)b / 255.0f;
   }
+}
+
+// The last job in [lo, hi] whose first box is <= i (jobs without boxes are skipped over).
+__device__ __forceinline__ int job_of_box(const int32_t* __restrict__ job_box_start, int lo, int hi, int i) {
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (job_box_start[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// One source box (x1, y1, x2, y2, cls) of job jb -> o = [cls, cx, cy, w, h] normalised; returns whether the box is kept.  Both box kernels
+// go through here, so their rows agree to the bit.
+__device__ __forceinline__ bool box_row(const cvx_aug_job& jb, const float* __restrict__ bx, float fW, float fH, float* o) {
+  float x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
+  const float fiw = (float)jb.iw, fih = (float)jb.ih, fnw = (float)jb.nw, fnh = (float)jb.nh, fdx = (float)jb.dx, fdy = (float)jb.dy;
+  if (jb.quad >= 0 && jb.flip) {                        // mosaic_body :231, with iw = columns
+    const float a = fiw - x2, c = fiw - x1;
+    x1 = a;
+    x2 = c;
+  }
+  x1 = x1 * fnw / fiw + fdx;
+  x2 = x2 * fnw / fiw + fdx;
+  y1 = y1 * fnh / fih + fdy;
+  y2 = y2 * fnh / fih + fdy;
+  if (jb.quad < 0 && jb.flip) {                         // get_random_data :212
+    const float a = fW - x2, c = fW - x1;
+    x1 = a;
+    x2 = c;
+  }
+  if (x1 < 0.0f) x1 = 0.0f;
+  if (y1 < 0.0f) y1 = 0.0f;
+  if (x2 > fW) x2 = fW;
+  if (y2 > fH) y2 = fH;
+  bool keep = (x2 - x1 > 1.0f) && (y2 - y1 > 1.0f);
+  if (keep && jb.quad >= 0) {                           // merge_bboxes :405-449
+    const int q = jb.quad;
+    const float cutx = (float)(q <= 1 ? jb.x1 : jb.x0), cuty = (float)((q == 0 || q == 3) ? jb.y1 : jb.y0);
+    const bool sy = y2 >= cuty && y1 <= cuty, sx = x2 >= cutx && x1 <= cutx;
+    if (q == 0) {
+      if (y1 > cuty || x1 > cutx) keep = false;
+      if (sy) y2 = cuty;
+      if (sx) x2 = cutx;
+    } else if (q == 1) {
+      if (y2 < cuty || x1 > cutx) keep = false;
+      if (sy) y1 = cuty;
+      if (sx) x2 = cutx;
+    } else if (q == 2) {
+      if (y2 < cuty || x2 < cutx) keep = false;
+      if (sy) y1 = cuty;
+      if (sx) x1 = cutx;
+    } else {
+      if (y1 > cuty || x2 < cutx) keep = false;
+      if (sy) y2 = cuty;
+      if (sx) x1 = cutx;
+    }
+  }
+  x1 = x1 / fW;                                         // detection_dataset.py:110-119
+  x2 = x2 / fW;
+  y1 = y1 / fH;
+  y2 = y2 / fH;
+  const float bw = x2 - x1, bh = y2 - y1;
+  o[0] = bx[4];
+  o[1] = x1 + bw / 2.0f;
+  o[2] = y1 + bh / 2.0f;
+  o[3] = bw;
+  o[4] = bh;
+  return keep;
+}
+
+// Rank of this thread's kept box among the 256 of the chunk, in thread order: ballot + popcount inside the wave, the four wave totals
+// through LDS.  Returns the chunk's total in *total.  Ends on a barrier, so wave_tot may be written again right after.
+__device__ __forceinline__ int chunk_rank(bool keep, int* wave_tot, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wave_tot[wave] = __popcll(m);
+  __syncthreads();
+  int pos = __popcll(m & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; ++w) pos += wave_tot[w];
+  *total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+  __syncthreads();
+  return pos;
 }
 
 // One workgroup walks all boxes in chunks of 256; kept boxes take consecutive output rows in source order (ballot scan per wave, wave
@@ -177,94 +271,68 @@ __global__ __launch_bounds__(256) void aug_boxes_kernel(const cvx_aug_job* __res
                                                         const float* __restrict__ boxes, int n_boxes, int H, int W, float* __restrict__ targets,
                                                         int32_t* __restrict__ count) {
   __shared__ int wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const float fW = (float)W, fH = (float)H;
   int base = 0;
   for (int c0 = 0; c0 < n_boxes; c0 += 256) {
     const int i = c0 + tid;
     bool keep = false;
-    float o0 = 0, o1 = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0;
+    float image = 0, o[5] = {0, 0, 0, 0, 0};
     if (i < n_boxes) {
-      int lo = 0, hi = n_jobs - 1;                          // the last job whose first box is <= i (jobs without boxes are skipped over)
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (job_box_start[mid] <= i) lo = mid;
-        else hi = mid - 1;
-      }
-      const cvx_aug_job jb = jobs[lo];
-      const float* bx = boxes + (size_t)i * 5;
-      float x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
-      const float fiw = (float)jb.iw, fih = (float)jb.ih, fnw = (float)jb.nw, fnh = (float)jb.nh, fdx = (float)jb.dx, fdy = (float)jb.dy;
-      if (jb.quad >= 0 && jb.flip) {                        // mosaic_body :231, with iw = columns
-        const float a = fiw - x2, c = fiw - x1;
-        x1 = a;
-        x2 = c;
-      }
-      x1 = x1 * fnw / fiw + fdx;
-      x2 = x2 * fnw / fiw + fdx;
-      y1 = y1 * fnh / fih + fdy;
-      y2 = y2 * fnh / fih + fdy;
-      if (jb.quad < 0 && jb.flip) {                         // get_random_data :212
-        const float a = fW - x2, c = fW - x1;
-        x1 = a;
-        x2 = c;
-      }
-      if (x1 < 0.0f) x1 = 0.0f;
-      if (y1 < 0.0f) y1 = 0.0f;
-      if (x2 > fW) x2 = fW;
-      if (y2 > fH) y2 = fH;
-      keep = (x2 - x1 > 1.0f) && (y2 - y1 > 1.0f);
-      if (keep && jb.quad >= 0) {                           // merge_bboxes :405-449
-        const int q = jb.quad;
-        const float cutx = (float)(q <= 1 ? jb.x1 : jb.x0), cuty = (float)((q == 0 || q == 3) ? jb.y1 : jb.y0);
-        const bool sy = y2 >= cuty && y1 <= cuty, sx = x2 >= cutx && x1 <= cutx;
-        if (q == 0) {
-          if (y1 > cuty || x1 > cutx) keep = false;
-          if (sy) y2 = cuty;
-          if (sx) x2 = cutx;
-        } else if (q == 1) {
-          if (y2 < cuty || x1 > cutx) keep = false;
-          if (sy) y1 = cuty;
-          if (sx) x2 = cutx;
-        } else if (q == 2) {
-          if (y2 < cuty || x2 < cutx) keep = false;
-          if (sy) y1 = cuty;
-          if (sx) x1 = cutx;
-        } else {
-          if (y1 > cuty || x2 < cutx) keep = false;
-          if (sy) y2 = cuty;
-          if (sx) x1 = cutx;
-        }
-      }
-      x1 = x1 / fW;                                         // detection_dataset.py:110-119
-      x2 = x2 / fW;
-      y1 = y1 / fH;
-      y2 = y2 / fH;
-      const float bw = x2 - x1, bh = y2 - y1;
-      o0 = (float)jb.out;
-      o1 = bx[4];
-      o2 = x1 + bw / 2.0f;
-      o3 = y1 + bh / 2.0f;
-      o4 = bw;
-      o5 = bh;
+      const cvx_aug_job jb = jobs[job_of_box(job_box_start, 0, n_jobs - 1, i)];
+      keep = box_row(jb, boxes + (size_t)i * 5, fW, fH, o);
+      image = (float)jb.out;
     }
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) pos += wave_tot[w];
+    int total;
+    const int pos = base + chunk_rank(keep, wave_tot, &total);
     if (keep) {
       float* t = targets + (size_t)pos * 6;
-      t[0] = o0; t[1] = o1; t[2] = o2; t[3] = o3; t[4] = o4; t[5] = o5;
+      t[0] = image; t[1] = o[0]; t[2] = o[1]; t[3] = o[2]; t[4] = o[3]; t[5] = o[4];
     }
-    base += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    __syncthreads();
+    base += total;
   }
   for (int i = base + tid; i < n_boxes; i += 256) {         // unused rows: image -1
     float* t = targets + (size_t)i * 6;
     t[0] = -1.0f; t[1] = 0.0f; t[2] = 0.0f; t[3] = 0.0f; t[4] = 0.0f; t[5] = 0.0f;
   }
   if (tid == 0) *count = base;
+}
+
+// One workgroup per output image: the boxes of its jobs (job_start[b] .. job_start[b+1]) in chunks of 256, kept ones to rows 0, 1, .. of
+// labels[b] in source order; rows past max_boxes are dropped and reported, unused rows are zero.
+__global__ __launch_bounds__(256) void aug_boxes_padded_kernel(const cvx_aug_job* __restrict__ jobs, const int32_t* __restrict__ job_start,
+                                                               const int32_t* __restrict__ job_box_start, const float* __restrict__ boxes, int H, int W,
+                                                               int max_boxes, float* __restrict__ labels, int32_t* __restrict__ counts,
+                                                               int32_t* __restrict__ overflow) {
+  __shared__ int wave_tot[4];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const float fW = (float)W, fH = (float)H;
+  const int j0 = job_start[b], j1 = job_start[b + 1];
+  const int b0 = j1 > j0 ? job_box_start[j0] : 0, b1 = j1 > j0 ? job_box_start[j1] : 0;
+  float* lab = labels + (size_t)b * max_boxes * 5;
+  int base = 0;
+  for (int c0 = b0; c0 < b1; c0 += 256) {
+    const int i = c0 + tid;
+    bool keep = false;
+    float o[5] = {0, 0, 0, 0, 0};
+    if (i < b1) {
+      const cvx_aug_job jb = jobs[job_of_box(job_box_start, j0, j1 - 1, i)];
+      keep = box_row(jb, boxes + (size_t)i * 5, fW, fH, o);
+    }
+    int total;
+    const int pos = base + chunk_rank(keep, wave_tot, &total);
+    if (keep && pos < max_boxes) {
+      float* t = lab + (size_t)pos * 5;
+      t[0] = o[0]; t[1] = o[1]; t[2] = o[2]; t[3] = o[3]; t[4] = o[4];
+    }
+    base += total;
+  }
+  const int kept = min(base, max_boxes);
+  for (int i = kept * 5 + tid; i < max_boxes * 5; i += 256) lab[i] = 0.0f;
+  if (tid == 0) {
+    counts[b] = kept;
+    if (base > max_boxes) *overflow = 1;                    // every workgroup that overflows stores the same word; the entry point cleared it
+  }
 }
 
 }  // namespace
@@ -276,7 +344,19 @@ extern "C" int cvx_aug_images(const cvx_aug_job* jobs, const int32_t* job_start,
   CVX_CHECK(batch > 0 && batch <= 65535 && H > 0 && W > 0 && (long long)H * W * 3 < (1ll << 31), "bad shape");
   const dim3 grid(cvx_cdiv(W, TW), cvx_cdiv(H, TH), batch);
   CVX_CHECK(grid.y <= 65535, "output too tall");
-  hipLaunchKernelGGL(aug_images_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, jobs, job_start, luts, out_nchw, H, W);
+  hipLaunchKernelGGL(aug_images_kernel<true>, grid, dim3(256), 0, (hipStream_t)hip_stream, jobs, job_start, luts, out_nchw, H, W);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int cvx_aug_images_plain(const cvx_aug_job* jobs, const int32_t* job_start, int32_t batch, float* out_nchw, int32_t H, int32_t W,
+                                    void* hip_stream) {
+  CVX_CHECK(jobs && job_start && out_nchw, "null pointer");
+  CVX_CHECK(batch > 0 && batch <= 65535 && H > 0 && W > 0 && (long long)H * W * 3 < (1ll << 31), "bad shape");
+  const dim3 grid(cvx_cdiv(W, TW), cvx_cdiv(H, TH), batch);
+  CVX_CHECK(grid.y <= 65535, "output too tall");
+  hipLaunchKernelGGL(aug_images_kernel<false>, grid, dim3(256), 0, (hipStream_t)hip_stream, jobs, job_start, (const uint8_t*)nullptr, out_nchw, H,
+                     W);
   CVX_HIP(hipGetLastError());
   return 0;
 }
@@ -287,6 +367,19 @@ extern "C" int cvx_aug_boxes(const cvx_aug_job* jobs, const int32_t* job_box_sta
   CVX_CHECK(n_boxes == 0 || (boxes && targets), "boxes without a buffer");
   hipLaunchKernelGGL(aug_boxes_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, jobs, job_box_start, n_jobs, boxes, n_boxes, H, W, targets,
                      count);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int cvx_aug_boxes_padded(const cvx_aug_job* jobs, const int32_t* job_start, const int32_t* job_box_start, int32_t batch,
+                                    const float* boxes, int32_t n_boxes, int32_t H, int32_t W, int32_t max_boxes, float* labels, int32_t* counts,
+                                    int32_t* overflow, void* hip_stream) {
+  CVX_CHECK(jobs && job_start && job_box_start && labels && counts && overflow, "null pointer");
+  CVX_CHECK(batch > 0 && n_boxes >= 0 && H > 0 && W > 0 && max_boxes > 0 && (long long)max_boxes * 5 < (1ll << 31), "bad arguments");
+  CVX_CHECK(n_boxes == 0 || boxes, "boxes without a buffer");
+  CVX_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t), (hipStream_t)hip_stream));
+  hipLaunchKernelGGL(aug_boxes_padded_kernel, dim3(batch), dim3(256), 0, (hipStream_t)hip_stream, jobs, job_start, job_box_start, boxes, H, W,
+                     max_boxes, labels, counts, overflow);
   CVX_HIP(hipGetLastError());
   return 0;
 }

@@ -38,12 +38,18 @@ class CenterNetA:
         lc = self.cfg.loss
         return CenterNetLoss(self.num_classes, lc.hm_weight, lc.wh_weight, lc.off_weight)
 
-    def draw_targets(self, labels):
+    def draw_targets(self, labels, counts=None):
         """What centernet_collate does image by image on the CPU (core/data/collate.py:52-68), for the batch in one launch: a list of
         (N_i, 6) label arrays [_, class id, cx, cy, w, h] -> [heatmap (B,h,w,nc), reg (B,K,2), wh (B,K,2), reg_mask (B,K), indices (B,K)] on
-        the device (``cvx_centernet_draw_targets``), K = cfg.train.max_num_boxes (longer lists are truncated, as in the reference)."""
+        the device (``cvx_centernet_draw_targets``), K = cfg.train.max_num_boxes (longer lists are truncated, as in the reference).  With
+        ``counts`` (B) int32, ``labels`` is the device tensor (B, K, 5) [class id, cx, cy, w, h] as ``cvx_aug_boxes_padded`` writes it, and
+        nothing is packed on the host."""
         dev = torch.device(self.device)
         K = int(getattr(self.cfg.train, "max_num_boxes", 30))
+        if counts is not None:
+            ratio = int(self.cfg.arch.downsampling_ratio)
+            return _engine.centernet_draw_targets(labels, counts, (self.cfg.arch.input_size[1] // ratio, self.cfg.arch.input_size[2] // ratio),
+                                                  self.num_classes)
         packed = torch.zeros(len(labels), K, 5)
         counts = []
         for i, l in enumerate(labels):

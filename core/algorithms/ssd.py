@@ -78,10 +78,15 @@ class Ssd:
         lab = torch.as_tensor(np.asarray(label, dtype=np.float32) if not torch.is_tensor(label) else label).float()
         return self.encode_targets([lab])[0]
 
-    def encode_targets(self, labels):
+    def encode_targets(self, labels, counts=None):
         """What ssd_collate does image by image on the CPU (core/data/collate.py:32-49), for the batch in two launches: a list of (N_i, 6)
-        label arrays -> y_true (B, 8732, 4 + (nc + 1) + 1) on the device (``cvx_ssd_encode_targets``)."""
+        label arrays -> y_true (B, 8732, 4 + (nc + 1) + 1) on the device (``cvx_ssd_encode_targets``).  With ``counts`` (B) int32, ``labels``
+        is the device tensor (B, Nmax, 5) [class id, cx, cy, w, h] as ``cvx_aug_boxes_padded`` writes it, and nothing is packed on the host."""
         dev = torch.device(self.device)
+        if counts is not None:
+            if self._priors_dev is None or self._priors_dev.device != labels.device:
+                self._priors_dev = torch.from_numpy(self.anchors).to(labels.device)
+            return _engine.ssd_encode_targets(labels, counts, self._priors_dev, self.num_classes, self.overlap_threshold, self.variance[::2].tolist())
         nmax = max([int(l.shape[0]) for l in labels] + [1])
         packed = torch.zeros(len(labels), nmax, 5)
         for i, l in enumerate(labels):

@@ -2,9 +2,12 @@
 ``train_loop`` keeps the reference's step semantics (zero_grad -> forward -> CombinedLoss -> backward -> Adam under AMP, :104-121) and
 runs it as the engine's fused step (``CenterNetTrainStep``: engine forward, ``cvx_centernet_loss``, engine backward, fused Adam with
 GradScaler's skip-on-overflow); with ``torch.distributed`` initialised the step also sums the gradients over the ranks (RCCL).
-The dataset readers and ``centernet_collate``'s CPU target drawing (core/data/collate.py:52-68, core/algorithms/centernet.py:66-120) are
-outside the hot path: a dataloader yielding ``(images, [heatmap, reg, wh, reg_mask, indices])`` is injected, or seeded synthetic
-batches of that format stand in."""
+The input side is the device pipeline: ``dataloader=`` / ``val_dataloader=`` take a ``DeviceAugLoader(fmt="centernet")`` over
+``DeviceAugmenter(target=CenterNetA(cfg, device))`` -- ``DetectionDataset`` + ``centernet_collate`` of the reference
+(core/data/collate.py:52-68, core/algorithms/centernet.py:66-120) as the augmentation launches followed by ``cvx_centernet_draw_targets``,
+without a host synchronisation -- or any iterable yielding ``(images, [heatmap, reg, wh, reg_mask, indices])``; without one, seeded
+synthetic batches of that format stand in.  ``evaluate_loop`` runs on ``val_dataloader`` when one is given
+(``DeviceAugmenter(train=False)``), else on the training loader."""
 from typing import Dict, List
 
 import torch
@@ -58,8 +61,8 @@ def get_optimizer(optimizer_name, model, initial_lr):
 
 @trainer_registry("centernet")
 class CenterNetTrainer(BaseTrainer):
-    def __init__(self, cfg: CenternetConfig, device, dataloader=None):
-        self._injected_loader = dataloader
+    def __init__(self, cfg: CenternetConfig, device, dataloader=None, val_dataloader=None):
+        self._injected_loader, self._injected_val_loader = dataloader, val_dataloader
         super().__init__(cfg, device, True)
         self.metric_names = ["loss"]
         self.show_option = [True]
@@ -74,7 +77,8 @@ class CenterNetTrainer(BaseTrainer):
     def load_data(self):
         loader = self._injected_loader or SyntheticCenterNetLoader(self.batch_size, self.input_image_size[1:], self.cfg.dataset.num_classes,
                                                                    getattr(self.cfg.train, "max_num_boxes", 30), self.cfg.arch.downsampling_ratio)
-        self.train_dataloader = self.val_dataloader = loader
+        self.train_dataloader = loader
+        self.val_dataloader = self._injected_val_loader if self._injected_val_loader is not None else loader
 
     def set_optimizer(self):
         self.optimizer = get_optimizer(self.optimizer_name, self.model, self.initial_lr)

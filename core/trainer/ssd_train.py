@@ -1,9 +1,11 @@
 """``SsdTrainer`` -- registered as ``trainer_ssd`` like the reference's (core/trainer/ssd_train.py).  ``train_loop`` keeps the reference's
 step semantics (zero_grad -> forward -> MultiBoxLossV2 -> backward -> Adam under AMP, :96-115) and runs it as the engine's fused step
 (``SsdTrainStep``: engine forward, ``cvx_multibox_loss``, engine backward, fused Adam with GradScaler's skip-on-overflow); with
-``torch.distributed`` initialised the step also sums the gradients over the ranks (RCCL).  The dataset readers and ``ssd_collate``'s CPU
-prior matching / target encoding (core/data/collate.py:32-49, core/algorithms/ssd.py:327-480) are outside the hot path: a dataloader
-yielding ``(images, y_true (B, 8732, 4 + (nc + 1) + 1))`` is injected, or seeded synthetic batches of that format stand in."""
+``torch.distributed`` initialised the step also sums the gradients over the ranks (RCCL).  The input side is the device pipeline: ``dataloader=`` / ``val_dataloader=`` take a ``DeviceAugLoader(fmt="ssd")`` over
+``DeviceAugmenter(target=Ssd(cfg, device))`` -- ``DetectionDataset`` + ``ssd_collate`` of the reference (core/data/collate.py:32-49,
+core/algorithms/ssd.py:327-480) as the augmentation launches followed by ``cvx_ssd_encode_targets``, without a host synchronisation -- or
+any iterable yielding ``(images, y_true (B, 8732, 4 + (nc + 1) + 1))``; without one, seeded synthetic batches of that format stand in.
+``evaluate_loop`` runs on ``val_dataloader`` when one is given (``DeviceAugmenter(train=False)``), else on the training loader."""
 from typing import Dict, List
 
 import torch
@@ -50,8 +52,8 @@ def get_optimizer(optimizer_name, model, initial_lr):
 
 @trainer_registry("ssd")
 class SsdTrainer(BaseTrainer):
-    def __init__(self, cfg: SsdConfig, device, dataloader=None):
-        self._injected_loader = dataloader
+    def __init__(self, cfg: SsdConfig, device, dataloader=None, val_dataloader=None):
+        self._injected_loader, self._injected_val_loader = dataloader, val_dataloader
         super().__init__(cfg, device, True)
         self.metric_names = ["loss", "loc_loss", "conf_loss"]
         self.show_option = [True, True, True]
@@ -65,7 +67,8 @@ class SsdTrainer(BaseTrainer):
 
     def load_data(self):
         loader = self._injected_loader or SyntheticSsdLoader(self.batch_size, self.input_image_size[1:], self.cfg.dataset.num_classes)
-        self.train_dataloader = self.val_dataloader = loader
+        self.train_dataloader = loader
+        self.val_dataloader = self._injected_val_loader if self._injected_val_loader is not None else loader
 
     def set_optimizer(self):
         self.optimizer = get_optimizer(self.optimizer_name, self.model, self.initial_lr)

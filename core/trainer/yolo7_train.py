@@ -2,8 +2,10 @@
 reference's step semantics (zero_grad -> forward -> Yolo7Loss(preds, targets, images) -> backward -> Adam under AMP, :79-97) and runs it
 as the engine's fused step (``Yolo7TrainStep``: engine forward, ``cvx_yolo7_loss`` -- candidate generation, SimOTA assignment and the loss
 terms on the device --, engine backward, fused Adam with GradScaler's skip-on-overflow); with ``torch.distributed`` initialised the step
-also sums the gradients over the ranks (RCCL).  The dataset readers / mosaic augmentation are outside the hot path: a dataloader yielding
-``(images, targets (N, 6) [image, class, cx, cy, w, h])`` (yolo7_collate's format) is injected, or seeded synthetic batches stand in."""
+also sums the gradients over the ranks (RCCL).  The input side is ``DeviceAugLoader(fmt="yolo7")`` (resize, mosaic, HSV and box
+arithmetic on the device) or any iterable yielding ``(images, targets (N, 6) [image, class, cx, cy, w, h])`` (yolo7_collate's format) as
+``dataloader=``; seeded synthetic batches stand in without one.  ``evaluate_loop`` runs on ``val_dataloader=`` when one is given
+(``DeviceAugmenter(train=False)``), else on the training loader."""
 from typing import Dict, List
 
 import torch
@@ -48,8 +50,8 @@ def get_optimizer(optimizer_name, model, initial_lr):
 
 @trainer_registry("yolo7")
 class Yolo7Trainer(BaseTrainer):
-    def __init__(self, cfg: Yolo7Config, device, dataloader=None):
-        self._injected_loader = dataloader
+    def __init__(self, cfg: Yolo7Config, device, dataloader=None, val_dataloader=None):
+        self._injected_loader, self._injected_val_loader = dataloader, val_dataloader
         super().__init__(cfg, device, True)
         self.metric_names = ["loss", "box_loss", "obj_loss", "cls_loss"]
         self.show_option = [True, True, True, True]
@@ -63,7 +65,8 @@ class Yolo7Trainer(BaseTrainer):
 
     def load_data(self):
         loader = self._injected_loader or SyntheticYolo7Loader(self.batch_size, self.input_image_size[1:], self.cfg.dataset.num_classes)
-        self.train_dataloader = self.val_dataloader = loader
+        self.train_dataloader = loader
+        self.val_dataloader = self._injected_val_loader if self._injected_val_loader is not None else loader
 
     def set_optimizer(self):
         self.optimizer = get_optimizer(self.optimizer_name, self.model, self.initial_lr)

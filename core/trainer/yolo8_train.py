@@ -2,6 +2,8 @@
 (core/trainer/yolo8_train.py:19-129).  ``train_loop`` keeps the reference's step semantics
 (zero_grad -> forward -> loss -> backward -> Adam over all parameters, :93-111) and runs it as the
 engine's fused step; with ``torch.distributed`` initialised the step also averages gradients (RCCL).
+``dataloader=`` takes a ``DeviceAugLoader(fmt="yolo8")`` or any iterable of yolo8_collate's format; ``evaluate_loop`` runs on
+``val_dataloader=`` when one is given (``DeviceAugmenter(train=False)``), else on the training loader.
 """
 from typing import Dict, List
 
@@ -43,8 +45,8 @@ def get_optimizer(optimizer_name, model, initial_lr):
 
 @trainer_registry("yolo8_det")
 class Yolo8Trainer(BaseTrainer):
-    def __init__(self, cfg: Yolo8DetConfig, device, dataloader=None):
-        self._injected_loader = dataloader
+    def __init__(self, cfg: Yolo8DetConfig, device, dataloader=None, val_dataloader=None):
+        self._injected_loader, self._injected_val_loader = dataloader, val_dataloader
         self.metric_names = ["loss"]
         self.show_option = [True]
         super().__init__(cfg, device, True)
@@ -60,7 +62,8 @@ class Yolo8Trainer(BaseTrainer):
     def load_data(self):
         loader = self._injected_loader or SyntheticDetectionLoader(self.batch_size, self.input_image_size[1:],
                                                                    self.cfg.dataset.num_classes)
-        self.train_dataloader = self.val_dataloader = loader
+        self.train_dataloader = loader
+        self.val_dataloader = self._injected_val_loader if self._injected_val_loader is not None else loader
 
     def set_optimizer(self):
         self.optimizer = get_optimizer(self.optimizer_name, self.model, self.initial_lr)

@@ -581,6 +581,19 @@ int cvx_aug_images(const cvx_aug_job* jobs, const int32_t* job_start, const uint
  * normalisation of __getitem__ (:100-130) and the image-index column + concatenation of the collate functions (collate.py:8-13,20-23). */
 int cvx_aug_boxes(const cvx_aug_job* jobs, const int32_t* job_box_start, int32_t n_jobs, const float* boxes, int32_t n_boxes, int32_t H, int32_t W,
                   float* targets, int32_t* count, void* hip_stream);
+/* The image half without the colour transform: paste + bicubic tap -> byte / 255, what DetectionDataset(train=False) composes
+ * (get_random_data(random=False), detection_dataset.py:137-150; there is no flip and no HSV step, and RGB -> HSV -> RGB would not be the
+ * identity in 8 bits).  Same jobs, job_start and output as cvx_aug_images, no tables.  A sibling entry point rather than a flag in
+ * cvx_aug_job.reserved: it is a second instance of the same kernel template, so the colour instance keeps its code (csrc/augment.hip). */
+int cvx_aug_images_plain(const cvx_aug_job* jobs, const int32_t* job_start, int32_t batch, float* out_nchw, int32_t H, int32_t W, void* hip_stream);
+/* The box half with per-image output, for the target kernels that take padded labels (cvx_ssd_encode_targets,
+ * cvx_centernet_draw_targets): one workgroup per output image, asynchronous.  jobs, job_box_start, boxes as for cvx_aug_boxes; job_start
+ * (batch + 1) int32 as for cvx_aug_images.  labels: (batch, max_boxes, 5) fp32 rows [cls, cx, cy, w, h], the kept boxes of image b in
+ * source order from row 0, unused rows zero; counts: (batch) int32 = min(kept, max_boxes); overflow: 1 int32 (device), cleared on the
+ * stream first and set non-zero when any image kept more than max_boxes (its first max_boxes boxes survive).  The arithmetic is the device
+ * function cvx_aug_boxes uses, so the rows of image b are bit-identical to cvx_aug_boxes' rows with image index b. */
+int cvx_aug_boxes_padded(const cvx_aug_job* jobs, const int32_t* job_start, const int32_t* job_box_start, int32_t batch, const float* boxes,
+                         int32_t n_boxes, int32_t H, int32_t W, int32_t max_boxes, float* labels, int32_t* counts, int32_t* overflow, void* hip_stream);
 
 /* ---- data-parallel gradient exchange over RCCL (csrc/comm.hip), SURVEY.md section 8(b) / 8(e) --------------------------------------
  * One process per GPU.  Rank 0 calls cvx_comm_unique_id (128 bytes, ncclGetUniqueId), ships them to every rank by any means, all ranks

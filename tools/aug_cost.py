@@ -1,6 +1,10 @@
-"""Cost of the device augmentation next to the train step it feeds: event time of the two launches (``cvx_aug_images`` + ``cvx_aug_boxes``)
-at batch 32, 640 x 640, sources around 500 x 375, plain and mosaic; the write-bound floor (output bytes / the achievable HBM store rate);
-and the YOLOv8-n fused train step at the same batch, measured in the same run.
+"""Cost of the device input pipeline next to the train step it feeds, all in one process, sources around 500 x 375:
+
+* YOLO formats: event time of the two launches (``cvx_aug_images`` + ``cvx_aug_boxes``) at batch 32, 640 x 640, plain and mosaic; the
+  write-bound floor (output bytes / the achievable HBM store rate); the YOLOv8-n fused train step at the same batch;
+* ``fmt="ssd"`` at 300 x 300, batch 32, and ``fmt="centernet"`` at 384 x 384, batch 16, training (plain, mosaic) and validation: event time
+  of the two launch groups -- image launch + ``cvx_aug_boxes_padded``, and the target kernel (``cvx_ssd_encode_targets`` /
+  ``cvx_centernet_draw_targets``) on the labels and counts the first group left on the device -- and the trainer's fused step on such a batch.
 
     python tools/aug_cost.py [--out profiles/aug_cost.txt]
 
@@ -76,6 +80,62 @@ def train_step_ms(dev):
     return event_ms(lambda: step(x, batch), warmup=10, iters=30)
 
 
+def target_case(dev, fmt, hw, batch, alg, train, mosaic):
+    """one ``fmt="ssd"`` / ``"centernet"`` batch through DeviceAugmenter (checked run), then its two launch groups alone on the same tables"""
+    import aug_restatement as R
+    from computervision.pytorch_amd import augment as A
+    rng = np.random.RandomState(5)
+    pics = [torch.from_numpy(R.synth_picture(h, w, 70 + i)).to(dev) for i, (h, w) in enumerate(SIZES)]
+    boxes = [R.synth_boxes(h, w, 8, 80 + i) for i, (h, w) in enumerate(SIZES)]
+    aug = A.DeviceAugmenter(hw, seed=9, train=train, target=alg)
+    groups, bgroups = [], []
+    for i in range(batch):
+        ids = [int(v) for v in rng.randint(0, len(pics), 4 if mosaic else 1)]
+        groups.append([pics[k] for k in ids] if mosaic else pics[ids[0]])
+        bgroups.append([boxes[k] for k in ids] if mosaic else boxes[ids[0]])
+    captured = {}
+    launch = aug._launch_padded
+
+    def spy(*args):
+        captured["args"] = args
+        launch(*args)
+
+    aug._launch_padded = spy
+    images, targets = aug(groups, bgroups, fmt=fmt)
+    aug._launch_padded = launch
+    labels, counts = captured["args"][5], captured["args"][6]
+    make = alg.encode_targets if fmt == "ssd" else alg.draw_targets
+    ms_aug = event_ms(lambda: launch(*captured["args"]))
+    ms_tgt = event_ms(lambda: make(labels, counts))
+    n_in = sum(len(b) for bg in bgroups for b in (bg if mosaic else [bg]))
+    return ms_aug, ms_tgt, n_in, int(counts.sum()), tuple(labels.shape), (images, targets)
+
+
+def target_lines(dev, name, fmt, hw, batch):
+    """the three cases of one target format and the trainer's fused step on the mosaic batch"""
+    import tempfile
+
+    import builder
+    cfg, alg_cls, trainer_cls = builder.export_from_registry(name)
+    cfg.arch.input_size = (3,) + hw
+    cfg.train.batch_size, cfg.train.epoch, cfg.train.pretrained = batch, 1, False
+    cfg.train.save_path = tempfile.mkdtemp()
+    alg = alg_cls(cfg, dev)
+    lines = [f'fmt="{fmt}", batch {batch}, {hw[0]} x {hw[1]}: image launch + cvx_aug_boxes_padded | target kernel (event time, 50 repeats each)']
+    batch_data = None
+    for label, train, mosaic in (("train plain ", True, False), ("train mosaic", True, True), ("validation  ", False, False)):
+        ms_aug, ms_tgt, n_in, n_out, shape, data = target_case(dev, fmt, hw, batch, alg, train, mosaic)
+        lines.append(f"  {label}: {ms_aug * 1e3:8.1f} us | {ms_tgt * 1e3:8.1f} us; boxes {n_in} -> {n_out}, labels {shape}")
+        if mosaic:
+            batch_data = data
+    torch.manual_seed(0)
+    tr = trainer_cls(cfg, dev, dataloader=[batch_data])
+    tr.model.train()
+    ts = event_ms(lambda: tr.train_loop(batch_data, None), warmup=10, iters=30)
+    lines.append(f"  {trainer_cls.__name__} fused train step on the mosaic batch, same run: {ts:.3f} ms")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aug_cost.txt"))
@@ -92,6 +152,8 @@ def main():
                      f"{ms / floor_ms:.1f} x the floor, {out_bytes / ms / 1e9:.2f} TB/s written; boxes {n_in} -> {n_out}; mean pixel {mean:.4f}")
     ts = train_step_ms(dev)
     lines.append(f"YOLOv8-n fused train step, same batch and size, same run: {ts:.3f} ms")
+    lines += target_lines(dev, "ssd", "ssd", (300, 300), 32)
+    lines += target_lines(dev, "centernet", "centernet", (384, 384), 16)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
