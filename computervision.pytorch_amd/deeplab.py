@@ -16,7 +16,7 @@ Mirrors ``core/models/deeplabv3plus.py:10-149`` + ``core/models/resnet.py:82-277
   at 513 input, ``align_corners=False``) land in the two slices of one 304-channel buffer; the classifier's 1x1 (+bias)
   writes fp32 logits rows, which one last kernel resizes to the input resolution as the reference's NCHW tensor.
 
-All parameters live in one flat fp32 arena, BN statistics in a second one; ``state_dict`` has the reference's 674 keys and
+Parameters and statistics are views of flat arenas (arena.py); ``state_dict`` has the reference's 674 keys and
 shapes in its order and is bit-identical to ``DeeplabV3Plus(num_classes, 16, pretrained_backbone=False)`` under the same
 global seed.
 
@@ -29,16 +29,14 @@ in three launches).  ``SegTrainStep`` is the reference's ``train_loop`` (segment
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
-from typing import Dict, List, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .ema import clone_model
-from .engine import Engine
-from .graph import Graph, TensorSlot
+from .arena import ArenaLayout, ArenaModel, EngineTrainStep
+from .graph import Graph
 
 LAYERS = (3, 4, 23, 3)                            # resnet101 (resnet.py:272-277)
 PLANES = (64, 128, 256, 512)
@@ -64,50 +62,16 @@ def _blocks():
     return out
 
 
-class DeepLabLayout:
+class DeepLabLayout(ArenaLayout):
     """Arena offsets for every tensor of the reference's DeeplabV3Plus ``state_dict`` (same keys, shapes, order)."""
 
     def __init__(self, nc: int = 21):
+        super().__init__()
         self.nc = nc
         self.nc_pad = (nc + 7) & ~7
-        self.slots: "OrderedDict[str, TensorSlot]" = OrderedDict()
-        self.nbt_keys: List[str] = []
-        self.convs: Dict[str, dict] = {}
         self.blocks = _blocks()
-        self._p = self._s = 0
         self._plan()
-        self.n_params = (self._p + 3) & ~3
-        self.n_stats = (self._s + 3) & ~3
-
-    def _take(self, arena, n):
-        if arena == "param":
-            off, self._p = self._p, (self._p + n + 3) & ~3
-        else:
-            off, self._s = self._s, (self._s + n + 3) & ~3
-        return off
-
-    def conv(self, key, cout, cin, k, bias=False):
-        ce = (cout + 7) & ~7
-        spec = dict(cout=cout, cout_eng=ce, cin=cin, k=k, w_off=self._take("param", ce * k * k * cin))
-        self.slots[key + ".weight"] = TensorSlot("param", spec["w_off"], (cout, cin, k, k), (k * k * cin, 1, k * cin, cin))
-        if bias:
-            spec["bias_off"] = self._take("param", ce)
-            self.slots[key + ".bias"] = TensorSlot("param", spec["bias_off"], (cout,), (1,))
-        self.convs[key] = spec
-        return spec
-
-    def bn(self, key, c, spec):
-        spec.update(gamma_off=self._take("param", c), beta_off=self._take("param", c), rmean_off=self._take("stat", c),
-                    rvar_off=self._take("stat", c))
-        self.slots[key + ".weight"] = TensorSlot("param", spec["gamma_off"], (c,), (1,))
-        self.slots[key + ".bias"] = TensorSlot("param", spec["beta_off"], (c,), (1,))
-        self.slots[key + ".running_mean"] = TensorSlot("stat", spec["rmean_off"], (c,), (1,), False)
-        self.slots[key + ".running_var"] = TensorSlot("stat", spec["rvar_off"], (c,), (1,), False)
-        self.slots[key + ".num_batches_tracked"] = TensorSlot("nbt", len(self.nbt_keys), (), (), False)
-        self.nbt_keys.append(key + ".num_batches_tracked")
-
-    def conv_bn(self, ckey, bkey, cout, cin, k):
-        self.bn(bkey, cout, self.conv(ckey, cout, cin, k))
+        self._finish()
 
     def _plan(self):
         """state_dict order = module registration order (a Bottleneck's downsample comes after its bn3, resnet.py:118-119)."""
@@ -148,9 +112,6 @@ class DeepLabLayout:
 
     def module_order(self, part):
         return [k for k in self.convs if k.startswith(part)]
-
-    def views(self, arena, which="param"):
-        return {k: torch.as_strided(arena, sl.shape, sl.strides, sl.offset) for k, sl in self.slots.items() if sl.arena == which}
 
 
 def conv_out(n, k, stride, pad, dil):
@@ -246,71 +207,36 @@ def build_deeplab_graph(lay: DeepLabLayout, H: int, W: int, dropout_p: float = 0
     return g
 
 
-class _Holder(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise L.CvxError("parameter holder: the engine executes the whole graph (call the DeepLabv3+ model)")
-
-
-class DeepLabV3PlusR101(nn.Module):
+class DeepLabV3PlusR101(ArenaModel):
     """``DeeplabV3Plus(num_classes, output_stride=16, pretrained_backbone=False)`` of the reference (deeplabv3plus.py:126-149)
     on the engine: ``model(x)`` returns the (B, num_classes, H, W) fp32 logits; in training mode (grad enabled) the tensor is
     connected to the engine's backward pass, and carries the low-resolution rows as ``.rows`` for the fused ``SegLoss``."""
 
+    bn_eps_momentum = (BN_EPS, BN_MOMENTUM)
+
     def __init__(self, num_classes: int = 21, loss_scale: float = 65536.0, dropout_p: float = 0.1):
-        super().__init__()
-        self.layout = lay = DeepLabLayout(num_classes)
-        self.num_classes = num_classes
-        self.loss_scale = float(loss_scale)          # torch.cuda.amp.GradScaler's initial scale (the reference trains under AMP)
+        # loss_scale: torch.cuda.amp.GradScaler's initial scale (the reference trains under AMP)
+        super().__init__(DeepLabLayout(num_classes), num_classes, loss_scale)
         self.dropout_p = float(dropout_p)            # aspp.project.3 = nn.Dropout(0.1); 0 disables it (parity tests)
         self.seed = 0                                # seed of the dropout masks (cvx_engine_set_seed)
-        self._flat = {"param": torch.zeros(lay.n_params), "stat": torch.zeros(lay.n_stats), "nbt": torch.zeros(len(lay.nbt_keys), dtype=torch.long),
-                      "grad": None}
-        self._anchor = torch.zeros(1, requires_grad=True)
-        self._grads_attached = False
-        self._engines: Dict = {}
-        self._build_tree()
-        self._attach_views()
-        self._init_like_reference()
         self.last_rows = None
 
-    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
+    def ctor_args(self):
+        return dict(super().ctor_args(), dropout_p=self.dropout_p)
 
-    def _build_tree(self):
-        for key in self.layout.slots:
-            mod = self
-            for name in key.split(".")[:-1]:
-                if name not in mod._modules:
-                    mod.add_module(name, _Holder())
-                mod = mod._modules[name]
+    def _build_graph(self, h, w):
+        return build_deeplab_graph(self.layout, h, w, self.dropout_p)
 
-    def _attach_views(self):
-        for key, sl in self.layout.slots.items():
-            mod = self
-            parts = key.split(".")
-            for name in parts[:-1]:
-                mod = mod._modules[name]
-            if sl.arena == "nbt":
-                mod._buffers[parts[-1]] = self._flat["nbt"][sl.offset]
-                continue
-            view = torch.as_strided(self._flat[sl.arena], sl.shape, sl.strides, sl.offset)
-            if sl.trainable:
-                old = mod._parameters.get(parts[-1])
-                mod._parameters[parts[-1]] = nn.Parameter(view, requires_grad=True if old is None else old.requires_grad)
-            else:
-                mod._buffers[parts[-1]] = view
+    def _engine_key(self, h, w, dev):
+        return (h, w, dev, self.dropout_p)
 
-    def _apply(self, fn, recurse=True):
-        self._flat["grad"] = None
-        self._grads_attached = False
-        self._anchor = fn(self._anchor.detach()).requires_grad_(True)
-        for k in ("param", "stat", "nbt"):
-            t = fn(self._flat[k])
-            if k != "nbt" and t.dtype != torch.float32:
-                raise L.CvxError("the engine keeps fp32 master parameters; half()/bfloat16() are not supported (compute is fp16 inside)")
-            self._flat[k] = t.long().contiguous() if k == "nbt" else t.contiguous()
-        self._attach_views()
-        self._engines.clear()
-        return self
+    def _after_bind(self, eng):
+        eng.set_seed(self.seed)
+
+    def _check_input(self, x, training):
+        super()._check_input(x, training)
+        if training and x.shape[0] < 2:
+            raise ValueError("training-mode BatchNorm needs more than one value per channel (ASPPPooling's 1x1 map): batch >= 2")
 
     def _init_like_reference(self):
         """The reference's RNG consumption, draw for draw (resnet.py:150-178, deeplabv3plus.py:99-110): every nn.Conv2d draws its
@@ -355,50 +281,8 @@ class DeepLabV3PlusR101(nn.Module):
                         sd[key].zero_()
             self._flat["nbt"].zero_()
 
-    # ---- engine plumbing ---------------------------------------------------------------------------------
-    @property
-    def flat_params(self) -> torch.Tensor:
-        return self._flat["param"]
-
-    @property
-    def flat_stats(self) -> torch.Tensor:
-        return self._flat["stat"]
-
-    @property
-    def flat_grads(self) -> torch.Tensor:
-        if self._flat["grad"] is None or self._flat["grad"].device != self._flat["param"].device:
-            self._flat["grad"] = torch.zeros_like(self._flat["param"])
-            self._grads_attached = False
-        return self._flat["grad"]
-
-    def engine_for(self, h: int, w: int) -> Engine:
-        dev = self._flat["param"].device
-        key = (h, w, dev, self.dropout_p)
-        eng = self._engines.get(key)
-        if eng is None:
-            if dev.type != "cuda":
-                raise L.CvxError("DeepLabV3PlusR101 runs on an MI355X only: move the model with .to('cuda') first (there is no CPU fallback)")
-            eng = Engine(build_deeplab_graph(self.layout, h, w, self.dropout_p), dev)
-            eng.set_bn(BN_EPS, BN_MOMENTUM)
-            self._engines[key] = eng
-        eng.bind(self._flat["param"], self.flat_grads if self.training else self._flat["grad"], self._flat["stat"])
-        eng.set_seed(self.seed)
-        return eng
-
-    def _run_forward(self, x: torch.Tensor, training: bool, pred: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """(B,3,H,W) -> the engine's fp32 logits rows (B, h*w, nc_pad) at the decoder's resolution (stride 4)."""
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected images of shape (B, 3, H, W)")
-        if training and x.shape[0] < 2:
-            raise ValueError("training-mode BatchNorm needs more than one value per channel (ASPPPooling's 1x1 map): batch >= 2")
-        eng = self.engine_for(int(x.shape[2]), int(x.shape[3]))
-        self._last_engine = eng
-        rows = eng.forward(x, training, pred)
-        if training:
-            self._flat["nbt"] += 1
-        return rows
-
     def forward_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """(B,3,H,W) -> the engine's fp32 logits rows (B, h*w, nc_pad) at the decoder's resolution (stride 4)."""
         return self._run_forward(x, self.training)
 
     def rows_to_nchw(self, rows: torch.Tensor, H: int, W: int) -> torch.Tensor:
@@ -411,26 +295,9 @@ class DeepLabV3PlusR101(nn.Module):
                                                       L.stream_ptr(rows.device)), "cvx_resize_bilinear_rows_to_nchw")
         return out
 
-    def attach_grads(self):
-        """Make ``p.grad`` of every parameter a view of the flat gradient arena (torch optimisers / GradScaler)."""
-        g = self.flat_grads
-        modules = dict(self.named_modules())
-        for key, slot in self.layout.slots.items():
-            if not slot.trainable:
-                continue
-            mod_name, attr = key.rsplit(".", 1)
-            modules[mod_name]._parameters[attr].grad = torch.as_strided(g, slot.shape, slot.strides, slot.offset)
-        self._grads_attached = True
-
     def backward_rows(self, dpred_f16: torch.Tensor, loss_scale: float):
         """Engine backward from loss_scale * dLoss/drows (B, h*w, nc_pad) fp16: parameter gradients are accumulated into the arena."""
-        first = next(p for p in self.parameters() if p.requires_grad)
-        if first.grad is None:               # optimizer.zero_grad(set_to_none=True) happened (or first step)
-            self.flat_grads.zero_()
-            self._grads_attached = False
-        self._last_engine.backward(dpred_f16, loss_scale)
-        if not self._grads_attached or first.grad is None:
-            self.attach_grads()
+        self._engine_backward(dpred_f16, loss_scale)
 
     def _backward_from_nchw(self, g: torch.Tensor):
         """Gradient w.r.t. the full-resolution logits -> rows (adjoint of the final resize) -> engine backward."""
@@ -545,50 +412,28 @@ class SegLoss:
         return self.op(rows, targets, hw, model.loss_scale)[0].reshape(())
 
 
-class SegTrainStep:
+class SegTrainStep(EngineTrainStep):
     """One optimisation step of the reference's ``DeeplabV3PlusTrainer.train_loop`` (segmentation_trainer.py:114-131:
     zero_grad -> forward -> criterion -> backward -> Adam under AMP) as C-ABI calls: engine forward (training), ``cvx_seg_loss``,
     engine backward, [gradient all-reduce over RCCL], fused Adam with the inf/nan check of GradScaler.step.  Returns the loss (1,).
     Data parallel: the flat gradient arena is summed over the ranks in a few large slices on a side stream after the backward
     pass (the mean's 1/world is folded into Adam); BatchNorm statistics stay per rank, as in the reference."""
 
-    def __init__(self, model: DeepLabV3PlusR101, criterion: SegLoss, optimizer, scaler=None, process_group=None, n_buckets: int = 4):
-        self.model, self.criterion, self.optimizer, self.scaler = model, criterion, optimizer, scaler
-        self.pg, self.n_buckets = process_group, n_buckets
-        self.world, self.distributed = 1, False
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-            self.distributed = True
-        self._pred = self._dpred = self._side = None
+    _pred = _dpred = None
 
     def __call__(self, images: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-        from .engine import check_finite
         m, crit = self.model, self.criterion
-        if not m.training:
-            raise L.CvxError("SegTrainStep: call model.train() first")
-        dev = m.flat_params.device
+        scale = self._begin()
         B, _, H, W = images.shape
-        self.optimizer.sync_lr()
         eng = m.engine_for(H, W)
         lh, lw = eng.graph.level_hw[0]
         if self._pred is None or self._pred.shape[0] != B or self._pred.shape[1] != lh * lw:
+            dev = m.flat_params.device
             self._pred = torch.empty(B, lh * lw, m.layout.nc_pad, device=dev)
             self._dpred = torch.empty(B, lh * lw, m.layout.nc_pad, device=dev, dtype=torch.float16)
-        scale = self.scaler.begin_step() if self.scaler is not None else m.loss_scale
         rows = m._run_forward(images, True, self._pred)
         crit.nc = m.num_classes
         loss, dpred = crit.op(rows, targets, (lh, lw), scale, self._dpred, check=False)   # no host sync in the step: crit.bad_targets() polls
-        if self.distributed and dev.type == "cuda":               # gradient exchange overlapped with the backward pass, bucket by bucket
-            if self._side is None:
-                from .train import OverlappedExchange
-                self._side = OverlappedExchange(self.pg, self.n_buckets)
-            self._side.backward(eng, m.flat_grads, dpred, scale)
-        else:
-            eng.backward(dpred, scale)
-        if self.scaler is not None:
-            check_finite(m.flat_grads, self.scaler.found_inf)
-            self.optimizer.found_inf = self.scaler.found_inf
-        self.optimizer.step(zero_grad=True, grad_scale=1.0 / self.world)
-        if self.scaler is not None:
-            self.scaler.end_step()
+        self._backward(eng, dpred, scale)
+        self._update()
         return loss

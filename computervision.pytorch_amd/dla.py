@@ -13,8 +13,8 @@ Mirrors ``core/models/centernet_model.py:9-379`` of the reference as an engine g
 * ``Tree.project`` of a two-level tree is dead code in the reference (its result is overwritten before use,
   centernet_model.py:141-146) and is not executed; ``base.final`` (the unused ImageNet classifier) is kept as parameters only.
 
-All parameters live in one flat fp32 arena, BN statistics in a second one; ``state_dict`` has the reference's 326 keys
-and shapes in its order and is bit-identical to ``CenterNet(cfg)`` under the same global seed.
+Parameters and statistics are views of flat arenas (arena.py); ``state_dict`` has the reference's 326 keys and shapes in
+its order and is bit-identical to ``CenterNet(cfg)`` under the same global seed.
 
 Training (``model.train()``): the same graph with batch-statistics BatchNorm and the backward of every op; ``CenterNetLoss``
 (csrc/loss_centernet.hip) and ``CenterNetTrainStep`` below are the reference's ``train_loop`` (centernet_train.py:104-121) as C-ABI calls.
@@ -22,15 +22,13 @@ Training (``model.train()``): the same graph with batch-statistics BatchNorm and
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .ema import clone_model
-from .engine import Engine
+from .arena import ArenaLayout, ArenaModel, EngineTrainStep
 from .graph import Graph, TensorSlot
 
 LEVELS = (1, 1, 1, 2, 2, 1)                      # dla34 (centernet_model.py:342-344)
@@ -74,52 +72,16 @@ def _dla_up_plan():
     return idas
 
 
-class DlaLayout:
+class DlaLayout(ArenaLayout):
     """Arena offsets for every tensor of the reference's CenterNet ``state_dict`` (same keys, shapes, order)."""
 
     def __init__(self, nc: int = 80):
+        super().__init__()
         self.nc = nc
         self.nc_pad = (nc + 7) & ~7
         self.pred_ld = self.nc_pad + 16                 # [heatmap | wh (2 of 8) | reg (2 of 8)]
-        self.slots: "OrderedDict[str, TensorSlot]" = OrderedDict()
-        self.nbt_keys: List[str] = []
-        self.convs: Dict[str, dict] = {}               # conv key -> offsets for the engine op
-        self._p = self._s = 0
         self._plan()
-        self.n_params = (self._p + 3) & ~3
-        self.n_stats = (self._s + 3) & ~3
-
-    def _take(self, arena, n):
-        if arena == "param":
-            off, self._p = self._p, (self._p + n + 3) & ~3
-        else:
-            off, self._s = self._s, (self._s + n + 3) & ~3
-        return off
-
-    # conv (+ optional bias) whose weights the engine reads as [cout][kh][kw][cin]
-    def conv(self, key, cout, cin, k, bias=False, w_off=None, b_off=None):
-        ce = (cout + 7) & ~7
-        spec = dict(cout=cout, cout_eng=ce, cin=cin, k=k,
-                    w_off=self._take("param", ce * k * k * cin) if w_off is None else w_off)
-        self.slots[key + ".weight"] = TensorSlot("param", spec["w_off"], (cout, cin, k, k), (k * k * cin, 1, k * cin, cin))
-        if bias:
-            spec["bias_off"] = self._take("param", ce) if b_off is None else b_off
-            self.slots[key + ".bias"] = TensorSlot("param", spec["bias_off"], (cout,), (1,))
-        self.convs[key] = spec
-        return spec
-
-    def bn(self, key, c, spec):
-        spec.update(gamma_off=self._take("param", c), beta_off=self._take("param", c), rmean_off=self._take("stat", c),
-                    rvar_off=self._take("stat", c))
-        self.slots[key + ".weight"] = TensorSlot("param", spec["gamma_off"], (c,), (1,))
-        self.slots[key + ".bias"] = TensorSlot("param", spec["beta_off"], (c,), (1,))
-        self.slots[key + ".running_mean"] = TensorSlot("stat", spec["rmean_off"], (c,), (1,), False)
-        self.slots[key + ".running_var"] = TensorSlot("stat", spec["rvar_off"], (c,), (1,), False)
-        self.slots[key + ".num_batches_tracked"] = TensorSlot("nbt", len(self.nbt_keys), (), (), False)
-        self.nbt_keys.append(key + ".num_batches_tracked")
-
-    def conv_bn(self, ckey, bkey, cout, cin, k):
-        self.bn(bkey, cout, self.conv(ckey, cout, cin, k))
+        self._finish()
 
     def _block(self, p):
         self.conv_bn(p["prefix"] + ".conv1", p["prefix"] + ".bn1", p["cout"], p["cin"], 3)
@@ -164,10 +126,6 @@ class DlaLayout:
             self.conv(f"backbone.{head}.0", HEAD_CONV, c[2], 3, True, w_off=w0 + n * HEAD_CONV * 9 * c[2], b_off=b0 + n * HEAD_CONV)
             self.conv(f"backbone.{head}.2", classes, HEAD_CONV, 1, True)
         self.head_first = dict(w_off=w0, bias_off=b0, cout=3 * HEAD_CONV, cin=c[2], k=3)
-
-    # -- reference-keyed dicts <-> flat arenas -------------------------------------------------------
-    def views(self, arena, which="param"):
-        return {k: torch.as_strided(arena, sl.shape, sl.strides, sl.offset) for k, sl in self.slots.items() if sl.arena == which}
 
 
 # --------------------------------------------------------------------------------------------------
@@ -306,73 +264,21 @@ def build_dla_graph(lay: DlaLayout, H: int, W: int) -> Graph:
 
 
 # --------------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise L.CvxError("parameter holder: the engine executes the whole graph (call the CenterNet model)")
-
-
-class CenterNetDLA34(nn.Module):
+class CenterNetDLA34(ArenaModel):
     """``CenterNet(cfg)`` of the reference (centernet_model.py:365-379) on the engine: ``model(x)`` returns the (B, H/4, W/4, nc + 4)
     NHWC tensor [heatmap | wh | reg].  In training mode (grad enabled) the tensor is connected to the engine's backward pass
     (batch-statistics BatchNorm + ReLU, the BasicBlock residual inside the ReLU, 2x2 max pools, the depthwise transposed
     convolutions' data and weight gradients, the concat copies, the biased head convolutions): any torch loss on it -- the
     reference's CombinedLoss is torch code on exactly this tensor -- trains the network."""
 
+    bn_eps_momentum = (BN_EPS, BN_MOMENTUM)
+
     def __init__(self, num_classes: int = 80, loss_scale: float = 1024.0):
-        super().__init__()
-        self.layout = lay = DlaLayout(num_classes)
-        self.num_classes = num_classes
-        self.loss_scale = float(loss_scale)
-        self._flat = {"param": torch.zeros(lay.n_params), "stat": torch.zeros(lay.n_stats), "nbt": torch.zeros(len(lay.nbt_keys), dtype=torch.long),
-                      "grad": None}
-        self._anchor = torch.zeros(1, requires_grad=True)
-        self._grads_attached = False
-        self._engines: Dict = {}
-        self._build_tree()
-        self._attach_views()
-        self._init_like_reference()
+        super().__init__(DlaLayout(num_classes), num_classes, loss_scale)
         self.last_raw = None
 
-    # ---- module tree with the reference's names (state_dict keys / order) --------------------------
-    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
-
-    def _build_tree(self):
-        for key in self.layout.slots:
-            mod = self
-            parts = key.split(".")
-            for name in parts[:-1]:
-                if name not in mod._modules:
-                    mod.add_module(name, _Holder())
-                mod = mod._modules[name]
-
-    def _attach_views(self):
-        for key, sl in self.layout.slots.items():
-            mod = self
-            parts = key.split(".")
-            for name in parts[:-1]:
-                mod = mod._modules[name]
-            if sl.arena == "nbt":
-                mod._buffers[parts[-1]] = self._flat["nbt"][sl.offset]
-                continue
-            view = torch.as_strided(self._flat[sl.arena], sl.shape, sl.strides, sl.offset)
-            if sl.trainable:
-                old = mod._parameters.get(parts[-1])
-                mod._parameters[parts[-1]] = nn.Parameter(view, requires_grad=True if old is None else old.requires_grad)
-            else:
-                mod._buffers[parts[-1]] = view
-
-    def _apply(self, fn, recurse=True):
-        self._flat["grad"] = None
-        self._grads_attached = False
-        self._anchor = fn(self._anchor.detach()).requires_grad_(True)
-        for k in ("param", "stat", "nbt"):
-            t = fn(self._flat[k])
-            if k != "nbt" and t.dtype != torch.float32:
-                raise L.CvxError("the engine keeps fp32 master parameters; half()/bfloat16() are not supported (compute is fp16 inside)")
-            self._flat[k] = t.long().contiguous() if k == "nbt" else t.contiguous()
-        self._attach_views()
-        self._engines.clear()
-        return self
+    def _build_graph(self, h, w):
+        return build_dla_graph(self.layout, h, w)
 
     def _init_like_reference(self):
         """torch's default Conv2d / ConvTranspose2d / BatchNorm2d initialisation, drawn from the global RNG in the reference's
@@ -399,70 +305,14 @@ class CenterNetDLA34(nn.Module):
                     sd[key].zero_()
             self._flat["nbt"].zero_()
 
-    # ---- engine plumbing ---------------------------------------------------------------------------------
-    def engine_for(self, h: int, w: int) -> Engine:
-        dev = self._flat["param"].device
-        key = (h, w, dev)
-        eng = self._engines.get(key)
-        if eng is None:
-            if dev.type != "cuda":
-                raise L.CvxError("CenterNetDLA34 runs on an MI355X only: move the model with .to('cuda') first (there is no CPU fallback)")
-            eng = Engine(build_dla_graph(self.layout, h, w), dev)
-            eng.set_bn(BN_EPS, BN_MOMENTUM)
-            self._engines[key] = eng
-        eng.bind(self._flat["param"], self.flat_grads if self.training else self._flat["grad"], self._flat["stat"])
-        return eng
-
-    @property
-    def flat_params(self) -> torch.Tensor:
-        return self._flat["param"]
-
-    @property
-    def flat_stats(self) -> torch.Tensor:
-        return self._flat["stat"]
-
-    @property
-    def flat_grads(self) -> torch.Tensor:
-        if self._flat["grad"] is None or self._flat["grad"].device != self._flat["param"].device:
-            self._flat["grad"] = torch.zeros_like(self._flat["param"])
-            self._grads_attached = False
-        return self._flat["grad"]
-
-    def attach_grads(self):
-        """Make ``p.grad`` of every parameter a view of the flat gradient arena (torch optimisers / GradScaler)."""
-        g = self.flat_grads
-        modules = dict(self.named_modules())
-        for key, slot in self.layout.slots.items():
-            if not slot.trainable:
-                continue
-            mod_name, attr = key.rsplit(".", 1)
-            modules[mod_name]._parameters[attr].grad = torch.as_strided(g, slot.shape, slot.strides, slot.offset)
-        self._grads_attached = True
-
-    def _run_forward(self, x: torch.Tensor, training: bool) -> torch.Tensor:
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected images of shape (B, 3, H, W)")
-        eng = self.engine_for(int(x.shape[2]), int(x.shape[3]))
-        self._last_engine = eng
-        raw = eng.forward(x, training)
-        if training:
-            self._flat["nbt"] += 1
-        return raw
-
     def forward_raw(self, x: torch.Tensor) -> torch.Tensor:
         """(B,3,H,W) -> the engine's fp32 head tensor (B, H/4 * W/4, nc_pad + 16): what ``centernet_decode`` reads."""
         return self._run_forward(x, self.training)
 
     def _backward_rows(self, g: torch.Tensor):
         """Gradient w.r.t. the fp32 head rows -> loss_scale * g in fp16 -> engine backward (parameter gradients accumulate)."""
-        first = next(p for p in self.parameters() if p.requires_grad)
-        if first.grad is None:               # optimizer.zero_grad(set_to_none=True) happened (or first step)
-            self.flat_grads.zero_()
-            self._grads_attached = False
         self.last_dpred = (g * self.loss_scale).to(torch.float16).contiguous()
-        self._last_engine.backward(self.last_dpred, self.loss_scale)
-        if not self._grads_attached or first.grad is None:
-            self.attach_grads()
+        self._engine_backward(self.last_dpred, self.loss_scale)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         raw = _RowsFn.apply(x, self._anchor, self) if (self.training and torch.is_grad_enabled()) else self.forward_raw(x)
@@ -502,14 +352,7 @@ class _CnLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        m = ctx.model
-        first = next(p for p in m.parameters() if p.requires_grad)
-        if first.grad is None:
-            m.flat_grads.zero_()
-            m._grads_attached = False
-        m._last_engine.backward(ctx.dpred, m.loss_scale / float(gout))
-        if not m._grads_attached or first.grad is None:
-            m.attach_grads()
+        ctx.model._engine_backward(ctx.dpred, ctx.model.loss_scale / float(gout))
         return None, None, None, None
 
 
@@ -569,45 +412,22 @@ class CenterNetLoss:
         return self.op(model.last_raw, targets, model._last_engine.graph.level_hw[0], model.loss_scale)[0][0].reshape(())
 
 
-class CenterNetTrainStep:
+class CenterNetTrainStep(EngineTrainStep):
     """One optimisation step of the reference's ``CenterNetTrainer.train_loop`` (core/trainer/centernet_train.py:104-121) as C-ABI calls:
     engine forward (training), ``cvx_centernet_loss``, engine backward, [gradient sum over the ranks], fused Adam with GradScaler's
     inf/nan check.  Returns the loss items (4,)."""
 
-    def __init__(self, model: "CenterNetDLA34", criterion: CenterNetLoss, optimizer, scaler=None, process_group=None, n_buckets: int = 4):
-        self.model, self.criterion, self.optimizer, self.scaler = model, criterion, optimizer, scaler
-        self.pg, self.n_buckets = process_group, n_buckets
-        self.world, self.distributed = 1, False
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-            self.distributed = True
-        self._dpred = self._side = None
+    _dpred = None
 
     def __call__(self, images: torch.Tensor, targets) -> torch.Tensor:
-        from .engine import check_finite
-        m, crit = self.model, self.criterion
-        if not m.training:
-            raise L.CvxError("CenterNetTrainStep: call model.train() first")
-        dev = m.flat_params.device
-        self.optimizer.sync_lr()
+        m = self.model
+        scale = self._begin()
         rows = m._run_forward(images, True)
         m.last_raw = rows
         eng = m._last_engine
         if self._dpred is None or self._dpred.shape != rows.shape:
-            self._dpred = torch.empty(rows.shape, device=dev, dtype=torch.float16)
-        scale = self.scaler.begin_step() if self.scaler is not None else m.loss_scale
-        items, dpred = crit.op(rows, targets, eng.graph.level_hw[0], scale, self._dpred, check=False)
-        if self.distributed and dev.type == "cuda":               # gradient exchange overlapped with the backward pass, bucket by bucket
-            if self._side is None:
-                from .train import OverlappedExchange
-                self._side = OverlappedExchange(self.pg, self.n_buckets)
-            self._side.backward(eng, m.flat_grads, dpred, scale)
-        else:
-            eng.backward(dpred, scale)
-        if self.scaler is not None:
-            check_finite(m.flat_grads, self.scaler.found_inf)
-            self.optimizer.found_inf = self.scaler.found_inf
-        self.optimizer.step(zero_grad=True, grad_scale=1.0 / self.world)
-        if self.scaler is not None:
-            self.scaler.end_step()
+            self._dpred = torch.empty(rows.shape, device=rows.device, dtype=torch.float16)
+        items, dpred = self.criterion.op(rows, targets, eng.graph.level_hw[0], scale, self._dpred, check=False)
+        self._backward(eng, dpred, scale)
+        self._update()
         return items

@@ -25,31 +25,18 @@ import torch
 from . import _lib as L
 from .engine import ema_update
 
-# class name -> constructor arguments read back from the instance
-_CTOR_ARGS = {
-    "Yolo8": lambda m: dict(scale_name=m.scale_name, num_classes=m.num_classes, loss_scale=m.loss_scale),
-    "DeepLabV3PlusR101": lambda m: dict(num_classes=m.num_classes, loss_scale=m.loss_scale, dropout_p=m.dropout_p),
-    "CenterNetDLA34": lambda m: dict(num_classes=m.num_classes, loss_scale=m.loss_scale),
-    "SSD300VGG": lambda m: dict(num_classes=m.num_classes, loss_scale=m.loss_scale),
-    "Yolo7L": lambda m: dict(num_classes=m.num_classes, loss_scale=m.loss_scale),
-}
 _ARENAS = ("param", "stat", "nbt")
-
-
-def _ctor_args(model):
-    for cls in type(model).__mro__:
-        if cls.__name__ in _CTOR_ARGS:
-            return _CTOR_ARGS[cls.__name__](model)
-    raise L.CvxError(f"clone_model: {type(model).__name__} is not one of the engine-backed models ({', '.join(_CTOR_ARGS)})")
 
 
 def clone_model(model, memo=None):
     """A model of the same class, constructor arguments, device and mode whose ``param`` / ``stat`` / ``nbt`` arenas are copies of
     ``model``'s; its parameters and buffers are views of those copies.  It has no engines and no gradient arena until it is run.
     (The signature doubles as ``__deepcopy__``.)"""
-    kwargs = _ctor_args(model)
+    from .arena import ArenaModel
+    if not isinstance(model, ArenaModel):
+        raise L.CvxError(f"clone_model: {type(model).__name__} is not one of the engine-backed models (an arena.ArenaModel)")
     with torch.random.fork_rng(devices=[]):          # the constructor draws an initialisation: not from the caller's stream
-        clone = type(model)(**kwargs)
+        clone = type(model)(**model.ctor_args())
     clone.to(model.flat_params.device)
     with torch.no_grad():
         for k in _ARENAS:

@@ -10,7 +10,7 @@ Mirrors ``core/models/ssd_model.py:6-191`` of the reference as an engine graph:
 * the six (loc, conf) 3x3 heads write fp32 rows (B, 1940, [loc 24 | conf 128]); ``forward`` returns the reference's tensors
   (B, 8732, 4) and (B, 8732, 21) -- flattened in NCHW order per level, as the reference does (no permute, :177-183).
 
-``state_dict``: the reference's 136 keys / shapes / order, bit-identical to ``SSD(cfg)`` under the same global seed (torch's
+``state_dict`` (views of flat arenas, arena.py): the reference's 136 keys / shapes / order, bit-identical to ``SSD(cfg)`` under the same global seed (torch's
 default initialisation in the reference's construction order: loc_i / conf_i alternately).
 
 Training (``model.train()``): the same graph with batch-statistics BatchNorm and the backward of every op; ``MultiBoxLoss``
@@ -19,15 +19,13 @@ Training (``model.train()``): the same graph with batch-statistics BatchNorm and
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
-from typing import Dict, Optional, List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .ema import clone_model
-from .engine import Engine
+from .arena import ArenaLayout, ArenaModel, EngineTrainStep
 from .graph import Graph, TensorSlot
 
 VGG_PARAMS = (64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 512, 512, 512)
@@ -55,18 +53,15 @@ def vgg_plan():
     return plan
 
 
-class SsdLayout:
+class SsdLayout(ArenaLayout):
     """Arena offsets for every tensor of the reference's SSD ``state_dict`` (same keys, shapes, order)."""
 
     def __init__(self, nc: int = 20):
+        super().__init__()
         self.nc = nc
         self.conf_cols = max((n * (nc + 1) + 7) & ~7 for n in BOXES_PER_PIXEL)
         self.pred_ld = LOC_COLS + self.conf_cols
-        self.slots: "OrderedDict[str, TensorSlot]" = OrderedDict()
-        self.nbt_keys: List[str] = []
-        self.convs: Dict[str, dict] = {}
         self.construction: List[str] = []
-        self._p = self._s = 0
         for item in vgg_plan():
             if item[1] != "conv":
                 continue
@@ -84,36 +79,14 @@ class SsdLayout:
             self.conv(key, cout, cin, 3, pad=1, construct=False)
         for i in range(6):                                        # construction order: loc_i, conf_i alternately (:131-162)
             self.construction += [f"locs.{i}", f"confs.{i}"]
-        self.n_params = (self._p + 3) & ~3
-        self.n_stats = (self._s + 3) & ~3
-
-    def _take(self, arena, n):
-        if arena == "param":
-            off, self._p = self._p, (self._p + n + 3) & ~3
-        else:
-            off, self._s = self._s, (self._s + n + 3) & ~3
-        return off
+        self._finish()
 
     def conv(self, key, cout, cin, k, stride=1, pad=0, dil=1, construct=True):
-        ce = (cout + 7) & ~7
-        spec = dict(cout=cout, cout_eng=ce, cin=cin, k=k, stride=stride, pad=pad, dil=dil, w_off=self._take("param", ce * k * k * cin),
-                    bias_off=self._take("param", ce))
-        self.slots[key + ".weight"] = TensorSlot("param", spec["w_off"], (cout, cin, k, k), (k * k * cin, 1, k * cin, cin))
-        self.slots[key + ".bias"] = TensorSlot("param", spec["bias_off"], (cout,), (1,))
-        self.convs[key] = spec
+        """every SSD convolution has a bias; ``construct``: drawn in state_dict order (the heads are not: ``construction``)"""
+        spec = super().conv(key, cout, cin, k, bias=True, stride=stride, pad=pad, dil=dil)
         if construct:
             self.construction.append(key)
         return spec
-
-    def bn(self, key, c, spec):
-        spec.update(gamma_off=self._take("param", c), beta_off=self._take("param", c), rmean_off=self._take("stat", c),
-                    rvar_off=self._take("stat", c))
-        self.slots[key + ".weight"] = TensorSlot("param", spec["gamma_off"], (c,), (1,))
-        self.slots[key + ".bias"] = TensorSlot("param", spec["beta_off"], (c,), (1,))
-        self.slots[key + ".running_mean"] = TensorSlot("stat", spec["rmean_off"], (c,), (1,), False)
-        self.slots[key + ".running_var"] = TensorSlot("stat", spec["rvar_off"], (c,), (1,), False)
-        self.slots[key + ".num_batches_tracked"] = TensorSlot("nbt", len(self.nbt_keys), (), (), False)
-        self.nbt_keys.append(key + ".num_batches_tracked")
 
 
 def conv_out(n, k, stride, pad, dil=1):
@@ -195,70 +168,24 @@ def build_ssd_graph(lay: SsdLayout, H: int, W: int) -> Graph:
     return g
 
 
-class _Holder(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise L.CvxError("parameter holder: the engine executes the whole graph (call the SSD model)")
-
-
-class SSD300VGG(nn.Module):
+class SSD300VGG(ArenaModel):
     """``SSD(cfg)`` of the reference (ssd_model.py:131-191) on the engine: ``model(x)`` returns (loc (B, 8732, 4), conf (B, 8732, nc + 1))
     fp32.  In training mode (grad enabled) the two tensors are connected to the engine's backward pass (VGG16-BN with batch
     statistics behind biased convolutions, ceil-mode and 3x3 stride-1 max pools, L2Normalize and its weight, the bias-only extra
     layers and heads): any torch loss on them -- the reference's MultiBoxLossV2 is torch code on exactly these tensors -- trains it."""
 
+    bn_eps_momentum = (BN_EPS, BN_MOMENTUM)
+
     def __init__(self, num_classes: int = 20, loss_scale: float = 1024.0):
-        super().__init__()
-        self.layout = lay = SsdLayout(num_classes)
-        self.num_classes = num_classes
-        self.loss_scale = float(loss_scale)
-        self._flat = {"param": torch.zeros(lay.n_params), "stat": torch.zeros(lay.n_stats), "nbt": torch.zeros(len(lay.nbt_keys), dtype=torch.long),
-                      "grad": None}
-        self._anchor = torch.zeros(1, requires_grad=True)
-        self._grads_attached = False
-        self._engines: Dict = {}
-        self._build_tree()
-        self._attach_views()
-        self._init_like_reference()
+        super().__init__(SsdLayout(num_classes), num_classes, loss_scale)
         self.last_rows = None
 
-    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
+    def _build_graph(self, h, w):
+        return build_ssd_graph(self.layout, h, w)
 
-    def _build_tree(self):
-        for key in self.layout.slots:
-            mod = self
-            for name in key.split(".")[:-1]:
-                if name not in mod._modules:
-                    mod.add_module(name, _Holder())
-                mod = mod._modules[name]
-
-    def _attach_views(self):
-        for key, sl in self.layout.slots.items():
-            mod = self
-            parts = key.split(".")
-            for name in parts[:-1]:
-                mod = mod._modules[name]
-            if sl.arena == "nbt":
-                mod._buffers[parts[-1]] = self._flat["nbt"][sl.offset]
-                continue
-            view = torch.as_strided(self._flat[sl.arena], sl.shape, sl.strides, sl.offset)
-            if sl.trainable:
-                old = mod._parameters.get(parts[-1])
-                mod._parameters[parts[-1]] = nn.Parameter(view, requires_grad=True if old is None else old.requires_grad)
-            else:
-                mod._buffers[parts[-1]] = view
-
-    def _apply(self, fn, recurse=True):
-        self._flat["grad"] = None
-        self._grads_attached = False
-        self._anchor = fn(self._anchor.detach()).requires_grad_(True)
-        for k in ("param", "stat", "nbt"):
-            t_ = fn(self._flat[k])
-            if k != "nbt" and t_.dtype != torch.float32:
-                raise L.CvxError("the engine keeps fp32 master parameters; half()/bfloat16() are not supported (compute is fp16 inside)")
-            self._flat[k] = t_.long().contiguous() if k == "nbt" else t_.contiguous()
-        self._attach_views()
-        self._engines.clear()
-        return self
+    def _check_input(self, x, training):
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("expected images of shape (B, 3, 300, 300)")
 
     def _init_like_reference(self):
         lay = self.layout
@@ -283,55 +210,6 @@ class SSD300VGG(nn.Module):
                         sd[key].zero_()
             sd["l2_norm.weight"].fill_(20.0)
             self._flat["nbt"].zero_()
-
-    def engine_for(self, h: int, w: int) -> Engine:
-        dev = self._flat["param"].device
-        key = (h, w, dev)
-        eng = self._engines.get(key)
-        if eng is None:
-            if dev.type != "cuda":
-                raise L.CvxError("SSD300VGG runs on an MI355X only: move the model with .to('cuda') first (there is no CPU fallback)")
-            eng = Engine(build_ssd_graph(self.layout, h, w), dev)
-            eng.set_bn(BN_EPS, BN_MOMENTUM)
-            self._engines[key] = eng
-        eng.bind(self._flat["param"], self.flat_grads if self.training else self._flat["grad"], self._flat["stat"])
-        return eng
-
-    @property
-    def flat_params(self) -> torch.Tensor:
-        return self._flat["param"]
-
-    @property
-    def flat_stats(self) -> torch.Tensor:
-        return self._flat["stat"]
-
-    @property
-    def flat_grads(self) -> torch.Tensor:
-        if self._flat["grad"] is None or self._flat["grad"].device != self._flat["param"].device:
-            self._flat["grad"] = torch.zeros_like(self._flat["param"])
-            self._grads_attached = False
-        return self._flat["grad"]
-
-    def attach_grads(self):
-        """Make ``p.grad`` of every parameter a view of the flat gradient arena (torch optimisers / GradScaler)."""
-        g = self.flat_grads
-        modules = dict(self.named_modules())
-        for key, slot in self.layout.slots.items():
-            if not slot.trainable:
-                continue
-            mod_name, attr = key.rsplit(".", 1)
-            modules[mod_name]._parameters[attr].grad = torch.as_strided(g, slot.shape, slot.strides, slot.offset)
-        self._grads_attached = True
-
-    def _run_forward(self, x: torch.Tensor, training: bool) -> torch.Tensor:
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected images of shape (B, 3, 300, 300)")
-        eng = self.engine_for(int(x.shape[2]), int(x.shape[3]))
-        self._last_engine = eng
-        rows = eng.forward(x, training)
-        if training:
-            self._flat["nbt"] += 1
-        return rows
 
     def forward_rows(self, x: torch.Tensor) -> torch.Tensor:
         return self._run_forward(x, self.training)
@@ -380,17 +258,8 @@ class SSD300VGG(nn.Module):
             if gc is not None:
                 L.check(lib.cvx_nchw_cols_grad_to_pred(L.ptr(gc), tot * nc1, co, n * nc1, B, eng.graph.anchors, a_off, hw, scale,
                                                        L.ptr(dpred), lay.pred_ld, LOC_COLS, st), "conf grad")
-        first = next(p for p in self.parameters() if p.requires_grad)
-        if first.grad is None:               # optimizer.zero_grad(set_to_none=True) happened (or first step)
-            self.flat_grads.zero_()
-            self._grads_attached = False
         self.last_dpred = dpred
-        if run_backward is not None:                              # (the data-parallel step runs it bucket by bucket)
-            run_backward(eng, dpred, scale)
-        else:
-            eng.backward(dpred, scale)
-        if not self._grads_attached or first.grad is None:
-            self.attach_grads()
+        self._engine_backward(dpred, scale, run_backward)
 
     def forward(self, x: torch.Tensor):
         if self.training and torch.is_grad_enabled():
@@ -469,44 +338,18 @@ class MultiBoxLoss:
         return items[0], items[1], items[2]
 
 
-class SsdTrainStep:
+class SsdTrainStep(EngineTrainStep):
     """One optimisation step of the reference's ``SsdTrainer.train_loop`` (core/trainer/ssd_train.py: zero_grad -> forward ->
     MultiBoxLossV2 -> backward -> Adam under AMP) as C-ABI calls: engine forward (training), the NCHW-order flattening, ``cvx_multibox_loss``,
     its adjoint onto the prediction rows, engine backward, [gradient sum over the ranks], fused Adam with GradScaler's inf/nan check."""
 
-    def __init__(self, model: SSD300VGG, criterion: MultiBoxLoss, optimizer, scaler=None, process_group=None, n_buckets: int = 4):
-        self.model, self.criterion, self.optimizer, self.scaler = model, criterion, optimizer, scaler
-        self.pg, self.n_buckets = process_group, n_buckets
-        self.world, self.distributed = 1, False
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-            self.distributed = True
-        self._side = None
-
     def __call__(self, images: torch.Tensor, y_true: torch.Tensor) -> torch.Tensor:
-        from .engine import check_finite
-        m, crit = self.model, self.criterion
-        if not m.training:
-            raise L.CvxError("SsdTrainStep: call model.train() first")
-        dev = m.flat_params.device
-        self.optimizer.sync_lr()
+        m = self.model
+        scale = self._begin()
         B, nc1 = int(images.shape[0]), m.num_classes + 1
         m.last_rows = m._run_forward(images, True)
         loc, conf = m._rows_to_outputs(m.last_rows)
-        scale = self.scaler.begin_step() if self.scaler is not None else m.loss_scale
-        items, dloc, dconf = crit.op(loc.view(B, -1, 4), conf.view(B, -1, nc1), y_true)
-        if self.distributed and dev.type == "cuda":               # gradient exchange overlapped with the backward pass, bucket by bucket
-            if self._side is None:
-                from .train import OverlappedExchange
-                self._side = OverlappedExchange(self.pg, self.n_buckets)
-            m._backward_outputs(dloc.view(B, -1), dconf.view(B, -1), scale,
-                                run_backward=lambda eng, dpred, sc: self._side.backward(eng, m.flat_grads, dpred, sc))
-        else:
-            m._backward_outputs(dloc.view(B, -1), dconf.view(B, -1), scale)
-        if self.scaler is not None:
-            check_finite(m.flat_grads, self.scaler.found_inf)
-            self.optimizer.found_inf = self.scaler.found_inf
-        self.optimizer.step(zero_grad=True, grad_scale=1.0 / self.world)
-        if self.scaler is not None:
-            self.scaler.end_step()
+        items, dloc, dconf = self.criterion.op(loc.view(B, -1, 4), conf.view(B, -1, nc1), y_true)
+        m._backward_outputs(dloc.view(B, -1), dconf.view(B, -1), scale, run_backward=self._backward)
+        self._update()
         return items

@@ -18,7 +18,8 @@ import ctypes as C
 import os
 
 from . import _lib as L
-from .engine import V8LossOp, _note_param_write, adam_ema_step_dev, adam_step, adam_step_dev, check_finite, ema_update
+from .arena import EngineTrainStep
+from .engine import V8LossOp, _note_param_write, adam_ema_step_dev, adam_step, adam_step_dev, ema_update
 from .graph import STRIDES
 from .model import PredList, Yolo8
 
@@ -332,7 +333,7 @@ class CvxComm:
             pass
 
 
-class FusedTrainStep:
+class FusedTrainStep(EngineTrainStep):
     """One optimisation step = forward, loss(+grad), backward, optional DP all-reduce, Adam.
 
     With ``world_size > 1`` (``torch.distributed`` initialised, backend nccl == RCCL) the flat gradient
@@ -342,26 +343,16 @@ class FusedTrainStep:
 
     def __init__(self, model: Yolo8, criterion: V8DetectionLoss, optimizer: FlatAdam, process_group=None, n_buckets: int = 4,
                  scaler: Optional[DynamicLossScale] = None, comm: Optional["CvxComm"] = None):
-        self.model, self.criterion, self.optimizer = model, criterion, optimizer
+        super().__init__(model, criterion, optimizer, scaler, process_group, n_buckets)   # scaler None: static loss scale (criterion.loss_scale)
         self.comm = comm               # CvxComm: the exchange runs behind the C ABI (cvx_engine_backward_exchange) instead of torch.distributed
-        self.scaler = scaler           # None: static loss scale (criterion.loss_scale)
-        self.pg = process_group
-        self.n_buckets = n_buckets
         # (Launches are eager.  The hipGraph replay of the step was removed in round 5: the multi-stream capture could not run under the
         # package's own default of one hardware queue, measured 13.9 ms under four, and even a single-stream chain replays no faster than it
         # launches -- profiles/r05_graph_main_chain_ab.txt.)
-        self.world = 1
-        self.distributed = False
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-            self.distributed = True     # a 1-rank group still exercises the RCCL exchange path (bench.py CVX_FORCE_DIST)
-        if comm is not None:
+        if comm is not None:           # (a 1-rank group still exercises the RCCL exchange path: bench.py CVX_FORCE_DIST)
             self.world, self.distributed = comm.world, True
         self._pred = None
         self._dpred = None
-        self._side = None
         self._buckets, self._buckets_key = None, None
-        self.found_inf = None
 
     def __call__(self, images: torch.Tensor, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         self.optimizer.sync_lr()
@@ -377,20 +368,14 @@ class FusedTrainStep:
             self._pred = torch.empty(B, A, no, device=dev)
             self._dpred = torch.zeros(B, A, no, device=dev, dtype=torch.float16)   # the loss never writes the padding
         targets = flatten_targets(batch, dev)
-        dynamic = self.scaler is not None
-        scale = self.scaler.begin_step() if dynamic else crit.loss_scale
+        scale = self.scaler.begin_step() if self.scaler is not None else crit.loss_scale
         pred = m._run_forward(images, training=True, pred=self._pred)
         items, dpred = crit.op(pred, targets, m.level_shapes(H, W), STRIDES, scale, self._dpred)
         if self.distributed and dev.type == "cuda":
             self._backward_overlapped(eng, dpred, scale)
         else:
             eng.backward(dpred, scale)
-        if dynamic:                                  # GradScaler.step: skip the update when a gradient is not finite
-            check_finite(m.flat_grads, self.scaler.found_inf)
-            self.optimizer.found_inf = self.scaler.found_inf
-        self.optimizer.step(zero_grad=True, grad_scale=1.0 / self.world)
-        if dynamic:
-            self.scaler.end_step()
+        self._update()
         return items
 
     def _backward_overlapped(self, eng, dpred, loss_scale):

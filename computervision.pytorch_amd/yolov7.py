@@ -14,7 +14,7 @@ Mirrors ``core/models/yolov7_model.py:14-525`` (phi = 'l') of the reference as a
 * the three heads write fp32 rows (B, 400 + 1600 + 6400, 3 * (5 + nc) padded to 8) in the order of the reference's outputs
   (coarsest first); ``forward`` returns them as the reference's NCHW tensors, ``cvx_yolo7_decode`` reads the rows in place.
 
-``state_dict``: the reference's 558 keys / shapes / order, bit-identical to ``Yolo7(cfg)`` (``cfg.train.pretrained = False``)
+``state_dict`` (views of flat arenas, arena.py): the reference's 558 keys / shapes / order, bit-identical to ``Yolo7(cfg)`` (``cfg.train.pretrained = False``)
 under the same global seed.
 
 Training (``model.train()``): the same graph with batch-statistics BatchNorm and the backward of every op; ``Yolo7Loss`` (csrc/loss_yolov7.hip,
@@ -23,16 +23,14 @@ SimOTA matching included) and ``Yolo7TrainStep`` below are the reference's ``tra
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
-from typing import Dict, Optional, List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .ema import clone_model
-from .engine import Engine
-from .graph import Graph, TensorSlot
+from .arena import ArenaLayout, ArenaModel, EngineTrainStep
+from .graph import Graph
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03                 # ConvBNSiLU / RepConv BatchNorms (yolov7_model.py:18,195-203)
 TC, BC, PC, E, N = 32, 32, 32, 2, 4               # phi = 'l' (yolov7_model.py:366-371)
@@ -77,18 +75,15 @@ REP = (("rep_conv_1", 4 * TC, 8 * TC), ("rep_conv_2", 8 * TC, 16 * TC), ("rep_co
 HEADS = (("yolo_head_P3", 8 * TC), ("yolo_head_P4", 16 * TC), ("yolo_head_P5", 32 * TC))
 
 
-class Yolo7Layout:
+class Yolo7Layout(ArenaLayout):
     """Arena offsets for every tensor of the reference's Yolo7 ``state_dict`` (same keys, shapes, order)."""
 
     def __init__(self, nc: int = 20):
+        super().__init__()
         self.nc = nc
         self.no = 3 * (5 + nc)
         self.no_pad = (self.no + 7) & ~7
-        self.slots: "OrderedDict[str, TensorSlot]" = OrderedDict()
-        self.nbt_keys: List[str] = []
-        self.convs: Dict[str, dict] = {}
         self.init_order: List[tuple] = []                       # ("conv" | "bn", key) in modules() order
-        self._p = self._s = 0
         for key, cout, cin, k, s in conv_bn_specs():
             self.conv_bn(key + ".conv", key + ".bn", cout, cin, k, stride=s)
         for key, c1, c2 in REP:
@@ -96,37 +91,15 @@ class Yolo7Layout:
             self.conv_bn(key + ".rbr_1x1.0", key + ".rbr_1x1.1", c2, c1, 1)
         for key, c in HEADS:
             self.conv(key, self.no, c, 1, bias=True)
-        self.n_params = (self._p + 3) & ~3
-        self.n_stats = (self._s + 3) & ~3
-
-    def _take(self, arena, n):
-        if arena == "param":
-            off, self._p = self._p, (self._p + n + 3) & ~3
-        else:
-            off, self._s = self._s, (self._s + n + 3) & ~3
-        return off
+        self._finish()
 
     def conv(self, key, cout, cin, k, bias=False, stride=1):
-        ce = (cout + 7) & ~7
-        spec = dict(cout=cout, cout_eng=ce, cin=cin, k=k, stride=stride, w_off=self._take("param", ce * k * k * cin))
-        self.slots[key + ".weight"] = TensorSlot("param", spec["w_off"], (cout, cin, k, k), (k * k * cin, 1, k * cin, cin))
-        if bias:
-            spec["bias_off"] = self._take("param", ce)
-            self.slots[key + ".bias"] = TensorSlot("param", spec["bias_off"], (cout,), (1,))
-        self.convs[key] = spec
+        spec = super().conv(key, cout, cin, k, bias=bias, stride=stride)
         self.init_order.append(("conv", key))
         return spec
 
     def conv_bn(self, ckey, bkey, cout, cin, k, stride=1):
-        spec = self.conv(ckey, cout, cin, k, stride=stride)
-        spec.update(gamma_off=self._take("param", cout), beta_off=self._take("param", cout), rmean_off=self._take("stat", cout),
-                    rvar_off=self._take("stat", cout))
-        self.slots[bkey + ".weight"] = TensorSlot("param", spec["gamma_off"], (cout,), (1,))
-        self.slots[bkey + ".bias"] = TensorSlot("param", spec["beta_off"], (cout,), (1,))
-        self.slots[bkey + ".running_mean"] = TensorSlot("stat", spec["rmean_off"], (cout,), (1,), False)
-        self.slots[bkey + ".running_var"] = TensorSlot("stat", spec["rvar_off"], (cout,), (1,), False)
-        self.slots[bkey + ".num_batches_tracked"] = TensorSlot("nbt", len(self.nbt_keys), (), (), False)
-        self.nbt_keys.append(bkey + ".num_batches_tracked")
+        super().conv_bn(ckey, bkey, cout, cin, k, stride=stride)
         self.init_order.append(("bn", bkey))
 
 
@@ -268,71 +241,21 @@ def build_yolov7_graph(lay: Yolo7Layout, H: int, W: int) -> Graph:
     return g
 
 
-class _Holder(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise L.CvxError("parameter holder: the engine executes the whole graph (call the YOLOv7 model)")
-
-
-class Yolo7L(nn.Module):
+class Yolo7L(ArenaModel):
     """``Yolo7(cfg)`` of the reference (phi 'l', yolov7_model.py:355-525) on the engine: ``model(x)`` returns (out0, out1, out2),
     each (B, 3 * (5 + nc), H_l, W_l) fp32, coarsest level first.  In training mode (grad enabled) the outputs are connected to the
     engine's backward pass: any torch loss on them (the reference's Yolo7Loss is plain torch code on these tensors,
     core/loss/yolo7_loss.py) back-propagates into batch-statistics BatchNorm, the RepConv sum inside the SiLU, 2x2 / 5x5 max pools,
     upsampling and every convolution's data / weight gradient; parameter gradients land in ``p.grad`` (views of one flat arena)."""
 
+    bn_eps_momentum = (BN_EPS, BN_MOMENTUM)
+
     def __init__(self, num_classes: int = 20, loss_scale: float = 1024.0):
-        super().__init__()
-        self.layout = lay = Yolo7Layout(num_classes)
-        self.num_classes = num_classes
-        self.loss_scale = float(loss_scale)
-        self._flat = {"param": torch.zeros(lay.n_params), "stat": torch.zeros(lay.n_stats), "nbt": torch.zeros(len(lay.nbt_keys), dtype=torch.long),
-                      "grad": None}
-        self._anchor = torch.zeros(1, requires_grad=True)
-        self._grads_attached = False
-        self._engines: Dict = {}
-        self._build_tree()
-        self._attach_views()
-        self._init_like_reference()
+        super().__init__(Yolo7Layout(num_classes), num_classes, loss_scale)
         self.last_rows = None
 
-    __deepcopy__ = clone_model       # copy.deepcopy(model): arenas copied, views rebuilt (ema.py)
-
-    def _build_tree(self):
-        for key in self.layout.slots:
-            mod = self
-            for name in key.split(".")[:-1]:
-                if name not in mod._modules:
-                    mod.add_module(name, _Holder())
-                mod = mod._modules[name]
-
-    def _attach_views(self):
-        for key, sl in self.layout.slots.items():
-            mod = self
-            parts = key.split(".")
-            for name in parts[:-1]:
-                mod = mod._modules[name]
-            if sl.arena == "nbt":
-                mod._buffers[parts[-1]] = self._flat["nbt"][sl.offset]
-                continue
-            view = torch.as_strided(self._flat[sl.arena], sl.shape, sl.strides, sl.offset)
-            if sl.trainable:
-                old = mod._parameters.get(parts[-1])
-                mod._parameters[parts[-1]] = nn.Parameter(view, requires_grad=True if old is None else old.requires_grad)
-            else:
-                mod._buffers[parts[-1]] = view
-
-    def _apply(self, fn, recurse=True):
-        self._flat["grad"] = None
-        self._grads_attached = False
-        self._anchor = fn(self._anchor.detach()).requires_grad_(True)
-        for k in ("param", "stat", "nbt"):
-            t_ = fn(self._flat[k])
-            if k != "nbt" and t_.dtype != torch.float32:
-                raise L.CvxError("the engine keeps fp32 master parameters; half()/bfloat16() are not supported (compute is fp16 inside)")
-            self._flat[k] = t_.long().contiguous() if k == "nbt" else t_.contiguous()
-        self._attach_views()
-        self._engines.clear()
-        return self
+    def _build_graph(self, h, w):
+        return build_yolov7_graph(self.layout, h, w)
 
     def _init_like_reference(self):
         """The reference's draws from the global RNG: every nn.Conv2d's default init at construction (weight, then bias), module
@@ -367,47 +290,8 @@ class Yolo7L(nn.Module):
                     sd[key + ".running_var"].fill_(1.0)
             self._flat["nbt"].zero_()
 
-    # ---- engine plumbing ---------------------------------------------------------------------------------
-    @property
-    def flat_params(self) -> torch.Tensor:
-        return self._flat["param"]
-
-    @property
-    def flat_stats(self) -> torch.Tensor:
-        return self._flat["stat"]
-
-    @property
-    def flat_grads(self) -> torch.Tensor:
-        if self._flat["grad"] is None or self._flat["grad"].device != self._flat["param"].device:
-            self._flat["grad"] = torch.zeros_like(self._flat["param"])
-            self._grads_attached = False
-        return self._flat["grad"]
-
-    def engine_for(self, h: int, w: int) -> Engine:
-        dev = self._flat["param"].device
-        key = (h, w, dev)
-        eng = self._engines.get(key)
-        if eng is None:
-            if dev.type != "cuda":
-                raise L.CvxError("Yolo7L runs on an MI355X only: move the model with .to('cuda') first (there is no CPU fallback)")
-            eng = Engine(build_yolov7_graph(self.layout, h, w), dev)
-            eng.set_bn(BN_EPS, BN_MOMENTUM)
-            self._engines[key] = eng
-        eng.bind(self._flat["param"], self.flat_grads if self.training else self._flat["grad"], self._flat["stat"])
-        return eng
-
-    def _run_forward(self, x: torch.Tensor, training: bool) -> torch.Tensor:
-        """(B,3,H,W) -> the engine's fp32 head rows (B, sum_l H_l*W_l, no_pad): what ``cvx_yolo7_decode`` reads."""
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected images of shape (B, 3, H, W)")
-        eng = self.engine_for(int(x.shape[2]), int(x.shape[3]))
-        self._last_engine = eng
-        rows = eng.forward(x, training)
-        if training:
-            self._flat["nbt"] += 1
-        return rows
-
     def forward_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """(B,3,H,W) -> the engine's fp32 head rows (B, sum_l H_l*W_l, no_pad): what ``cvx_yolo7_decode`` reads."""
         return self._run_forward(x, self.training)
 
     def _rows_to_levels(self, rows: torch.Tensor):
@@ -422,17 +306,6 @@ class Yolo7L(nn.Module):
             a_off += hh * ww
         return outs
 
-    def attach_grads(self):
-        """Make ``p.grad`` of every parameter a view of the flat gradient arena (torch optimisers / GradScaler)."""
-        g = self.flat_grads
-        modules = dict(self.named_modules())
-        for key, slot in self.layout.slots.items():
-            if not slot.trainable:
-                continue
-            mod_name, attr = key.rsplit(".", 1)
-            modules[mod_name]._parameters[attr].grad = torch.as_strided(g, slot.shape, slot.strides, slot.offset)
-        self._grads_attached = True
-
     def _backward_levels(self, grads):
         """Gradients w.r.t. the three (B, no_pad, h, w) level tensors -> loss_scale * dLoss/drows in fp16 -> engine backward."""
         eng, lay, lib = self._last_engine, self.layout, L.load()
@@ -445,14 +318,8 @@ class Yolo7L(nn.Module):
                 L.check(lib.cvx_nchw_grad_to_dpred(L.ptr(g.contiguous().float()), B, A, lay.no_pad, a_off, hh, ww, self.loss_scale, L.ptr(dpred),
                                                    L.stream_ptr(ref.device)), "cvx_nchw_grad_to_dpred")
             a_off += hh * ww
-        first = next(p for p in self.parameters() if p.requires_grad)
-        if first.grad is None:               # optimizer.zero_grad(set_to_none=True) happened (or first step)
-            self.flat_grads.zero_()
-            self._grads_attached = False
         self.last_dpred = dpred
-        eng.backward(dpred, self.loss_scale)
-        if not self._grads_attached or first.grad is None:
-            self.attach_grads()
+        self._engine_backward(dpred, self.loss_scale)
 
     def forward(self, x: torch.Tensor):
         if self.training and torch.is_grad_enabled():
@@ -496,14 +363,7 @@ class _Y7LossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        m = ctx.model
-        first = next(p for p in m.parameters() if p.requires_grad)
-        if first.grad is None:
-            m.flat_grads.zero_()
-            m._grads_attached = False
-        m._last_engine.backward(ctx.dpred, m.loss_scale / float(gout))
-        if not m._grads_attached or first.grad is None:
-            m.attach_grads()
+        ctx.model._engine_backward(ctx.dpred, ctx.model.loss_scale / float(gout))
         return None, None, None, None, None
 
 
@@ -567,44 +427,21 @@ class Yolo7Loss:
         return it[0], it[1], it[2], it[3]
 
 
-class Yolo7TrainStep:
+class Yolo7TrainStep(EngineTrainStep):
     """One optimisation step of the reference's ``Yolo7Trainer.train_loop`` (core/trainer/yolo7_train.py:79-97) as C-ABI calls: engine
     forward (training), ``cvx_yolo7_loss``, engine backward, [gradient sum over the ranks], fused Adam with GradScaler's inf/nan check."""
 
-    def __init__(self, model: Yolo7L, criterion: Yolo7Loss, optimizer, scaler=None, process_group=None, n_buckets: int = 4):
-        self.model, self.criterion, self.optimizer, self.scaler = model, criterion, optimizer, scaler
-        self.pg, self.n_buckets = process_group, n_buckets
-        self.world, self.distributed = 1, False
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-            self.distributed = True
-        self._dpred = self._side = None
+    _dpred = None
 
     def __call__(self, images: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-        from .engine import check_finite
-        m, crit = self.model, self.criterion
-        if not m.training:
-            raise L.CvxError("Yolo7TrainStep: call model.train() first")
-        dev = m.flat_params.device
-        self.optimizer.sync_lr()
+        m = self.model
+        scale = self._begin()
         rows = m._run_forward(images, True)
         m.last_rows = rows
         eng = m._last_engine
         if self._dpred is None or self._dpred.shape != rows.shape:
-            self._dpred = torch.empty(rows.shape, device=dev, dtype=torch.float16)
-        scale = self.scaler.begin_step() if self.scaler is not None else m.loss_scale
-        items, dpred = crit.op(rows, eng.graph.level_hw, targets, float(images.shape[2]), scale, self._dpred)
-        if self.distributed and dev.type == "cuda":               # gradient exchange overlapped with the backward pass, bucket by bucket
-            if self._side is None:
-                from .train import OverlappedExchange
-                self._side = OverlappedExchange(self.pg, self.n_buckets)
-            self._side.backward(eng, m.flat_grads, dpred, scale)
-        else:
-            eng.backward(dpred, scale)
-        if self.scaler is not None:
-            check_finite(m.flat_grads, self.scaler.found_inf)
-            self.optimizer.found_inf = self.scaler.found_inf
-        self.optimizer.step(zero_grad=True, grad_scale=1.0 / self.world)
-        if self.scaler is not None:
-            self.scaler.end_step()
+            self._dpred = torch.empty(rows.shape, device=rows.device, dtype=torch.float16)
+        items, dpred = self.criterion.op(rows, eng.graph.level_hw, targets, float(images.shape[2]), scale, self._dpred)
+        self._backward(eng, dpred, scale)
+        self._update()
         return items
