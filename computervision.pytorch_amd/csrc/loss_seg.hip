@@ -17,6 +17,12 @@
 //   K2 resize_grad_rows adjoint of the bilinear resize as a gather (deterministic): one thread per (image, class, source pixel)
 //                       collects the label pixels that interpolate from it -> dpred (B, ih*iw, ld) fp16
 //   K3 finalize         loss = sum / normaliser
+//
+// Evaluation (cvx_seg_eval, the reference's evaluate_loop, segmentation_trainer.py:133-159, and evaluate_on_voc,
+// segmentation_2d.py:146-157): seg_eval_kernel walks the label pixels the same way -- the same taps, the same online softmax, the same
+// loss definitions -- and keeps the arg max instead of a gradient: confusion[target][argmax] += 1 and the batch's criterion value, with
+// no (B, nc, H, W) tensor and no gradient written.  K3 finishes its loss sum.
+#include "bilinear.h"
 #include "cvx_common.h"
 #include "../../include/cvx_engine.h"
 
@@ -24,14 +30,85 @@ namespace {
 
 constexpr int SEG_MAX_NC = 4096;  // sanity bound only: the kernels loop over the classes
 
-__device__ __forceinline__ void bilinear_src(int d, float scale, int in_size, int* i0, int* i1, float* lam) {
-  float s = ((float)d + 0.5f) * scale - 0.5f;
-  if (s < 0.f) s = 0.f;
-  int a = (int)s;
-  if (a > in_size - 1) a = in_size - 1;
-  *i0 = a;
-  *i1 = a + (a < in_size - 1 ? 1 : 0);
-  *lam = s - (float)a;
+// The four source rows of one label pixel and its weights; logit(c) is the value cvx_resize_bilinear_rows_to_nchw writes for class c
+// there (bilinear_src / bilinear_mix, bilinear.h).
+struct PixelTaps {
+  const float *r00, *r01, *r10, *r11;
+  float lx, ly;
+  __device__ __forceinline__ PixelTaps(const float* rows, int ld, int b, int ih, int iw, int OH, int OW, int oy, int ox) {
+    int y0, y1, x0, x1;
+    bilinear_src(oy, (float)ih / (float)OH, ih, &y0, &y1, &ly);
+    bilinear_src(ox, (float)iw / (float)OW, iw, &x0, &x1, &lx);
+    const float* base = rows + (long long)b * ih * iw * ld;
+    r00 = base + ((long long)y0 * iw + x0) * ld;
+    r01 = base + ((long long)y0 * iw + x1) * ld;
+    r10 = base + ((long long)y1 * iw + x0) * ld;
+    r11 = base + ((long long)y1 * iw + x1) * ld;
+  }
+  __device__ __forceinline__ float logit(int c) const { return bilinear_mix(r00[c], r01[c], r10[c], r11[c], lx, ly); }
+  // eight classes at a time with 16-byte loads issued together (rows with ld % 8 == 0 on a 16-byte boundary)
+  __device__ __forceinline__ void logits8(int c0, float* z) const {
+    float a[8], bq[8], cq[8], d[8];
+    *reinterpret_cast<float4*>(a) = *reinterpret_cast<const float4*>(r00 + c0);
+    *reinterpret_cast<float4*>(a + 4) = *reinterpret_cast<const float4*>(r00 + c0 + 4);
+    *reinterpret_cast<float4*>(bq) = *reinterpret_cast<const float4*>(r01 + c0);
+    *reinterpret_cast<float4*>(bq + 4) = *reinterpret_cast<const float4*>(r01 + c0 + 4);
+    *reinterpret_cast<float4*>(cq) = *reinterpret_cast<const float4*>(r10 + c0);
+    *reinterpret_cast<float4*>(cq + 4) = *reinterpret_cast<const float4*>(r10 + c0 + 4);
+    *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(r11 + c0);
+    *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(r11 + c0 + 4);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) z[k] = bilinear_mix(a[k], bq[k], cq[k], d[k], lx, ly);
+  }
+};
+
+// f(c, logit) for every class in order.  Rows with ld % 8 == 0 (the engine's: 16-byte aligned, padded to 8 columns) take logits8; a class
+// loop of scalar loads waits for memory 4 * nc times per pass.
+template <class F>
+__device__ __forceinline__ void each_logit(const PixelTaps& tp, int nc, bool vec, F f) {
+  if (vec) {
+    for (int c0 = 0; c0 < nc; c0 += 8) {
+      float z[8];
+      tp.logits8(c0, z);
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c0 + k < nc) f(c0 + k, z[k]);
+    }
+  } else {
+    for (int c = 0; c < nc; ++c) f(c, tp.logit(c));
+  }
+}
+
+// The criterion's value of one valid pixel from its cross-entropy, and d loss / d ce.
+__device__ __forceinline__ float pixel_loss(float ce, int mode, float alpha, float gamma, float* coef) {
+  if (mode == 0) {
+    const float pt = expf(-ce);
+    const float om = fmaxf(1.f - pt, 0.f);
+    const float w = powf(om, gamma);
+    // d/dce [alpha (1 - pt)^gamma ce], d pt / d ce = -pt
+    *coef = alpha * (w + (gamma > 0.f ? gamma * powf(om, gamma - 1.f) * pt * ce : 0.f));
+    return alpha * w * ce;
+  }
+  *coef = 1.f;
+  return ce;
+}
+
+// Block sums of (loss, valid pixels) in a fixed order; one pair per workgroup, summed in index order by seg_loss_finalize_kernel
+// (deterministic, no same-address atomics).
+__device__ __forceinline__ void block_pair_to_part(double my_loss, double my_cnt, double* s_sum, double* s_cnt, double* part) {
+  for (int o = 32; o > 0; o >>= 1) {
+    my_loss += __shfl_xor(my_loss, o);
+    my_cnt += __shfl_xor(my_cnt, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_sum[threadIdx.x >> 6] = my_loss;
+    s_cnt[threadIdx.x >> 6] = my_cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[2 * (long long)blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+    part[2 * (long long)blockIdx.x + 1] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+  }
 }
 
 // mode 0: focal (alpha, gamma), mean over ALL pixels (ignored ones count in the denominator: focal_loss.mean());
@@ -48,43 +125,13 @@ __global__ __launch_bounds__(256) void seg_loss_pixel_kernel(const float* rows, 
     long long t = i / OW;
     const int oy = (int)(t % OH);
     const int b = (int)(t / OH);
-    int y0, y1, x0, x1;
-    float ly, lx;
-    bilinear_src(oy, (float)ih / (float)OH, ih, &y0, &y1, &ly);
-    bilinear_src(ox, (float)iw / (float)OW, iw, &x0, &x1, &lx);
-    const float* base = rows + (long long)b * ih * iw * ld;
-    const float* r00 = base + ((long long)y0 * iw + x0) * ld;
-    const float* r01 = base + ((long long)y0 * iw + x1) * ld;
-    const float* r10 = base + ((long long)y1 * iw + x0) * ld;
-    const float* r11 = base + ((long long)y1 * iw + x1) * ld;
-    auto logit = [&](int c) {
-      const float top = r00[c] * (1.f - lx) + r01[c] * lx, bot = r10[c] * (1.f - lx) + r11[c] * lx;
-      return top * (1.f - ly) + bot * ly;
-    };
+    const PixelTaps tp(rows, ld, b, ih, iw, OH, OW, oy, ox);
     const long long tg = target[i];
     const bool ignored = tg == ignore_index;
     const bool valid = !ignored && tg >= 0 && tg < nc;
     if (!ignored && !valid) atomicOr(bad, 1);  // torch raises a device assert here
     // pass 1: running maximum and rescaled sum of exponentials (no per-thread array: the class count is a run-time value)
-    // rows with ld % 8 == 0 (the engine's: 16-byte aligned, padded to 8 columns) are read eight classes at a time with 16-byte loads
-    // issued together; a class loop of scalar loads waits for memory 4 * nc times per pass
     const bool vec = (ld & 7) == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
-    auto logits8 = [&](int c0, float* z) {
-      float a[8], bq[8], cq[8], d[8];
-      *reinterpret_cast<float4*>(a) = *reinterpret_cast<const float4*>(r00 + c0);
-      *reinterpret_cast<float4*>(a + 4) = *reinterpret_cast<const float4*>(r00 + c0 + 4);
-      *reinterpret_cast<float4*>(bq) = *reinterpret_cast<const float4*>(r01 + c0);
-      *reinterpret_cast<float4*>(bq + 4) = *reinterpret_cast<const float4*>(r01 + c0 + 4);
-      *reinterpret_cast<float4*>(cq) = *reinterpret_cast<const float4*>(r10 + c0);
-      *reinterpret_cast<float4*>(cq + 4) = *reinterpret_cast<const float4*>(r10 + c0 + 4);
-      *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(r11 + c0);
-      *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(r11 + c0 + 4);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float top = a[k] * (1.f - lx) + bq[k] * lx, bot = cq[k] * (1.f - lx) + d[k] * lx;
-        z[k] = top * (1.f - ly) + bot * ly;
-      }
-    };
     float zmax = -INFINITY, se = 0.f, zt = 0.f;
     auto online = [&](int c, float z) {
       if (c == (int)tg) zt = z;
@@ -95,32 +142,11 @@ __global__ __launch_bounds__(256) void seg_loss_pixel_kernel(const float* rows, 
         se += expf(z - zmax);
       }
     };
-    if (vec) {
-      for (int c0 = 0; c0 < nc; c0 += 8) {
-        float z[8];
-        logits8(c0, z);
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-          if (c0 + k < nc) online(c0 + k, z[k]);
-      }
-    } else {
-      for (int c = 0; c < nc; ++c) online(c, logit(c));
-    }
+    each_logit(tp, nc, vec, online);
     const float lse = zmax + logf(se);
     float coef = 0.f;  // d loss / d ce
     if (valid) {
-      const float ce = lse - zt;
-      if (mode == 0) {
-        const float pt = expf(-ce);
-        const float om = fmaxf(1.f - pt, 0.f);
-        const float w = powf(om, gamma);
-        my_loss = (double)(alpha * w * ce);
-        // d/dce [alpha (1 - pt)^gamma ce], d pt / d ce = -pt
-        coef = alpha * (w + (gamma > 0.f ? gamma * powf(om, gamma - 1.f) * pt * ce : 0.f));
-      } else {
-        my_loss = (double)ce;
-        coef = 1.f;
-      }
+      my_loss = (double)pixel_loss(lse - zt, mode, alpha, gamma, &coef);
       my_cnt = 1.0;
     }
     float* dl = dlogits + (long long)b * nc * OH * OW + (long long)oy * OW + ox;
@@ -128,32 +154,71 @@ __global__ __launch_bounds__(256) void seg_loss_pixel_kernel(const float* rows, 
       const float p = expf(z - lse);
       dl[(long long)c * OH * OW] = valid ? coef * (p - (c == (int)tg ? 1.f : 0.f)) : 0.f;
     };
-    if (vec) {
-      for (int c0 = 0; c0 < nc; c0 += 8) {
-        float z[8];
-        logits8(c0, z);
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-          if (c0 + k < nc) emit(c0 + k, z[k]);
+    each_logit(tp, nc, vec, emit);
+  }
+  block_pair_to_part(my_loss, my_cnt, s_sum, s_cnt, part);
+}
+
+// Evaluation: EV_PIX label pixels per thread (chunks of 256 consecutive pixels, so a wave still reads along x), the arg max of the
+// interpolated logits (strict >, so the lowest class wins a tie, like torch.argmax) counted against the target, and the criterion's
+// value as in seg_loss_pixel_kernel.  LDS_HIST: the workgroup counts in nc * nc uint32 cells of LDS (nc <= 90: 32 KB) and adds its
+// non-zero cells to the global int64 matrix once at the end; otherwise every pixel goes to the global matrix directly.
+constexpr int EV_PIX = 8, EV_LDS_CELLS = 8192;
+template <bool LDS_HIST>
+__global__ __launch_bounds__(256) void seg_eval_kernel(const float* rows, int ld, int B, int nc, int ih, int iw, int OH, int OW,
+                                                       const long long* target, int mode, float alpha, float gamma, long long ignore_index,
+                                                       unsigned long long* confusion, double* part) {
+  extern __shared__ unsigned int hist[];
+  __shared__ double s_sum[4], s_cnt[4];
+  if (LDS_HIST) {
+    for (int i = threadIdx.x; i < nc * nc; i += 256) hist[i] = 0u;
+    __syncthreads();
+  }
+  const long long n = (long long)B * OH * OW;
+  const bool vec = (ld & 7) == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
+  double my_loss = 0.0, my_cnt = 0.0;
+  for (int it = 0; it < EV_PIX; ++it) {
+    const long long i = ((long long)blockIdx.x * EV_PIX + it) * 256 + threadIdx.x;
+    if (i >= n) break;
+    const int ox = (int)(i % OW);
+    const long long t = i / OW;
+    const int oy = (int)(t % OH);
+    const int b = (int)(t / OH);
+    const PixelTaps tp(rows, ld, b, ih, iw, OH, OW, oy, ox);
+    const long long tg = target[i];
+    const bool in_range = tg >= 0 && tg < nc;
+    const bool valid = in_range && tg != ignore_index;
+    float zmax = -INFINITY, se = 0.f, zt = 0.f;
+    int arg = 0;
+    each_logit(tp, nc, vec, [&](int c, float z) {
+      if (c == (int)tg) zt = z;
+      if (z > zmax) {
+        se = se * expf(zmax - z) + 1.f;
+        zmax = z;
+        arg = c;
+      } else {
+        se += expf(z - zmax);
       }
-    } else {
-      for (int c = 0; c < nc; ++c) emit(c, logit(c));
+    });
+    if (valid) {
+      float coef;
+      my_loss += (double)pixel_loss(zmax + logf(se) - zt, mode, alpha, gamma, &coef);
+      my_cnt += 1.0;
+    }
+    if (in_range) {
+      const int cell = (int)tg * nc + arg;
+      if (LDS_HIST) atomicAdd(&hist[cell], 1u);
+      else atomicAdd(confusion + cell, 1ull);
     }
   }
-  // block sums (fixed order inside the block; one double atomic per block)
-  for (int o = 32; o > 0; o >>= 1) {
-    my_loss += __shfl_xor(my_loss, o);
-    my_cnt += __shfl_xor(my_cnt, o);
+  if (LDS_HIST) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nc * nc; i += 256) {
+      const unsigned int v = hist[i];
+      if (v) atomicAdd(confusion + i, (unsigned long long)v);
+    }
   }
-  if ((threadIdx.x & 63) == 0) {
-    s_sum[threadIdx.x >> 6] = my_loss;
-    s_cnt[threadIdx.x >> 6] = my_cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {  // one pair per workgroup, summed in index order by seg_loss_finalize_kernel (deterministic, no same-address atomics)
-    part[2 * (long long)blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-    part[2 * (long long)blockIdx.x + 1] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-  }
+  block_pair_to_part(my_loss, my_cnt, s_sum, s_cnt, part);
 }
 
 __device__ __forceinline__ void bilinear_dst_range(int s, float scale, int out_size, int* lo, int* hi) {
@@ -299,6 +364,34 @@ extern "C" int cvx_resize_bilinear_nchw_grad_to_rows(const float* grad_nchw, int
   const long long nlow = (long long)batch * ih * iw;
   hipLaunchKernelGGL(resize_grad_rows_kernel, dim3((unsigned)cvx_cdiv(nlow, RG_PIX)), dim3(256), (size_t)RG_PIX * ld * 2, (hipStream_t)hip_stream, grad_nchw,
                      batch, nc, ih, iw, oh, ow, scale, 0, 1.0, nullptr, (half_t*)dpred_f16, ld);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+static long long seg_eval_blocks(long long npix) { return cvx_cdiv(npix, 256 * EV_PIX); }
+extern "C" int64_t cvx_seg_eval_workspace_bytes(int32_t batch, int32_t oh, int32_t ow) {
+  return 64 + seg_eval_blocks((long long)batch * oh * ow) * 16;  // totals, the per-workgroup (loss, count) pairs
+}
+
+extern "C" int cvx_seg_eval(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                            const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, int64_t* confusion,
+                            float* loss_out, void* workspace, void* hip_stream) {
+  CVX_CHECK(rows_f32 && target && confusion && loss_out && workspace, "null arguments");
+  CVX_CHECK(batch > 0 && nc > 0 && nc <= SEG_MAX_NC && nc <= ld && ld <= 4096 && ih > 0 && iw > 0 && oh > 0 && ow > 0, "bad sizes");
+  CVX_CHECK(mode == 0 || mode == 1, "mode: 0 focal, 1 cross-entropy");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long npix = (long long)batch * oh * ow;
+  const long long nblk = seg_eval_blocks(npix);
+  CVX_CHECK(nblk < (1LL << 31), "too many pixels");
+  double* acc = (double*)workspace;
+  double* part = (double*)((char*)workspace + 64);
+  if (nc * nc <= EV_LDS_CELLS)
+    hipLaunchKernelGGL(seg_eval_kernel<true>, dim3((unsigned)nblk), dim3(256), (size_t)nc * nc * 4, st, rows_f32, ld, batch, nc, ih, iw, oh, ow,
+                       (const long long*)target, mode, alpha, gamma, (long long)ignore_index, (unsigned long long*)confusion, part);
+  else
+    hipLaunchKernelGGL(seg_eval_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, st, rows_f32, ld, batch, nc, ih, iw, oh, ow,
+                       (const long long*)target, mode, alpha, gamma, (long long)ignore_index, (unsigned long long*)confusion, part);
+  hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nblk, acc, mode, (double)npix, loss_out);
   CVX_HIP(hipGetLastError());
   return 0;
 }

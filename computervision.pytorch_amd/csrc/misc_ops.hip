@@ -2,6 +2,7 @@
 // packing, gradient-slab reduction, fused Adam.  16-byte accesses wherever the layout allows.
 #include <algorithm>
 #include "misc_ops.h"
+#include "bilinear.h"
 #include "bn_common.h"
 
 namespace {
@@ -413,17 +414,8 @@ __global__ __launch_bounds__(256) void avgpool_global_kernel(ViewDesc in, ViewDe
   }
 }
 
-// ---- bilinear resize, align_corners = False (F.interpolate(..., mode="bilinear"), deeplabv3plus.py:38,117-122,147):
-// src = (dst + 0.5) * (in / out) - 0.5, clamped at 0; a 1x1 input degenerates to a broadcast ----
-__device__ __forceinline__ void bilinear_src(int d, float scale, int in_size, int* i0, int* i1, float* lam) {
-  float s = ((float)d + 0.5f) * scale - 0.5f;
-  if (s < 0.f) s = 0.f;
-  int a = (int)s;
-  if (a > in_size - 1) a = in_size - 1;
-  *i0 = a;
-  *i1 = a + (a < in_size - 1 ? 1 : 0);
-  *lam = s - (float)a;
-}
+// ---- bilinear resize, align_corners = False (F.interpolate(..., mode="bilinear"), deeplabv3plus.py:38,117-122,147): bilinear_src and
+// bilinear_mix of bilinear.h ----
 __global__ void resize_bilinear_kernel(ViewDesc in, ViewDesc out, int B, int IH, int IW, int OH, int OW, int CG, float sh, float sw) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long n = (long long)B * OH * OW * CG;
@@ -571,16 +563,10 @@ __global__ __launch_bounds__(256) void resize_bilinear_f32_nchw_kernel(const flo
       const float4 cq = *reinterpret_cast<const float4*>(r10 + c), d = *reinterpret_cast<const float4*>(r11 + c);
       const float va[4] = {a.x, a.y, a.z, a.w}, vb[4] = {bq.x, bq.y, bq.z, bq.w}, vc[4] = {cq.x, cq.y, cq.z, cq.w}, vd[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float top = va[k] * (1.f - lx) + vb[k] * lx, bot = vc[k] * (1.f - lx) + vd[k] * lx;
-        o[(long long)(c + k) * plane] = top * (1.f - ly) + bot * ly;
-      }
+      for (int k = 0; k < 4; ++k) o[(long long)(c + k) * plane] = bilinear_mix(va[k], vb[k], vc[k], vd[k], lx, ly);
     }
   }
-  for (; c < C; ++c) {
-    const float top = r00[c] * (1.f - lx) + r01[c] * lx, bot = r10[c] * (1.f - lx) + r11[c] * lx;
-    o[(long long)c * plane] = top * (1.f - ly) + bot * ly;
-  }
+  for (; c < C; ++c) o[(long long)c * plane] = bilinear_mix(r00[c], r01[c], r10[c], r11[c], lx, ly);
 }
 
 // ---- depthwise ConvTranspose2d, kernel 2f, stride f, padding f/2 (IDAUp.up_i, centernet_model.py:256): every output pixel

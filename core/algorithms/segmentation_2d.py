@@ -1,9 +1,11 @@
 """DeepLabv3+ algorithm wrapper -- the duck-typed interface of the reference's ``DeeplabV3PlusA``
 (core/algorithms/segmentation_2d.py:43-201): ``__init__(cfg, device)``, ``build_model() -> (nn.Module, name)``,
 ``build_loss()`` (FocalLoss / CrossEntropyLoss, :59-64, as the engine's fused ``SegLoss``), ``postprocess_seg2d`` (argmax ->
-colour map), ``predict``.  The network runs on the MI355X engine (``computervision.pytorch_amd.deeplab``).
+colour map), ``predict``, ``evaluate_on_voc`` (:115-166, the fused validation pass over an injected device loader).  The network runs
+on the MI355X engine (``computervision.pytorch_amd.deeplab``).
 """
 import os
+import time
 
 import numpy as np
 import torch
@@ -85,3 +87,29 @@ class DeeplabV3PlusA:
             cv2.imwrite(os.path.join(self.cfg.decode.test_results, os.path.basename(image_path).split(".")[0] + "@cvx.jpg"), result)
             return None
         return result
+
+    def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None):
+        """Reference :115-166: the validation metrics of ``model`` over VOC-``subset``, printed and written to
+        ``results_out_root/DeepLabV3Plus/DeepLabV3Plus_<dataset>_<time>.txt`` as four lines (Overall Acc, Mean Acc, FreqW Acc, Mean IoU).
+        Reading VOC from disk is outside the hot path: ``dataloader`` is a ``DeviceSegLoader`` over the pictures with
+        ``DeviceSegAugmenter(crop_hw=cfg.arch.crop_size, base_size=max(cfg.arch.input_size[1:]), colormap=voc_colormap(), train=False)``.
+        Each batch is one engine forward and one ``cvx_seg_eval`` launch; the host waits once, at the end.  Returns the path written."""
+        from core.trainer.segmentation_trainer import SegmentationMetrics, fused_evaluation
+        if subset != "val":
+            raise ValueError(f"不支持VOC-{subset}")
+        if dataloader is None:
+            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader=DeviceSegLoader(source, batch_size, "
+                             "DeviceSegAugmenter(crop_hw, base_size, colormap=voc_colormap(), train=False)) over the VOC-val pictures")
+        model_name = "DeepLabV3Plus"
+        results_out_root = os.path.join(results_out_root, model_name)
+        os.makedirs(results_out_root, exist_ok=True)
+        results_filepath = os.path.join(results_out_root, f"{model_name}_{self.dataset_name}_{time.strftime('%Y-%m-%d-%H-%M-%S')}.txt")
+        r = fused_evaluation(model, self.build_loss(), SegmentationMetrics(num_classes=self.num_classes, device=self.device), dataloader, self.device)
+        formatted = (f"Overall Acc: {r['Overall Acc']}\n"
+                     f"Mean Acc: {r['Mean Acc']}\n"
+                     f"FreqW Acc: {r['FreqW Acc']}\n"
+                     f"Mean IoU: {r['Mean IoU']}")
+        print(f"结果：\n{formatted}")
+        with open(results_filepath, mode="w", encoding="utf-8") as f:
+            f.write(formatted)
+        return results_filepath

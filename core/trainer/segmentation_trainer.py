@@ -4,12 +4,18 @@ criterion -> backward -> Adam under AMP, :114-131) and runs it as the engine's f
 ``cvx_seg_loss``, engine backward, fused Adam with GradScaler's skip-on-overflow); with ``torch.distributed`` initialised the step
 also sums the gradients over the ranks (RCCL).  ``evaluate_loop`` reports the reference's numbers (loss, Overall / Mean / FreqW
 accuracy, Mean IoU, :133-159) from a confusion matrix accumulated on the device.  The VOC / Cityscapes / SBD readers are outside
-the hot path: a dataloader is injected, or seeded synthetic batches stand in.
+the hot path: a dataloader is injected, or seeded synthetic batches stand in.  The input side is the device
+pipeline: ``dataloader=`` / ``val_dataloader=`` take a ``DeviceSegLoader`` (computervision.pytorch_amd/seg_pipeline.py, the reference's
+segmentation transforms as one launch per batch).  With ``val_dataloader=`` given, ``evaluate_loop`` is the fused pass: engine forward to
+the low-resolution logits rows, then ``cvx_seg_eval`` (upsampling + arg max + confusion matrix + criterion in one launch, no
+full-resolution logits, no gradient), one host synchronisation after the last batch; without it the unfused loop runs on the training
+loader as before.
 """
 from typing import Dict, List
 
 import torch
 
+from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd.deeplab import SegTrainStep
 from computervision.pytorch_amd.train import DynamicLossScale, FlatAdam
 from configs import DeeplabV3PlusConfig
@@ -40,14 +46,53 @@ class SyntheticSegmentationLoader:
 
 
 class SegmentationMetrics:
-    """core/metrics/seg_metrics.py:4-44 with the confusion matrix kept on the device (one bincount per batch)."""
+    """core/metrics/seg_metrics.py:4-44 with the confusion matrix kept on the device: ``add_batch`` takes predictions (one bincount per
+    batch, into the float64 ``confusion_matrix``), ``add_rows`` the engine's low-resolution logits rows (``cvx_seg_eval``: one launch, into
+    the exact int64 ``counts``).  ``fold()`` adds ``counts`` into ``confusion_matrix`` and clears them; ``get_results`` folds first."""
 
     def __init__(self, num_classes, device="cpu"):
         self.num_classes = num_classes
         self.confusion_matrix = torch.zeros(num_classes, num_classes, dtype=torch.float64, device=device)
+        self.counts = None                  # (nc, nc) int64 on the rows' device, created by the first add_rows
+        self._ws = None
 
     def reset(self):
         self.confusion_matrix.zero_()
+        if self.counts is not None:
+            self.counts.zero_()
+
+    def fold(self):
+        """``confusion_matrix`` += what ``add_rows`` has counted since the last fold (float64 is exact below 2^53); returns the matrix."""
+        if self.counts is not None:
+            self.confusion_matrix += self.counts.to(self.confusion_matrix.device).double()
+            self.counts.zero_()
+        return self.confusion_matrix
+
+    def add_rows(self, rows, targets, hw, criterion, loss_slot):
+        """One validation batch from the logits rows ``(B, lh*lw, ld)`` fp32 of ``model.forward_rows`` and the targets ``(B, H, W)`` int64:
+        ``confusion[target][argmax of the upsampled logits] += 1`` and ``criterion``'s (a ``SegLoss``) value of the batch into
+        ``loss_slot``, a one-element float32 view on the rows' device.  Asynchronous: nothing is read back."""
+        if not (torch.is_tensor(rows) and rows.is_cuda):
+            raise L.CvxError("SegmentationMetrics.add_rows runs on an MI355X only (there is no CPU path); add_batch takes host predictions")
+        lib = L.load()
+        dev = rows.device
+        B, A, ld = rows.shape
+        lh, lw = int(hw[0]), int(hw[1])
+        if targets.dim() != 3 or targets.shape[0] != B or A != lh * lw or rows.dtype != torch.float32 or not rows.is_contiguous():
+            raise ValueError("rows must be contiguous fp32 (B, lh*lw, ld) and targets (B, H, W)")
+        if loss_slot.dtype != torch.float32 or loss_slot.numel() != 1 or loss_slot.device != dev:
+            raise ValueError("loss_slot: one float32 element on the rows' device")
+        H, W = int(targets.shape[1]), int(targets.shape[2])
+        targets = targets.to(device=dev, dtype=torch.long).contiguous()
+        if self.counts is None or self.counts.device != dev:
+            self.counts = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64, device=dev)
+        need = int(lib.cvx_seg_eval_workspace_bytes(B, H, W))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.cvx_seg_eval(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets), criterion.mode, criterion.alpha,
+                                     criterion.gamma, criterion.ignore_index, L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws),
+                                     L.stream_ptr(dev)), "cvx_seg_eval")
 
     def add_batch(self, predictions, gts):
         predictions, gts = torch.as_tensor(predictions).reshape(-1), torch.as_tensor(gts).reshape(-1)
@@ -56,7 +101,7 @@ class SegmentationMetrics:
         self.confusion_matrix += torch.bincount(idx, minlength=self.num_classes ** 2).reshape(self.num_classes, self.num_classes).double()
 
     def get_results(self):
-        hist = self.confusion_matrix.cpu()
+        hist = self.fold().cpu()
         diag = torch.diag(hist)
         acc = float(diag.sum() / hist.sum())
         acc_cls = diag / hist.sum(1)
@@ -75,8 +120,16 @@ def get_optimizer(optimizer_name, model, initial_lr):
 
 @trainer_registry("deeplabv3plus")
 class DeeplabV3PlusTrainer(BaseTrainer):
-    def __init__(self, cfg: DeeplabV3PlusConfig, device, dataloader=None):
-        self._injected_loader = dataloader
+    def __init__(self, cfg: DeeplabV3PlusConfig, device, dataloader=None, val_dataloader=None):
+        if val_dataloader is not None:
+            # the trainer's device, and the device the loader declares if it declares one (DeviceSegLoader does); a loader without a
+            # ``device`` attribute is taken at its word, and host batches it yields are moved by evaluate_loop
+            on = [torch.device(device)] + ([torch.device(val_dataloader.device)] if hasattr(val_dataloader, "device") else [])
+            if any(d.type != "cuda" for d in on):
+                raise L.CvxError("val_dataloader= selects the fused evaluation (cvx_seg_eval), which runs on an MI355X only: the trainer's "
+                                 f"device and the loader's (here {', '.join(str(d) for d in on)}) must be GPUs, "
+                                 "e.g. DeviceSegLoader(..., device='cuda')")
+        self._injected_loader, self._injected_val_loader = dataloader, val_dataloader
         super().__init__(cfg, device, False)
         self.metrics = SegmentationMetrics(num_classes=cfg.dataset.num_classes, device=device)
         self.metric_names = ["loss"]
@@ -91,7 +144,8 @@ class DeeplabV3PlusTrainer(BaseTrainer):
 
     def load_data(self):
         loader = self._injected_loader or SyntheticSegmentationLoader(self.batch_size, self.cfg.arch.crop_size, self.cfg.dataset.num_classes)
-        self.train_dataloader = self.val_dataloader = loader
+        self.train_dataloader = loader
+        self.val_dataloader = self._injected_val_loader if self._injected_val_loader is not None else loader
 
     def set_optimizer(self):
         self.optimizer = get_optimizer(self.optimizer_name, self.model, self.initial_lr)
@@ -122,6 +176,8 @@ class DeeplabV3PlusTrainer(BaseTrainer):
         return [self._step(images, targets)]
 
     def evaluate_loop(self) -> Dict:
+        if self._injected_val_loader is not None:
+            return fused_evaluation(self.eval_model, self.criterion, self.metrics, self.val_dataloader, self.device)
         model = self.eval_model                        # the weight average when cfg.train.ema is on
         model.eval()
         self.metrics.reset()
@@ -136,3 +192,24 @@ class DeeplabV3PlusTrainer(BaseTrainer):
         r = self.metrics.get_results()
         return {"Loss": total / max(n, 1), "Overall Acc": r["Overall Acc"], "Mean Acc": r["Mean Acc"], "FreqW Acc": r["FreqW Acc"],
                 "Mean IoU": r["Mean IoU"]}
+
+
+def fused_evaluation(model, criterion, metrics: SegmentationMetrics, dataloader, device) -> Dict:
+    """The reference's validation pass (:133-159) without the full-resolution logits: per batch ``model.forward_rows`` and
+    ``metrics.add_rows`` into a per-batch loss buffer; the host synchronises ONCE, when the buffer and the matrix are read after the
+    last batch.  Returns the reference's five numbers."""
+    model.eval()
+    metrics.reset()
+    losses = torch.zeros(max(len(dataloader), 1), dtype=torch.float32, device=device)
+    n = 0
+    with torch.no_grad():
+        for images, targets in dataloader:
+            if n >= losses.numel():              # a loader that yields more batches than its len()
+                losses = torch.cat([losses, torch.zeros_like(losses)])
+            rows = model.forward_rows(images.to(device, non_blocking=True))
+            metrics.add_rows(rows, targets, model._last_engine.graph.level_hw[0], criterion, losses[n:n + 1])
+            n += 1
+    total = float(losses[:n].double().sum()) if n else 0.0
+    r = metrics.get_results()
+    return {"Loss": total / max(n, 1), "Overall Acc": r["Overall Acc"], "Mean Acc": r["Mean Acc"], "FreqW Acc": r["FreqW Acc"],
+            "Mean IoU": r["Mean IoU"]}

@@ -424,6 +424,21 @@ int64_t cvx_seg_loss_workspace_bytes(int32_t batch, int32_t nc, int32_t oh, int3
 int cvx_seg_loss(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                  const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, float loss_scale, float* loss_out,
                  void* dpred_f16, int32_t* bad_target, void* workspace, void* hip_stream);
+/* Segmentation evaluation of one batch in one pass, for the DeepLabv3+ validation loop.  rows, target, mode, alpha, gamma,
+ * ignore_index as for cvx_seg_loss.  Per label pixel the nc logits are interpolated with the device function
+ * cvx_resize_bilinear_rows_to_nchw uses (bit-identical values), their arg max is taken (the lowest class wins a tie, like torch.argmax) and
+ * confusion[target * nc + argmax] += 1 for targets in [0, nc); other targets are left out, as SegmentationMetrics does.  confusion:
+ * (nc, nc) int64 (device) that ACCUMULATES over calls -- the caller zeroes it.  loss_out: 1 float (device) = the criterion's value of
+ * this batch, cvx_seg_loss's definitions (a target that is neither ignore_index nor a class contributes nothing).  No gradient and no
+ * full-resolution tensor is written.  A workgroup counts in LDS for nc <= 90 (nc * nc uint32 cells, 32 KB) and adds its non-zero cells
+ * to the matrix with 64-bit atomics; larger nc goes to the matrix directly.  workspace: cvx_seg_eval_workspace_bytes() bytes.
+ * Asynchronous on hip_stream.
+ * Replaces: F.interpolate + criterion(preds, targets) + torch.argmax(preds, dim=1) + SegmentationMetrics.add_batch,
+ * core/trainer/segmentation_trainer.py:141-150 and core/algorithms/segmentation_2d.py:154-157. */
+int64_t cvx_seg_eval_workspace_bytes(int32_t batch, int32_t oh, int32_t ow);
+int cvx_seg_eval(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                 const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, int64_t* confusion, float* loss_out,
+                 void* workspace, void* hip_stream);
 /* CenterNet's CombinedLoss with its gradient.  rows: the engine's fp32 head rows (batch, anchors = h*w, ld): heat-map logits in columns
  * [0, nc), the loss's "reg" pair at columns col_a, col_a+1 (= the model output's columns nc, nc+1) and its "wh" pair at col_b, col_b+1 (= the
  * output's last two) -- the reference's loss names are swapped against the heads that produce them, reproduced as is.  Targets as
@@ -594,6 +609,28 @@ int cvx_aug_images_plain(const cvx_aug_job* jobs, const int32_t* job_start, int3
  * function cvx_aug_boxes uses, so the rows of image b are bit-identical to cvx_aug_boxes' rows with image index b. */
 int cvx_aug_boxes_padded(const cvx_aug_job* jobs, const int32_t* job_start, const int32_t* job_box_start, int32_t batch, const float* boxes,
                          int32_t n_boxes, int32_t H, int32_t W, int32_t max_boxes, float* labels, int32_t* counts, int32_t* overflow, void* hip_stream);
+
+/* ---- device-side segmentation input pipeline (csrc/seg_pipeline.hip) ------------------------------------------------------------------
+ * One job per output image.  image: uint8 HWC (ih, iw, 3) in device memory; mask: its label picture, uint8 (ih, iw, 3) colour coded
+ * (mask_channels = 3) or uint8 (ih, iw) class indices (mask_channels = 1).  (rh, rw): the size the reference's Resize gives the picture;
+ * (i, j): the crop origin (row, column) inside it, 0 <= i <= rh - H, 0 <= j <= rw - W; flip: mirror the crop.  Validation is a job with
+ * (rh, rw) = (H, W), i = j = flip = 0.  64 bytes. */
+typedef struct cvx_seg_job {
+  const uint8_t* image;
+  const uint8_t* mask;
+  int32_t ih, iw, rh, rw, i, j, flip, mask_channels, reserved[4];
+} cvx_seg_job;
+/* One launch for the whole batch, asynchronous on hip_stream.  jobs: (batch) in device memory; colours: (n_colours, 3) uint8 in device
+ * memory, the colour of class k in row k (n_colours <= 256; not read for index masks); mean3 / std3: 3 HOST floats each (passed by
+ * value to the kernel).  out_nchw: (batch, 3, H, W) fp32 = (bilinear resize of byte / 255 - mean) / std; targets: (batch, H, W) int64.
+ * No resized intermediate is stored: an output pixel maps back through flip and crop to the resized picture and on to the four taps of
+ * the source, with torch's fp32 coordinate arithmetic (align_corners = False, no antialiasing).  label_mode 0: the taps' class indices are
+ * mixed as floats and rounded half to even (what torchvision's F.resize does to an integer tensor; the reference's behaviour); 1: nearest
+ * (floor(dst * in / out)).  A colour that is not in the table is class 0, as in the reference's 2^24-entry table.
+ * Replaces: ToTensor, RGB2idx / label_indices, Resize, RandomCrop (the crop itself), RandomHorizontalFlip (the mirror itself), Normalize and
+ * the DataLoader's default collate, core/data/segmentation_dataset.py:70-198,256-293. */
+int cvx_seg_pipeline(const cvx_seg_job* jobs, int32_t batch, const uint8_t* colours, int32_t n_colours, int32_t label_mode, const float* mean3,
+                     const float* std3, float* out_nchw, int64_t* targets, int32_t H, int32_t W, void* hip_stream);
 
 /* ---- data-parallel gradient exchange over RCCL (csrc/comm.hip), SURVEY.md section 8(b) / 8(e) --------------------------------------
  * One process per GPU.  Rank 0 calls cvx_comm_unique_id (128 bytes, ncclGetUniqueId), ships them to every rank by any means, all ranks
