@@ -134,6 +134,8 @@ PROTOTYPES = {
     "cvx_seg_loss": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _F, _P, _P, _P, _P, _P]),
     "cvx_seg_eval_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "cvx_seg_eval": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _P, _P, _P, _P]),
+    "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
+    "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
     "cvx_seg_pipeline": (_I32, [_P, _I32, _P, _I32, _I32, C.POINTER(_F), C.POINTER(_F), _P, _P, _I32, _I32, _P]),
     "cvx_resize_bilinear_nchw_grad_to_rows": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _I32, _P]),
     "cvx_maxpool3_train_nhwc": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -1,0 +1,343 @@
+// VOC mAP evaluation of the four detectors on gfx950: detection-to-ground-truth matching per batch (cvx_det_match) and the per-class
+// precision / recall / AP reduction once per evaluation (cvx_det_ap).  Nothing is read by the host between the batches.
+//
+// Reference semantics (file:line under the reference tree):
+//   get_map                      core/metrics/mAP.py:302-834     detections of a class sorted by float(score text) descending (stable, file order
+//                                                                then line order); per detection the ground truth of its class and image with
+//                                                                the largest IoU (+1 pixel convention, strict >, first in file order wins a tie,
+//                                                                difficult boxes included, the `used` flags ignored); IoU >= 0.5: difficult ->
+//                                                                neither TP nor FP, unused -> TP (and used), used -> FP; otherwise FP
+//   voc_ap                       core/metrics/mAP.py:107-148     sentinels, suffix maximum of the precision, sum over the recall change points
+//   the detection writers        core/algorithms/*.py::evaluate_on_voc   "class str(score)[:6] int(l) int(t) int(r) int(b)"
+//
+//   K1 det_match    one workgroup per image.  Its ground truth and one (match, score) pair per detection live in LDS.  Pass 1: every
+//                   detection maps its box to the original image (mode 1: (x - px) * gx, uncontracted), truncates it, quantises its score
+//                   to the 4 decimals the reference's text keeps and picks its ground truth.  Because that choice ignores `used`, the
+//                   sequential rule is the same as: of the detections of one image that chose ground truth g with IoU >= threshold, the TP
+//                   is the first by (score descending, row ascending) -- an LDS atomic-min on that key.  Pass 2 writes the flags.  Records go
+//                   to [cursor + prefix(counts)[image], ...): image order, then row order, whatever order the workgroups run in.
+//   K2 det_cursor   cursor += sum(counts) (a launch of its own: K1 reads the cursor of the previous batch)
+//   K3 det_ap       one workgroup per class over the records in the reference's order: chunked inclusive scans of TP and FP -> precision
+//                   and recall in fp64; a second, backward sweep carries the suffix maximum and sums the change-point terms
+//   K4 det_map      mean of the APs of the classes that have a non-difficult ground truth
+#include "cvx_common.h"
+#include "../../include/cvx_engine.h"
+
+namespace {
+
+constexpr int DET_THREADS = 256;
+constexpr int DET_MAX_ROWS = 16384;       // what cvx_nms can return per image
+constexpr int DET_MAX_GT = 1024;
+constexpr int DET_MAX_LDS = 160 * 1024;
+enum { ST_CURSOR = 0, ST_OVERFLOW = 1, ST_LOW_SCORE = 2, ST_BAD_CLASS = 3 };
+enum { FLAG_FP = 0, FLAG_TP = 1, FLAG_NEITHER = 2 };
+
+__host__ __device__ inline int det_gt_slots(int G) { return (G + 1) & ~1; }
+__host__ __device__ inline int det_row_slots(int max_det) { return (max_det + 3) & ~3; }
+inline size_t det_match_lds(int max_det, int G) { return 32 + (size_t)32 * det_gt_slots(G) + (size_t)8 * det_row_slots(max_det); }
+
+// str(np.float32(x))[:6] for x in [1e-4, 1]: the 4-decimal number k / 1e4 nearest to x is the text itself when it rounds back to x (the
+// shortest round-trip text is then no longer than it), otherwise the text has more digits and the cut truncates.  x * 1e4 is exact in fp64.
+__device__ __forceinline__ float det_quantize(float x) {
+  const double p = (double)x * 1e4;
+  const double k = rint(p);
+  if ((float)(k / 1e4) == x) return x;
+  return (float)(floor(p) / 1e4);
+}
+
+__device__ __forceinline__ int det_count(int c, int max_det) { return (c < 0 || c > max_det) ? 0 : c; }
+
+__global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int B, int max_det,
+                                                                int box_mode, const float* __restrict__ box_map, const int* __restrict__ gt,
+                                                                const int* __restrict__ gt_counts, int G, int nc, double min_overlap, int quantize,
+                                                                float* __restrict__ rec_score, int* __restrict__ rec_class, int* __restrict__ rec_flag,
+                                                                long long capacity, unsigned long long* state, unsigned long long* gt_per_class) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  long long* red = reinterpret_cast<long long*>(smem);                                   // 4 wave partials
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(smem + 32);           // rank key of the TP per ground truth
+  int* gbox = reinterpret_cast<int*>(smem + 32 + 8 * det_gt_slots(G));                   // [cls, l, t, r, b, difficult] per ground truth
+  int* match = reinterpret_cast<int*>(smem + 32 + 32 * det_gt_slots(G));                 // per detection: ground truth, -1 FP, -2 neither
+  float* qscore = reinterpret_cast<float*>(smem + 32 + 32 * det_gt_slots(G) + 4 * det_row_slots(max_det));
+  const int b = blockIdx.x, tid = threadIdx.x;
+
+  // records of the images before this one in the batch
+  long long before = 0;
+  for (int i = tid; i < b; i += DET_THREADS) before += det_count(counts[i], max_det);
+  for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
+  if ((tid & 63) == 0) red[tid >> 6] = before;
+  __syncthreads();
+  const long long base = (long long)state[ST_CURSOR] + red[0] + red[1] + red[2] + red[3];
+
+  const int n_raw = counts[b], ng_raw = gt_counts[b];
+  const bool bad_image = n_raw < 0 || n_raw > max_det || ng_raw < 0 || ng_raw > G || base + det_count(n_raw, max_det) > capacity;
+  if (bad_image) {  // NMS overflow (-1), a count past its block, or no room left: counted, and the image contributes nothing
+    if (tid == 0) atomicAdd(&state[ST_OVERFLOW], 1ull);
+    return;
+  }
+  const int n = n_raw, ng = ng_raw;
+  unsigned long long bad_class = 0, low_score = 0;
+
+  for (int g = tid; g < ng; g += DET_THREADS) {
+    const int* src = gt + ((long long)b * G + g) * 6;
+    int cls = src[0];
+    const int difficult = src[5] != 0;
+    if (cls < 0 || cls >= nc) {
+      ++bad_class;
+      cls = -1;  // matches no detection
+    } else if (!difficult) {
+      atomicAdd(&gt_per_class[cls], 1ull);
+    }
+    gbox[g * 6 + 0] = cls;
+    gbox[g * 6 + 1] = src[1];
+    gbox[g * 6 + 2] = src[2];
+    gbox[g * 6 + 3] = src[3];
+    gbox[g * 6 + 4] = src[4];
+    gbox[g * 6 + 5] = difficult;
+    best[g] = ~0ull;
+  }
+  __syncthreads();
+
+  float px = 0.f, py = 0.f, gx = 1.f, gy = 1.f;
+  if (box_mode == 1) {
+    px = box_map[b * 4 + 0];
+    py = box_map[b * 4 + 1];
+    gx = box_map[b * 4 + 2];
+    gy = box_map[b * 4 + 3];
+  }
+  for (int r = tid; r < n; r += DET_THREADS) {
+    const float* row = rows + ((long long)b * max_det + r) * 6;
+    float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
+    const float score = row[4];
+    int cls = __float2int_rz(row[5]);
+    if (box_mode == 1) {  // core/utils/boxes.py:undo_letterbox in fp32, one rounding per operation
+      x1 = __fmul_rn(__fsub_rn(x1, px), gx);
+      y1 = __fmul_rn(__fsub_rn(y1, py), gy);
+      x2 = __fmul_rn(__fsub_rn(x2, px), gx);
+      y2 = __fmul_rn(__fsub_rn(y2, py), gy);
+    }
+    const long long l = __float2int_rz(x1), t = __float2int_rz(y1), rr = __float2int_rz(x2), bb = __float2int_rz(y2);  // int(): towards zero
+    if (!(score >= 1e-4f)) ++low_score;  // the reference prints these in scientific notation: rejected at the end, not emulated
+    const float q = quantize ? det_quantize(score) : score;
+    if (cls < 0 || cls >= nc) {
+      ++bad_class;
+      cls = 0;
+    }
+    double ovmax = -1.0;
+    int m = -1;
+    const long long area = (rr - l + 1) * (bb - t + 1);
+    for (int g = 0; g < ng; ++g) {
+      if (gbox[g * 6] != cls) continue;
+      const long long gl = gbox[g * 6 + 1], gtp = gbox[g * 6 + 2], gr = gbox[g * 6 + 3], gb = gbox[g * 6 + 4];
+      const long long iw = min(rr, gr) - max(l, gl) + 1, ih = min(bb, gb) - max(t, gtp) + 1;
+      if (iw > 0 && ih > 0) {
+        const long long inter = iw * ih;
+        const long long ua = area + (gr - gl + 1) * (gb - gtp + 1) - inter;
+        const double ov = (double)inter / (double)ua;  // integers below 2^53: the one rounding Python's iw * ih / ua has
+        if (ov > ovmax) {
+          ovmax = ov;
+          m = g;
+        }
+      }
+    }
+    const unsigned long long key = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(q)) << 32) | (unsigned)r;
+    if (m >= 0 && ovmax >= min_overlap) {
+      if (gbox[m * 6 + 5])
+        m = -2;
+      else
+        atomicMin(&best[m], key);
+    } else {
+      m = -1;
+    }
+    match[r] = m;
+    qscore[r] = q;
+    rec_score[base + r] = q;
+    rec_class[base + r] = cls;
+  }
+  __syncthreads();
+  for (int r = tid; r < n; r += DET_THREADS) {
+    const int m = match[r];
+    int flag = FLAG_FP;
+    if (m == -2) {
+      flag = FLAG_NEITHER;
+    } else if (m >= 0) {
+      const unsigned long long key = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(qscore[r])) << 32) | (unsigned)r;
+      flag = best[m] == key ? FLAG_TP : FLAG_FP;
+    }
+    rec_flag[base + r] = flag;
+  }
+  if (bad_class) atomicAdd(&state[ST_BAD_CLASS], bad_class);
+  if (low_score) atomicAdd(&state[ST_LOW_SCORE], low_score);
+}
+
+__global__ __launch_bounds__(DET_THREADS) void det_cursor_kernel(const int* __restrict__ counts, int B, int max_det, long long capacity,
+                                                                 unsigned long long* state) {
+  __shared__ long long red[DET_THREADS / 64];
+  long long total = 0;
+  for (int i = threadIdx.x; i < B; i += DET_THREADS) total += det_count(counts[i], max_det);
+  for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const long long next = (long long)state[ST_CURSOR] + red[0] + red[1] + red[2] + red[3];
+    state[ST_CURSOR] = (unsigned long long)(next < capacity ? next : capacity);
+  }
+}
+
+// ---- cvx_det_ap --------------------------------------------------------------------------------------------------------------------------
+// inclusive scan over the workgroup's 256 values (Hillis-Steele through LDS; the segments are short and this runs once per evaluation)
+template <typename T, typename Op>
+__device__ __forceinline__ T det_block_scan(T v, T* buf, int lane, bool backward, Op op) {
+  const int i = backward ? DET_THREADS - 1 - lane : lane;
+  buf[i] = v;
+  __syncthreads();
+  for (int o = 1; o < DET_THREADS; o <<= 1) {
+    T other = v;
+    const bool has = i >= o;
+    if (has) other = buf[i - o];
+    __syncthreads();
+    if (has) v = op(other, v);
+    buf[i] = v;
+    __syncthreads();
+  }
+  return v;
+}
+
+__device__ __forceinline__ bool det_score_reaches(float s, double threshold, int quantize) {
+  return (quantize ? rint((double)s * 1e4) / 1e4 : (double)s) >= threshold;  // float("0.xxxx") >= score_threshold
+}
+
+__global__ __launch_bounds__(DET_THREADS) void det_ap_kernel(const float* __restrict__ score, const int* __restrict__ flag,
+                                                             const long long* __restrict__ seg_off, const unsigned long long* __restrict__ gt_per_class,
+                                                             double score_threshold, int quantize, double* prec, double* rec, double* stats) {
+  __shared__ unsigned long long sbuf[DET_THREADS];
+  __shared__ double dbuf[DET_THREADS];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const long long lo = seg_off[c], hi = seg_off[c + 1], n = hi - lo;
+  const long long n_gt = (long long)gt_per_class[c];
+  const double gt_div = (double)(n_gt > 1 ? n_gt : 1);  // np.maximum(gt_counter_per_class, 1)
+
+  // forward sweep: TP, FP and "score >= threshold" counts, packed 20 bits apart inside a chunk (each field adds at most 256 there) and
+  // carried unpacked from chunk to chunk
+  const unsigned long long field = (1ull << 20) - 1;
+  long long tp_before = 0, fp_before = 0, reach = 0;
+  for (long long start = lo; start < hi; start += DET_THREADS) {
+    const long long i = start + tid;
+    unsigned long long v = 0;
+    if (i < hi) {
+      const int f = flag[i];
+      v = (f == FLAG_TP ? 1ull : 0ull) | (f == FLAG_FP ? 1ull << 20 : 0ull) |
+          (det_score_reaches(score[i], score_threshold, quantize) ? 1ull << 40 : 0ull);
+    }
+    v = det_block_scan(v, sbuf, tid, false, [](unsigned long long a, unsigned long long x) { return a + x; });
+    if (i < hi) {
+      const long long tp = tp_before + (long long)(v & field), fp = fp_before + (long long)((v >> 20) & field);
+      rec[i] = (double)tp / gt_div;
+      prec[i] = (double)tp / (double)(tp + fp > 1 ? tp + fp : 1);
+    }
+    const unsigned long long chunk = sbuf[DET_THREADS - 1];
+    tp_before += (long long)(chunk & field);
+    fp_before += (long long)((chunk >> 20) & field);
+    reach += (long long)((chunk >> 40) & field);
+    __syncthreads();  // sbuf is rewritten by the next chunk
+  }
+  __threadfence_block();
+  __syncthreads();  // the backward sweep reads prec / rec other threads of this workgroup wrote
+
+  // backward sweep: mpre[i] = max(prec[i:], 0) and the sum of (mrec[i] - mrec[i-1]) * mpre[i] where the recall changes.  The closing
+  // sentinel pair (recall 1, precision 0) adds (1 - rec[n-1]) * 0 and is left out.
+  double later_max = 0.0, ap = 0.0;
+  const long long chunks = (n + DET_THREADS - 1) / DET_THREADS;
+  for (long long k = chunks - 1; k >= 0; --k) {
+    const long long i = lo + k * DET_THREADS + tid;
+    const bool valid = i < hi;
+    double m = valid ? prec[i] : 0.0;
+    m = det_block_scan(m, dbuf, tid, true, [](double a, double x) { return a > x ? a : x; });
+    const double chunk_max = dbuf[DET_THREADS - 1];  // the backward scan's last slot is thread 0's: the maximum of the chunk
+    __syncthreads();
+    m = m > later_max ? m : later_max;
+    double term = 0.0;
+    if (valid) {
+      const double r = rec[i], r_prev = i > lo ? rec[i - 1] : 0.0;
+      if (r != r_prev) term = (r - r_prev) * m;
+    }
+    dbuf[tid] = term;
+    __syncthreads();
+    for (int o = DET_THREADS / 2; o > 0; o >>= 1) {  // fixed tree: the same bits every run
+      if (tid < o) dbuf[tid] += dbuf[tid + o];
+      __syncthreads();
+    }
+    ap += dbuf[0];
+    later_max = later_max > chunk_max ? later_max : chunk_max;
+    __syncthreads();
+  }
+
+  if (tid == 0) {
+    // values "at the threshold": the last index whose score reaches it (scores descend), index 0 when none does
+    double p = 0.0, r = 0.0, f1 = 0.0;
+    if (n > 0) {
+      const long long idx = lo + (reach > 0 ? reach - 1 : 0);
+      p = prec[idx];
+      r = rec[idx];
+      const double s = p + r;
+      f1 = r * p * 2 / (s == 0.0 ? 1.0 : s);
+    }
+    double* out = stats + (long long)c * 8;
+    out[0] = ap;
+    out[1] = p;
+    out[2] = r;
+    out[3] = f1;
+    out[4] = (double)tp_before;
+    out[5] = (double)n;
+    out[6] = (double)n_gt;
+    out[7] = 0.0;
+  }
+}
+
+__global__ void det_map_kernel(const unsigned long long* __restrict__ gt_per_class, int nc, double* stats) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double sum = 0.0;
+  long long classes = 0;
+  for (int c = 0; c < nc; ++c)
+    if (gt_per_class[c] > 0) {
+      sum += stats[(long long)c * 8];
+      ++classes;
+    }
+  stats[(long long)nc * 8 + 0] = classes ? sum / (double)classes : 0.0;
+  stats[(long long)nc * 8 + 1] = (double)classes;
+}
+
+unsigned long long g_match_optin = 0;
+
+}  // namespace
+
+extern "C" int cvx_det_match(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, int32_t box_mode, const float* box_map,
+                             const int32_t* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc, double min_overlap, int32_t quantize,
+                             float* rec_score, int32_t* rec_class, int32_t* rec_flag, int64_t capacity, int64_t* state, int64_t* gt_per_class,
+                             void* hip_stream) {
+  CVX_CHECK(rows && counts && gt_counts && rec_score && rec_class && rec_flag && state && gt_per_class, "null arguments");
+  CVX_CHECK(batch > 0 && max_det > 0 && max_det <= DET_MAX_ROWS && max_gt >= 0 && max_gt <= DET_MAX_GT && nc > 0 && capacity > 0, "bad sizes");
+  CVX_CHECK(max_gt == 0 || gt, "null ground truth");
+  CVX_CHECK(box_mode == 0 || (box_mode == 1 && box_map), "box_mode: 0 final boxes, 1 (x - px) * gx with box_map (batch, 4)");
+  const size_t lds = det_match_lds(max_det, max_gt);
+  CVX_CHECK(lds <= (size_t)DET_MAX_LDS, "max_det and max_gt do not fit the LDS");
+  if (lds > 65536) CVX_TRY(cvx_lds_optin((const void*)det_match_kernel, DET_MAX_LDS, &g_match_optin));
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(det_match_kernel, dim3((unsigned)batch), dim3(DET_THREADS), lds, st, rows, counts, batch, max_det, box_mode, box_map, gt, gt_counts,
+                     max_gt, nc, min_overlap, quantize, rec_score, rec_class, rec_flag, (long long)capacity, (unsigned long long*)state,
+                     (unsigned long long*)gt_per_class);
+  hipLaunchKernelGGL(det_cursor_kernel, dim3(1), dim3(DET_THREADS), 0, st, counts, batch, max_det, (long long)capacity, (unsigned long long*)state);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int cvx_det_ap(const float* score, const int32_t* flag, const int64_t* seg_off, const int64_t* gt_per_class, int32_t nc,
+                          double score_threshold, int32_t quantize, double* prec, double* rec, double* stats, void* hip_stream) {
+  CVX_CHECK(score && flag && seg_off && gt_per_class && prec && rec && stats, "null arguments");
+  CVX_CHECK(nc > 0, "bad sizes");
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(det_ap_kernel, dim3((unsigned)nc), dim3(DET_THREADS), 0, st, score, flag, (const long long*)seg_off,
+                     (const unsigned long long*)gt_per_class, score_threshold, quantize, prec, rec, stats);
+  hipLaunchKernelGGL(det_map_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)gt_per_class, nc, stats);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}

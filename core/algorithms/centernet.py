@@ -74,6 +74,44 @@ class CenterNetA:
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
         return _engine.centernet_decode(raw, fh, fw, self.num_classes, nc_pad, nc_pad + 8, self.K, conf, self.nms_threshold, self.use_nms)
 
+    def evaluate_rows(self, model, images, image_hw, conf_threshold=0.001):
+        """The forward, ``decode_raw`` and ``_finish``'s inverse letterbox for a whole device batch, with no host read: (rows (B, K, 6)
+        [x1, y1, x2, y2, score, cls] in original-image pixels, counts (B) int32 -- -1 where the decode overflowed, as ``_finish`` raises)."""
+        from computervision.pytorch_amd import det_eval
+        with torch.no_grad():
+            raw = model.forward_raw(images.to(self.device))
+        out = self.decode_raw(raw, images.shape[2] // 4, images.shape[3] // 4, conf_threshold)
+        keep = out["keep"].long()
+        boxes = out["boxes"].gather(1, keep.unsqueeze(2).expand(-1, -1, 4))
+        scores, classes = out["scores"].gather(1, keep), out["classes"].gather(1, keep)
+        boxes = det_eval.reverse_letterbox_device(boxes, self.input_size, image_hw)
+        return torch.cat((boxes, scores.unsqueeze(2), classes.to(torch.float32).unsqueeze(2)), 2), out["counts"]
+
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+        """Reference :137-229: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
+        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
+        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
+        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
+        ``dr_files_list.sort()`` decides equal scores).
+        Per batch: the forward, ``decode_raw``, ``_finish``'s inverse letterbox restated as float32 tensor operations on the device batch
+        and one ``cvx_det_match`` launch (mode 0); the counts stay on the device, so the host reads once, at the end.  An image without
+        detections contributes none (the reference writes one all-zero line of class 0 for it).  Returns ``DetectionEvaluator.results()``."""
+        if subset not in ("val", "test"):
+            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
+        if dataloader is None:
+            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
+                             "device over the VOC-" + subset + " pictures in sorted-id order")
+        from computervision.pytorch_amd import det_eval
+        from configs.dataset_cfg import VOC_CFG
+        model.eval()
+
+        def rows_of(images, meta):
+            rows, counts = self.evaluate_rows(model, images, meta["image_hw"])
+            return rows, counts, None
+
+        return det_eval.evaluate_detector(rows_of, dataloader, self.num_classes, self.device, map_out_root,
+                                          det_eval.class_names(VOC_CFG, self.num_classes), self.K, capacity)
+
     def _finish(self, out, b, h, w):
         n = int(out["counts"][b])
         if n < 0:

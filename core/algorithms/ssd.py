@@ -156,6 +156,35 @@ class Ssd:
             results.append(o if len(o) else [])
         return results
 
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+        """Reference :96-188: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
+        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
+        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
+        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
+        ``dr_files_list.sort()`` decides equal scores).
+        Per batch: the forward, ``decode_device`` (with the host reads it makes), ``_correct_boxes`` restated as float32 tensor
+        operations on the device batch and one ``cvx_det_match`` launch (mode 0).  An image without detections contributes none (the
+        reference writes one all-zero line of class 0 for it).  Returns ``DetectionEvaluator.results()``."""
+        if subset not in ("val", "test"):
+            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
+        if dataloader is None:
+            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
+                             "device over the VOC-" + subset + " pictures in sorted-id order")
+        from computervision.pytorch_amd import det_eval
+        from configs.dataset_cfg import VOC_CFG
+        model.eval()
+
+        def rows_of(images, meta):
+            with torch.no_grad():
+                preds = model(images)
+            per_image = [torch.cat((det[:, :4], det[:, 5:6], det[:, 4:5]), 1) for det, _ in self.decode_device(preds, 0.001)]   # -> [box, score, cls]
+            rows, counts = det_eval.pack_rows(per_image, images.device)
+            rows[..., :4] = det_eval.correct_boxes_device(rows[..., :4], self.input_image_size, meta["image_hw"], self.letterbox_image)
+            return rows, counts, None
+
+        return det_eval.evaluate_detector(rows_of, dataloader, self.num_classes, self.device, map_out_root,
+                                          det_eval.class_names(VOC_CFG, self.num_classes), 16384, capacity)
+
     def _correct_boxes(self, box_xy, box_wh, input_shape, image_shape):
         """yolo_correct_boxes (core/utils/image_process.py:161-181)."""
         xywh = np.concatenate([box_xy, box_wh], axis=-1)

@@ -8,7 +8,9 @@ import torch
 
 from computervision.pytorch_amd._lib import CvxError
 
+from computervision.pytorch_amd import det_eval
 from computervision.pytorch_amd import engine as _engine
+from computervision.pytorch_amd.det_eval import class_names as _class_names
 from computervision.pytorch_amd.model import Yolo8
 from computervision.pytorch_amd.train import V8DetectionLoss
 from configs import Yolo8DetConfig
@@ -59,6 +61,32 @@ class YOLOv8:
         out = self.non_max_suppression(preds, conf_threshold)
         assert len(out) == 1, "仅支持单张图片的预测"
         return undo_letterbox(out[0].cpu().numpy(), self.input_image_size, (image_h, image_w), self.letterbox_image)
+
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+        """Reference :244-326: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
+        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
+        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
+        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
+        ``dr_files_list.sort()`` decides equal scores).
+        Per batch: one engine forward, ``cvx_nms`` with the counts kept on the device and one ``cvx_det_match`` launch that undoes the
+        letterbox (box-map mode 1); the host reads once, at the end.  Returns ``DetectionEvaluator.results()``.  No COCO metric, no plots."""
+        if subset not in ("val", "test"):
+            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
+        if dataloader is None:
+            raise CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
+                           "device over the VOC-" + subset + " pictures in sorted-id order")
+        from configs.dataset_cfg import VOC_CFG
+        model.eval()
+
+        def rows_of(images, meta):
+            with torch.no_grad():
+                preds = model(images.to(self.device))
+            y = preds[0] if isinstance(preds, (list, tuple)) else preds
+            rows, _, counts = _engine.nms(y, 0.001, self.iou_threshold, self.max_det)
+            return rows, counts, det_eval.letterbox_box_map(meta["image_hw"], self.input_image_size, self.letterbox_image)
+
+        return det_eval.evaluate_detector(rows_of, dataloader, self.num_classes, self.device, map_out_root, _class_names(VOC_CFG, self.num_classes),
+                                          self.max_det, capacity)
 
     def predict_tensor(self, model, image: torch.Tensor, image_h: int, image_w: int):
         """``predict`` minus file I/O and drawing: image (1,3,H,W) in [0,1] already letterboxed."""

@@ -439,6 +439,33 @@ int64_t cvx_seg_eval_workspace_bytes(int32_t batch, int32_t oh, int32_t ow);
 int cvx_seg_eval(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                  const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, int64_t* confusion, float* loss_out,
                  void* workspace, void* hip_stream);
+/* VOC mAP evaluation of a detector (get_map at IoU min_overlap), accumulated on the device batch by batch.
+ * cvx_det_match, once per batch: rows (batch, max_det, 6) [x1,y1,x2,y2,score,cls] fp32 and counts (batch) int32 exactly as cvx_nms /
+ * cvx_nms_variant write them; a count of -1 (or one past max_det) adds 1 to the overflow counter and the image contributes nothing.
+ * box_mode 0: the boxes are final; 1: x -> (x - px) * gx, y -> (y - py) * gy in fp32 with one rounding per operation, box_map (batch, 4)
+ * fp32 [px, py, gx, gy] (core/utils/boxes.py:undo_letterbox for both letterbox settings).  Then the coordinates are truncated towards
+ * zero, as the writers' int() does.  gt (batch, max_gt, 6) int32 [cls, l, t, r, b, difficult], gt_counts (batch) int32.  quantize != 0:
+ * the score becomes what str(float32)[:6] keeps of it (4 decimals; exact for scores in [1e-4, 1]).  One workgroup per image: per
+ * detection the ground truth of its class with the largest IoU (+1 pixel convention, integer products and one fp64 division, strict >,
+ * first in order wins a tie, difficult boxes included); of the detections that chose one non-difficult ground truth with IoU >=
+ * min_overlap the first by (score descending, row ascending) is the TP, the others are FP; a difficult match is neither.  Appends
+ * (score fp32, class int32, flag int32: 0 FP, 1 TP, 2 neither) to rec_score / rec_class / rec_flag (capacity records each) in (image, row)
+ * order at the device cursor; gt_per_class (nc) int64 counts the non-difficult ground truths.  state: 4 int64 (device), zeroed by the
+ * caller before the first batch: [cursor, overflow (NMS overflow, bad counts, no room left), scores below 1e-4, classes outside [0, nc)].
+ * max_det <= 16384, max_gt <= 1024.  No host read; asynchronous on hip_stream.
+ * cvx_det_ap, once per evaluation, over the records in get_map's order (class ascending, score descending, stable): seg_off (nc + 1)
+ * int64 = the first record of each class.  Per class: inclusive scans of TP and FP, rec = tp / max(gt, 1) and prec = tp / max(tp + fp, 1)
+ * in fp64 (written to prec / rec, one double per record), voc_ap (suffix maximum, sum over the recall change points) and the values at
+ * the last record whose score reaches score_threshold (record 0 when none does).  stats: (nc * 8 + 8) doubles: per class [ap, precision,
+ * recall, f1, tp, detections, ground truths, 0], then [mAP over the classes with a ground truth, their number].
+ * Replaces: get_map and voc_ap, core/metrics/mAP.py:107-148, 302-834, and the text files the evaluate_on_voc writers exchange with it,
+ * core/algorithms/yolo_v8.py:244-326 (yolo_v7.py:94-186, ssd.py:96-188, centernet.py:137-229). */
+int cvx_det_match(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, int32_t box_mode, const float* box_map,
+                  const int32_t* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc, double min_overlap, int32_t quantize,
+                  float* rec_score, int32_t* rec_class, int32_t* rec_flag, int64_t capacity, int64_t* state, int64_t* gt_per_class,
+                  void* hip_stream);
+int cvx_det_ap(const float* score, const int32_t* flag, const int64_t* seg_off, const int64_t* gt_per_class, int32_t nc,
+               double score_threshold, int32_t quantize, double* prec, double* rec, double* stats, void* hip_stream);
 /* CenterNet's CombinedLoss with its gradient.  rows: the engine's fp32 head rows (batch, anchors = h*w, ld): heat-map logits in columns
  * [0, nc), the loss's "reg" pair at columns col_a, col_a+1 (= the model output's columns nc, nc+1) and its "wh" pair at col_b, col_b+1 (= the
  * output's last two) -- the reference's loss names are swapped against the heads that produce them, reproduced as is.  Targets as
