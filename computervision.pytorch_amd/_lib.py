@@ -136,6 +136,9 @@ PROTOTYPES = {
     "cvx_seg_eval": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _P, _P, _P, _P]),
     "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
+    "cvx_coco_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "cvx_coco_accumulate": (_I32, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "cvx_coco_summarize": (_I32, [_P, _P, _I32, _P, _P]),
     "cvx_seg_pipeline": (_I32, [_P, _I32, _P, _I32, _I32, C.POINTER(_F), C.POINTER(_F), _P, _P, _I32, _I32, _P]),
     "cvx_resize_bilinear_nchw_grad_to_rows": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _I32, _P]),
     "cvx_maxpool3_train_nhwc": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -20,32 +20,19 @@
 //   K3 det_ap       one workgroup per class over the records in the reference's order: chunked inclusive scans of TP and FP -> precision
 //                   and recall in fp64; a second, backward sweep carries the suffix maximum and sums the change-point terms
 //   K4 det_map      mean of the APs of the classes that have a non-difficult ground truth
-#include "cvx_common.h"
+#include "det_common.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
 
-constexpr int DET_THREADS = 256;
 constexpr int DET_MAX_ROWS = 16384;       // what cvx_nms can return per image
 constexpr int DET_MAX_GT = 1024;
 constexpr int DET_MAX_LDS = 160 * 1024;
-enum { ST_CURSOR = 0, ST_OVERFLOW = 1, ST_LOW_SCORE = 2, ST_BAD_CLASS = 3 };
 enum { FLAG_FP = 0, FLAG_TP = 1, FLAG_NEITHER = 2 };
 
 __host__ __device__ inline int det_gt_slots(int G) { return (G + 1) & ~1; }
 __host__ __device__ inline int det_row_slots(int max_det) { return (max_det + 3) & ~3; }
 inline size_t det_match_lds(int max_det, int G) { return 32 + (size_t)32 * det_gt_slots(G) + (size_t)8 * det_row_slots(max_det); }
-
-// str(np.float32(x))[:6] for x in [1e-4, 1]: the 4-decimal number k / 1e4 nearest to x is the text itself when it rounds back to x (the
-// shortest round-trip text is then no longer than it), otherwise the text has more digits and the cut truncates.  x * 1e4 is exact in fp64.
-__device__ __forceinline__ float det_quantize(float x) {
-  const double p = (double)x * 1e4;
-  const double k = rint(p);
-  if ((float)(k / 1e4) == x) return x;
-  return (float)(floor(p) / 1e4);
-}
-
-__device__ __forceinline__ int det_count(int c, int max_det) { return (c < 0 || c > max_det) ? 0 : c; }
 
 __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int B, int max_det,
                                                                 int box_mode, const float* __restrict__ box_map, const int* __restrict__ gt,
@@ -109,12 +96,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __r
     float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
     const float score = row[4];
     int cls = __float2int_rz(row[5]);
-    if (box_mode == 1) {  // core/utils/boxes.py:undo_letterbox in fp32, one rounding per operation
-      x1 = __fmul_rn(__fsub_rn(x1, px), gx);
-      y1 = __fmul_rn(__fsub_rn(y1, py), gy);
-      x2 = __fmul_rn(__fsub_rn(x2, px), gx);
-      y2 = __fmul_rn(__fsub_rn(y2, py), gy);
-    }
+    if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, px, py, gx, gy);
     const long long l = __float2int_rz(x1), t = __float2int_rz(y1), rr = __float2int_rz(x2), bb = __float2int_rz(y2);  // int(): towards zero
     if (!(score >= 1e-4f)) ++low_score;  // the reference prints these in scientific notation: rejected at the end, not emulated
     const float q = quantize ? det_quantize(score) : score;
@@ -167,39 +149,6 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __r
   }
   if (bad_class) atomicAdd(&state[ST_BAD_CLASS], bad_class);
   if (low_score) atomicAdd(&state[ST_LOW_SCORE], low_score);
-}
-
-__global__ __launch_bounds__(DET_THREADS) void det_cursor_kernel(const int* __restrict__ counts, int B, int max_det, long long capacity,
-                                                                 unsigned long long* state) {
-  __shared__ long long red[DET_THREADS / 64];
-  long long total = 0;
-  for (int i = threadIdx.x; i < B; i += DET_THREADS) total += det_count(counts[i], max_det);
-  for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const long long next = (long long)state[ST_CURSOR] + red[0] + red[1] + red[2] + red[3];
-    state[ST_CURSOR] = (unsigned long long)(next < capacity ? next : capacity);
-  }
-}
-
-// ---- cvx_det_ap --------------------------------------------------------------------------------------------------------------------------
-// inclusive scan over the workgroup's 256 values (Hillis-Steele through LDS; the segments are short and this runs once per evaluation)
-template <typename T, typename Op>
-__device__ __forceinline__ T det_block_scan(T v, T* buf, int lane, bool backward, Op op) {
-  const int i = backward ? DET_THREADS - 1 - lane : lane;
-  buf[i] = v;
-  __syncthreads();
-  for (int o = 1; o < DET_THREADS; o <<= 1) {
-    T other = v;
-    const bool has = i >= o;
-    if (has) other = buf[i - o];
-    __syncthreads();
-    if (has) v = op(other, v);
-    buf[i] = v;
-    __syncthreads();
-  }
-  return v;
 }
 
 __device__ __forceinline__ bool det_score_reaches(float s, double threshold, int quantize) {

@@ -11,7 +11,7 @@ keeps that order among equal scores.  ``add_batch`` keeps (call order, image ord
 ORDER to reproduce the reference's tie-breaks.
 
 Not reproduced: scores below 1e-4 (the reference's text is scientific notation there; ``results()`` raises if one was seen -- the
-writers use ``conf_threshold=0.001``), ``get_coco_map``, the plots, ``images-optional`` and the log-average miss rate.
+writers use ``conf_threshold=0.001``), the plots, ``images-optional`` and the log-average miss rate.
 """
 import os
 
@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import coco_eval
 
 FLAG_FP, FLAG_TP, FLAG_NEITHER = 0, 1, 2
 MAX_ROWS, MAX_GT = 16384, 1024
@@ -268,11 +269,13 @@ def class_names(dataset_cfg, num_classes):
     return names if len(names) == num_classes else [str(c) for c in range(num_classes)]
 
 
-def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_root, class_names, max_det, capacity=None):
+def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_root, class_names, max_det, capacity=None, coco_metric=False):
     """The loop the four ``evaluate_on_voc`` methods share.  ``evaluator_rows(images, meta)`` -> (rows, counts, box_map or None) on the
     device.  ``capacity`` defaults to batches x batch size x min(max_det, 1024) records.  Writes ``<map_out_root>/results/results.txt`` and
-    returns the ``results()`` dict."""
-    ev = None
+    returns the ``results()`` dict.  ``coco_metric``: the same pass also feeds a ``CocoEvaluator`` what ``get_coco_map`` (mAP.py:930-959)
+    reads from the writers' text files -- truncated boxes, cut scores, the ground truth as ``preprocess_gt`` converts it; its results are
+    the ``"coco"`` entry and its twelve lines go to ``<map_out_root>/coco_results.txt``."""
+    ev = coco = None
     for images, meta in dataloader:
         rows, counts, box_map = evaluator_rows(images, meta)
         if ev is None:
@@ -281,10 +284,17 @@ def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_r
                     raise L.CvxError("evaluate_on_voc: a dataloader without len() needs capacity= (the records of the whole evaluation)")
                 capacity = len(dataloader) * int(rows.shape[0]) * min(int(max_det), 1024)
             ev = DetectionEvaluator(num_classes, max_det, capacity, rows.device)
+            if coco_metric:
+                coco = coco_eval.CocoEvaluator(num_classes, max_det, capacity, rows.device, truncate_boxes=True, quantize_scores=True)
         ev.add_batch(rows, counts, meta["gt"], meta["gt_counts"], box_map)
+        if coco is not None:
+            coco.add_batch(rows, counts, coco_eval.voc_gt_to_coco(meta["gt"]), meta["gt_counts"], box_map)
     if ev is None:
         raise L.CvxError("evaluate_on_voc: the dataloader yielded no batch")
     res = ev.results()
     ev.write_report(os.path.join(map_out_root, "results", "results.txt"), class_names)
     print("metrics = {0:.2f}%".format(res["mAP"] * 100))
+    if coco is not None:
+        res = dict(res, coco=coco.results())
+        coco_eval.write_summary(coco, map_out_root)
     return res

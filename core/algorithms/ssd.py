@@ -156,7 +156,7 @@ class Ssd:
             results.append(o if len(o) else [])
         return results
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
         """Reference :96-188: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
         ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
         images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
@@ -164,7 +164,9 @@ class Ssd:
         ``dr_files_list.sort()`` decides equal scores).
         Per batch: the forward, ``decode_device`` (with the host reads it makes), ``_correct_boxes`` restated as float32 tensor
         operations on the device batch and one ``cvx_det_match`` launch (mode 0).  An image without detections contributes none (the
-        reference writes one all-zero line of class 0 for it).  Returns ``DetectionEvaluator.results()``."""
+        reference writes one all-zero line of class 0 for it).  Returns ``DetectionEvaluator.results()``.
+        ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
+        entry of the result."""
         if subset not in ("val", "test"):
             raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
         if dataloader is None:
@@ -173,6 +175,12 @@ class Ssd:
         from computervision.pytorch_amd import det_eval
         from configs.dataset_cfg import VOC_CFG
         model.eval()
+        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
+                                          det_eval.class_names(VOC_CFG, self.num_classes), 16384, capacity, coco_metric)
+
+    def _evaluation_rows(self, model):
+        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``"""
+        from computervision.pytorch_amd import det_eval
 
         def rows_of(images, meta):
             with torch.no_grad():
@@ -182,8 +190,19 @@ class Ssd:
             rows[..., :4] = det_eval.correct_boxes_device(rows[..., :4], self.input_image_size, meta["image_hw"], self.letterbox_image)
             return rows, counts, None
 
-        return det_eval.evaluate_detector(rows_of, dataloader, self.num_classes, self.device, map_out_root,
-                                          det_eval.class_names(VOC_CFG, self.num_classes), 16384, capacity)
+        return rows_of
+
+    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+        """Reference :183-234: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and scores unrounded.
+        Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields ``(images, meta)`` with
+        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt_coco (B, G, 7)
+        float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER.
+        The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
+        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
+        from computervision.pytorch_amd import coco_eval
+        coco_eval.check_coco_arguments(subset, dataloader)
+        model.eval()
+        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, 16384, capacity)
 
     def _correct_boxes(self, box_xy, box_wh, input_shape, image_shape):
         """yolo_correct_boxes (core/utils/image_process.py:161-181)."""

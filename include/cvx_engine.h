@@ -466,6 +466,33 @@ int cvx_det_match(const float* rows, const int32_t* counts, int32_t batch, int32
                   void* hip_stream);
 int cvx_det_ap(const float* score, const int32_t* flag, const int64_t* seg_off, const int64_t* gt_per_class, int32_t nc,
                double score_threshold, int32_t quantize, double* prec, double* rec, double* stats, void* hip_stream);
+/* COCO detection metric of a detector (pycocotools' COCOeval(gt, dt, 'bbox'): iouThrs linspace(.5, .95, 10), recThrs linspace(0, 1, 101),
+ * maxDets 1 / 10 / 100, areas all / small / medium / large, useCats), accumulated on the device batch by batch.
+ * cvx_coco_match, once per batch: rows, counts, box_mode and box_map as cvx_det_match takes them.  truncate != 0: the mapped corners are
+ * cut towards zero (the VOC writers' int()); quantize != 0: the score becomes what str(float32)[:6] keeps (cvx_det_match's rule).  Box
+ * widths x2 - x1 and y2 - y1 are taken in fp32 and widened; everything after is fp64 without contraction.  gt (batch, max_gt, 7) fp64
+ * [cls, x, y, w, h, area, iscrowd], gt_counts (batch) int32.  iou_thrs: the 10 thresholds, fp64 on the device.  One workgroup per image:
+ * the rows ordered by (class, score descending, row), each class cut to 100, then evaluateImg's greedy walk for each (class present, area
+ * range a, threshold t).  Appends per detection, in (image, row) order at the device cursor: rec_score fp32, rec_class int32, rec_rank int32
+ * (place in its (image, class) list; >= 100: not evaluated), rec_matched and rec_ignored int64 (bit a * 10 + t).  npig (nc, 4) int64 counts
+ * the ground truths that are neither crowd nor outside the area range.  state: 4 int64 (device), zeroed by the caller: [cursor, overflow
+ * (NMS overflow, bad counts, no room left), unusable scores (below 1e-4 when quantize, negative or NaN otherwise), classes outside
+ * [0, nc)].  max_det <= 16384 and max_gt <= 1024, together within the 160 KB LDS.  No host read; asynchronous on hip_stream.
+ * cvx_coco_accumulate, once per evaluation, over the records in (class ascending, score descending, stable) order: rank, matched, ignored
+ * in that order, seg_off (nc + 1) int64 = the first record of each class, rec_thrs: the 101 recall thresholds, fp64 on the device.  One
+ * workgroup per (class, area, maxDet): precision (10, 101, nc, 4, 3) and recall (10, nc, 4, 3) fp64, -1 where the class has no counted
+ * ground truth in the area range.
+ * cvx_coco_summarize: stats (12) fp64 = AP, AP50, AP75, APs, APm, APl (maxDets 100), AR1, AR10, AR100, ARs, ARm, ARl: means over the
+ * entries > -1 (-1 when there is none), summed in a fixed order.
+ * Replaces: COCOeval.evaluate / accumulate / summarize as core/metrics/mAP.py:930-959 (get_coco_map) and the detectors' evaluate_on_coco
+ * (core/algorithms/yolo_v8.py:330-381) call them, and the JSON files they exchange. */
+int cvx_coco_match(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, int32_t box_mode, const float* box_map,
+                   int32_t truncate, int32_t quantize, const double* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc,
+                   const double* iou_thrs, float* rec_score, int32_t* rec_class, int32_t* rec_rank, int64_t* rec_matched, int64_t* rec_ignored,
+                   int64_t capacity, int64_t* state, int64_t* npig, void* hip_stream);
+int cvx_coco_accumulate(const int32_t* rank, const int64_t* matched, const int64_t* ignored, const int64_t* seg_off, const int64_t* npig,
+                        int32_t nc, const double* rec_thrs, double* precision, double* recall, void* hip_stream);
+int cvx_coco_summarize(const double* precision, const double* recall, int32_t nc, double* stats, void* hip_stream);
 /* CenterNet's CombinedLoss with its gradient.  rows: the engine's fp32 head rows (batch, anchors = h*w, ld): heat-map logits in columns
  * [0, nc), the loss's "reg" pair at columns col_a, col_a+1 (= the model output's columns nc, nc+1) and its "wh" pair at col_b, col_b+1 (= the
  * output's last two) -- the reference's loss names are swapped against the heads that produce them, reproduced as is.  Targets as
