@@ -1,0 +1,81 @@
+"""What the detector wrappers share.  ``Detector``: the two evaluation drivers of the algorithm-class contract, ``evaluate_on_voc`` and
+``evaluate_on_coco``, over the model's own ``_evaluation_rows``.  For the two anchor decodes that end in ``cvx_nms_variant`` (YOLOv7,
+SSD): ``nms_with_room``, the call that grows its row block until nothing is cut short, and ``NmsDetector``, the map of the kept corner
+boxes to the original image."""
+from computervision.pytorch_amd import _lib as L
+from computervision.pytorch_amd import engine as _engine
+from core.utils.boxes import correct_boxes
+
+MAX_DET = 1024          # rows per NMS block cvx_nms_variant is first asked for; a full block is retried with 4x the room, up to ...
+MAX_CANDIDATES = 16384  # ... the candidates per block the in-LDS sort holds (the reference's NMS has no limit: only beyond this it raises)
+
+
+def nms_with_room(y, conf_threshold, nms_threshold, overflow_message, **kw):
+    """``cvx_nms_variant`` (vanilla) on ``y`` with room for every kept row, as the reference's unlimited NMS has: MAX_DET rows per block
+    first, four times as many while a block comes back full (it may have been cut short), up to MAX_CANDIDATES.  One host read, of the
+    counts, per attempt.  Returns (rows, index, counts, the counts on the host); a count of -1 -- more candidates in a block than the
+    sort holds -- raises ``CvxError(overflow_message(block))``."""
+    max_det = MAX_DET
+    while True:
+        rows, index, counts = _engine.nms(y, conf_threshold, nms_threshold, max_det=max_det, variant="vanilla", **kw)
+        counts_h = counts.cpu()
+        found = counts_h.tolist()
+        if min(found, default=0) < 0:
+            raise L.CvxError(overflow_message(next(i for i, n in enumerate(found) if n < 0)))
+        if max(found, default=0) < max_det or max_det >= MAX_CANDIDATES:
+            return rows, index, counts, counts_h
+        max_det = min(max_det * 4, MAX_CANDIDATES)
+
+
+class Detector:
+    """Needs ``num_classes``, ``device``, ``eval_max_det`` (the most rows per image ``_evaluation_rows`` returns) and
+    ``_evaluation_rows(model) -> rows_of(images, meta) -> (rows, counts, box map or None)`` at ``conf_threshold=0.001``."""
+
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
+        """The reference's ``evaluate_on_voc``: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
+        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
+        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
+        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
+        ``dr_files_list.sort()`` decides equal scores).
+        Per batch: the model's ``_evaluation_rows`` (its docstring says what that launches and reads) and one ``cvx_det_match`` launch.
+        An image without detections contributes none (the reference writes one all-zero line of class 0 for it, YOLOv8's writes
+        nothing).  Returns ``DetectionEvaluator.results()``.  No plots.
+        ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
+        entry of the result."""
+        if subset not in ("val", "test"):
+            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
+        if dataloader is None:
+            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
+                             "device over the VOC-" + subset + " pictures in sorted-id order")
+        from computervision.pytorch_amd import det_eval
+        from configs.dataset_cfg import VOC_CFG
+        model.eval()
+        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
+                                          det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric)
+
+    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+        """The reference's ``evaluate_on_coco``: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and
+        scores unrounded.  Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields
+        ``(images, meta)`` with images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes,
+        gt_coco (B, G, 7) float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN
+        SORTED-ID ORDER.
+        The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
+        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
+        from computervision.pytorch_amd import coco_eval
+        coco_eval.check_coco_arguments(subset, dataloader)
+        model.eval()
+        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, self.eval_max_det, capacity)
+
+
+class NmsDetector(Detector):
+    """Needs ``input_image_size`` and ``letterbox_image`` besides."""
+    eval_max_det = MAX_CANDIDATES
+
+    def _correct_boxes(self, box_xy, box_wh, input_shape, image_shape):
+        return correct_boxes(box_xy, box_wh, input_shape, image_shape, self.letterbox_image)
+
+    def _to_image(self, det, image_h, image_w):
+        """Rows that begin with normalised corners [x1, y1, x2, y2] (numpy, changed in place) -> the same rows in original-image pixels"""
+        xy, wh = (det[:, 0:2] + det[:, 2:4]) / 2, det[:, 2:4] - det[:, 0:2]
+        det[:, :4] = self._correct_boxes(xy, wh, self.input_image_size, [image_h, image_w])
+        return det

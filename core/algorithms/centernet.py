@@ -12,11 +12,12 @@ from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd import engine as _engine
 from computervision.pytorch_amd.dla import CenterNetDLA34, CenterNetLoss
 from configs import CenternetConfig
+from core.algorithms.base import Detector
 from registry import model_registry
 
 
 @model_registry("centernet")
-class CenterNetA:
+class CenterNetA(Detector):
     def __init__(self, cfg: CenternetConfig, device):
         self.cfg, self.device = cfg, device
         self.num_classes = cfg.dataset.num_classes
@@ -87,47 +88,19 @@ class CenterNetA:
         boxes = det_eval.reverse_letterbox_device(boxes, self.input_size, image_hw)
         return torch.cat((boxes, scores.unsqueeze(2), classes.to(torch.float32).unsqueeze(2)), 2), out["counts"]
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
-        """Reference :137-229: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
-        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
-        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
-        ``dr_files_list.sort()`` decides equal scores).
-        Per batch: the forward, ``decode_raw``, ``_finish``'s inverse letterbox restated as float32 tensor operations on the device batch
-        and one ``cvx_det_match`` launch (mode 0); the counts stay on the device, so the host reads once, at the end.  An image without
-        detections contributes none (the reference writes one all-zero line of class 0 for it).  Returns ``DetectionEvaluator.results()``.
-        ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
-        entry of the result."""
-        if subset not in ("val", "test"):
-            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
-        if dataloader is None:
-            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
-                             "device over the VOC-" + subset + " pictures in sorted-id order")
-        from computervision.pytorch_amd import det_eval
-        from configs.dataset_cfg import VOC_CFG
-        model.eval()
-        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
-                                          det_eval.class_names(VOC_CFG, self.num_classes), self.K, capacity, coco_metric)
+    @property
+    def eval_max_det(self):
+        return self.K
 
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``"""
+        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        ``evaluate_rows`` -- the forward, ``decode_raw`` and ``_finish``'s inverse letterbox restated as float32 tensor operations on the
+        device batch; the counts stay on the device, so the host reads once, at the end (``cvx_det_match`` mode 0)."""
         def rows_of(images, meta):
             rows, counts = self.evaluate_rows(model, images, meta["image_hw"])
             return rows, counts, None
 
         return rows_of
-
-    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
-        """Reference :222-269: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and scores unrounded.
-        Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt_coco (B, G, 7)
-        float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER.
-        The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
-        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
-        from computervision.pytorch_amd import coco_eval
-        coco_eval.check_coco_arguments(subset, dataloader)
-        model.eval()
-        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, self.K, capacity)
 
     def _finish(self, out, b, h, w):
         n = int(out["counts"][b])

@@ -1,7 +1,8 @@
-"""SSD algorithm wrapper -- the duck-typed interface of the reference's ``Ssd`` (core/algorithms/ssd.py:27-535) for the INFERENCE
-path: ``__init__(cfg, device)`` (prior boxes included), ``build_model() -> (nn.Module, name)``,
-``decode_boxes(preds, h, w, conf_threshold=None)``, ``predict``.  Network, softmax + box decode and the per-class NMS run on the
-MI355X engine (``computervision.pytorch_amd.ssd``, ``cvx_ssd_decode``, ``cvx_nms_variant``); ``build_loss`` (MultiBoxLossV2) raises.
+"""SSD algorithm wrapper -- the duck-typed interface of the reference's ``Ssd`` (core/algorithms/ssd.py:27-535): ``__init__(cfg, device)``
+(prior boxes included), ``build_model() -> (nn.Module, name)``, ``build_loss()``, ``decode_boxes(preds, h, w, conf_threshold=None)``,
+``predict``, ``evaluate_on_voc`` / ``evaluate_on_coco`` (core/algorithms/base.py).  Network, softmax + box decode and the per-class NMS run
+on the MI355X engine (``computervision.pytorch_amd.ssd``, ``cvx_ssd_decode``, ``cvx_nms_variant``); ``build_loss`` returns the engine's
+fused MultiBoxLoss; the target encoding of the reference's collate (``generate_targets``) is ``cvx_ssd_encode_targets`` for the batch.
 """
 import numpy as np
 import torch
@@ -10,13 +11,12 @@ from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd import engine as _engine
 from computervision.pytorch_amd.ssd import MultiBoxLoss, SSD300VGG
 from configs import SsdConfig
+from core.algorithms.base import NmsDetector, nms_with_room
 from registry import model_registry
-
-MAX_DET = 1024          # rows per image and class cvx_nms_variant is first asked for (a full block is retried with 4x the room)
 
 
 @model_registry("ssd")
-class Ssd:
+class Ssd(NmsDetector):
     def __init__(self, cfg: SsdConfig, device):
         self.cfg, self.device = cfg, device
         self.input_image_size = cfg.arch.input_size[1:]
@@ -115,26 +115,17 @@ class Ssd:
         empty = (torch.zeros(0, 6, device=dev), torch.zeros(0, 2, dtype=torch.long, device=dev))
         if not classes:
             return [empty for _ in range(B)]
-        # one NMS launch per class that has a score above the threshold, all queued back to back; ONE host read (the counts of every
-        # class and image) afterwards, and one masked gather per image instead of a cat per (class, image)
         # ONE NMS launch for all active classes: (class, image) pairs are the launch's batch -- a workgroup per pair, C' * B of them, instead
         # of C' launches of B workgroups (measured with 256 planted candidates per image, 20 classes active: 4.7 -> 0.6 ms per batch of 32)
         nc_act = len(classes)
         cidx = torch.tensor(classes, device=dev)
         stacked = torch.cat((bt.unsqueeze(0).expand(nc_act, -1, -1, -1), prob.index_select(2, cidx).permute(2, 0, 1).unsqueeze(2)), 2).reshape(nc_act * B, 5, A)
-        max_det = MAX_DET
-        while True:
-            r_, i_, c_ = _engine.nms(stacked, float(conf_thr), self.nms_threshold, max_det=max_det, variant="vanilla", boxes_xyxy=True)
-            rows = r_.view(nc_act, B, *r_.shape[1:])                             # (C', B, max_det, 6)
-            index = i_.long().view(nc_act, B, -1)                                # (C', B, max_det)
-            counts = c_.view(nc_act, B)                                          # (C', B)
-            counts_h = counts.cpu()                                              # the one host read (one more per retry)
-            if bool((counts_h < 0).any()):  # 8732 priors never exceed the 16384 candidates the in-LDS sort holds; kept for other prior sets
-                raise L.CvxError("cvx_nms: more than 16384 candidates of one class above the confidence threshold in one image")
-            # a full row block may have been cut short: ask again with room for every prior (the reference's decode_boxes has no limit)
-            if int(counts_h.max()) < max_det or max_det >= 16384:
-                break
-            max_det = min(max_det * 4, 16384)
+        # 8732 priors never exceed the 16384 candidates the in-LDS sort holds: the overflow error is kept for other prior sets
+        overflow = "cvx_nms: more than 16384 candidates of one class above the confidence threshold in one image"
+        r_, i_, counts, counts_h = nms_with_room(stacked, float(conf_thr), self.nms_threshold, lambda block: overflow, boxes_xyxy=True)
+        rows = r_.view(nc_act, B, *r_.shape[1:])                                 # (C', B, max_det, 6)
+        index = i_.long().view(nc_act, B, -1)                                    # (C', B, max_det)
+        counts, counts_h = counts.view(nc_act, B), counts_h.view(nc_act, B)      # (C', B), on the device and on the host
         cls_col = torch.tensor(classes, device=dev).view(-1, 1, 1).expand(-1, B, rows.shape[2])      # class column per slot
         valid = torch.arange(rows.shape[2], device=dev).view(1, 1, -1) < counts.unsqueeze(2)         # (C', B, MAX_DET)
         det = torch.cat((rows[..., :4], (cls_col - 1).unsqueeze(3).to(rows.dtype), rows[..., 4:5]), 3)
@@ -150,36 +141,13 @@ class Ssd:
         results = []
         for det, _ in self.decode_device(preds, conf_threshold):
             o = det.cpu().numpy()
-            if len(o):
-                xy, wh = (o[:, 0:2] + o[:, 2:4]) / 2, o[:, 2:4] - o[:, 0:2]
-                o[:, :4] = self._correct_boxes(xy, wh, self.input_image_size, [h, w])
-            results.append(o if len(o) else [])
+            results.append(self._to_image(o, h, w) if len(o) else [])
         return results
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
-        """Reference :96-188: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
-        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
-        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
-        ``dr_files_list.sort()`` decides equal scores).
-        Per batch: the forward, ``decode_device`` (with the host reads it makes), ``_correct_boxes`` restated as float32 tensor
-        operations on the device batch and one ``cvx_det_match`` launch (mode 0).  An image without detections contributes none (the
-        reference writes one all-zero line of class 0 for it).  Returns ``DetectionEvaluator.results()``.
-        ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
-        entry of the result."""
-        if subset not in ("val", "test"):
-            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
-        if dataloader is None:
-            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
-                             "device over the VOC-" + subset + " pictures in sorted-id order")
-        from computervision.pytorch_amd import det_eval
-        from configs.dataset_cfg import VOC_CFG
-        model.eval()
-        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
-                                          det_eval.class_names(VOC_CFG, self.num_classes), 16384, capacity, coco_metric)
-
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``"""
+        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        the forward, ``decode_device`` (with the host reads it makes) and ``_correct_boxes`` restated as float32 tensor operations on the
+        device batch (``correct_boxes_device``); the evaluators take the boxes as final (``cvx_det_match`` mode 0)."""
         from computervision.pytorch_amd import det_eval
 
         def rows_of(images, meta):
@@ -191,33 +159,6 @@ class Ssd:
             return rows, counts, None
 
         return rows_of
-
-    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
-        """Reference :183-234: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and scores unrounded.
-        Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt_coco (B, G, 7)
-        float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER.
-        The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
-        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
-        from computervision.pytorch_amd import coco_eval
-        coco_eval.check_coco_arguments(subset, dataloader)
-        model.eval()
-        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, 16384, capacity)
-
-    def _correct_boxes(self, box_xy, box_wh, input_shape, image_shape):
-        """yolo_correct_boxes (core/utils/image_process.py:161-181)."""
-        xywh = np.concatenate([box_xy, box_wh], axis=-1)
-        if self.letterbox_image:
-            ih, iw = image_shape
-            h, w = input_shape
-            scale = max(ih / h, iw / w)
-            top, left = (h - ih / scale) // 2, (w - iw / scale) // 2
-            cx, cy, bw, bh = xywh[:, 0] * w - left, xywh[:, 1] * h - top, xywh[:, 2] * w, xywh[:, 3] * h
-            return np.stack([(cx - bw / 2) * scale, (cy - bh / 2) * scale, (cx + bw / 2) * scale, (cy + bh / 2) * scale], -1)
-        out = np.stack([xywh[:, 0] - xywh[:, 2] / 2, xywh[:, 1] - xywh[:, 3] / 2, xywh[:, 0] + xywh[:, 2] / 2, xywh[:, 1] + xywh[:, 3] / 2], -1)
-        out[:, ::2] *= image_shape[1]
-        out[:, 1::2] *= image_shape[0]
-        return out
 
     def predict_tensor(self, model, images: torch.Tensor, h, w, conf_threshold=None):
         model.eval()

@@ -1,8 +1,8 @@
-"""YOLOv7 algorithm wrapper -- the duck-typed interface of the reference's ``YOLOv7`` (core/algorithms/yolo_v7.py:27-424) for the
-INFERENCE path: ``__init__(cfg, device)``, ``get_anchors``, ``build_model() -> (nn.Module, name)``,
-``decode_box(preds, image_h, image_w, conf_threshold=None)``, ``predict``.  Network, anchor decode and per-class NMS run on
-the MI355X engine (``computervision.pytorch_amd.yolov7``, ``cvx_yolo7_decode``, ``cvx_nms_variant``); ``build_loss``
-(Yolo7Loss with SimOTA matching) raises.
+"""YOLOv7 algorithm wrapper -- the duck-typed interface of the reference's ``YOLOv7`` (core/algorithms/yolo_v7.py:27-424):
+``__init__(cfg, device)``, ``get_anchors``, ``build_model() -> (nn.Module, name)``, ``build_loss()``,
+``decode_box(preds, image_h, image_w, conf_threshold=None)``, ``predict``, ``evaluate_on_voc`` / ``evaluate_on_coco``
+(core/algorithms/base.py).  Network, anchor decode and per-class NMS run on the MI355X engine (``computervision.pytorch_amd.yolov7``,
+``cvx_yolo7_decode``, ``cvx_nms_variant``); ``build_loss`` returns the engine's fused Yolo7Loss (SimOTA matching on the device).
 """
 import numpy as np
 import torch
@@ -11,14 +11,12 @@ from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd import engine as _engine
 from computervision.pytorch_amd.yolov7 import Yolo7L, Yolo7Loss
 from configs import Yolo7Config
+from core.algorithms.base import MAX_CANDIDATES, NmsDetector, nms_with_room
 from registry import model_registry
-
-MAX_DET = 1024          # rows per image cvx_nms_variant is first asked for; a full block is retried with 4x the room, up to ...
-MAX_CANDIDATES = 16384  # ... the candidates per image the in-LDS sort holds (the reference's _nms has no limit: only beyond this it raises)
 
 
 @model_registry("yolo7")
-class YOLOv7:
+class YOLOv7(NmsDetector):
     def __init__(self, cfg: Yolo7Config, device) -> None:
         self.cfg, self.device = cfg, device
         self.anchors = self.get_anchors()
@@ -65,17 +63,10 @@ class YOLOv7:
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
         # cvx_nms keeps scores > threshold (ultralytics_ops.py:190), the reference here keeps >= : the next float below
         thr = float(np.nextafter(np.float32(conf), np.float32(-1.0)))
-        max_det = MAX_DET
-        while True:
-            rows, index, counts = _engine.nms(y, thr, self.nms_threshold, max_det=max_det, variant="vanilla")
-            counts_h = counts.cpu().tolist()                       # the ONE host read of the tail (one more per retry)
-            for b, n in enumerate(counts_h):
-                if n < 0:  # the in-LDS sort holds 16384 candidates per image: only then is the reference's unlimited _nms out of reach
-                    raise L.CvxError(f"cvx_nms: more than {MAX_CANDIDATES} candidates above the confidence threshold in image {b}")
-            # a full row block may have been cut short: ask again with room for every candidate (mAP-style runs at conf 0.001)
-            if max(counts_h, default=0) < max_det or max_det >= MAX_CANDIDATES:
-                break
-            max_det = min(max_det * 4, MAX_CANDIDATES)
+        # the in-LDS sort holds 16384 candidates per image: only beyond that is the reference's unlimited _nms out of reach
+        overflow = f"cvx_nms: more than {MAX_CANDIDATES} candidates above the confidence threshold in image "
+        rows, index, counts, counts_h = nms_with_room(y, thr, self.nms_threshold, lambda b: overflow + str(b))
+        counts_h = counts_h.tolist()
         # re-order every image's kept rows at once (no per-image kernels): class ascending, cvx_nms's descending score inside a class;
         # rows past an image's count sort to the end
         B, K = rows.shape[0], rows.shape[1]
@@ -98,37 +89,14 @@ class YOLOv7:
             if det is None:
                 results.append(None)
                 continue
-            o = det.cpu().numpy()
-            xy, wh = (o[:, 0:2] + o[:, 2:4]) / 2, o[:, 2:4] - o[:, 0:2]
-            o[:, :4] = self._correct_boxes(xy, wh, self.input_image_size, [image_h, image_w])
-            results.append(o)
+            results.append(self._to_image(det.cpu().numpy(), image_h, image_w))
         return results
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
-        """Reference :94-186: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
-        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
-        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
-        ``dr_files_list.sort()`` decides equal scores).
-        Per batch: the forward, ``decode_rows`` and ``nms_device`` (with the one host read it makes), ``_correct_boxes`` restated as
-        float32 tensor operations on the device batch, score = objectness * class probability, and one ``cvx_det_match`` launch (mode 0).
-        An image without detections contributes none (the reference writes one all-zero line of class 0 for it).  Returns
-        ``DetectionEvaluator.results()``.
-        ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
-        entry of the result."""
-        if subset not in ("val", "test"):
-            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
-        if dataloader is None:
-            raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
-                             "device over the VOC-" + subset + " pictures in sorted-id order")
-        from computervision.pytorch_amd import det_eval
-        from configs.dataset_cfg import VOC_CFG
-        model.eval()
-        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
-                                          det_eval.class_names(VOC_CFG, self.num_classes), MAX_CANDIDATES, capacity, coco_metric)
-
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``"""
+        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        the forward, ``decode_rows`` and ``nms_device`` (with the one host read it makes), score = objectness * class probability, and
+        ``_correct_boxes`` restated as float32 tensor operations on the device batch (``correct_boxes_device``); the evaluators take the
+        boxes as final (``cvx_det_match`` mode 0)."""
         from computervision.pytorch_amd import det_eval
 
         def rows_of(images, meta):
@@ -146,35 +114,6 @@ class YOLOv7:
             return rows, counts, None
 
         return rows_of
-
-    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
-        """Reference :181-232: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and scores unrounded.
-        Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt_coco (B, G, 7)
-        float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER.
-        The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
-        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
-        from computervision.pytorch_amd import coco_eval
-        coco_eval.check_coco_arguments(subset, dataloader)
-        model.eval()
-        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, MAX_CANDIDATES, capacity)
-
-    def _correct_boxes(self, box_xy, box_wh, input_shape, image_shape):
-        """yolo_correct_boxes (core/utils/image_process.py:161-181): letterbox inverse, or plain scaling to the image size."""
-        xywh = np.concatenate([box_xy, box_wh], axis=-1)
-        if self.letterbox_image:
-            ih, iw = image_shape
-            h, w = input_shape
-            scale = max(ih / h, iw / w)
-            top, left = (h - ih / scale) // 2, (w - iw / scale) // 2
-            cx, cy = xywh[:, 0] * w - left, xywh[:, 1] * h - top
-            bw, bh = xywh[:, 2] * w, xywh[:, 3] * h
-            out = np.stack([(cx - bw / 2) * scale, (cy - bh / 2) * scale, (cx + bw / 2) * scale, (cy + bh / 2) * scale], -1)
-            return out
-        out = np.stack([xywh[:, 0] - xywh[:, 2] / 2, xywh[:, 1] - xywh[:, 3] / 2, xywh[:, 0] + xywh[:, 2] / 2, xywh[:, 1] + xywh[:, 3] / 2], -1)
-        out[:, ::2] *= image_shape[1]
-        out[:, 1::2] *= image_shape[0]
-        return out
 
     def predict_tensor(self, model, images: torch.Tensor, image_h, image_w, conf_threshold=None):
         model.eval()

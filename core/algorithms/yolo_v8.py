@@ -10,10 +10,10 @@ from computervision.pytorch_amd._lib import CvxError
 
 from computervision.pytorch_amd import det_eval
 from computervision.pytorch_amd import engine as _engine
-from computervision.pytorch_amd.det_eval import class_names as _class_names
 from computervision.pytorch_amd.model import Yolo8
 from computervision.pytorch_amd.train import V8DetectionLoss
 from configs import Yolo8DetConfig
+from core.algorithms.base import Detector
 from core.utils.boxes import undo_letterbox
 from registry import model_registry
 
@@ -23,7 +23,7 @@ _NAMES = {"n": "YOLOv8n", "s": "YOLOv8s", "m": "YOLOv8m", "l": "YOLOv8l", "x": "
 
 
 @model_registry("yolo8_det")
-class YOLOv8:
+class YOLOv8(Detector):
     def __init__(self, cfg: Yolo8DetConfig, device):
         self.cfg = cfg
         self.device = device
@@ -62,28 +62,14 @@ class YOLOv8:
         assert len(out) == 1, "仅支持单张图片的预测"
         return undo_letterbox(out[0].cpu().numpy(), self.input_image_size, (image_h, image_w), self.letterbox_image)
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
-        """Reference :244-326: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
-        ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
-        [cls, l, t, r, b, difficult], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER (the reference's
-        ``dr_files_list.sort()`` decides equal scores).
-        Per batch: one engine forward, ``cvx_nms`` with the counts kept on the device and one ``cvx_det_match`` launch that undoes the
-        letterbox (box-map mode 1); the host reads once, at the end.  Returns ``DetectionEvaluator.results()``.  No plots.
-        ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
-        entry of the result."""
-        if subset not in ("val", "test"):
-            raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
-        if dataloader is None:
-            raise CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader= yielding (images, dict(image_hw, gt, gt_counts)) on the "
-                           "device over the VOC-" + subset + " pictures in sorted-id order")
-        from configs.dataset_cfg import VOC_CFG
-        model.eval()
-        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
-                                          _class_names(VOC_CFG, self.num_classes), self.max_det, capacity, coco_metric)
+    @property
+    def eval_max_det(self):
+        return self.max_det
 
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, box map) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``"""
+        """(images, meta) -> (rows, counts, box map) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        one engine forward and ``cvx_nms`` with the counts kept on the device; the evaluators' match launch undoes the letterbox (box-map
+        mode 1), so the host reads once, at the end."""
         def rows_of(images, meta):
             with torch.no_grad():
                 preds = model(images.to(self.device))
@@ -92,18 +78,6 @@ class YOLOv8:
             return rows, counts, det_eval.letterbox_box_map(meta["image_hw"], self.input_image_size, self.letterbox_image)
 
         return rows_of
-
-    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
-        """Reference :330-381: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and scores unrounded.
-        Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields ``(images, meta)`` with
-        images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt_coco (B, G, 7)
-        float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN SORTED-ID ORDER.
-        The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
-        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
-        from computervision.pytorch_amd import coco_eval
-        coco_eval.check_coco_arguments(subset, dataloader)
-        model.eval()
-        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, self.max_det, capacity)
 
     def predict_tensor(self, model, image: torch.Tensor, image_h: int, image_w: int):
         """``predict`` minus file I/O and drawing: image (1,3,H,W) in [0,1] already letterboxed."""

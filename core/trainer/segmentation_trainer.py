@@ -17,10 +17,9 @@ import torch
 
 from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd.deeplab import SegTrainStep
-from computervision.pytorch_amd.train import DynamicLossScale, FlatAdam
 from configs import DeeplabV3PlusConfig
 from core.algorithms.segmentation_2d import DeeplabV3PlusA
-from core.trainer.base import BaseTrainer, LinearWarmup
+from core.trainer.engine_trainer import EngineTrainer
 from registry import trainer_registry
 
 
@@ -111,15 +110,11 @@ class SegmentationMetrics:
                 "Mean IoU": float(torch.nanmean(iu)), "Class IoU": dict(zip(range(self.num_classes), iu.tolist()))}
 
 
-def get_optimizer(optimizer_name, model, initial_lr):
-    """reference core/trainer/lr_scheduler.py:37-43 (Adam only)."""
-    if optimizer_name.lower() == "adam":
-        return FlatAdam(model, lr=initial_lr)
-    raise ValueError(f"{optimizer_name} is not supported")
-
-
 @trainer_registry("deeplabv3plus")
-class DeeplabV3PlusTrainer(BaseTrainer):
+class DeeplabV3PlusTrainer(EngineTrainer):
+    algorithm_cls, step_cls = DeeplabV3PlusA, SegTrainStep
+    use_iter_milestones = False
+
     def __init__(self, cfg: DeeplabV3PlusConfig, device, dataloader=None, val_dataloader=None):
         if val_dataloader is not None:
             # the trainer's device, and the device the loader declares if it declares one (DeviceSegLoader does); a loader without a
@@ -129,35 +124,11 @@ class DeeplabV3PlusTrainer(BaseTrainer):
                 raise L.CvxError("val_dataloader= selects the fused evaluation (cvx_seg_eval), which runs on an MI355X only: the trainer's "
                                  f"device and the loader's (here {', '.join(str(d) for d in on)}) must be GPUs, "
                                  "e.g. DeviceSegLoader(..., device='cuda')")
-        self._injected_loader, self._injected_val_loader = dataloader, val_dataloader
-        super().__init__(cfg, device, False)
+        super().__init__(cfg, device, dataloader, val_dataloader)
         self.metrics = SegmentationMetrics(num_classes=cfg.dataset.num_classes, device=device)
-        self.metric_names = ["loss"]
-        self.show_option = [True]
 
-    def set_model_algorithm(self):
-        self.model_algorithm = DeeplabV3PlusA(self.cfg, self.device)
-
-    def initialize_model(self):
-        self.model, self.model_name = self.model_algorithm.build_model()
-        self.model.to(device=self.device)
-
-    def load_data(self):
-        loader = self._injected_loader or SyntheticSegmentationLoader(self.batch_size, self.cfg.arch.crop_size, self.cfg.dataset.num_classes)
-        self.train_dataloader = loader
-        self.val_dataloader = self._injected_val_loader if self._injected_val_loader is not None else loader
-
-    def set_optimizer(self):
-        self.optimizer = get_optimizer(self.optimizer_name, self.model, self.initial_lr)
-
-    def set_lr_scheduler(self):
-        """EnhancedMultiStepLR + LinearWarmup (reference :98-111; an empty milestone list means 'never', lr_scheduler.py:87-91)."""
-        milestones = list(self.milestones) or [int(1e8), int(1e8) + 1]
-        self.lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=milestones, gamma=self.gamma,
-                                                                 last_epoch=self.last_iter if self.last_iter > 0 else -1)
-        if self.warmup_iters > 0:
-            self.warmup_scheduler = LinearWarmup(self.optimizer, warmup_period=self.warmup_iters,
-                                                 last_step=self.last_iter if self.last_iter > 0 else -1)
+    def synthetic_loader(self):
+        return SyntheticSegmentationLoader(self.batch_size, self.cfg.arch.crop_size, self.cfg.dataset.num_classes)
 
     def set_criterion(self):
         # dropout masks (aspp.project.3, deeplabv3plus.py:67) are a counter-based hash of (seed, training pass, op, element) on the engine:
@@ -166,9 +137,7 @@ class DeeplabV3PlusTrainer(BaseTrainer):
         import torch.distributed as dist
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         self.model.seed = (int(torch.initial_seed()) * 0x9E3779B97F4A7C15 + rank * 0xBF58476D1CE4E5B9 + int(self.last_iter) * 0x94D049BB133111EB) & (2 ** 64 - 1)
-        self.criterion = self.model_algorithm.build_loss()
-        scaler = DynamicLossScale(self.device, init_scale=self.model.loss_scale) if self.mixed_precision else None   # GradScaler()
-        self._step = SegTrainStep(self.model, self.criterion, self.optimizer, scaler=scaler)
+        super().set_criterion()
 
     def train_loop(self, batch_data, scaler) -> List:
         images = batch_data[0].to(self.device, non_blocking=True)

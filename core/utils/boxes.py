@@ -25,3 +25,21 @@ def undo_letterbox(rows: np.ndarray, input_hw, image_hw, letterbox: bool = True)
         box[:, 0::2] *= img_w / in_w
         box[:, 1::2] *= img_h / in_h
     return box, conf, cls
+
+
+def correct_boxes(box_xy, box_wh, input_shape, image_shape, letterbox: bool):
+    """yolo_correct_boxes (reference core/utils/image_process.py:161-181), what the YOLOv7 and SSD wrappers end their decode with:
+    normalised centres (n, 2) and sizes (n, 2) on the (h, w) network input -> corners (n, 4) in pixels of the (h, w) original image, by
+    the letterbox inverse or by plain scaling to the image size."""
+    xywh = np.concatenate([box_xy, box_wh], axis=-1)
+    if letterbox:
+        ih, iw = image_shape
+        h, w = input_shape
+        scale = max(ih / h, iw / w)
+        top, left = (h - ih / scale) // 2, (w - iw / scale) // 2
+        cx, cy, bw, bh = xywh[:, 0] * w - left, xywh[:, 1] * h - top, xywh[:, 2] * w, xywh[:, 3] * h
+        return np.stack([(cx - bw / 2) * scale, (cy - bh / 2) * scale, (cx + bw / 2) * scale, (cy + bh / 2) * scale], -1)
+    out = np.stack([xywh[:, 0] - xywh[:, 2] / 2, xywh[:, 1] - xywh[:, 3] / 2, xywh[:, 0] + xywh[:, 2] / 2, xywh[:, 1] + xywh[:, 3] / 2], -1)
+    out[:, ::2] *= image_shape[1]
+    out[:, 1::2] *= image_shape[0]
+    return out
