@@ -114,6 +114,10 @@ PROTOTYPES = {
     "cvx_bn_silu_bwd_nhwc": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _I32, _P]),
     "cvx_letterbox_geometry": (_I32, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_letterbox_u8_to_nchw": (_I32, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "cvx_letterbox_batch_u8_to_nchw": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "cvx_det_to_image": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "cvx_draw_detections": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P]),
+    "cvx_seg_overlay": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P]),
     "cvx_aug_images": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _P]),
     "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_aug_images_plain": (_I32, [_P, _P, _I32, _P, _I32, _I32, _P]),

@@ -1,0 +1,253 @@
+"""Batched prediction on the device, input and output side: a list of uint8 HWC frames of any sizes becomes the network batch in one launch
+(``cvx_letterbox_batch_u8_to_nchw``, or ``cvx_aug_images_plain`` jobs for the bicubic stretch), the NMS rows become image coordinates
+without a read-back (``cvx_det_to_image``), and the result is painted into the frames in place (``cvx_draw_detections``,
+``cvx_seg_overlay``; csrc/render.hip).  ``FrameBatch`` puts every job table of a batch into ONE pinned blob and one asynchronous copy, so
+none of this waits on the host.  There is no CPU path: frames that are not in GPU memory raise ``CvxError``.
+
+``palette``, ``format_label`` and ``FONT`` are the host statement of the drawing rules, shared with the tests'
+restatement (tests/render_restatement.py)."""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .augment import JOB_DTYPE as AUG_JOB_DTYPE
+
+LETTERBOX_JOB_DTYPE = np.dtype([("src", "<u8"), ("h", "<i4"), ("w", "<i4"), ("out", "<i4"), ("reserved", "<i4")])
+FRAME_JOB_DTYPE = np.dtype([("data", "<u8"), ("h", "<i4"), ("w", "<i4"), ("stride", "<i4"), ("reserved", "<i4")])
+assert LETTERBOX_JOB_DTYPE.itemsize == 24 and FRAME_JOB_DTYPE.itemsize == 24      # struct cvx_letterbox_job / cvx_frame_job, include/cvx_engine.h
+
+GLYPHS = "0123456789:.%"
+# the project's 5 x 7 font: one byte per glyph row, bit 4 is the left column (csrc/render.hip holds the same table)
+FONT = {
+    "0": (0x0E, 0x11, 0x13, 0x15, 0x19, 0x11, 0x0E), "1": (0x04, 0x0C, 0x04, 0x04, 0x04, 0x04, 0x0E), "2": (0x0E, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1F),
+    "3": (0x1F, 0x02, 0x04, 0x02, 0x01, 0x11, 0x0E), "4": (0x02, 0x06, 0x0A, 0x12, 0x1F, 0x02, 0x02), "5": (0x1F, 0x10, 0x1E, 0x01, 0x01, 0x11, 0x0E),
+    "6": (0x06, 0x08, 0x10, 0x1E, 0x11, 0x11, 0x0E), "7": (0x1F, 0x01, 0x02, 0x04, 0x08, 0x08, 0x08), "8": (0x0E, 0x11, 0x11, 0x0E, 0x11, 0x11, 0x0E),
+    "9": (0x0E, 0x11, 0x11, 0x0F, 0x01, 0x02, 0x0C), ":": (0x00, 0x0C, 0x0C, 0x00, 0x0C, 0x0C, 0x00), ".": (0x00, 0x00, 0x00, 0x00, 0x00, 0x0C, 0x0C),
+    "%": (0x18, 0x19, 0x02, 0x04, 0x08, 0x13, 0x03),
+}
+MAX_CLASS, MAX_TENTHS = 9999, 9999      # what a label spells; larger values are clamped
+
+
+def palette(n: int = 256) -> np.ndarray:
+    """(n, 3) uint8 RGB: the bit-spread PASCAL VOC palette of ``segmentation_2d.voc_colormap``.  Entry 0 is black, so class ``c`` of a
+    detector is drawn with entry ``c + 1``."""
+    from core.algorithms.segmentation_2d import voc_colormap
+    return np.asarray(voc_colormap(int(n)), dtype=np.uint8).reshape(int(n), 3)
+
+
+def format_label(cls, score) -> str:
+    """``"{cls}:{p}%"``: the class index and ``'{:.1f}'.format`` of the float32 product ``score * 100`` -- round-half-even on the exact
+    value, i.e. ``tenths = rint(double(score * 100.0f) * 10.0)`` (the product by 10 is exact in fp64), which is what the kernel computes."""
+    cls = min(max(int(cls), 0), MAX_CLASS)
+    t = np.rint(np.float64(np.float32(score) * np.float32(100.0)) * 10.0)
+    tenths = int(min(max(t, 0.0), float(MAX_TENTHS))) if t == t else 0
+    return f"{cls}:{tenths // 10}.{tenths % 10}%"
+
+
+def _align(n, a=16):
+    return (n + a - 1) // a * a
+
+
+def _check_frames(frames) -> torch.device:
+    if len(frames) == 0 or not all(torch.is_tensor(t) and t.is_cuda for t in frames):
+        raise L.CvxError("batched prediction takes uint8 HWC frames in GPU memory (there is no CPU path)")
+    dev = frames[0].device
+    for t in frames:
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] <= 0 or t.shape[1] <= 0 or t.device != dev:
+            raise L.CvxError(f"frame {tuple(t.shape)} {t.dtype} on {t.device}: expected (h, w, 3) uint8 on {dev}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]:
+            raise L.CvxError(f"frame strides {t.stride()}: pixels are 3 adjacent bytes and rows do not overlap")
+    return dev
+
+
+class FrameBatch:
+    """The job tables of one batch of frames in device memory, from one pinned blob and one asynchronous copy: ``frame_jobs`` (the frames
+    themselves, with their row strides, for the two painters), ``input_jobs`` (the pictures for the input side: ``cvx_letterbox_job`` rows,
+    or ``cvx_aug_job`` rows + ``job_start`` that stretch each picture to ``input_hw``), ``image_hw`` (B, 2) int32 and, for ``letterbox`` not
+    None, ``box_map`` (B, 4) float32 (``det_eval.letterbox_box_map``, worked out on the host from the sizes)."""
+
+    def __init__(self, frames: Sequence[torch.Tensor], input_hw=None, letterbox: Optional[bool] = None):
+        self.device = _check_frames(frames)
+        self.frames = list(frames)
+        B = self.n = len(frames)
+        self.max_h, self.max_w = max(int(t.shape[0]) for t in frames), max(int(t.shape[1]) for t in frames)
+        self.letterbox = letterbox
+        # the input side reads tightly packed pictures; a frame with padded rows is copied on the device (no host wait)
+        self.sources = [t if t.is_contiguous() else t.contiguous() for t in frames] if input_hw is not None else []
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in frames]
+        o_frame = 0
+        o_hw = _align(o_frame + 24 * B)
+        o_map = _align(o_hw + 8 * B)
+        o_in = _align(o_map + 16 * B)
+        o_js = _align(o_in + (24 if letterbox else 64) * B)
+        total = _align(o_js + 4 * (B + 1))
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        hv = host.numpy()
+        hv[:] = 0
+        hv[o_frame:o_frame + 24 * B].view(FRAME_JOB_DTYPE)[:] = np.array([(t.data_ptr(), h, w, t.stride(0), 0) for t, (h, w) in zip(frames, sizes)],
+                                                                           dtype=FRAME_JOB_DTYPE)
+        hv[o_hw:o_hw + 8 * B].view(np.int32).reshape(B, 2)[:] = sizes
+        if input_hw is not None:
+            H, W = int(input_hw[0]), int(input_hw[1])
+            self.input_hw = (H, W)
+            from . import det_eval
+            bm = det_eval.letterbox_box_map(torch.tensor(sizes, dtype=torch.int64), (H, W), bool(letterbox))
+            hv[o_map:o_map + 16 * B].view(np.float32).reshape(B, 4)[:] = bm.numpy()
+            if letterbox:
+                from .engine import letterbox_geometry
+                for h, w in sizes:
+                    letterbox_geometry(h, w, H, W)            # raises CvxError where a picture collapses to nothing, as the per-image entry does
+                hv[o_in:o_in + 24 * B].view(LETTERBOX_JOB_DTYPE)[:] = np.array(
+                    [(s.data_ptr(), h, w, i, 0) for i, (s, (h, w)) in enumerate(zip(self.sources, sizes))], dtype=LETTERBOX_JOB_DTYPE)
+            else:                                             # DeviceAugmenter's validation job with the picture stretched over the whole canvas
+                hv[o_in:o_in + 64 * B].view(AUG_JOB_DTYPE)[:] = np.array(
+                    [(s.data_ptr(), h, w, H, W, 0, 0, 0, i, 0, 0, W, H, -1, 0) for i, (s, (h, w)) in enumerate(zip(self.sources, sizes))],
+                    dtype=AUG_JOB_DTYPE)
+                hv[o_js:o_js + 4 * (B + 1)].view(np.int32)[:] = np.arange(B + 1)
+        self.blob = torch.empty(total, dtype=torch.uint8, device=self.device)
+        self.blob.copy_(host, non_blocking=True)
+        self._host = host                                     # alive until the copy has run
+        base = self.blob.data_ptr()
+        self.frame_jobs, self.input_jobs, self.job_start = L.C.c_void_p(base + o_frame), L.C.c_void_p(base + o_in), L.C.c_void_p(base + o_js)
+        self.image_hw = self.blob[o_hw:o_hw + 8 * B].view(torch.int32).view(B, 2)
+        self.box_map = self.blob[o_map:o_map + 16 * B].view(torch.float32).view(B, 4) if input_hw is not None else None
+
+    def network_input(self, swap_rb: bool = False) -> torch.Tensor:
+        """The (B, 3, H, W) fp32 batch in [0, 1], one launch: the reference's letter_box + to_tensor per picture when ``letterbox``, else the
+        bicubic stretch to the network size (the host ``cv2.resize(..., INTER_CUBIC)`` of ``read_image_and_convert_to_tensor``)."""
+        H, W = self.input_hw
+        out = torch.empty(self.n, 3, H, W, dtype=torch.float32, device=self.device)
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            stream = L.stream_ptr(self.device)
+            if self.letterbox:
+                L.check(lib.cvx_letterbox_batch_u8_to_nchw(self.input_jobs, self.n, 1, int(bool(swap_rb)), L.ptr(out), H, W, stream),
+                        "cvx_letterbox_batch_u8_to_nchw")
+            else:
+                if swap_rb:
+                    raise L.CvxError("the bicubic stretch keeps the channel order: pass RGB frames")
+                L.check(lib.cvx_aug_images_plain(self.input_jobs, self.job_start, self.n, L.ptr(out), H, W, stream), "cvx_aug_images_plain")
+        return out
+
+
+def letterbox_batch(frames: Sequence[torch.Tensor], input_hw, letterbox: bool = True, swap_rb: bool = False) -> torch.Tensor:
+    """``cvx_letterbox_batch_u8_to_nchw``: frames of any sizes -> (B, 3, H, W) fp32, slot i bit-identical to ``engine.letterbox_u8`` of frame
+    i.  ``letterbox=False`` is that entry's plain nearest resize."""
+    H, W = int(input_hw[0]), int(input_hw[1])
+    fb = _letterbox_table(frames)
+    if letterbox:
+        from .engine import letterbox_geometry
+        for t in frames:
+            letterbox_geometry(int(t.shape[0]), int(t.shape[1]), H, W)      # raises CvxError where a picture collapses, as the per-image entry does
+    out = torch.empty(fb.n, 3, H, W, dtype=torch.float32, device=fb.device)
+    with torch.cuda.device(fb.device):
+        L.check(L.load().cvx_letterbox_batch_u8_to_nchw(fb.input_jobs, fb.n, 1 if letterbox else 0, int(bool(swap_rb)), L.ptr(out), H, W,
+                                                        L.stream_ptr(fb.device)), "cvx_letterbox_batch_u8_to_nchw")
+    return out
+
+
+def _letterbox_table(frames):
+    """A bare FrameBatch that holds only the ``cvx_letterbox_job`` rows of ``frames`` (slot i for frame i)"""
+    fb = FrameBatch.__new__(FrameBatch)
+    fb.device = _check_frames(frames)
+    fb.n = len(frames)
+    fb.sources = [t.contiguous() for t in frames]
+    table = np.array([(s.data_ptr(), int(s.shape[0]), int(s.shape[1]), i, 0) for i, s in enumerate(fb.sources)], dtype=LETTERBOX_JOB_DTYPE)
+    host = torch.empty(24 * fb.n, dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:] = table.view(np.uint8)
+    fb.blob = torch.empty(24 * fb.n, dtype=torch.uint8, device=fb.device)
+    fb.blob.copy_(host, non_blocking=True)
+    fb._host = host
+    fb.input_jobs = L.C.c_void_p(fb.blob.data_ptr())
+    return fb
+
+
+def det_to_image(rows: torch.Tensor, counts: torch.Tensor, box_map: Optional[torch.Tensor] = None, overflow: Optional[torch.Tensor] = None):
+    """``cvx_det_to_image``: rows (B, K, 6) fp32 and counts (B) int32 as the NMS leaves them, ``box_map`` (B, 4) fp32 or None (boxes already
+    final) -> (rows in image coordinates with the rows past each count zero, counts with -1 / too large replaced by 0, the overflow word
+    (1) int32 -- ``overflow`` is added to when given).  No host read."""
+    if not (torch.is_tensor(rows) and rows.is_cuda):
+        raise L.CvxError("det_to_image runs on an MI355X only: there is no CPU path")
+    if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or rows.shape[1] <= 0:
+        raise ValueError(f"rows: (B, K, 6) float32, got {tuple(rows.shape)} {rows.dtype}")
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    if counts.dtype != torch.int32 or counts.numel() != B or counts.device != rows.device:
+        raise ValueError("counts: (B) int32 on the rows' device")
+    if box_map is not None and (box_map.dtype != torch.float32 or tuple(box_map.shape) != (B, 4) or box_map.device != rows.device):
+        raise ValueError("box_map: (B, 4) float32 [px, py, gx, gy] on the rows' device")
+    rows, counts = rows.contiguous(), counts.contiguous()
+    box_map = None if box_map is None else box_map.contiguous()
+    out_rows, out_counts = torch.empty_like(rows), torch.empty_like(counts)
+    if overflow is None:
+        overflow = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        L.check(L.load().cvx_det_to_image(L.ptr(rows), L.ptr(counts), B, K, 0 if box_map is None else 1, L.ptr(box_map), L.ptr(out_rows),
+                                          L.ptr(out_counts), L.ptr(overflow), L.stream_ptr(rows.device)), "cvx_det_to_image")
+    return out_rows, out_counts, overflow
+
+
+_lut_cache = {}
+
+
+def _device_lut(n, device, lut=None):
+    if lut is not None:
+        t = torch.as_tensor(lut)
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != 3 or not t.is_cuda:
+            raise ValueError("lut: (n, 3) uint8 on the device")
+        return t.contiguous()
+    key = (int(n), torch.device(device))
+    if key not in _lut_cache:
+        host = torch.from_numpy(palette(n)).pin_memory()
+        _lut_cache[key] = (host.to(device, non_blocking=True), host)
+    return _lut_cache[key][0]
+
+
+def draw_detections(frames, rows: torch.Tensor, counts: torch.Tensor, lut=None, thickness: int = 2, font_scale: int = 2, batch: FrameBatch = None):
+    """``cvx_draw_detections``: paints rows[b, :counts[b]] (image coordinates) into frames[b], in place.  ``lut``: (n, 3) uint8 device
+    colours in the frames' channel order, default ``palette(256)``.  ``batch``: the frames' ``FrameBatch`` when the caller has one."""
+    fb = batch if batch is not None else FrameBatch(frames)
+    if rows.dim() != 3 or rows.shape[0] != fb.n or rows.shape[2] != 6 or rows.dtype != torch.float32 or rows.device != fb.device:
+        raise ValueError(f"rows: ({fb.n}, K, 6) float32 on {fb.device}")
+    if counts.dtype != torch.int32 or counts.numel() != fb.n or counts.device != fb.device:
+        raise ValueError("counts: (B) int32 on the frames' device")
+    rows, counts = rows.contiguous(), counts.contiguous()
+    lut = _device_lut(256, fb.device, lut)
+    with torch.cuda.device(fb.device):
+        L.check(L.load().cvx_draw_detections(fb.frame_jobs, fb.n, fb.max_h, fb.max_w, L.ptr(rows), L.ptr(counts), int(rows.shape[1]), L.ptr(lut),
+                                             int(lut.shape[0]), int(thickness), int(font_scale), L.stream_ptr(fb.device)), "cvx_draw_detections")
+    return fb.frames
+
+
+def seg_overlay(frames, logits_rows: torch.Tensor, nc: int, level_hw, net_hw, lut=None, bgr: bool = False, batch: FrameBatch = None):
+    """``cvx_seg_overlay``: logits_rows (B, lh * lw, ld) fp32 as ``forward_rows`` leaves them for a ``net_hw`` input -> class colours
+    blended 50/50 into the RGB frames, in place; ``bgr`` writes B, G, R.  ``lut``: (nc, 3) uint8 RGB on the device, default the VOC palette."""
+    fb = batch if batch is not None else FrameBatch(frames)
+    lh, lw = int(level_hw[0]), int(level_hw[1])
+    if (logits_rows.dim() != 3 or logits_rows.shape[0] != fb.n or logits_rows.shape[1] != lh * lw or logits_rows.shape[2] < nc
+            or logits_rows.dtype != torch.float32 or logits_rows.device != fb.device):
+        raise ValueError(f"logits_rows: ({fb.n}, {lh * lw}, >= {nc}) float32 on {fb.device}, got {tuple(logits_rows.shape)} {logits_rows.dtype}")
+    logits_rows = logits_rows.contiguous()
+    lut = _device_lut(nc, fb.device, lut)
+    if lut.shape[0] < nc:
+        raise ValueError(f"lut: at least {nc} colours")
+    with torch.cuda.device(fb.device):
+        L.check(L.load().cvx_seg_overlay(fb.frame_jobs, fb.n, fb.max_h, fb.max_w, L.ptr(logits_rows), int(logits_rows.shape[2]), int(nc), lh, lw,
+                                         int(net_hw[0]), int(net_hw[1]), L.ptr(lut), int(bool(bgr)), L.stream_ptr(fb.device)), "cvx_seg_overlay")
+    return fb.frames
+
+
+def read_detections(rows: torch.Tensor, counts: torch.Tensor, overflow: torch.Tensor) -> List[tuple]:
+    """ONE host read of (rows, counts, overflow) -> per image ``(boxes (k, 4) float32, scores (k) float32, classes (k) int64)``, the format of
+    ``decode_box``.  Raises ``CvxError`` when an image was dropped (NMS count -1 or a count past its block)."""
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    flat = torch.cat((rows.reshape(-1), counts.view(torch.float32).reshape(-1), overflow.view(torch.float32).reshape(-1))).cpu().numpy()
+    r = flat[:B * K * 6].reshape(B, K, 6)
+    tail = flat[B * K * 6:].view(np.int32)
+    if int(tail[B]):
+        raise L.CvxError(f"predict_batch: {int(tail[B])} image(s) dropped: an NMS count of -1 (more candidates than cvx_nms sorts) or a count "
+                         "past its block; raise the confidence threshold")
+    return [(r[b, :n, :4].copy(), r[b, :n, 4].copy(), r[b, :n, 5].astype(np.int64)) for b, n in enumerate(int(v) for v in tail[:B])]

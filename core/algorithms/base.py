@@ -27,9 +27,68 @@ def nms_with_room(y, conf_threshold, nms_threshold, overflow_message, **kw):
         max_det = min(max_det * 4, MAX_CANDIDATES)
 
 
-class Detector:
+class FramePredictor:
+    """``detect_frames`` over the class's own ``predict_batch``: what the five algorithm classes share of the video path."""
+
+    def _need_gpu(self, what):
+        import torch
+        if torch.device(self.device).type != "cuda":
+            raise L.CvxError(f"{what} runs on an MI355X only (device {self.device}): there is no CPU path")
+
+    def detect_frames(self, model, frames, batch_size):
+        """Generator over any iterable of uint8 HWC RGB device frames: yields the list of drawn frames of each batch of ``batch_size`` (the
+        last one may be short).  Each batch is one ``predict_batch(..., draw=True, sync=False)``: nothing inside the loop waits on the
+        host, so the caller synchronises (or reads a frame) when it needs the pixels."""
+        self._need_gpu("detect_frames")
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size is positive")
+
+        def batches():
+            batch = []
+            for frame in frames:
+                batch.append(frame)
+                if len(batch) == int(batch_size):
+                    self.predict_batch(model, batch, draw=True, sync=False)
+                    yield batch
+                    batch = []
+            if batch:
+                self.predict_batch(model, batch, draw=True, sync=False)
+                yield batch
+
+        return batches()
+
+
+class Detector(FramePredictor):
     """Needs ``num_classes``, ``device``, ``eval_max_det`` (the most rows per image ``_evaluation_rows`` returns) and
-    ``_evaluation_rows(model) -> rows_of(images, meta) -> (rows, counts, box map or None)`` at ``conf_threshold=0.001``."""
+    ``_evaluation_rows(model) -> rows_of(images, meta, conf_threshold=0.001) -> (rows, counts, box map or None)``."""
+
+    def _predict_input(self):
+        """(network input (H, W), letterbox) of ``predict``'s own preprocessing"""
+        size = self.input_image_size if hasattr(self, "input_image_size") else self.input_size
+        return (int(size[0]), int(size[1])), bool(self.letterbox_image)
+
+    def predict_batch(self, model, frames, conf_threshold=None, draw=False, sync=True):
+        """``predict`` for a batch, on the device: ``frames`` is a list of uint8 HWC RGB device tensors of any sizes.  One launch builds the
+        network batch (``cvx_letterbox_batch_u8_to_nchw`` when ``cfg.decode.letterbox_image``, else the bicubic stretch through
+        ``cvx_aug_images_plain`` jobs -- the host ``INTER_CUBIC`` resize of ``predict``), one forward, the class's own decode + NMS tail
+        (``_evaluation_rows`` at ``conf_threshold``, default the configured one) and ``cvx_det_to_image``.  ``draw=True`` paints the
+        detections into the frames, in place (``cvx_draw_detections``).  Returns ``(rows (B, K, 6) [x1, y1, x2, y2, score, cls] in
+        original-image pixels, counts (B) int32)`` on the device; with ``sync=True`` one host read turns them into a list of ``(boxes,
+        scores, classes)`` numpy triples in ``decode_box``'s format (and raises ``CvxError`` if an image overflowed the NMS)."""
+        from computervision.pytorch_amd import render
+        self._need_gpu("predict_batch")
+        frames = list(frames)
+        input_hw, letterbox = self._predict_input()
+        batch = render.FrameBatch(frames, input_hw, letterbox)
+        model.eval()
+        conf = self.conf_threshold if conf_threshold is None else conf_threshold
+        rows, counts, box_map = self._evaluation_rows(model)(batch.network_input(), {"image_hw": batch.image_hw}, conf)
+        rows, counts, overflow = render.det_to_image(rows, counts, box_map)
+        if draw:
+            render.draw_detections(frames, rows, counts, batch=batch)
+        if sync:
+            return render.read_detections(rows, counts, overflow)
+        return rows, counts
 
     def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
         """The reference's ``evaluate_on_voc``: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to

@@ -93,11 +93,11 @@ class CenterNetA(Detector):
         return self.K
 
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        """(images, meta, conf_threshold=0.001) -> (rows, counts, None) of one batch, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
         ``evaluate_rows`` -- the forward, ``decode_raw`` and ``_finish``'s inverse letterbox restated as float32 tensor operations on the
         device batch; the counts stay on the device, so the host reads once, at the end (``cvx_det_match`` mode 0)."""
-        def rows_of(images, meta):
-            rows, counts = self.evaluate_rows(model, images, meta["image_hw"])
+        def rows_of(images, meta, conf_threshold=0.001):
+            rows, counts = self.evaluate_rows(model, images, meta["image_hw"], conf_threshold)
             return rows, counts, None
 
         return rows_of

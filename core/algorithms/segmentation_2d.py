@@ -13,6 +13,7 @@ import torch
 from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd.deeplab import DeepLabV3PlusR101, SegLoss
 from configs import DeeplabV3PlusConfig
+from core.algorithms.base import FramePredictor
 from registry import model_registry
 
 
@@ -41,7 +42,7 @@ def postprocess_seg2d(dataset_type, pred, device):
 
 
 @model_registry("deeplabv3plus")
-class DeeplabV3PlusA:
+class DeeplabV3PlusA(FramePredictor):
     def __init__(self, cfg: DeeplabV3PlusConfig, device) -> None:
         self.cfg, self.device = cfg, device
         self.loss_type = cfg.loss.loss_type
@@ -87,6 +88,26 @@ class DeeplabV3PlusA:
             cv2.imwrite(os.path.join(self.cfg.decode.test_results, os.path.basename(image_path).split(".")[0] + "@cvx.jpg"), result)
             return None
         return result
+
+    def predict_batch(self, model, frames, draw=True, sync=False, bgr=False):
+        """``predict`` for a batch, on the device: ``frames`` is a list of uint8 HWC RGB device tensors of any sizes.  One launch stretches
+        them to ``cfg.arch.input_size`` (``cvx_aug_images_plain`` jobs: bicubic, / 255, no mean / std -- what ``predict`` feeds; it resizes
+        with OpenCV's default bilinear filter), one ``forward_rows``, and with ``draw`` one ``cvx_seg_overlay``
+        launch colours, resizes (nearest) and blends 50/50 into the frames, in place (``bgr``: written as B, G, R, the channel order
+        ``predict`` returns).  Returns the logits rows (B, h * w, nc_pad) on the device; nothing waits on the host unless ``sync``."""
+        from computervision.pytorch_amd import render
+        self._need_gpu("predict_batch")
+        frames = list(frames)
+        net_hw = tuple(int(v) for v in self.cfg.arch.input_size[1:])
+        batch = render.FrameBatch(frames, net_hw, letterbox=False)
+        model.eval()
+        with torch.no_grad():
+            rows = model.forward_rows(batch.network_input())
+        if draw:
+            render.seg_overlay(frames, rows, self.num_classes, model._last_engine.graph.level_hw[0], net_hw, bgr=bgr, batch=batch)
+        if sync:
+            torch.cuda.synchronize(rows.device)
+        return rows
 
     def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None):
         """Reference :115-166: the validation metrics of ``model`` over VOC-``subset``, printed and written to

@@ -145,15 +145,15 @@ class Ssd(NmsDetector):
         return results
 
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        """(images, meta, conf_threshold=0.001) -> (rows, counts, None) of one batch, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
         the forward, ``decode_device`` (with the host reads it makes) and ``_correct_boxes`` restated as float32 tensor operations on the
         device batch (``correct_boxes_device``); the evaluators take the boxes as final (``cvx_det_match`` mode 0)."""
         from computervision.pytorch_amd import det_eval
 
-        def rows_of(images, meta):
+        def rows_of(images, meta, conf_threshold=0.001):
             with torch.no_grad():
                 preds = model(images)
-            per_image = [torch.cat((det[:, :4], det[:, 5:6], det[:, 4:5]), 1) for det, _ in self.decode_device(preds, 0.001)]   # -> [box, score, cls]
+            per_image = [torch.cat((det[:, :4], det[:, 5:6], det[:, 4:5]), 1) for det, _ in self.decode_device(preds, conf_threshold)]   # -> [box, score, cls]
             rows, counts = det_eval.pack_rows(per_image, images.device)
             rows[..., :4] = det_eval.correct_boxes_device(rows[..., :4], self.input_image_size, meta["image_hw"], self.letterbox_image)
             return rows, counts, None

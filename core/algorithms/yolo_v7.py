@@ -93,18 +93,18 @@ class YOLOv7(NmsDetector):
         return results
 
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, None) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        """(images, meta, conf_threshold=0.001) -> (rows, counts, None) of one batch, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
         the forward, ``decode_rows`` and ``nms_device`` (with the one host read it makes), score = objectness * class probability, and
         ``_correct_boxes`` restated as float32 tensor operations on the device batch (``correct_boxes_device``); the evaluators take the
         boxes as final (``cvx_det_match`` mode 0)."""
         from computervision.pytorch_amd import det_eval
 
-        def rows_of(images, meta):
+        def rows_of(images, meta, conf_threshold=0.001):
             with torch.no_grad():
                 model(images)
             dec, y = self.decode_rows(model, model.last_rows)
             per_image = []
-            for det, _ in self.nms_device(y, dec, 0.001):
+            for det, _ in self.nms_device(y, dec, conf_threshold):
                 if det is None:
                     per_image.append(torch.zeros(0, 6, device=images.device))
                 else:

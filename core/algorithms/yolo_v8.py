@@ -67,14 +67,14 @@ class YOLOv8(Detector):
         return self.max_det
 
     def _evaluation_rows(self, model):
-        """(images, meta) -> (rows, counts, box map) of one batch at ``conf_threshold=0.001``, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
+        """(images, meta, conf_threshold=0.001) -> (rows, counts, box map) of one batch, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
         one engine forward and ``cvx_nms`` with the counts kept on the device; the evaluators' match launch undoes the letterbox (box-map
         mode 1), so the host reads once, at the end."""
-        def rows_of(images, meta):
+        def rows_of(images, meta, conf_threshold=0.001):
             with torch.no_grad():
                 preds = model(images.to(self.device))
             y = preds[0] if isinstance(preds, (list, tuple)) else preds
-            rows, _, counts = _engine.nms(y, 0.001, self.iou_threshold, self.max_det)
+            rows, _, counts = _engine.nms(y, conf_threshold, self.iou_threshold, self.max_det)
             return rows, counts, det_eval.letterbox_box_map(meta["image_hw"], self.input_image_size, self.letterbox_image)
 
         return rows_of

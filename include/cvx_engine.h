@@ -248,6 +248,18 @@ int cvx_pack_targets(const float* batch_idx, const float* cls, const float* bbox
 int cvx_letterbox_geometry(int32_t h, int32_t w, int32_t H, int32_t W, int32_t* new_h, int32_t* new_w, int32_t* top, int32_t* left, double* scale);
 int cvx_letterbox_u8_to_nchw(const uint8_t* image_hwc, int32_t h, int32_t w, int32_t letterbox, int32_t swap_rb, float* out_chw, int32_t H,
                              int32_t W, void* hip_stream);
+/* The same for a batch of pictures of different sizes in ONE launch, asynchronous on hip_stream.  jobs: n_jobs rows in DEVICE memory --
+ * src uint8 (h, w, 3) HWC in device memory, out the slot of out_nchw (slots, 3, H, W) the picture goes to.  The geometry of each picture is
+ * worked out on the device with cvx_letterbox_geometry's arithmetic and the pixels by the device function cvx_letterbox_u8_to_nchw runs,
+ * so slot `out` is bit-identical to that entry's output for the same picture.  A picture that collapses to nothing at this size (the
+ * per-image entry fails on it) leaves its slot all padding: callers that know the sizes check first.  24 bytes per job.
+ * Replaces: the per-image loop over read_image_and_convert_to_tensor in predict / scripts/detect.py:detect_video. */
+typedef struct cvx_letterbox_job {
+  const uint8_t* src;
+  int32_t h, w, out, reserved;
+} cvx_letterbox_job;
+int cvx_letterbox_batch_u8_to_nchw(const cvx_letterbox_job* jobs, int32_t n_jobs, int32_t letterbox, int32_t swap_rb, float* out_nchw, int32_t H,
+                                   int32_t W, void* hip_stream);
 
 /* ---- optimiser ------------------------------------------------------------------------------------
  * torch.optim.Adam semantics (core/trainer/lr_scheduler.py:37-43): lr, betas, eps, no weight decay;
@@ -702,6 +714,46 @@ int cvx_allreduce_f32(float* data, int64_t count, void* comm, void* hip_stream);
 int cvx_allreduce_grads(cvx_engine* e, void* comm, void* hip_stream);
 int cvx_engine_backward_exchange(cvx_engine* e, const void* dpred_f16, float loss_scale, void* comm, const int64_t* buckets, int32_t n_buckets,
                                  void* comm_stream);
+
+/* ---- output side of batched prediction (csrc/render.hip) ------------------------------------------------------------------------------
+ * All three entries are one launch, asynchronous on hip_stream, and read nothing back.  A frame is a uint8 HWC picture in device memory
+ * with its own size and row stride in bytes (stride >= 3 * w); the frames of a batch may differ.  24 bytes per job. */
+typedef struct cvx_frame_job {
+  uint8_t* data;
+  int32_t h, w, stride, reserved;
+} cvx_frame_job;
+/* NMS rows -> original-image coordinates.  rows (batch, max_det, 6) fp32 [x1, y1, x2, y2, score, cls] and counts (batch) int32 as cvx_nms,
+ * cvx_nms_variant and the SSD / CenterNet decode tails leave them; box_mode 0: the boxes are final and are copied, 1: (x - px) * gx with
+ * box_map (batch, 4) fp32 [px, py, gx, gy] -- the device function cvx_det_match maps its boxes with, two roundings per coordinate, so the
+ * result is undo_letterbox's to the bit.  out_rows (batch, max_det, 6): score and class copied, the rows past the count zero; out_counts
+ * (batch).  A count of -1 (the NMS overflow mark) or above max_det gives out count 0 and adds 1 to *overflow (1 int32, device, cleared
+ * by the caller).
+ * Replaces: core/utils/boxes.py:undo_letterbox after the .cpu() of YOLOv8.decode_box (reference core/algorithms/yolo_v8.py:229-242,
+ * reverse_letter_box_numpy, core/utils/image_process.py:69-97). */
+int cvx_det_to_image(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, int32_t box_mode, const float* box_map, float* out_rows,
+                     int32_t* out_counts, int32_t* overflow, void* hip_stream);
+/* Paints the detections of frame b -- rows[b, 0 .. counts[b]) in image coordinates -- into jobs[b], in place.  (max_h, max_w): the largest
+ * frame of the batch (the grid).  Painter's order: box 0 first; per box the outline, the label tag, the label text.  Coordinates are
+ * truncated towards zero (boxes.astype(int)).  Outline of thickness t: the pixels inside the box grown by t / 2 and outside the box shrunk
+ * by (t + 1) / 2 (integer divisions), clipped to the frame; x1 < x0 or y1 < y0 (or a NaN) paints nothing.  Label "{cls}:{p}%": cls the
+ * class index, p = tenths / 10 with one decimal, tenths = rint(double(score * 100.0f) * 10.0) -- Python's '{:.1f}'.format of the fp32
+ * product; the project's own 5 x 7 font at font_scale; the tag is (6 * chars + 1) * font_scale wide and 9 * font_scale high, its left edge
+ * at x0, above the box when y0 - height >= 0 and otherwise from y0 down.  Colours: entry (cls + 1) mod lut_entries of lut (entries x 3
+ * bytes in the frame's channel order) for the outline, each channel * 7 / 10 for the tag, text black when the channel sum exceeds 382 and
+ * white otherwise.  Every painted pixel is written once; no pixel is read.
+ * Replaces: Draw.draw_boxes_on_image / show_detection_results (reference core/utils/visualize.py) behind every detector's predict; the
+ * reference's colour table and OpenCV's Hershey font are not reproduced. */
+int cvx_draw_detections(const cvx_frame_job* jobs, int32_t batch, int32_t max_h, int32_t max_w, const float* rows, const int32_t* counts, int32_t max_det,
+                        const uint8_t* lut, int32_t lut_entries, int32_t thickness, int32_t font_scale, void* hip_stream);
+/* Colours a segmentation result and blends it 50/50 into RGB frame b, in place, with no full-resolution logits or colour image in memory.
+ * logits_rows (batch, lh * lw, ld) fp32 as the DeepLab engine's forward leaves them, for a (net_h, net_w) network input.  Per frame pixel:
+ * the nearest pixel at network size (cv2.resize(..., INTER_NEAREST)'s index rule), the nc logits there by the taps of
+ * cvx_resize_bilinear_rows_to_nchw / cvx_seg_eval (bit-identical), arg max (the lowest class wins a tie), lut (nc x 3 bytes, RGB), and
+ * (a + b) / 2 rounded half to even per channel; bgr_out != 0 writes the pixel as B, G, R.
+ * Replaces: postprocess_seg2d, cv2.resize(INTER_NEAREST), cv2.addWeighted(.5, .5) and [..., ::-1] in DeeplabV3PlusA.predict
+ * (reference core/algorithms/segmentation_2d.py:20-30, 80-113). */
+int cvx_seg_overlay(const cvx_frame_job* jobs, int32_t batch, int32_t max_h, int32_t max_w, const float* logits_rows, int32_t ld, int32_t nc, int32_t lh,
+                    int32_t lw, int32_t net_h, int32_t net_w, const uint8_t* lut, int32_t bgr_out, void* hip_stream);
 
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
