@@ -7,8 +7,10 @@
 // inside one row y (centernet.py:279-280,324); it reads the centre offsets from the "wh" head's two channels and the sizes
 // from the "reg" head's (:276-277); the letterbox inverse stays on the host (a handful of scalars per image).
 // Tie order of the top-K (torch.topk leaves it undefined): score descending, flat (y, x, c) index ascending, as
-// oracle/centernet_ref.py defines it.  All box arithmetic in fp32 with explicit round-to-nearest intrinsics (no FMA
-// contraction): identical operation order to the reference's torch ops.
+// oracle/centernet_ref.py defines it.  All box arithmetic in fp32, every operation rounded on its own in the order of the
+// reference's torch ops: plain operators under `#pragma clang fp contract(off)` in diou / center_box below, as ema_mix in
+// misc_ops.hip (this toolchain's __fmul_rn / __fadd_rn are header functions around `*` and `+` that carry the contract flag wherever
+// they are inlined, so they do not keep the backend from fusing a product into the sum that follows it).
 //
 //   K1 peak_scores   one thread per (b, y, x, c): window max on the LOGITS (sigmoid is monotone: the arg-max is the same,
 //                    and `heat == hmax` is evaluated on the two sigmoid values exactly as the reference does) -> fp32 scores
@@ -68,21 +70,37 @@ struct DecodeOut {
 };
 
 __device__ __forceinline__ float diou(const float4& a, const float4& b) {  // core/utils/iou.py:8-64
+#pragma clang fp contract(off)
   const float eps = 1e-6f;
-  const float a1 = __fmul_rn(__fsub_rn(a.z, a.x), __fsub_rn(a.w, a.y));
-  const float a2 = __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y));
-  const float iw = fmaxf(__fsub_rn(fminf(a.z, b.z), fmaxf(a.x, b.x)), 0.f);
-  const float ih = fmaxf(__fsub_rn(fminf(a.w, b.w), fmaxf(a.y, b.y)), 0.f);
-  const float inter = __fmul_rn(iw, ih);
-  const float iou = __fdiv_rn(inter, fmaxf(__fsub_rn(__fadd_rn(a1, a2), inter), eps));
-  const float cx1 = __fdiv_rn(__fadd_rn(a.x, a.z), 2.f), cy1 = __fdiv_rn(__fadd_rn(a.y, a.w), 2.f);
-  const float cx2 = __fdiv_rn(__fadd_rn(b.x, b.z), 2.f), cy2 = __fdiv_rn(__fadd_rn(b.y, b.w), 2.f);
-  const float ew = fmaxf(__fsub_rn(fmaxf(a.z, b.z), fminf(a.x, b.x)), 0.f);
-  const float eh = fmaxf(__fsub_rn(fmaxf(a.w, b.w), fminf(a.y, b.y)), 0.f);
-  const float c_sq = __fadd_rn(__fmul_rn(ew, ew), __fmul_rn(eh, eh));
-  const float dx = __fsub_rn(cx1, cx2), dy = __fsub_rn(cy1, cy2);
-  const float d_sq = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-  return __fsub_rn(iou, __fdiv_rn(d_sq, fmaxf(c_sq, eps)));
+  const float a1 = (a.z - a.x) * (a.w - a.y);
+  const float a2 = (b.z - b.x) * (b.w - b.y);
+  const float iw = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
+  const float ih = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+  const float inter = iw * ih;
+  const float sum = a1 + a2;
+  const float iou = inter / fmaxf(sum - inter, eps);
+  const float cx1 = (a.x + a.z) / 2.f, cy1 = (a.y + a.w) / 2.f;
+  const float cx2 = (b.x + b.z) / 2.f, cy2 = (b.y + b.w) / 2.f;
+  const float ew = fmaxf(fmaxf(a.z, b.z) - fminf(a.x, b.x), 0.f);
+  const float eh = fmaxf(fmaxf(a.w, b.w) - fminf(a.y, b.y), 0.f);
+  const float ew2 = ew * ew, eh2 = eh * eh;
+  const float c_sq = ew2 + eh2;
+  const float dx = cx1 - cx2, dy = cy1 - cy2;
+  const float dx2 = dx * dx, dy2 = dy * dy;
+  const float d_sq = dx2 + dy2;
+  return iou - d_sq / fmaxf(c_sq, eps);
+}
+
+// A winner's box (centernet.py:288-297): centre = pixel + offset, normalised and clamped with the size, then corners.
+__device__ __forceinline__ float4 center_box(int x, int y, float off_x, float off_y, float bw, float bh, int W, int H) {
+#pragma clang fp contract(off)
+  float cx = (float)x + off_x, cy = (float)y + off_y;
+  cx = fminf(fmaxf(cx / (float)W, 0.f), 1.f);
+  bw = fminf(fmaxf(bw / (float)W, 0.f), 1.f);
+  cy = fminf(fmaxf(cy / (float)H, 0.f), 1.f);
+  bh = fminf(fmaxf(bh / (float)H, 0.f), 1.f);
+  const float hw2 = bw / 2.f, hh2 = bh / 2.f;
+  return make_float4(cx - hw2, cy - hh2, cx + hw2, cy + hh2);
 }
 
 // Sorted top-K of n non-negative floats (their bit patterns, `key`) by (value descending, index ascending); zeros never
@@ -295,14 +313,7 @@ __global__ __launch_bounds__(SEL_THREADS) void finish_kernel(const float* pred, 
     const int y = (int)(pix / (unsigned)W), x = (int)(pix % (unsigned)W);
     const float* row = pred + ((long long)b * H * W + pix) * ld;
     const float score = sc[idx];
-    float cx = __fadd_rn((float)x, row[reg_off]), cy = __fadd_rn((float)y, row[reg_off + 1]);
-    float bw = row[wh_off], bh = row[wh_off + 1];
-    cx = fminf(fmaxf(__fdiv_rn(cx, (float)W), 0.f), 1.f);
-    bw = fminf(fmaxf(__fdiv_rn(bw, (float)W), 0.f), 1.f);
-    cy = fminf(fmaxf(__fdiv_rn(cy, (float)H), 0.f), 1.f);
-    bh = fminf(fmaxf(__fdiv_rn(bh, (float)H), 0.f), 1.f);
-    const float hw2 = __fdiv_rn(bw, 2.f), hh2 = __fdiv_rn(bh, 2.f);
-    const float4 bx = make_float4(__fsub_rn(cx, hw2), __fsub_rn(cy, hh2), __fadd_rn(cx, hw2), __fadd_rn(cy, hh2));
+    const float4 bx = center_box(x, y, row[reg_off], row[reg_off + 1], row[wh_off], row[wh_off + 1], W, H);
     s_box[tid] = bx;
     s_alive[tid] = score >= conf ? 1 : 0;
     float* ob = o.boxes + ((long long)b * K + tid) * 4;

@@ -5,8 +5,11 @@
 //
 // NMS semantics are those of oracle/nms_ref.py (torchvision 0.14.1 batched_nms restated): candidates with
 // best-class score > conf, ordered by (score desc, anchor index asc), greedy suppression when
-// inter/(area_i+area_j-inter) > iou_thres, evaluated in fp32 with the same operation order (explicit
-// round-to-nearest intrinsics: no FMA contraction), first max_det survivors.  Both strategies of the library:
+// inter/(area_i+area_j-inter) > iou_thres, evaluated in fp32 with the same operation order, every operation rounded on
+// its own (plain operators under `#pragma clang fp contract(off)` in box_corners / class_shift / box_area / iou_gt below: this
+// toolchain's __fmul_rn / __fadd_rn are header functions around `*` and `+` that carry the contract flag wherever they are inlined,
+// so they do not keep the backend from fusing a product into the sum that follows it), first max_det survivors.
+// Both strategies of the library:
 // VANILLA (boxes interact inside a class only) and OFFSET (_batched_nms_coordinate_trick: every box shifted by
 // cls * (max coordinate + 1) in fp32, class-agnostic pass over the shifted, re-rounded boxes), plus the library's own
 // switch between them by candidate count.
@@ -145,12 +148,32 @@ __global__ void decode_rows_kernel(const float* pred, int B, int A, int no, int 
   for (int c = 0; c < nc; ++c) o[(long long)(4 + c) * A] = cvx_sigmoid(p[4 * REG + c]);
 }
 
+// The arithmetic the suite pins bit for bit: plain operators with contraction switched off in each helper, as ema_mix in misc_ops.hip
+// (the pragma does not reach into the _rn intrinsics' own bodies, so they are not used here).
+// (cx, cy, w, h) -> corners, ultralytics_ops.py:360-375
+__device__ __forceinline__ float4 box_corners(float cx, float cy, float w, float h) {
+#pragma clang fp contract(off)
+  const float hw = w * 0.5f, hh = h * 0.5f;
+  return make_float4(cx - hw, cy - hh, cx + hw, cy + hh);
+}
+// box + cls * (boxes.max() + 1): _batched_nms_coordinate_trick
+__device__ __forceinline__ float4 class_shift(const float4& bx, int cls, float unit) {
+#pragma clang fp contract(off)
+  const float off = (float)cls * unit;
+  return make_float4(bx.x + off, bx.y + off, bx.z + off, bx.w + off);
+}
+__device__ __forceinline__ float box_area(const float4& b) {
+#pragma clang fp contract(off)
+  return (b.z - b.x) * (b.w - b.y);
+}
 // fp32 IoU exactly as torchvision's nms_kernel / oracle.nms_ref.greedy_nms_per_class
 __device__ __forceinline__ bool iou_gt(const float4& a, float area_a, const float4& b, float area_b, float thr) {
-  float w = fmaxf(0.f, __fsub_rn(fminf(a.z, b.z), fmaxf(a.x, b.x)));
-  float h = fmaxf(0.f, __fsub_rn(fminf(a.w, b.w), fmaxf(a.y, b.y)));
-  float inter = __fmul_rn(w, h);
-  float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
+  const float h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+  const float inter = w * h;
+  const float sum = area_a + area_b;
+  const float ovr = inter / (sum - inter);
   return ovr > thr;
 }
 
@@ -233,8 +256,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
     if (xyxy) {  // CVX_NMS_BOXES_XYXY: rows 0..3 already hold corners (SSD's clipped decode): taken as they are
       box[i] = make_float4(cx, cy, w, h);
     } else {
-      float hw = __fmul_rn(w, 0.5f), hh = __fmul_rn(h, 0.5f);
-      box[i] = make_float4(__fsub_rn(cx, hw), __fsub_rn(cy, hh), __fadd_rn(cx, hw), __fadd_rn(cy, hh));
+      box[i] = box_corners(cx, cy, w, h);
     }
     float best = -1.f;
     int bc = 0;
@@ -265,12 +287,8 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
     for (int w = 1; w < NMS_THREADS / 64; ++w) mx = fmaxf(mx, s_wmax[w]);
     const float unit = __fadd_rn(mx, 1.0f);
     for (int i = tid; i < n; i += NMS_THREADS) {
-      float4 bx = box[i];
-      if (offset_mode) {
-        const float off = __fmul_rn((float)cls[i], unit);
-        bx = make_float4(__fadd_rn(bx.x, off), __fadd_rn(bx.y, off), __fadd_rn(bx.z, off), __fadd_rn(bx.w, off));
-      }
-      boxs[i] = bx;
+      const float4 bx = box[i];
+      boxs[i] = offset_mode ? class_shift(bx, cls[i], unit) : bx;
     }
   }
   __syncthreads();
@@ -282,13 +300,13 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
     unsigned long long bits = 0;
     if (wj * 64 + 63 > i) {
       float4 bi = boxs[i];
-      float ai = __fmul_rn(__fsub_rn(bi.z, bi.x), __fsub_rn(bi.w, bi.y));
+      float ai = box_area(bi);
       int ci = cls[i];
       int j0 = max(wj * 64, i + 1), j1 = min(n, wj * 64 + 64);
       for (int j = j0; j < j1; ++j) {
         if (!offset_mode && cls[j] != ci) continue;
         float4 bj = boxs[j];
-        float aj = __fmul_rn(__fsub_rn(bj.z, bj.x), __fsub_rn(bj.w, bj.y));
+        float aj = box_area(bj);
         if (iou_gt(bi, ai, bj, aj, iou_thres)) bits |= 1ull << (j - wj * 64);
       }
     }
