@@ -5,6 +5,7 @@
 #pragma once
 #include "cvx_common.h"
 #include "bn_act.h"  // cvx_stat_replicas
+#include "conv_plan.h"  // ConvTap, tap traits, phase classes: the launch geometry (host side)
 
 enum {
   CVX_EPI_RAW_STATS = 0,    // train fwd: raw conv output FP32 (out32) + per-channel (sum, sumsq) into the fixed-point replica slabs
@@ -14,11 +15,6 @@ enum {
 };
 
 #define CVX_MAX_TAPS 64
-
-// One tap of the gather: input pixel = (o2*IS + dh, o2w*IS + dw); weight block index wtap.
-struct ConvTap {
-  int dh, dw, wtap, pad_;
-};
 
 struct ConvParams {
   // ---- gathered operand (activations for fwd, output-gradients for dgrad) ----
@@ -80,7 +76,7 @@ struct ConvParams {
   const half_t* tile_packed;
   int tile_packed_bn;
   int no_tile;                     // unit tests / A-B timing: keep this launch off the row-band kernel
-  // Data gradient of a stride-2 convolution as ONE stride-1 GEMM (engine.hip: plan_ps_dgrads): the four output phases are channel blocks
+  // Data gradient of a stride-2 convolution as ONE stride-1 GEMM (conv_plan.h: cvx_conv_ps_dgrad; engine.hip: fill_conv_ps): the four output phases are channel blocks
   // of ps_cin channels each -- output channel n = (2 * ph + pw) * ps_cin + c goes to pixel (oh2 * OS + ph, ow2 * OS + pw), channel c
   // (OS = 2, oph = opw = 0).  0: off.  Served by the GEMM-shaped kernel only (plain epilogue).
   int ps_cin;
@@ -95,27 +91,13 @@ __device__ __forceinline__ void cvx_store_raw4(const ConvParams& p, long long of
   else *reinterpret_cast<f4*>(p.out32 + off) = v;
 }
 
-// Packs a 9-entry tap table whose offsets all lie in the 3x3 neighbourhood into two 64-bit words, 4 bits per tap:
-// pos = (dh+1)*4 + (dw+1), wt = weight tap index.  Kernel arguments instead of a device table: the halo kernel reads
-// no tap memory at all.  Returns false (and the generic kernels are used) for any other table.
-inline bool cvx_halo_pack_taps(const ConvTap* t, int n, unsigned long long* pos, unsigned long long* wt) {
-  *pos = *wt = 0;
-  if (n != 9) return false;
-  for (int i = 0; i < 9; ++i) {
-    if (t[i].dh < -1 || t[i].dh > 1 || t[i].dw < -1 || t[i].dw > 1 || t[i].wtap < 0 || t[i].wtap > 15) return false;
-    *pos |= (unsigned long long)(((t[i].dh + 1) << 2) | (t[i].dw + 1)) << (4 * i);
-    *wt |= (unsigned long long)t[i].wtap << (4 * i);
-  }
-  return true;
-}
-
 // tuning aid: when set (cvx_debug_clock_buffer), the DMA-ring and halo kernels store per-block phase timestamps there
 extern unsigned long long* g_cvx_clk;
 // share of the chip a persistent conv launch should size its grid for: 1 = all CUs, n = 1/n of them (set by the engine
 // around launches on concurrent lanes, so that side-by-side persistent kernels do not queue behind each other)
 extern int g_cvx_grid_div;
-// Validates and dispatches to one of the kernels below (m_blocks: legacy out-parameter, always 0).
-int cvx_conv_igemm_launch(const ConvParams& p, hipStream_t stream, int* m_blocks);
+// Validates and dispatches to one of the kernels below.
+int cvx_conv_igemm_launch(const ConvParams& p, hipStream_t stream);
 // LDS-DMA ring kernel (conv_igemm_dma.hip): every shape the two persistent kernels do not take
 int cvx_conv_igemm_dma_launch(const ConvParams& p, hipStream_t stream);
 // 3x3 stride-1 halo-tile kernel (conv_halo.hip)
@@ -124,12 +106,6 @@ int cvx_conv_halo_launch(const ConvParams& p, hipStream_t stream);
 // 7x7 first layer on the 8-channel-padded image (conv_stem7.hip)
 bool cvx_conv_stem7_supported(const ConvParams& p);
 int cvx_conv_stem7_launch(const ConvParams& p, hipStream_t stream);
-inline int cvx_taps_std7x7(const ConvTap* t, int n) {
-  if (n != 49) return 0;
-  for (int i = 0; i < 49; ++i)
-    if (t[i].dh != i / 7 - 3 || t[i].dw != i % 7 - 3 || t[i].wtap != i) return 0;
-  return 1;
-}
 // GEMM-shaped kernel for the big-channel layers (conv_gemm.hip)
 // one layer's weights -> ring image order ([channel tile][chunk][K-step][k-half][BN rows][8]); blocks [blk0, blk0 + nblk) of the batched launch
 struct GemmPackJob {
@@ -163,7 +139,6 @@ void cvx_conv_tile_release();
 // pointwise (1x1 stride-1) persistent GEMM kernel (conv_pw.hip)
 bool cvx_conv_pw_supported(const ConvParams& p);
 int cvx_conv_pw_launch(const ConvParams& p, hipStream_t stream);
-inline int cvx_taps_pointwise(const ConvTap* t, int n) { return (n == 1 && t[0].dh == 0 && t[0].dw == 0 && t[0].wtap == 0) ? 1 : 0; }
 
 // Weight gradient: dW[co][tap][ci] partial sums over a slice of the pixels, written as fp32 slabs.
 struct WgradParams {
@@ -203,9 +178,3 @@ int cvx_conv_wgrad_stream_launch(const WgradParams& p, hipStream_t stream);
 bool cvx_conv_wgrad_k3_supported(const WgradParams& p);
 int cvx_conv_wgrad_k3_nsplit(const WgradParams& p, bool wide = false);  // wide: the tail of the backward pass -- the whole chip
 int cvx_conv_wgrad_k3_launch(const WgradParams& p, hipStream_t stream);
-inline int cvx_taps_std3x3(const ConvTap* t, int n) {
-  if (n != 9) return 0;
-  for (int i = 0; i < 9; ++i)
-    if (t[i].dh != i / 3 - 1 || t[i].dw != i % 3 - 1 || t[i].wtap != i) return 0;
-  return 1;
-}

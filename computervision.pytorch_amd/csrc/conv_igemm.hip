@@ -12,7 +12,7 @@
 unsigned long long* g_cvx_clk = nullptr;
 int g_cvx_grid_div = 1;
 
-int cvx_conv_igemm_launch(const ConvParams& p_in, hipStream_t stream, int* m_blocks) {
+int cvx_conv_igemm_launch(const ConvParams& p_in, hipStream_t stream) {
   ConvParams p = p_in;
   p.clk = g_cvx_clk;
   CVX_CHECK(p.Cin % 8 == 0 && p.in_ld % 8 == 0 && p.wt_ld % 8 == 0, "conv: channel counts must be multiples of 8");
@@ -21,7 +21,6 @@ int cvx_conv_igemm_launch(const ConvParams& p_in, hipStream_t stream, int* m_blo
   CVX_CHECK(((uintptr_t)p.in % 16) == 0 && ((uintptr_t)p.wt % 16) == 0, "conv: operands must be 16-byte aligned");
   CVX_CHECK(p.zeros && ((uintptr_t)p.zeros % 16) == 0, "conv: needs a 16-byte aligned zero page (padding source of the LDS DMA)");
   CVX_CHECK((long long)p.B * p.OH2 * p.OW2 > 0, "conv: empty output");
-  if (m_blocks) *m_blocks = 0;
   if (p.ps_cin > 0) {  // stride-2 data gradient as one GEMM with a pixel-shuffle store: the GEMM-shaped kernel's plain epilogue only
     CVX_CHECK(p.epi == CVX_EPI_PLAIN && p.nphase <= 1 && p.OS == 2 && p.oph == 0 && p.opw == 0 && p.ps_cin % 8 == 0 && p.Cout == 4 * p.ps_cin &&
                   cvx_conv_gemm_shape_ok(p),

@@ -35,12 +35,26 @@ extern "C" int cvx_abi_version(void) { return CVX_ABI_VERSION; }
 
 namespace {
 
-struct DgClass {
-  ConvTap* taps = nullptr;
-  bool halo_ok = false;
-  int pointwise = 0;
-  unsigned long long halo_pos = 0, halo_wt = 0;
+// one phase class of a data gradient (conv_plan.h: DgradPhase) with its tap table in device memory
+struct PhaseRt {
+  const ConvTap* taps = nullptr;
+  TapTraits tr;
   int ntaps = 0, oph = 0, opw = 0, OH2 = 0, OW2 = 0;
+};
+PhaseRt make_phase(const DgradPhase& d, const ConvTap* dev_taps) {
+  PhaseRt r;
+  r.taps = dev_taps;
+  r.tr = cvx_tap_traits(d.taps);
+  r.ntaps = (int)d.taps.size();
+  r.oph = d.oph;
+  r.opw = d.opw;
+  r.OH2 = d.OH2;
+  r.OW2 = d.OW2;
+  return r;
+}
+
+struct DgClass {
+  PhaseRt ph;
   const half_t* gemm_pk = nullptr;  // data-gradient weights in the GEMM-shaped kernel's ring image order (per batch plan), channel tiles of gemm_bn rows
   int gemm_bn = 0, gemm_kc = 0;
   const half_t* tile_pk = nullptr;  // ... and in the row-band kernel's LDS image order (conv_tile.hip), channel blocks of tile_bn rows
@@ -50,11 +64,7 @@ struct DgClass {
 struct ConvRt {
   // static
   ConvTap* taps_fwd = nullptr;
-  bool halo_ok = false;
-  int pointwise = 0;
-  int std3x3 = 0;
-  int std7x7 = 0;
-  unsigned long long halo_pos = 0, halo_wt = 0;
+  TapTraits tr;
   int ntaps = 0;
   DgClass dg[16];
   int ndg = 0;
@@ -291,6 +301,158 @@ unsigned long long dropout_seed(const cvx_engine* e, int op) {
   return e->seed * 0x9E3779B97F4A7C15ULL + (unsigned long long)e->train_pass * 1000003ULL + (unsigned long long)op;
 }
 
+// ---- parameter-block fillers: geometry and views in, one block out.  Every ConvParams / WgradParams of this file is made by one of
+// them -- the batch planner, the launches of the passes and the single-op entries describe a launch through the same function, so the
+// kernel a plan packs weights for is the kernel the launch gets (only the view of dy may differ: see dense_dy / dy_view). ----
+struct ConvGeom {
+  int B, ih, iw, cin, oh, ow, cout, stride, ntaps;  // cin: gathered channels (the view's, a multiple of 8); ntaps = k * k
+};
+ConvGeom geom_of(const cvx_op_desc& o, int B) { return ConvGeom{B, o.ih, o.iw, o.in.c, o.oh, o.ow, o.out.c, o.stride, o.k * o.k}; }
+
+// forward: the epilogue and the output view are the caller's
+void fill_conv_fwd(const ConvGeom& g, ViewDesc in, const half_t* wt, const ConvTap* taps, const TapTraits& tr, const half_t* zeros, ConvParams* cp) {
+  memset(cp, 0, sizeof(*cp));
+  cp->in = in.p;
+  cp->in_bstride = in.bstride;
+  cp->in_ld = in.ld;
+  cp->IH = g.ih;
+  cp->IW = g.iw;
+  cp->Cin = g.cin;
+  cp->wt = wt;
+  cp->wt_ld = g.ntaps * g.cin;
+  cp->Cout = g.cout;
+  cp->B = g.B;
+  cp->OH2 = g.oh;
+  cp->OW2 = g.ow;
+  cp->IS = g.stride;
+  cp->OS = 1;
+  cp->OWr = g.ow;
+  cp->ntaps = g.ntaps;
+  cp->taps = taps;
+  cp->zeros = zeros;
+  cp->halo_taps_ok = tr.halo_ok ? 1 : 0;
+  cp->pointwise = tr.pointwise;
+  cp->halo_pos = tr.halo_pos;
+  cp->halo_wt = tr.halo_wt;
+  cp->std7x7 = tr.std7x7;
+  cp->std3x3 = tr.std3x3;
+}
+
+// data gradient, one phase class: gathers dy, writes (or accumulates into) the pixels of its phase in gin; wt_t = transposed weights [cin][taps][cout]
+void fill_conv_dgrad(const ConvGeom& g, const PhaseRt& ph, ViewDesc dy, ViewDesc gin, const half_t* wt_t, const half_t* zeros, int accumulate, ConvParams* cp) {
+  memset(cp, 0, sizeof(*cp));
+  cp->in = dy.p;
+  cp->in_bstride = dy.bstride;
+  cp->in_ld = dy.ld;
+  cp->IH = g.oh;
+  cp->IW = g.ow;
+  cp->Cin = g.cout;
+  cp->wt = wt_t;
+  cp->wt_ld = g.ntaps * g.cout;
+  cp->Cout = g.cin;
+  cp->B = g.B;
+  cp->OH2 = ph.OH2;
+  cp->OW2 = ph.OW2;
+  cp->IS = 1;
+  cp->OS = g.stride;
+  cp->oph = ph.oph;
+  cp->opw = ph.opw;
+  cp->OWr = g.iw;
+  cp->ntaps = ph.ntaps;
+  cp->taps = ph.taps;
+  cp->zeros = zeros;
+  cp->halo_taps_ok = ph.tr.halo_ok ? 1 : 0;
+  cp->pointwise = ph.tr.pointwise;
+  cp->halo_pos = ph.tr.halo_pos;
+  cp->halo_wt = ph.tr.halo_wt;
+  cp->epi = CVX_EPI_PLAIN;
+  cp->accumulate = accumulate;
+  cp->out16 = gin.p;
+  cp->out_ld = gin.ld;
+  cp->out_bstride = gin.bstride;
+}
+// ... all n (2 ... 4) phase classes as one launch of the DMA-ring kernel (blockIdx.z selects the phase); *cp was filled for phase 0
+void set_merged_phases(const DgClass* dg, int n, ConvParams* cp) {
+  cp->nphase = n;
+  for (int z = 0; z < n; ++z) cp->phase[z] = ConvParams::Phase{dg[z].ph.taps, dg[z].ph.ntaps, dg[z].ph.OH2, dg[z].ph.OW2, dg[z].ph.oph, dg[z].ph.opw};
+  cp->halo_taps_ok = 0;
+  cp->pointwise = 0;
+}
+
+// The data gradient of a 3x3 / stride-2 convolution as ONE launch of the GEMM-shaped kernel.  dx[2i + p, 2j + q] only sees dy[i + a, j + b],
+// a, b in {0, 1}: a stride-1 convolution over dy with the 2 x 2 window as its taps and 4 x Cin outputs -- phase (p, q) = channel block
+// 2p + q -- stored with a pixel shuffle (ConvParams::ps_cin).  7 of the 16 (phase, window position) weight blocks are zero (16 / 9 of the
+// multiplications), but it is one GEMM with K = 4 C and N = 4 Cin where the merged-phase launch of the ring kernel is four with K = C .. 4 C
+// and N = Cin: measured in DESIGN 5c.  ps_wt = cvx_pack_ps_weights' image, window_taps = cvx_conv_ps_window_taps on the device.
+void fill_conv_ps(const ConvGeom& g, ViewDesc dy, ViewDesc gin, const half_t* ps_wt, const ConvTap* window_taps, const half_t* zeros, int accumulate, ConvParams* cp) {
+  memset(cp, 0, sizeof(*cp));
+  cp->in = dy.p;
+  cp->in_bstride = dy.bstride;
+  cp->in_ld = dy.ld;
+  cp->IH = g.oh;
+  cp->IW = g.ow;
+  cp->Cin = g.cout;
+  cp->wt = ps_wt;
+  cp->wt_ld = 4 * g.cout;
+  cp->Cout = 4 * g.cin;
+  cp->B = g.B;
+  cp->OH2 = g.oh;
+  cp->OW2 = g.ow;
+  cp->IS = 1;
+  cp->OS = 2;
+  cp->OWr = g.iw;
+  cp->ntaps = 4;
+  cp->taps = window_taps;
+  cp->zeros = zeros;
+  cp->epi = CVX_EPI_PLAIN;
+  cp->ps_cin = g.cin;
+  cp->accumulate = accumulate;
+  cp->out16 = gin.p;
+  cp->out_ld = gin.ld;
+  cp->out_bstride = gin.bstride;
+}
+
+// weight gradient: x (*) dy -> nsplit fp32 slabs; taps = the forward table
+void fill_wgrad(const ConvGeom& g, ViewDesc x, ViewDesc dy, const ConvTap* taps, int std3x3, float* slabs, int nsplit, WgradParams* wp) {
+  memset(wp, 0, sizeof(*wp));
+  wp->x = x.p;
+  wp->x_bstride = x.bstride;
+  wp->x_ld = x.ld;
+  wp->IH = g.ih;
+  wp->IW = g.iw;
+  wp->Cin = g.cin;
+  wp->dy = dy.p;
+  wp->dy_bstride = dy.bstride;
+  wp->dy_ld = dy.ld;
+  wp->Cout = g.cout;
+  wp->B = g.B;
+  wp->OH = g.oh;
+  wp->OW = g.ow;
+  wp->stride = g.stride;
+  wp->ntaps = g.ntaps;
+  wp->taps = taps;
+  wp->slabs = slabs;
+  wp->nsplit = nsplit;
+  wp->cin_pad16 = round_up(g.cin, 16);
+  wp->std3x3 = std3x3;
+}
+
+// Gradient w.r.t. the raw output of conv op i: the layer's own dense dybuf, or -- the head's output convs -- its slice of dpred.  The batch
+// planner passes dpred = nullptr (the tensor arrives with the backward pass): the view then carries the strides only.
+ViewDesc dense_dy(const cvx_op_desc& o, half_t* p = nullptr) { return ViewDesc{p, (long long)o.oh * o.ow * o.out.c, o.out.c}; }
+ViewDesc dy_view(const cvx_engine* e, int i, half_t* dpred) {
+  const cvx_op_desc& o = e->ops[i];
+  if (o.act != CVX_ACT_BIAS) return dense_dy(o, e->conv[i].dybuf);
+  const Buf& pb = e->bufs[e->pred_buf];
+  return ViewDesc{dpred ? dpred + (long long)o.out.pix_off * pb.d.c + o.out.coff : nullptr, (long long)pb.d.h * pb.d.w * pb.d.c, pb.d.c};
+}
+// the stem's weight gradient reads the caller's fp32 images (stem.hip): no fp16 view of x exists
+void fill_wgrad(const cvx_engine* e, int i, int B, ViewDesc dy, float* slabs, int nsplit, WgradParams* wp) {
+  const ConvRt& c = e->conv[i];
+  const ViewDesc x = c.stem ? ViewDesc{nullptr, 0, 0} : make_view(e, e->ops[i].in, false);
+  fill_wgrad(geom_of(e->ops[i], B), x, dy, c.taps_fwd, c.tr.std3x3, slabs, nsplit, wp);
+}
+
 int build_static(cvx_engine* e) {
   const int nops = (int)e->ops.size();
   e->conv.assign(nops, ConvRt());
@@ -329,17 +491,14 @@ int build_static(cvx_engine* e) {
     }
     CVX_CHECK(o.in.c % 8 == 0 && o.out.c % 8 == 0 && o.in.coff % 8 == 0 && o.out.coff % 8 == 0, "conv views must be 8-channel aligned");
     CVX_CHECK(o.w_cin <= o.in.c && o.w_cin > o.in.c - 8, "w_cin vs view channels");
+    CVX_CHECK(o.oh == cvx_conv_out_size(o.ih, o.k, o.stride, o.pad, o.dil) && o.ow == cvx_conv_out_size(o.iw, o.k, o.stride, o.pad, o.dil),
+              "conv output size does not follow from (ih, iw, k, stride, pad, dil)");
     c.cin_g = o.in.c;
     c.cin_pad16 = round_up(o.in.c, 16);
     c.ntaps = T;
-    std::vector<ConvTap> taps(T);
-    for (int r = 0; r < o.k; ++r)
-      for (int s = 0; s < o.k; ++s) taps[r * o.k + s] = ConvTap{r * o.dil - o.pad, s * o.dil - o.pad, r * o.k + s, 0};
+    const std::vector<ConvTap> taps = cvx_conv_fwd_taps(o.k, o.pad, o.dil);
     CVX_TRY(upload(e, e->static_allocs, e->static_bytes, &c.taps_fwd, taps));
-    c.halo_ok = cvx_halo_pack_taps(taps.data(), T, &c.halo_pos, &c.halo_wt);
-    c.pointwise = cvx_taps_pointwise(taps.data(), T);
-    c.std3x3 = cvx_taps_std3x3(taps.data(), T);
-    c.std7x7 = cvx_taps_std7x7(taps.data(), T);
+    c.tr = cvx_tap_traits(taps);
     // shadow weights
     PackDesc pd;
     pd.src_off = o.w_off;
@@ -360,40 +519,17 @@ int build_static(cvx_engine* e) {
       // data-gradient tap classes: one per output phase of the forward stride
       const int S = o.stride;
       CVX_CHECK(S * S <= 16, "stride too large");
-      // 3x3 / stride 2 / pad 1 on an even map: every phase's taps lie in the 2 x 2 window (dh, dw in {0, 1}) of dy -- the four phases are
-      // four channel blocks of ONE stride-1 GEMM (pixel-shuffle data gradient, see ConvRt::sh_ps)
-      bool ps_shape = S == 2 && o.k == 3 && o.pad == 1 && o.dil == 1 && o.ih == 2 * o.oh && o.iw == 2 * o.ow && o.out.c % 32 == 0;
-      for (int q = 0; q < 16; ++q) c.ps_desc.wtap[q] = -1;
-      for (int ph = 0; ph < S; ++ph)
-        for (int pw = 0; pw < S; ++pw) {
-          std::vector<ConvTap> dt;
-          for (int r = 0; r < o.k; ++r) {
-            int nh = ph + o.pad - r * o.dil;
-            if (((nh % S) + S) % S != 0) continue;
-            for (int s = 0; s < o.k; ++s) {
-              int nw = pw + o.pad - s * o.dil;
-              if (((nw % S) + S) % S != 0) continue;
-              dt.push_back(ConvTap{nh / S, nw / S, r * o.k + s, 0});  // exact division
-              if (ps_shape) {
-                const int dh = nh / S, dw = nw / S;
-                if (dh < 0 || dh > 1 || dw < 0 || dw > 1)
-                  ps_shape = false;
-                else
-                  c.ps_desc.wtap[(ph * 2 + pw) * 4 + dh * 2 + dw] = r * o.k + s;
-              }
-            }
-          }
-          DgClass& dc = c.dg[c.ndg++];
-          dc.ntaps = (int)dt.size();
-          dc.oph = ph;
-          dc.opw = pw;
-          dc.OH2 = (o.ih - ph + S - 1) / S;
-          dc.OW2 = (o.iw - pw + S - 1) / S;
-          if (dc.ntaps > 0) CVX_TRY(upload(e, e->static_allocs, e->static_bytes, &dc.taps, dt));
-          dc.halo_ok = cvx_halo_pack_taps(dt.data(), dc.ntaps, &dc.halo_pos, &dc.halo_wt);
-          dc.pointwise = dc.ntaps > 0 ? cvx_taps_pointwise(dt.data(), dc.ntaps) : 0;
-        }
-      if (ps_shape) {
+      const std::vector<DgradPhase> phases = cvx_conv_dgrad_phases(o.k, S, o.pad, o.dil, o.ih, o.iw);
+      for (const DgradPhase& d : phases) {
+        ConvTap* dev = nullptr;
+        if (!d.taps.empty()) CVX_TRY(upload(e, e->static_allocs, e->static_bytes, &dev, d.taps));
+        c.dg[c.ndg++].ph = make_phase(d, dev);
+      }
+      // the four phases of a 3x3 / stride-2 data gradient as ONE stride-1 GEMM (pixel-shuffle data gradient, see ConvRt::sh_ps): the
+      // channel counts the GEMM-shaped kernel's 32-wide K-steps take (plan_gemm_packs then asks cvx_conv_gemm_supported)
+      const PsDgrad ps = cvx_conv_ps_dgrad(o.k, S, o.pad, o.dil, o.ih, o.iw, phases);
+      for (int q = 0; q < 16; ++q) c.ps_desc.wtap[q] = ps.wtap[q];
+      if (ps.qualifies && o.out.c % 32 == 0) {
         c.sh_ps = sh;
         sh += 16LL * pd.Cin_pad * pd.Cout;
         sh = (sh + 7) & ~7LL;
@@ -402,9 +538,7 @@ int build_static(cvx_engine* e) {
         c.ps_desc.cin_pad = pd.Cin_pad;
         c.ps_desc.T = T;
         c.ps_desc.C = pd.Cout;
-        std::vector<ConvTap> pt(4);
-        for (int tau = 0; tau < 4; ++tau) pt[tau] = ConvTap{tau >> 1, tau & 1, tau, 0};
-        CVX_TRY(upload(e, e->static_allocs, e->static_bytes, &c.ps_taps, pt));
+        CVX_TRY(upload(e, e->static_allocs, e->static_bytes, &c.ps_taps, cvx_conv_ps_window_taps()));
       }
     }
     const int total = pd.Cout * T * pd.Cin_pad;
@@ -752,30 +886,9 @@ int plan_batch(cvx_engine* e, int B, bool training) {
       const bool tail_layer = (int)i <= tail_convs;
       bool wgg = false;
       int ws_splits = 0;  // > 0: the streaming kernel (conv_wgrad_stream.hip) takes the layer, with its planner's pixel splits
+      WgradParams q;
+      fill_wgrad(e, (int)i, B, dy_view(e, (int)i, nullptr), nullptr, 0, &q);
       if (!c.stem) {
-        WgradParams q;
-        memset(&q, 0, sizeof(q));
-        const Buf& xb = e->bufs[o.in.buf];
-        q.x_ld = xb.d.c;
-        q.x_bstride = (long long)xb.d.h * xb.d.w * xb.d.c;
-        q.IH = o.ih;
-        q.IW = o.iw;
-        q.Cin = c.cin_g;
-        q.dy_ld = C;
-        q.dy_bstride = (long long)o.oh * o.ow * C;
-        if (o.act == CVX_ACT_BIAS) {  // the head's output convs: dy is a slice of dpred
-          const Buf& pb = e->bufs[e->pred_buf];
-          q.dy_ld = pb.d.c;
-          q.dy_bstride = (long long)pb.d.h * pb.d.w * pb.d.c;
-        }
-        q.Cout = C;
-        q.B = B;
-        q.OH = o.oh;
-        q.OW = o.ow;
-        q.stride = o.stride;
-        q.ntaps = c.ntaps;
-        q.cin_pad16 = c.cin_pad16;
-        q.std3x3 = c.std3x3;
         if (cvx_conv_wgrad_k3_supported(q)) {
           ws_splits = cvx_conv_wgrad_k3_nsplit(q, tail_layer);
         } else if (cvx_conv_wgrad_stream_supported(q)) {
@@ -808,22 +921,11 @@ int plan_batch(cvx_engine* e, int B, bool training) {
       ns = std::min(ns, std::max<long long>(1, (slab_cap_mb << 20) / (slab_elems * 4)));
       ns = std::min<long long>(ns, ns_cap);
       {  // 3x3 stride-1 layers take the register-tile kernel: few, fat workgroups per pixel split
-        WgradParams probe;
-        memset(&probe, 0, sizeof(probe));
-        probe.std3x3 = c.std3x3;
-        probe.stride = o.stride;
-        probe.ntaps = c.ntaps;
-        probe.Cin = c.cin_g;
-        probe.Cout = C;
-        probe.IH = o.ih;
-        probe.IW = o.iw;
-        probe.OH = o.oh;
-        probe.OW = o.ow;
         if (c.stem) {
           ns = cvx_stem_wgrad_splits(M);
         } else if (ws_splits > 0) {
           ns = ws_splits;
-        } else if (cvx_conv_wgrad_halo_supported(probe)) {
+        } else if (cvx_conv_wgrad_halo_supported(q)) {
           int gx, gy;
           cvx_conv_wgrad_halo_grid(C, c.cin_g, &gx, &gy);
           const long long ptiles = cvx_conv_wgrad_halo_tiles(B, o.oh, o.ow);
@@ -937,34 +1039,8 @@ int plan_batch(cvx_engine* e, int B, bool training) {
 }
 
 void fill_conv_fwd(const cvx_engine* e, int i, int B, ConvParams* cp) {
-  const cvx_op_desc& o = e->ops[i];
   const ConvRt& c = e->conv[i];
-  ViewDesc in = make_view(e, o.in, false);
-  memset(cp, 0, sizeof(*cp));
-  cp->in = in.p;
-  cp->in_bstride = in.bstride;
-  cp->in_ld = in.ld;
-  cp->IH = o.ih;
-  cp->IW = o.iw;
-  cp->Cin = c.cin_g;
-  cp->wt = e->shadow + c.sh_fwd;
-  cp->wt_ld = c.ntaps * c.cin_g;
-  cp->Cout = o.out.c;
-  cp->B = B;
-  cp->OH2 = o.oh;
-  cp->OW2 = o.ow;
-  cp->IS = o.stride;
-  cp->OS = 1;
-  cp->OWr = o.ow;
-  cp->ntaps = c.ntaps;
-  cp->taps = c.taps_fwd;
-  cp->zeros = e->zero_page;
-  cp->halo_taps_ok = c.halo_ok ? 1 : 0;
-  cp->pointwise = c.pointwise;
-  cp->halo_pos = c.halo_pos;
-  cp->halo_wt = c.halo_wt;
-  cp->std7x7 = c.std7x7;
-  cp->std3x3 = c.std3x3;
+  fill_conv_fwd(geom_of(e->ops[i], B), make_view(e, e->ops[i].in, false), e->shadow + c.sh_fwd, c.taps_fwd, c.tr, e->zero_page, cp);
   cp->wt_packed = c.gemm_fwd;
   cp->wt_packed_bn = c.gemm_fwd_bn;
   cp->wt_packed_kc = c.gemm_fwd_kc;
@@ -991,67 +1067,25 @@ void free_gemm_packs(cvx_engine* e) {
   }
 }
 
-// the launch geometry of one phase class of a data gradient, as far as the dispatcher's choice of kernel depends on it
-void fill_conv_dgrad_shape(const cvx_engine* e, int i, int q, int B, ConvParams* cp) {
-  const cvx_op_desc& o = e->ops[i];
+// Phase class q of op i's data gradient, with the packed weight images of the current batch plan.  The pack planners pass dense_dy: the
+// kernel choice reads the strides of dy only, and they assume the dense dy of a BatchNorm / bias layer (a head's dpred slice is wider; a
+// launch whose choice differs packs its weights itself).
+void fill_conv_dgrad(const cvx_engine* e, int i, int q, int B, ViewDesc dy, ConvParams* cp) {
   const ConvRt& c = e->conv[i];
   const DgClass& dc = c.dg[q];
-  const int C = o.out.c;
-  memset(cp, 0, sizeof(*cp));
-  cp->in_ld = C;
-  cp->in_bstride = (long long)o.oh * o.ow * C;  // dy of a BN layer is dense; a head's dpred slice is wider (the launch re-checks its own view)
-  cp->IH = o.oh;
-  cp->IW = o.ow;
-  cp->Cin = C;
-  cp->wt = e->shadow + c.sh_dg;
-  cp->wt_ld = c.ntaps * C;
-  cp->Cout = o.in.c;
-  cp->B = B;
-  cp->OH2 = dc.OH2;
-  cp->OW2 = dc.OW2;
-  cp->IS = 1;
-  cp->OS = o.stride;
-  cp->ntaps = dc.ntaps;
-  cp->taps = dc.taps;
-  cp->zeros = e->zero_page;
-  cp->oph = dc.oph;
-  cp->opw = dc.opw;
-  cp->OWr = o.iw;
-  cp->halo_taps_ok = dc.halo_ok ? 1 : 0;
-  cp->halo_pos = dc.halo_pos;
-  cp->halo_wt = dc.halo_wt;
-  cp->pointwise = dc.pointwise;
+  fill_conv_dgrad(geom_of(e->ops[i], B), dc.ph, dy, make_view(e, e->ops[i].in, true), e->shadow + c.sh_dg, e->zero_page, c.in_accum, cp);
+  cp->wt_packed = dc.gemm_pk;
+  cp->wt_packed_bn = dc.gemm_bn;
+  cp->wt_packed_kc = dc.gemm_kc;
+  cp->tile_packed = dc.tile_pk;
+  cp->tile_packed_bn = dc.tile_bn;
 }
-
-// The data gradient of a 3x3 / stride-2 convolution as ONE launch of the GEMM-shaped kernel.  dx[2i + p, 2j + q] only sees dy[i + a, j + b],
-// a, b in {0, 1}: a stride-1 convolution over dy with the 2 x 2 window as its taps and 4 x Cin outputs -- phase (p, q) = channel block
-// 2p + q -- stored with a pixel shuffle (ConvParams::ps_cin).  7 of the 16 (phase, window position) weight blocks are zero (16 / 9 of the
-// multiplications), but it is one GEMM with K = 4 C and N = 4 Cin where the merged-phase launch of the ring kernel is four with K = C .. 4 C
-// and N = Cin: measured in DESIGN 5c.
-void fill_conv_ps_shape(const cvx_engine* e, int i, int B, ConvParams* cp) {
-  const cvx_op_desc& o = e->ops[i];
+void fill_conv_ps(const cvx_engine* e, int i, int B, ViewDesc dy, ConvParams* cp) {
   const ConvRt& c = e->conv[i];
-  const int C = o.out.c;
-  memset(cp, 0, sizeof(*cp));
-  cp->in_ld = C;
-  cp->in_bstride = (long long)o.oh * o.ow * C;
-  cp->IH = o.oh;
-  cp->IW = o.ow;
-  cp->Cin = C;
-  cp->wt = e->shadow + c.sh_ps;
-  cp->wt_ld = 4 * C;
-  cp->Cout = 4 * o.in.c;
-  cp->B = B;
-  cp->OH2 = o.oh;
-  cp->OW2 = o.ow;
-  cp->IS = 1;
-  cp->OS = 2;
-  cp->OWr = o.iw;
-  cp->ntaps = 4;
-  cp->taps = c.ps_taps;
-  cp->zeros = e->zero_page;
-  cp->epi = CVX_EPI_PLAIN;
-  cp->ps_cin = o.in.c;
+  fill_conv_ps(geom_of(e->ops[i], B), dy, make_view(e, e->ops[i].in, true), e->shadow + c.sh_ps, c.ps_taps, e->zero_page, c.in_accum, cp);
+  cp->wt_packed = c.ps_pk;
+  cp->wt_packed_bn = c.ps_bn;
+  cp->wt_packed_kc = c.ps_kc;
 }
 
 // Every conv launch the dispatcher will give to the GEMM-shaped kernel (conv_gemm.hip) gets its weights in ring image order from one
@@ -1090,9 +1124,9 @@ int plan_gemm_packs(cvx_engine* e, int B, bool training) {
       const cvx_op_desc& o = e->ops[i];
       const ConvRt& c = e->conv[i];
       if (o.type != CVX_OP_CONV || c.stem || !o.needs_dgrad || c.sh_dg < 0 || c.ndg != 1) continue;  // strided data gradients go out as merged phases
-      if (c.dg[0].OH2 <= 0 || c.dg[0].OW2 <= 0 || c.dg[0].ntaps <= 0) continue;
+      if (c.dg[0].ph.OH2 <= 0 || c.dg[0].ph.OW2 <= 0 || c.dg[0].ph.ntaps <= 0) continue;
       ConvParams cp;
-      fill_conv_dgrad_shape(e, (int)i, 0, B, &cp);
+      fill_conv_dgrad(e, (int)i, 0, B, dense_dy(e->ops[i]), &cp);
       add(cp, (int)i, 0);
     }
     static const bool ps_off = cvx_tune_set("CVX_NO_PS_DGRAD");
@@ -1101,7 +1135,7 @@ int plan_gemm_packs(cvx_engine* e, int B, bool training) {
       ConvRt& c = e->conv[i];
       if (o.type != CVX_OP_CONV || c.stem || !o.needs_dgrad || c.sh_ps < 0 || c.ndg != 4) continue;
       ConvParams cp;
-      fill_conv_ps_shape(e, (int)i, B, &cp);
+      fill_conv_ps(e, (int)i, B, dense_dy(e->ops[i]), &cp);
       if (!cvx_conv_gemm_supported(cp)) continue;
       const size_t before = jobs.size();
       add(cp, (int)i, kPsRef);
@@ -1183,9 +1217,9 @@ int plan_tile_packs(cvx_engine* e, int B, bool training) {
       const cvx_op_desc& o = e->ops[i];
       const ConvRt& c = e->conv[i];
       if (o.type != CVX_OP_CONV || c.stem || !o.needs_dgrad || c.sh_dg < 0 || c.ndg != 1) continue;
-      if (c.dg[0].OH2 <= 0 || c.dg[0].OW2 <= 0 || c.dg[0].ntaps <= 0) continue;
+      if (c.dg[0].ph.OH2 <= 0 || c.dg[0].ph.OW2 <= 0 || c.dg[0].ph.ntaps <= 0) continue;
       ConvParams cp;
-      fill_conv_dgrad_shape(e, (int)i, 0, B, &cp);
+      fill_conv_dgrad(e, (int)i, 0, B, dense_dy(e->ops[i]), &cp);
       add(cp, (int)i, 0);
     }
   }
@@ -1752,7 +1786,7 @@ extern "C" int cvx_engine_forward(cvx_engine* e, const float* images, int32_t ba
       cp.out_ld = pb.d.c;
       cp.out_bstride = A * pb.d.c;
       ProfScope ps(e, PROF_CONV_FWD, conv_flops(o, B), conv_bytes(o, B) + 2.0 * M * C, st);
-      CVX_TRY(cvx_conv_igemm_launch(cp, st, nullptr));
+      CVX_TRY(cvx_conv_igemm_launch(cp, st));
       continue;
     }
     ViewDesc outv = make_view(e, o.out, false);
@@ -1769,10 +1803,9 @@ extern "C" int cvx_engine_forward(cvx_engine* e, const float* images, int32_t ba
       }
       cp.stats = c.stat_fwd;
       cp.stats_replicas = cvx_stat_replicas(C);
-      int P = 0;
       {
         ProfScope ps(e, PROF_CONV_FWD, conv_flops(o, B), conv_bytes(o, B) + (c.raw16 ? 0.0 : 2.0 * M * C), st);
-        CVX_TRY(cvx_conv_igemm_launch(cp, st, &P));
+        CVX_TRY(cvx_conv_igemm_launch(cp, st));
       }
       ProfScope ps(e, PROF_BN_FWD, 0, (c.raw16 ? 4.0 : resv.p ? 10.0 : 8.0) * M * C, st);
       BnTrainArgs ta{c.stat_fwd,           e->params + o.gamma_off, e->params + o.beta_off, c.mean, c.invstd, e->stats + o.rmean_off,
@@ -1794,7 +1827,7 @@ extern "C" int cvx_engine_forward(cvx_engine* e, const float* images, int32_t ba
       cp.res_ld = resv.ld;
       cp.res_bstride = resv.bstride;
       ProfScope ps(e, PROF_CONV_FWD, conv_flops(o, B), conv_bytes(o, B), st);
-      CVX_TRY(cvx_conv_igemm_launch(cp, st, nullptr));
+      CVX_TRY(cvx_conv_igemm_launch(cp, st));
     }
   }
   if (lane_used) {
@@ -1916,8 +1949,6 @@ int backward_begin(cvx_engine* e, const void* dpred_f16, float loss_scale) {
 int backward_op(cvx_engine* e, int i) {
   cvx_bw_state& w = bw_of(e);
   const int B = w.B;
-  const Buf& pb = e->bufs[e->pred_buf];
-  const long long A = (long long)pb.d.h * pb.d.w;
   const cvx_op_desc& o = e->ops[i];
   e->cur_op = i;
     hipStream_t st = e->stream;
@@ -2019,20 +2050,13 @@ int backward_op(cvx_engine* e, int i) {
     const long long M = (long long)B * o.oh * o.ow;
     const int C = o.out.c;
     const int hw = o.oh * o.ow;
-    ViewDesc dyv;  // gradient w.r.t. the raw conv output
-    if (o.act == CVX_ACT_BIAS) {
-      dyv.p = w.dpred + (long long)o.out.pix_off * pb.d.c + o.out.coff;
-      dyv.ld = pb.d.c;
-      dyv.bstride = A * pb.d.c;
-      // (the bias gradient = column sums of dy went out with all the others in backward_begin: cvx_colsum_multi)
-    } else if (o.act == CVX_ACT_BIAS_RELU || o.act == CVX_ACT_BIAS_LINEAR) {
+    const ViewDesc dyv = dy_view(e, i, w.dpred);  // gradient w.r.t. the raw conv output
+    // (CVX_ACT_BIAS: dy is dpred's slice, and the bias gradient = column sums of dy went out with all the others in backward_begin: cvx_colsum_multi)
+    if (o.act == CVX_ACT_BIAS_RELU || o.act == CVX_ACT_BIAS_LINEAR) {
       ProfScope ps(e, PROF_BN_BWD, 0, 6.0 * M * C, st);
       CVX_TRY(cvx_bias_act_bwd(make_view(e, o.out, true), make_view(e, o.out, false), o.act == CVX_ACT_BIAS_RELU ? 1 : 0, M, C, hw, c.dybuf, c.stat_bwd,
                                w.inv_scale, e->grads + o.bias_off, st));
-      dyv.p = c.dybuf;
-      dyv.ld = C;
-      dyv.bstride = (long long)hw * C;
-    } else {
+    } else if (o.act != CVX_ACT_BIAS) {
       ViewDesc gout = make_view(e, o.out, true);
       ViewDesc gres = make_view(e, o.res, true);
       BnCoef k{c.invstd, e->params + o.gamma_off, e->params + o.beta_off, c.raw16 ? c.mean : nullptr};
@@ -2059,37 +2083,13 @@ int backward_op(cvx_engine* e, int i) {
       if (one == 1 && !c.stem)
         CVX_TRY(cvx_bn_bwd_apply(c.ybuf, M, C, hw, k, c.stat_bwd, w.inv_scale, e->grads + o.gamma_off, e->grads + o.beta_off, gout, ak, c.dybuf,
                                  gres, c.res_accum, st));
-      dyv.p = c.dybuf;
-      dyv.ld = C;
-      dyv.bstride = (long long)hw * C;
     }
     // dy of this layer is complete here; the side stream learns it through an event, recorded once per `w.wg_batch`
     // layers (a marker packet between two main-chain kernels costs ~5 us, see flush_wgrads below)
     // ---- weight gradient -> fp32 slabs (queued for the side stream) ----
     auto queue_wgrad = [&]() -> int {
-      ViewDesc xin = c.stem ? ViewDesc{nullptr, 0, 0} : make_view(e, o.in, false);
       WgradParams wp;
-      memset(&wp, 0, sizeof(wp));
-      wp.x = xin.p;
-      wp.x_bstride = xin.bstride;
-      wp.x_ld = xin.ld;
-      wp.IH = o.ih;
-      wp.IW = o.iw;
-      wp.Cin = c.cin_g;
-      wp.dy = dyv.p;
-      wp.dy_bstride = dyv.bstride;
-      wp.dy_ld = dyv.ld;
-      wp.Cout = C;
-      wp.B = B;
-      wp.OH = o.oh;
-      wp.OW = o.ow;
-      wp.stride = o.stride;
-      wp.ntaps = c.ntaps;
-      wp.taps = c.taps_fwd;
-      wp.slabs = e->slabs + c.slab_off;
-      wp.nsplit = c.nsplit;
-      wp.cin_pad16 = c.cin_pad16;
-      wp.std3x3 = c.std3x3;
+      fill_wgrad(e, i, B, dyv, e->slabs + c.slab_off, c.nsplit, &wp);
       PendingWgrad pw{wp, c.stem, StemParams{}, ViewDesc{nullptr, 0, 0}, BnCoef{nullptr, nullptr, nullptr}, nullptr, 0.f, nullptr, nullptr,
                       conv_flops(o, B), conv_bytes(o, B) + 4.0 * c.nsplit * C * c.ntaps * c.cin_pad16, i};
       if (c.stem) {
@@ -2124,85 +2124,35 @@ int backward_op(cvx_engine* e, int i) {
       static const bool merge_off = cvx_tune_set("CVX_NO_PHASE_MERGE");
       bool merged = !merge_off && c.ndg > 1 && c.ndg <= 4;
       for (int q = 0; q < c.ndg && merged; ++q)
-        if (c.dg[q].OH2 <= 0 || c.dg[q].OW2 <= 0 || c.dg[q].ntaps <= 0) merged = false;
+        if (c.dg[q].ph.OH2 <= 0 || c.dg[q].ph.OW2 <= 0 || c.dg[q].ph.ntaps <= 0) merged = false;
       // stride > kernel (ResNet's 1x1 stride-2 downsample): input pixels of the tap-less phases receive no gradient -- the first
       // writer of the slice zeroes it, the phases with taps then overwrite their own pixels
       bool empty_phase = false;
-      for (int q = 0; q < c.ndg; ++q) empty_phase |= c.dg[q].OH2 > 0 && c.dg[q].OW2 > 0 && c.dg[q].ntaps == 0;
+      for (int q = 0; q < c.ndg; ++q) empty_phase |= c.dg[q].ph.OH2 > 0 && c.dg[q].ph.OW2 > 0 && c.dg[q].ph.ntaps == 0;
       if (empty_phase && !c.in_accum) CVX_TRY(cvx_zero_slice(gin, B, o.ih * o.iw, o.in.c, st));
-      if (c.ps_on) {  // the four phases as one GEMM with a pixel-shuffle store (fill_conv_ps_shape)
+      if (c.ps_on) {  // the four phases as one GEMM with a pixel-shuffle store (fill_conv_ps)
         ConvParams cp;
-        fill_conv_ps_shape(e, i, B, &cp);
-        cp.in = dyv.p;
-        cp.in_bstride = dyv.bstride;
-        cp.in_ld = dyv.ld;
-        cp.accumulate = c.in_accum;
-        cp.wt_packed = c.ps_pk;
-        cp.wt_packed_bn = c.ps_bn;
-        cp.wt_packed_kc = c.ps_kc;
-        cp.out16 = gin.p;
-        cp.out_ld = gin.ld;
-        cp.out_bstride = gin.bstride;
+        fill_conv_ps(e, i, B, dyv, &cp);
         const double fl = 2.0 * B * o.oh * o.ow * (double)o.in.c * c.ntaps * C;  // the useful multiplications (the zero blocks are not counted)
         ProfScope ps(e, PROF_CONV_DGRAD, fl, conv_bytes(o, B) + (c.in_accum ? 2.0 * B * o.ih * o.iw * o.in.c : 0.0), st);
-        CVX_TRY(cvx_conv_igemm_launch(cp, st, nullptr));
+        CVX_TRY(cvx_conv_igemm_launch(cp, st));
       }
       for (int q = 0; q < c.ndg && !c.ps_on; ++q) {
         if (merged && q > 0) break;  // everything went out with phase 0
         const DgClass& dc = c.dg[q];
-        if (dc.OH2 <= 0 || dc.OW2 <= 0 || dc.ntaps == 0) continue;
+        if (dc.ph.OH2 <= 0 || dc.ph.OW2 <= 0 || dc.ph.ntaps == 0) continue;
         ConvParams cp;
-        memset(&cp, 0, sizeof(cp));
-        cp.in = dyv.p;
-        cp.in_bstride = dyv.bstride;
-        cp.in_ld = dyv.ld;
-        cp.IH = o.oh;
-        cp.IW = o.ow;
-        cp.Cin = C;
-        cp.wt = e->shadow + c.sh_dg;
-        cp.wt_ld = c.ntaps * C;
-        cp.Cout = o.in.c;
-        cp.B = B;
-        cp.OH2 = dc.OH2;
-        cp.OW2 = dc.OW2;
-        cp.IS = 1;
-        cp.OS = o.stride;
-        cp.oph = dc.oph;
-        cp.opw = dc.opw;
-        cp.OWr = o.iw;
-        cp.ntaps = dc.ntaps;
-        cp.taps = dc.taps;
-        cp.epi = CVX_EPI_PLAIN;
-        cp.zeros = e->zero_page;
-        cp.halo_taps_ok = dc.halo_ok ? 1 : 0;
-        cp.pointwise = dc.pointwise;
-        cp.halo_pos = dc.halo_pos;
-        cp.halo_wt = dc.halo_wt;
-        cp.accumulate = c.in_accum;
-        cp.wt_packed = dc.gemm_pk;
-        cp.wt_packed_bn = dc.gemm_bn;
-        cp.wt_packed_kc = dc.gemm_kc;
-        cp.tile_packed = dc.tile_pk;
-        cp.tile_packed_bn = dc.tile_bn;
-        cp.out16 = gin.p;
-        cp.out_ld = gin.ld;
-        cp.out_bstride = gin.bstride;
-        double fl = 2.0 * B * dc.OH2 * dc.OW2 * (double)o.in.c * dc.ntaps * C;
+        fill_conv_dgrad(e, i, q, B, dyv, &cp);
+        double fl = 2.0 * B * dc.ph.OH2 * dc.ph.OW2 * (double)o.in.c * dc.ph.ntaps * C;
         double by = (conv_bytes(o, B) + (c.in_accum ? 2.0 * B * o.ih * o.iw * o.in.c : 0.0)) / c.ndg;
         if (merged) {
-          cp.nphase = c.ndg;
+          set_merged_phases(c.dg, c.ndg, &cp);
           fl = 0;
-          for (int z = 0; z < c.ndg; ++z) {
-            const DgClass& dz = c.dg[z];
-            cp.phase[z] = ConvParams::Phase{dz.taps, dz.ntaps, dz.OH2, dz.OW2, dz.oph, dz.opw};
-            fl += 2.0 * B * dz.OH2 * dz.OW2 * (double)o.in.c * dz.ntaps * C;
-          }
+          for (int z = 0; z < c.ndg; ++z) fl += 2.0 * B * c.dg[z].ph.OH2 * c.dg[z].ph.OW2 * (double)o.in.c * c.dg[z].ph.ntaps * C;
           by *= c.ndg;
-          cp.halo_taps_ok = 0;
-          cp.pointwise = 0;
         }
         ProfScope ps(e, PROF_CONV_DGRAD, fl, by, st);
-        CVX_TRY(cvx_conv_igemm_launch(cp, st, nullptr));
+        CVX_TRY(cvx_conv_igemm_launch(cp, st));
       }
     }
     if (!wgrad_first) CVX_TRY(queue_wgrad());
@@ -2496,20 +2446,40 @@ extern "C" int cvx_check_finite(const float* grads, int64_t n, int32_t* found_in
   return cvx_check_finite_launch(grads, n, found_inf, (hipStream_t)hip_stream);
 }
 
-// ---- single-op entry points --------------------------------------------------------------------
+// ---- single-op entry points: the engine's geometry (conv_plan.h) and fillers on dense caller tensors ------------------------------
 namespace {
-int make_taps(std::vector<ConvTap>& host, ConvTap** dev) {
-  // the tap table is followed by a 256-byte zero page (DMA padding source of the second-generation kernel)
-  const size_t tb = ((host.size() * sizeof(ConvTap) + 255) / 256) * 256;
-  CVX_HIP(hipMalloc((void**)dev, tb + 256));
-  CVX_HIP(hipMemset(*dev, 0, tb + 256));
-  CVX_HIP(hipMemcpy(*dev, host.data(), host.size() * sizeof(ConvTap), hipMemcpyHostToDevice));
-  return 0;
-}
-const half_t* zeros_after(const ConvTap* dev, size_t ntaps) {
-  const size_t tb = ((ntaps * sizeof(ConvTap) + 255) / 256) * 256;
-  return reinterpret_cast<const half_t*>(reinterpret_cast<const char*>(dev) + tb);
-}
+// device temporaries of one call (tap tables, pixel-shuffle weights, the reducer's tables): freed on every return path
+struct DevTemps {
+  std::vector<void*> ptrs;
+  DevTemps() = default;
+  DevTemps(const DevTemps&) = delete;
+  DevTemps& operator=(const DevTemps&) = delete;
+  ~DevTemps() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  template <typename T>
+  int alloc(T** out, size_t bytes) {
+    void* p = nullptr;
+    CVX_HIP(hipMalloc(&p, bytes));
+    ptrs.push_back(p);
+    *out = (T*)p;
+    return 0;
+  }
+  // a tap table followed by a 256-byte zero page (DMA padding source of the conv kernels)
+  int taps(const std::vector<ConvTap>& host, const ConvTap** dev, const half_t** zeros = nullptr) {
+    const size_t tb = ((host.size() * sizeof(ConvTap) + 255) / 256) * 256;
+    char* p = nullptr;
+    CVX_TRY(alloc(&p, tb + 256));
+    CVX_HIP(hipMemset(p, 0, tb + 256));
+    CVX_HIP(hipMemcpy(p, host.data(), host.size() * sizeof(ConvTap), hipMemcpyHostToDevice));
+    *dev = reinterpret_cast<const ConvTap*>(p);
+    if (zeros) *zeros = reinterpret_cast<const half_t*>(p + tb);
+    return 0;
+  }
+};
+ViewDesc dense_view(const void* p, long long pixels, int c) { return ViewDesc{(half_t*)p, pixels * c, c}; }
+// pixel splits of the single-op weight gradient; its workspace is sized with the same count
+long long unit_wgrad_splits(long long M) { return std::min<long long>(std::max<long long>(1, M / 256), 64); }
 }  // namespace
 
 extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, const void* w_f16, int32_t cout,
@@ -2522,36 +2492,15 @@ extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int
   const bool force_tile = (mode & 0x2000) != 0;  // likewise the row-band kernel (conv_tile.hip); 0x4000: never the row-band kernel
   const bool no_tile = (mode & 0x4000) != 0;
   mode &= 0xff;
-  const int oh = (ih + 2 * pad - dil * (k - 1) - 1) / stride + 1, ow = (iw + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-  std::vector<ConvTap> taps;
-  for (int r = 0; r < k; ++r)
-    for (int s = 0; s < k; ++s) taps.push_back(ConvTap{r * dil - pad, s * dil - pad, r * k + s, 0});
-  ConvTap* dt = nullptr;
-  CVX_TRY(make_taps(taps, &dt));
+  const int oh = cvx_conv_out_size(ih, k, stride, pad, dil), ow = cvx_conv_out_size(iw, k, stride, pad, dil);
+  const std::vector<ConvTap> taps = cvx_conv_fwd_taps(k, pad, dil);
+  DevTemps tmp;
+  const ConvTap* dt = nullptr;
+  const half_t* zeros = nullptr;
+  CVX_TRY(tmp.taps(taps, &dt, &zeros));
   ConvParams cp;
-  memset(&cp, 0, sizeof(cp));
-  cp.in = (const half_t*)x_f16;
-  cp.in_bstride = (long long)ih * iw * cin;
-  cp.in_ld = cin;
-  cp.IH = ih;
-  cp.IW = iw;
-  cp.Cin = cin;
-  cp.wt = (const half_t*)w_f16;
-  cp.wt_ld = k * k * cin;
-  cp.Cout = cout;
-  cp.B = batch;
-  cp.OH2 = oh;
-  cp.OW2 = ow;
-  cp.IS = stride;
-  cp.OS = 1;
-  cp.OWr = ow;
-  cp.ntaps = k * k;
-  cp.taps = dt;
-  cp.zeros = zeros_after(dt, taps.size());
-  cp.halo_taps_ok = cvx_halo_pack_taps(taps.data(), (int)taps.size(), &cp.halo_pos, &cp.halo_wt) ? 1 : 0;
-  cp.pointwise = cvx_taps_pointwise(taps.data(), (int)taps.size());
-  cp.std7x7 = dil == 1 ? cvx_taps_std7x7(taps.data(), (int)taps.size()) : 0;
-  cp.std3x3 = dil == 1 ? cvx_taps_std3x3(taps.data(), (int)taps.size()) : 0;
+  fill_conv_fwd(ConvGeom{batch, ih, iw, cin, oh, ow, cout, stride, k * k}, dense_view(x_f16, (long long)ih * iw, cin), (const half_t*)w_f16, dt,
+                cvx_tap_traits(taps), zeros, &cp);
   cp.out_ld = cout;
   cp.out_bstride = (long long)oh * ow * cout;
   if (mode == 0) {
@@ -2576,24 +2525,17 @@ extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int
   int rc;
   cp.gemm_variant = gemm_variant;
   if (force_gemm) {
-    if (!cvx_conv_gemm_shape_ok(cp)) {
-      (void)hipFree(dt);
-      CVX_CHECK(false, "shape outside the GEMM-shaped kernel (cin % 8, cout % 4)");
-    }
+    CVX_CHECK(cvx_conv_gemm_shape_ok(cp), "shape outside the GEMM-shaped kernel (cin % 8, cout % 4)");
     rc = cvx_conv_gemm_launch(cp, st);
   } else if (force_tile) {
-    if (!cvx_conv_tile_shape_ok(cp)) {
-      (void)hipFree(dt);
-      CVX_CHECK(false, "shape outside the row-band kernel (3x3 stride 1, cin % 8, cin >= 32)");
-    }
+    CVX_CHECK(cvx_conv_tile_shape_ok(cp), "shape outside the row-band kernel (3x3 stride 1, cin % 8, cin >= 32)");
     cp.clk = g_cvx_clk;
     rc = cvx_conv_tile_launch(cp, st);
   } else {
     cp.no_tile = no_tile ? 1 : 0;
-    rc = cvx_conv_igemm_launch(cp, st, nullptr);
+    rc = cvx_conv_igemm_launch(cp, st);
   }
   (void)hipStreamSynchronize(st);
-  (void)hipFree(dt);
   return rc;
 }
 
@@ -2601,125 +2543,52 @@ extern "C" int cvx_conv2d_dgrad_nhwc(const void* dy_f16, int32_t batch, int32_t 
                                      int32_t k, int32_t stride, int32_t pad, int32_t dil, void* dx_f16, void* hip_stream) {
   CVX_CHECK(dy_f16 && wt_f16 && dx_f16 && k * k <= CVX_MAX_TAPS && stride >= 1 && stride <= 4, "bad arguments");
   hipStream_t st = (hipStream_t)hip_stream;
-  const int oh = (ih + 2 * pad - dil * (k - 1) - 1) / stride + 1, ow = (iw + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-  int rc = 0;
+  const int oh = cvx_conv_out_size(ih, k, stride, pad, dil), ow = cvx_conv_out_size(iw, k, stride, pad, dil);
+  const ConvGeom g{batch, ih, iw, cin, oh, ow, cout, stride, k * k};
+  const ViewDesc dy = dense_view(dy_f16, (long long)oh * ow, cout), dx = dense_view(dx_f16, (long long)ih * iw, cin);
+  const std::vector<DgradPhase> phases = cvx_conv_dgrad_phases(k, stride, pad, dil, ih, iw);
   // 3x3 / stride 2 / pad 1 on an even map: the engine's route -- ONE launch of the GEMM-shaped kernel over the 2 x 2 window of dy, the four
   // phases as channel blocks, pixel-shuffle store (ConvParams::ps_cin) -- where that kernel takes the shape
-  if (k == 3 && stride == 2 && pad == 1 && dil == 1 && ih == 2 * oh && iw == 2 * ow && cout % 32 == 0 && cin % 8 == 0) {
-    PsPackDesc pd;
-    pd.dg_off = pd.ps_off = 0;
-    pd.cin_pad = cin;
-    pd.T = 9;
-    pd.C = cout;
-    for (int q = 0; q < 16; ++q) pd.wtap[q] = -1;
-    for (int ph = 0; ph < 2; ++ph)
-      for (int pw = 0; pw < 2; ++pw)
-        for (int r = 0; r < 3; ++r)
-          for (int s = 0; s < 3; ++s) {
-            const int nh = ph + 1 - r, nw = pw + 1 - s;
-            if ((nh & 1) || (nw & 1)) continue;
-            pd.wtap[(ph * 2 + pw) * 4 + (nh / 2) * 2 + nw / 2] = r * 3 + s;
-          }
-    std::vector<ConvTap> pt(4);
-    for (int tau = 0; tau < 4; ++tau) pt[tau] = ConvTap{tau >> 1, tau & 1, tau, 0};
-    ConvTap* dt = nullptr;
-    CVX_TRY(make_taps(pt, &dt));
+  const PsDgrad ps = cvx_conv_ps_dgrad(k, stride, pad, dil, ih, iw, phases);
+  if (ps.qualifies && cout % 32 == 0 && cin % 8 == 0) {
+    DevTemps tmp;
+    const ConvTap* dt = nullptr;
+    const half_t* zeros = nullptr;
+    CVX_TRY(tmp.taps(cvx_conv_ps_window_taps(), &dt, &zeros));
     ConvParams cp;
-    memset(&cp, 0, sizeof(cp));
-    cp.in = (const half_t*)dy_f16;
-    cp.in_bstride = (long long)oh * ow * cout;
-    cp.in_ld = cout;
-    cp.IH = oh;
-    cp.IW = ow;
-    cp.Cin = cout;
-    cp.wt_ld = 4 * cout;
-    cp.Cout = 4 * cin;
-    cp.B = batch;
-    cp.OH2 = oh;
-    cp.OW2 = ow;
-    cp.IS = 1;
-    cp.OS = 2;
-    cp.OWr = iw;
-    cp.ntaps = 4;
-    cp.taps = dt;
-    cp.zeros = zeros_after(dt, pt.size());
-    cp.epi = CVX_EPI_PLAIN;
-    cp.ps_cin = cin;
-    cp.out16 = (half_t*)dx_f16;
-    cp.out_ld = cin;
-    cp.out_bstride = (long long)ih * iw * cin;
+    fill_conv_ps(g, dy, dx, nullptr, dt, zeros, 0, &cp);
     if (cvx_conv_gemm_supported(cp)) {
       half_t* psw = nullptr;
-      if (hipMalloc((void**)&psw, (size_t)16 * cin * cout * 2) != hipSuccess) {
-        (void)hipFree(dt);
-        CVX_CHECK(false, "dgrad: out of memory for the pixel-shuffle weights");
-      }
+      CVX_CHECK(tmp.alloc(&psw, (size_t)16 * cin * cout * 2) == 0, "dgrad: out of memory for the pixel-shuffle weights");
       cp.wt = psw;
-      rc = cvx_pack_ps_weights((const half_t*)wt_f16, psw, pd, st);
-      if (rc == 0) rc = cvx_conv_igemm_launch(cp, st, nullptr);
+      PsPackDesc pd{0, 0, cin, k * k, cout, {}};
+      for (int q = 0; q < 16; ++q) pd.wtap[q] = ps.wtap[q];
+      int rc = cvx_pack_ps_weights((const half_t*)wt_f16, psw, pd, st);
+      if (rc == 0) rc = cvx_conv_igemm_launch(cp, st);
       (void)hipStreamSynchronize(st);
-      (void)hipFree(psw);
-      (void)hipFree(dt);
       return rc;
     }
-    (void)hipFree(dt);
   }
-  for (int ph = 0; ph < stride && rc == 0; ++ph)
-    for (int pw = 0; pw < stride && rc == 0; ++pw) {
-      std::vector<ConvTap> taps;
-      for (int r = 0; r < k; ++r) {
-        int nh = ph + pad - r * dil;
-        if (((nh % stride) + stride) % stride) continue;
-        for (int s = 0; s < k; ++s) {
-          int nw = pw + pad - s * dil;
-          if (((nw % stride) + stride) % stride) continue;
-          taps.push_back(ConvTap{nh / stride, nw / stride, r * k + s, 0});
-        }
-      }
-      const int OH2 = (ih - ph + stride - 1) / stride, OW2 = (iw - pw + stride - 1) / stride;
-      if (OH2 <= 0 || OW2 <= 0) continue;
-      CVX_CHECK(!taps.empty(), "dgrad phase without taps");
-      ConvTap* dt = nullptr;
-      CVX_TRY(make_taps(taps, &dt));
-      ConvParams cp;
-      memset(&cp, 0, sizeof(cp));
-      cp.in = (const half_t*)dy_f16;
-      cp.in_bstride = (long long)oh * ow * cout;
-      cp.in_ld = cout;
-      cp.IH = oh;
-      cp.IW = ow;
-      cp.Cin = cout;
-      cp.wt = (const half_t*)wt_f16;
-      cp.wt_ld = k * k * cout;
-      cp.Cout = cin;
-      cp.B = batch;
-      cp.OH2 = OH2;
-      cp.OW2 = OW2;
-      cp.IS = 1;
-      cp.OS = stride;
-      cp.oph = ph;
-      cp.opw = pw;
-      cp.OWr = iw;
-      cp.ntaps = (int)taps.size();
-      cp.taps = dt;
-      cp.zeros = zeros_after(dt, taps.size());
-      cp.halo_taps_ok = cvx_halo_pack_taps(taps.data(), (int)taps.size(), &cp.halo_pos, &cp.halo_wt) ? 1 : 0;
-      cp.pointwise = cvx_taps_pointwise(taps.data(), (int)taps.size());
-      cp.epi = CVX_EPI_PLAIN;
-      cp.out16 = (half_t*)dx_f16;
-      cp.out_ld = cin;
-      cp.out_bstride = (long long)ih * iw * cin;
-      rc = cvx_conv_igemm_launch(cp, st, nullptr);
-      (void)hipStreamSynchronize(st);
-      (void)hipFree(dt);
-    }
+  // every other shape: one launch per phase class (the engine merges the classes of a strided gradient into one launch of the ring kernel)
+  int rc = 0;
+  for (size_t q = 0; q < phases.size() && rc == 0; ++q) {
+    const DgradPhase& d = phases[q];
+    if (d.OH2 <= 0 || d.OW2 <= 0) continue;
+    CVX_CHECK(!d.taps.empty(), "dgrad phase without taps");
+    DevTemps tmp;
+    const ConvTap* dt = nullptr;
+    const half_t* zeros = nullptr;
+    CVX_TRY(tmp.taps(d.taps, &dt, &zeros));
+    ConvParams cp;
+    fill_conv_dgrad(g, make_phase(d, dt), dy, dx, (const half_t*)wt_f16, zeros, 0, &cp);
+    rc = cvx_conv_igemm_launch(cp, st);
+    (void)hipStreamSynchronize(st);
+  }
   return rc;
 }
 
 extern "C" int64_t cvx_conv2d_wgrad_workspace_bytes(int32_t batch, int32_t oh, int32_t ow, int32_t cin, int32_t cout, int32_t k) {
-  const long long M = (long long)batch * oh * ow;
-  long long ns = std::min<long long>(std::max<long long>(1, M / 256), 64);
-  return ns * cout * k * k * round_up(cin, 16) * 4 + 4096;
+  return unit_wgrad_splits((long long)batch * oh * ow) * cout * k * k * round_up(cin, 16) * 4 + 4096;
 }
 
 extern "C" int cvx_conv2d_wgrad_nhwc(const void* x_f16, const void* dy_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, int32_t cout,
@@ -2727,36 +2596,16 @@ extern "C" int cvx_conv2d_wgrad_nhwc(const void* x_f16, const void* dy_f16, int3
                                      void* hip_stream) {
   CVX_CHECK(x_f16 && dy_f16 && dw && workspace && k * k <= CVX_MAX_TAPS, "bad arguments");
   hipStream_t st = (hipStream_t)hip_stream;
-  const int oh = (ih + 2 * pad - dil * (k - 1) - 1) / stride + 1, ow = (iw + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+  const int oh = cvx_conv_out_size(ih, k, stride, pad, dil), ow = cvx_conv_out_size(iw, k, stride, pad, dil);
   CVX_CHECK(workspace_bytes >= cvx_conv2d_wgrad_workspace_bytes(batch, oh, ow, cin, cout, k), "workspace too small");
-  const long long M = (long long)batch * oh * ow;
-  std::vector<ConvTap> taps;
-  for (int r = 0; r < k; ++r)
-    for (int s = 0; s < k; ++s) taps.push_back(ConvTap{r * dil - pad, s * dil - pad, r * k + s, 0});
-  ConvTap* dt = nullptr;
-  CVX_TRY(make_taps(taps, &dt));
+  const std::vector<ConvTap> taps = cvx_conv_fwd_taps(k, pad, dil);
+  DevTemps tmp;
+  const ConvTap* dt = nullptr;
+  CVX_TRY(tmp.taps(taps, &dt));
   WgradParams wp;
-  memset(&wp, 0, sizeof(wp));
-  wp.x = (const half_t*)x_f16;
-  wp.x_bstride = (long long)ih * iw * cin;
-  wp.x_ld = cin;
-  wp.IH = ih;
-  wp.IW = iw;
-  wp.Cin = cin;
-  wp.dy = (const half_t*)dy_f16;
-  wp.dy_bstride = (long long)oh * ow * cout;
-  wp.dy_ld = cout;
-  wp.Cout = cout;
-  wp.B = batch;
-  wp.OH = oh;
-  wp.OW = ow;
-  wp.stride = stride;
-  wp.ntaps = k * k;
-  wp.taps = dt;
-  wp.slabs = (float*)workspace;
-  wp.nsplit = (int)std::min<long long>(std::max<long long>(1, M / 256), 64);
-  wp.cin_pad16 = round_up(cin, 16);
-  wp.std3x3 = cvx_taps_std3x3(taps.data(), (int)taps.size());
+  fill_wgrad(ConvGeom{batch, ih, iw, cin, oh, ow, cout, stride, k * k}, dense_view(x_f16, (long long)ih * iw, cin),
+             dense_view(dy_f16, (long long)oh * ow, cout), dt, cvx_tap_traits(taps).std3x3, (float*)workspace,
+             (int)unit_wgrad_splits((long long)batch * oh * ow), &wp);
   int rc = cvx_conv_wgrad_launch(wp, st);
   if (rc == 0) {
     // reduce the slabs into dw (overwrite): zero, then the table-driven reducer with one descriptor
@@ -2767,18 +2616,14 @@ extern "C" int cvx_conv2d_wgrad_nhwc(const void* x_f16, const void* dy_f16, int3
     for (long long s0 = 0; s0 < total; s0 += 256 / sd.lanes) blocks.push_back(BlockRef{0, (int)s0});
     SlabDesc* dsd = nullptr;
     BlockRef* dbl = nullptr;
-    if (hipMalloc((void**)&dsd, sizeof(sd)) != hipSuccess || hipMalloc((void**)&dbl, blocks.size() * sizeof(BlockRef)) != hipSuccess) rc = -1;
+    if (tmp.alloc(&dsd, sizeof(sd)) != 0 || tmp.alloc(&dbl, blocks.size() * sizeof(BlockRef)) != 0) rc = -1;
     if (rc == 0) {
       (void)hipMemcpy(dsd, &sd, sizeof(sd), hipMemcpyHostToDevice);
       (void)hipMemcpy(dbl, blocks.data(), blocks.size() * sizeof(BlockRef), hipMemcpyHostToDevice);
       rc = cvx_reduce_slabs((float*)workspace, dw, 1.0f, dsd, dbl, (int)blocks.size(), st);
     }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(dsd);
-    (void)hipFree(dbl);
   }
   (void)hipStreamSynchronize(st);
-  (void)hipFree(dt);
   return rc;
 }
 
@@ -2791,30 +2636,13 @@ extern "C" int cvx_wgrad_time_unit(const void* x_f16, const void* dy_f16, int32_
                                    float* us_out, int32_t* nsplit_out, void* hip_stream) {
   CVX_CHECK(x_f16 && dy_f16 && workspace && us_out && reps >= 1 && (k == 1 || k == 3), "bad arguments");
   hipStream_t st = (hipStream_t)hip_stream;
-  std::vector<ConvTap> taps;
-  for (int r = 0; r < k; ++r)
-    for (int s = 0; s < k; ++s) taps.push_back(ConvTap{r - k / 2, s - k / 2, r * k + s, 0});
-  ConvTap* dt = nullptr;
-  CVX_TRY(make_taps(taps, &dt));
+  const std::vector<ConvTap> taps = cvx_conv_fwd_taps(k, k / 2, 1);
+  DevTemps tmp;
+  const ConvTap* dt = nullptr;
+  CVX_TRY(tmp.taps(taps, &dt));
   WgradParams wp;
-  memset(&wp, 0, sizeof(wp));
-  wp.x = (const half_t*)x_f16;
-  wp.x_bstride = (long long)h * w * x_ld;
-  wp.x_ld = x_ld;
-  wp.IH = wp.OH = h;
-  wp.IW = wp.OW = w;
-  wp.Cin = cin;
-  wp.dy = (const half_t*)dy_f16;
-  wp.dy_bstride = (long long)h * w * dy_ld;
-  wp.dy_ld = dy_ld;
-  wp.Cout = cout;
-  wp.B = batch;
-  wp.stride = 1;
-  wp.ntaps = k * k;
-  wp.taps = dt;
-  wp.slabs = (float*)workspace;
-  wp.cin_pad16 = round_up(cin, 16);
-  wp.std3x3 = cvx_taps_std3x3(taps.data(), (int)taps.size());
+  fill_wgrad(ConvGeom{batch, h, w, cin, h, w, cout, 1, k * k}, ViewDesc{(half_t*)x_f16, (long long)h * w * x_ld, x_ld},
+             ViewDesc{(half_t*)dy_f16, (long long)h * w * dy_ld, dy_ld}, dt, cvx_tap_traits(taps).std3x3, (float*)workspace, 0, &wp);
   wp.nsplit = nsplit > 0 ? nsplit : (cvx_conv_wgrad_k3_supported(wp) ? cvx_conv_wgrad_k3_nsplit(wp) : cvx_conv_wgrad_stream_supported(wp) ? cvx_conv_wgrad_stream_nsplit(wp) : 1);
   if (nsplit_out) *nsplit_out = wp.nsplit;
   int rc = 0;
@@ -2836,7 +2664,6 @@ extern "C" int cvx_wgrad_time_unit(const void* x_f16, const void* dy_f16, int32_
   (void)hipStreamSynchronize(st);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(dt);
   return rc;
 }
 #endif
