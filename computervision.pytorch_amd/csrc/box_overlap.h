@@ -1,0 +1,33 @@
+// The overlap arithmetic the suite pins bit for bit, shared by the NMS (nms.hip) and the tile merge (tiles.hip): plain operators with
+// contraction switched off in each helper, every operation rounded on its own (the pragma does not reach into the _rn intrinsics' own
+// bodies, so they are not used here).  Each translation unit gets its own copy (anonymous namespace).
+#pragma once
+#include "cvx_common.h"
+
+namespace {
+
+__device__ __forceinline__ float box_area(const float4& b) {
+#pragma clang fp contract(off)
+  return (b.z - b.x) * (b.w - b.y);
+}
+// fp32 IoU exactly as torchvision's nms_kernel / oracle.nms_ref.greedy_nms_per_class
+__device__ __forceinline__ bool iou_gt(const float4& a, float area_a, const float4& b, float area_b, float thr) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
+  const float h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+  const float inter = w * h;
+  const float sum = area_a + area_b;
+  const float ovr = inter / (sum - inter);
+  return ovr > thr;
+}
+// intersection over the smaller box, the same `inter`: a box cut by a tile border lies inside the whole box of the neighbouring tile
+__device__ __forceinline__ bool ios_gt(const float4& a, float area_a, const float4& b, float area_b, float thr) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
+  const float h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+  const float inter = w * h;
+  const float ovr = inter / fminf(area_a, area_b);
+  return ovr > thr;
+}
+
+}  // namespace

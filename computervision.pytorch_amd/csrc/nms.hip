@@ -18,6 +18,7 @@
 // (<= 16384 candidates = 128 KB of the CU's 160 KB LDS), the suppression matrix is built as 64-bit
 // row masks in HBM by all 16 waves, and one wave walks it.
 #include <cstring>
+#include "box_overlap.h"
 #include "cvx_common.h"
 #include "../../include/cvx_engine.h"
 
@@ -162,20 +163,7 @@ __device__ __forceinline__ float4 class_shift(const float4& bx, int cls, float u
   const float off = (float)cls * unit;
   return make_float4(bx.x + off, bx.y + off, bx.z + off, bx.w + off);
 }
-__device__ __forceinline__ float box_area(const float4& b) {
-#pragma clang fp contract(off)
-  return (b.z - b.x) * (b.w - b.y);
-}
-// fp32 IoU exactly as torchvision's nms_kernel / oracle.nms_ref.greedy_nms_per_class
-__device__ __forceinline__ bool iou_gt(const float4& a, float area_a, const float4& b, float area_b, float thr) {
-#pragma clang fp contract(off)
-  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
-  const float h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
-  const float inter = w * h;
-  const float sum = area_a + area_b;
-  const float ovr = inter / (sum - inter);
-  return ovr > thr;
-}
+// box_area / iou_gt: box_overlap.h, shared with the tile merge
 
 struct NmsWs {
   float4* box;              // [B][cap] sorted boxes (xyxy)

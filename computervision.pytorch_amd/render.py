@@ -4,6 +4,10 @@ without a read-back (``cvx_det_to_image``), and the result is painted into the f
 ``cvx_seg_overlay``; csrc/render.hip).  ``FrameBatch`` puts every job table of a batch into ONE pinned blob and one asynchronous copy, so
 none of this waits on the host.  There is no CPU path: frames that are not in GPU memory raise ``CvxError``.
 
+Tiled prediction for frames much larger than the network input (csrc/tiles.hip): ``tile_grid`` is the host geometry,
+``TileBatch`` the ``FrameBatch`` idea for tiles (``cvx_tiles_u8_to_nchw`` crops every tile of every frame into the batch in one launch), and
+``merge_tiles`` suppresses the duplicates across tile borders (``cvx_det_merge_tiles``, one workgroup per frame).
+
 ``palette``, ``format_label`` and ``FONT`` are the host statement of the drawing rules, shared with the tests'
 restatement (tests/render_restatement.py)."""
 from __future__ import annotations
@@ -190,6 +194,185 @@ def det_to_image(rows: torch.Tensor, counts: torch.Tensor, box_map: Optional[tor
     return out_rows, out_counts, overflow
 
 
+# ---- tiled prediction for large frames (csrc/tiles.hip) --------------------------------------------------------------
+TILE_JOB_DTYPE = np.dtype([("src", "<u8"), ("h", "<i4"), ("w", "<i4"), ("stride", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("th", "<i4"), ("tw", "<i4"),
+                           ("out", "<i4")])
+assert TILE_JOB_DTYPE.itemsize == 40                 # struct cvx_tile_job, include/cvx_engine.h
+MERGE_CAP = 8192                                     # candidates per frame cvx_det_merge_tiles sorts
+MERGE_METRICS = {"iou": 0, "ios": 1}
+
+
+def _axis_tiles(n, T, stride):
+    if n <= T:
+        return [(0, n)]
+    starts, s = [], 0
+    while s + T < n:
+        starts.append(s)
+        s += stride
+    if not starts or starts[-1] != n - T:
+        starts.append(n - T)                         # the last tile is shifted back inside the frame, never padded
+    return [(s, T) for s in starts]
+
+
+def tile_grid(h, w, tile_hw, overlap):
+    """The tiles of an (h, w) frame at tile size ``tile_hw = (TH, TW)``, row-major, as ``(y0, x0, th, tw)``.  Per axis the stride is
+    ``T - int(T * overlap)``; an axis no longer than the tile has one tile of its own extent at 0, a longer one has tiles at 0, stride,
+    2 * stride, ... while ``start + T < n`` and a last one at ``n - T``.  Every tile lies inside the frame and their union covers it."""
+    h, w, TH, TW = int(h), int(w), int(tile_hw[0]), int(tile_hw[1])
+    if h <= 0 or w <= 0 or TH <= 0 or TW <= 0:
+        raise ValueError("tile_grid: sizes are positive")
+    if not 0 <= overlap < 1:
+        raise ValueError(f"tile_grid: overlap {overlap} outside [0, 1)")
+    sy, sx = TH - int(TH * overlap), TW - int(TW * overlap)
+    if sy < 1 or sx < 1:
+        raise ValueError(f"tile_grid: overlap {overlap} leaves no stride at tile size {(TH, TW)}")
+    return [(y0, x0, th, tw) for y0, th in _axis_tiles(h, TH, sy) for x0, tw in _axis_tiles(w, TW, sx)]
+
+
+class TileBatch:
+    """``FrameBatch`` for tiles: every table of one batch of large frames in device memory, from one pinned blob and one asynchronous copy.
+    Frame f contributes the slots of ``tile_grid(h, w, input_hw, tile_overlap)`` and, with ``full_frame``, one more slot after them that
+    holds the whole picture at network size (letterboxed, or stretched when ``letterbox`` is false -- the input ``predict_batch`` builds).
+    ``tile_jobs`` (``cvx_tile_job`` rows, slot order), ``slot_map`` (slots, 4) int32 [frame, x0, y0, 0], ``frame_hw`` (n, 2) int32,
+    ``image_hw`` (slots, 2) int32 -- ``input_hw`` for a tile slot, so the class's own box map is the identity there, and the frame's size
+    for a full-frame slot -- and ``frame_jobs`` for the painters.  ``tiles[f]`` is the frame's grid, ``slot_frame`` the frame of each slot."""
+
+    def __init__(self, frames: Sequence[torch.Tensor], input_hw, tile_overlap: float = 0.2, full_frame: bool = True, letterbox: bool = True):
+        self.device = _check_frames(frames)
+        self.frames = list(frames)
+        F = self.n = len(frames)
+        H, W = int(input_hw[0]), int(input_hw[1])
+        self.input_hw, self.letterbox, self.full_frame = (H, W), bool(letterbox), bool(full_frame)
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in frames]
+        self.max_h, self.max_w = max(h for h, _ in sizes), max(w for _, w in sizes)
+        self.tiles = [tile_grid(h, w, (H, W), tile_overlap) for h, w in sizes]
+        tile_jobs, slot_map, image_hw, self.slot_frame, full_slots = [], [], [], [], []
+        for f, (t, (h, w)) in enumerate(zip(frames, sizes)):
+            for y0, x0, th, tw in self.tiles[f]:
+                tile_jobs.append((t.data_ptr(), h, w, t.stride(0), y0, x0, th, tw, len(slot_map)))
+                slot_map.append((f, x0, y0, 0))
+                image_hw.append((H, W))
+            if full_frame:
+                full_slots.append(len(slot_map))
+                slot_map.append((f, 0, 0, 0))
+                image_hw.append((h, w))
+            self.slot_frame += [f] * (len(slot_map) - len(self.slot_frame))
+        T, S = self.n_tiles, self.slots = len(tile_jobs), len(slot_map)
+        # the whole-picture path reads tightly packed pictures; a frame with padded rows is copied on the device (no host wait)
+        self.sources = [t if t.is_contiguous() else t.contiguous() for t in frames] if full_frame else []
+        o_frame = 0
+        o_fhw = _align(o_frame + 24 * F)
+        o_tile = _align(o_fhw + 8 * F)
+        o_map = _align(o_tile + 40 * T)
+        o_hw = _align(o_map + 16 * S)
+        o_in = _align(o_hw + 8 * S)
+        o_js = _align(o_in + (24 if letterbox else 64) * F)
+        o_full = _align(o_js + 4 * (F + 1))
+        total = _align(o_full + 8 * F)
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        hv = host.numpy()
+        hv[:] = 0
+        hv[o_frame:o_frame + 24 * F].view(FRAME_JOB_DTYPE)[:] = np.array([(t.data_ptr(), h, w, t.stride(0), 0) for t, (h, w) in zip(frames, sizes)],
+                                                                           dtype=FRAME_JOB_DTYPE)
+        hv[o_fhw:o_fhw + 8 * F].view(np.int32).reshape(F, 2)[:] = sizes
+        hv[o_tile:o_tile + 40 * T].view(TILE_JOB_DTYPE)[:] = np.array(tile_jobs, dtype=TILE_JOB_DTYPE)
+        hv[o_map:o_map + 16 * S].view(np.int32).reshape(S, 4)[:] = slot_map
+        hv[o_hw:o_hw + 8 * S].view(np.int32).reshape(S, 2)[:] = image_hw
+        if full_frame:
+            if letterbox:
+                from .engine import letterbox_geometry
+                for h, w in sizes:
+                    letterbox_geometry(h, w, H, W)            # raises CvxError where a picture collapses to nothing, as the per-image entry does
+                hv[o_in:o_in + 24 * F].view(LETTERBOX_JOB_DTYPE)[:] = np.array(
+                    [(s.data_ptr(), h, w, slot, 0) for slot, s, (h, w) in zip(full_slots, self.sources, sizes)], dtype=LETTERBOX_JOB_DTYPE)
+            else:                                             # FrameBatch's stretch jobs: they fill a batch of their own, moved to the slots after
+                hv[o_in:o_in + 64 * F].view(AUG_JOB_DTYPE)[:] = np.array(
+                    [(s.data_ptr(), h, w, H, W, 0, 0, 0, i, 0, 0, W, H, -1, 0) for i, (s, (h, w)) in enumerate(zip(self.sources, sizes))],
+                    dtype=AUG_JOB_DTYPE)
+                hv[o_js:o_js + 4 * (F + 1)].view(np.int32)[:] = np.arange(F + 1)
+            hv[o_full:o_full + 8 * F].view(np.int64)[:] = full_slots
+        self.blob = torch.empty(total, dtype=torch.uint8, device=self.device)
+        self.blob.copy_(host, non_blocking=True)
+        self._host = host                                     # alive until the copy has run
+        base = self.blob.data_ptr()
+        P = L.C.c_void_p
+        self.frame_jobs, self.tile_jobs, self.input_jobs, self.job_start = P(base + o_frame), P(base + o_tile), P(base + o_in), P(base + o_js)
+        self.frame_hw = self.blob[o_fhw:o_fhw + 8 * F].view(torch.int32).view(F, 2)
+        self.slot_map = self.blob[o_map:o_map + 16 * S].view(torch.int32).view(S, 4)
+        self.image_hw = self.blob[o_hw:o_hw + 8 * S].view(torch.int32).view(S, 2)
+        self.full_slots = self.blob[o_full:o_full + 8 * F].view(torch.int64) if full_frame else None
+
+    def network_input(self, swap_rb: bool = False) -> torch.Tensor:
+        """The (slots, 3, H, W) fp32 batch in [0, 1]: one ``cvx_tiles_u8_to_nchw`` launch for every tile of every frame and, with
+        ``full_frame``, the whole-picture launch of ``FrameBatch.network_input`` for the frames' own slots."""
+        H, W = self.input_hw
+        out = torch.empty(self.slots, 3, H, W, dtype=torch.float32, device=self.device)
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            stream = L.stream_ptr(self.device)
+            L.check(lib.cvx_tiles_u8_to_nchw(self.tile_jobs, self.n_tiles, int(bool(swap_rb)), L.ptr(out), H, W, stream), "cvx_tiles_u8_to_nchw")
+            if self.full_frame and self.letterbox:
+                L.check(lib.cvx_letterbox_batch_u8_to_nchw(self.input_jobs, self.n, 1, int(bool(swap_rb)), L.ptr(out), H, W, stream),
+                        "cvx_letterbox_batch_u8_to_nchw")
+            elif self.full_frame:
+                if swap_rb:
+                    raise L.CvxError("the bicubic stretch keeps the channel order: pass RGB frames")
+                whole = torch.empty(self.n, 3, H, W, dtype=torch.float32, device=self.device)
+                L.check(lib.cvx_aug_images_plain(self.input_jobs, self.job_start, self.n, L.ptr(whole), H, W, stream), "cvx_aug_images_plain")
+                out.index_copy_(0, self.full_slots, whole)
+        return out
+
+
+_merge_ws = {}
+
+
+def merge_tiles(rows: torch.Tensor, counts: torch.Tensor, slot_map: torch.Tensor, frame_hw: torch.Tensor, metric: str = "ios",
+                threshold: float = 0.5, class_agnostic: bool = False, max_det: int = 300, overflow: Optional[torch.Tensor] = None):
+    """``cvx_det_merge_tiles``: rows (slots, K, 6) fp32 and counts (slots) int32 as ``det_to_image`` leaves them, boxes in each slot's own
+    pixels; ``slot_map`` (slots, 4) int32 [frame, x0, y0, 0] and ``frame_hw`` (frames, 2) int32 on the same device.  Per frame the rows of
+    its slots are moved to frame coordinates, clamped to the frame, ordered by (score, ordinal) and suppressed greedily: a candidate goes
+    when an earlier kept one (of its class, unless ``class_agnostic``) overlaps it by more than ``threshold`` in ``metric`` -- ``"iou"`` or
+    ``"ios"``, intersection over the smaller box, which removes the part-boxes tile borders cut.  Returns (rows (frames, max_det, 6), counts
+    (frames) int32, source (frames, max_det) int32 -- slot * K + row of each kept row, -1 past the count --, the overflow word (1) int32,
+    added to when given).  A frame with more than ``MERGE_CAP`` candidates has count -1 and adds 1 to the overflow word.  No host read."""
+    if not (torch.is_tensor(rows) and rows.is_cuda):
+        raise L.CvxError("merge_tiles runs on an MI355X only: there is no CPU path")
+    if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or rows.shape[0] <= 0 or rows.shape[1] <= 0:
+        raise ValueError(f"rows: (slots, K, 6) float32, got {tuple(rows.shape)} {rows.dtype}")
+    S, K = int(rows.shape[0]), int(rows.shape[1])
+    if S * K >= 2 ** 31:
+        raise ValueError("rows: slots * K must stay below 2^31 (the ordinal is 32 bits)")
+    if counts.dtype != torch.int32 or counts.numel() != S or counts.device != rows.device:
+        raise ValueError("counts: (slots) int32 on the rows' device")
+    if slot_map.dtype != torch.int32 or tuple(slot_map.shape) != (S, 4) or slot_map.device != rows.device:
+        raise ValueError("slot_map: (slots, 4) int32 [frame, x0, y0, 0] on the rows' device")
+    if frame_hw.dtype != torch.int32 or frame_hw.dim() != 2 or frame_hw.shape[1] != 2 or frame_hw.shape[0] <= 0 or frame_hw.device != rows.device:
+        raise ValueError("frame_hw: (frames, 2) int32 on the rows' device")
+    if metric not in MERGE_METRICS:
+        raise ValueError(f"metric: one of {sorted(MERGE_METRICS)}, got {metric!r}")
+    if not 0.0 <= float(threshold) <= 1.0:
+        raise ValueError("threshold lies in [0, 1]")
+    if not 1 <= int(max_det) <= MERGE_CAP:
+        raise ValueError(f"max_det lies in [1, {MERGE_CAP}]")
+    F = int(frame_hw.shape[0])
+    rows, counts, slot_map, frame_hw = rows.contiguous(), counts.contiguous(), slot_map.contiguous(), frame_hw.contiguous()
+    out_rows = torch.empty(F, int(max_det), 6, dtype=torch.float32, device=rows.device)
+    out_counts = torch.empty(F, dtype=torch.int32, device=rows.device)
+    out_source = torch.empty(F, int(max_det), dtype=torch.int32, device=rows.device)
+    if overflow is None:
+        overflow = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    lib = L.load()
+    need = int(lib.cvx_det_merge_workspace_bytes(F))
+    ws = _merge_ws.get(rows.device)
+    if ws is None or ws.numel() < need:
+        ws = _merge_ws[rows.device] = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    with torch.cuda.device(rows.device):
+        L.check(lib.cvx_det_merge_tiles(L.ptr(rows), L.ptr(counts), S, K, L.ptr(slot_map), L.ptr(frame_hw), F, MERGE_METRICS[metric], float(threshold),
+                                        int(bool(class_agnostic)), int(max_det), L.ptr(out_rows), L.ptr(out_counts), L.ptr(out_source),
+                                        L.ptr(overflow), L.ptr(ws), ws.numel(), L.stream_ptr(rows.device)), "cvx_det_merge_tiles")
+    return out_rows, out_counts, out_source, overflow
+
+
 _lut_cache = {}
 
 
@@ -248,6 +431,6 @@ def read_detections(rows: torch.Tensor, counts: torch.Tensor, overflow: torch.Te
     r = flat[:B * K * 6].reshape(B, K, 6)
     tail = flat[B * K * 6:].view(np.int32)
     if int(tail[B]):
-        raise L.CvxError(f"predict_batch: {int(tail[B])} image(s) dropped: an NMS count of -1 (more candidates than cvx_nms sorts) or a count "
-                         "past its block; raise the confidence threshold")
+        raise L.CvxError(f"predict_batch: {int(tail[B])} image(s) dropped: an NMS count of -1 (more candidates than cvx_nms sorts), a count "
+                         f"past its block or, tiled, a frame with more than {MERGE_CAP} candidates; raise the confidence threshold")
     return [(r[b, :n, :4].copy(), r[b, :n, 4].copy(), r[b, :n, 5].astype(np.int64)) for b, n in enumerate(int(v) for v in tail[:B])]

@@ -35,24 +35,36 @@ class FramePredictor:
         if torch.device(self.device).type != "cuda":
             raise L.CvxError(f"{what} runs on an MI355X only (device {self.device}): there is no CPU path")
 
-    def detect_frames(self, model, frames, batch_size):
+    def detect_frames(self, model, frames, batch_size, tiled=None):
         """Generator over any iterable of uint8 HWC RGB device frames: yields the list of drawn frames of each batch of ``batch_size`` (the
         last one may be short).  Each batch is one ``predict_batch(..., draw=True, sync=False)``: nothing inside the loop waits on the
-        host, so the caller synchronises (or reads a frame) when it needs the pixels."""
+        host, so the caller synchronises (or reads a frame) when it needs the pixels.  ``tiled``: a dict of ``predict_tiled`` keywords
+        (the four detectors) -- each batch is then one ``predict_tiled(..., draw=True, sync=False, **tiled)``."""
         self._need_gpu("detect_frames")
         if int(batch_size) <= 0:
             raise ValueError("batch_size is positive")
+        if tiled is None:
+            predict = self.predict_batch
+        else:
+            if not hasattr(self, "predict_tiled"):
+                raise L.CvxError(f"{type(self).__name__} has no tiled prediction")
+            tiled = dict(tiled)
+            if {"draw", "sync"} & set(tiled):
+                raise ValueError("detect_frames draws and does not wait: tiled= takes neither draw nor sync")
+
+            def predict(model, batch, draw, sync):
+                return self.predict_tiled(model, batch, draw=draw, sync=sync, **tiled)
 
         def batches():
             batch = []
             for frame in frames:
                 batch.append(frame)
                 if len(batch) == int(batch_size):
-                    self.predict_batch(model, batch, draw=True, sync=False)
+                    predict(model, batch, draw=True, sync=False)
                     yield batch
                     batch = []
             if batch:
-                self.predict_batch(model, batch, draw=True, sync=False)
+                predict(model, batch, draw=True, sync=False)
                 yield batch
 
         return batches()
@@ -84,6 +96,49 @@ class Detector(FramePredictor):
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
         rows, counts, box_map = self._evaluation_rows(model)(batch.network_input(), {"image_hw": batch.image_hw}, conf)
         rows, counts, overflow = render.det_to_image(rows, counts, box_map)
+        if draw:
+            render.draw_detections(frames, rows, counts, batch=batch)
+        if sync:
+            return render.read_detections(rows, counts, overflow)
+        return rows, counts
+
+    def predict_tiled(self, model, frames, overlap=0.2, full_frame=True, match="ios", match_threshold=0.5, class_agnostic=False, max_det=300,
+                      conf_threshold=None, batch_size=32, draw=False, sync=True):
+        """``predict_batch`` for frames much larger than the network input, where shrinking the whole picture loses the small objects: every
+        frame is cut into tiles of the network's input size that overlap by ``overlap`` (``render.tile_grid``; no resampling, zoom 1), with
+        ``full_frame`` one more slot per frame holds the whole picture as ``predict_batch`` would feed it, and one ``cvx_tiles_u8_to_nchw``
+        launch builds all slots.  The slots run through the class's own tail (``_evaluation_rows`` at ``conf_threshold``) in chunks of
+        ``batch_size`` and through ``cvx_det_to_image``; the chunks are padded to one row block on the device, and one
+        ``cvx_det_merge_tiles`` launch moves every row to frame coordinates and suppresses the duplicates across tile borders (``match``:
+        ``"ios"`` intersection over the smaller box, or ``"iou"``; above ``match_threshold``; inside a class unless ``class_agnostic``;
+        at most ``max_det`` rows per frame).  ``draw`` and ``sync`` as in ``predict_batch``: returns ``(rows (frames, max_det, 6), counts
+        (frames) int32)`` on the device, or with ``sync=True`` the list of ``(boxes, scores, classes)`` triples from one host read, which
+        raises ``CvxError`` when a slot overflowed its NMS or a frame has more than 8192 candidates."""
+        import torch
+        from computervision.pytorch_amd import render
+        self._need_gpu("predict_tiled")
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size is positive")
+        frames = list(frames)
+        input_hw, letterbox = self._predict_input()
+        batch = render.TileBatch(frames, input_hw, overlap, full_frame, letterbox)
+        model.eval()
+        conf = self.conf_threshold if conf_threshold is None else conf_threshold
+        rows_of = self._evaluation_rows(model)
+        x = batch.network_input()
+        parts, overflow = [], None
+        for c0 in range(0, batch.slots, int(batch_size)):
+            c1 = min(c0 + int(batch_size), batch.slots)
+            rows, counts, box_map = rows_of(x[c0:c1], {"image_hw": batch.image_hw[c0:c1]}, conf)
+            rows, counts, overflow = render.det_to_image(rows, counts, box_map, overflow)
+            parts.append((c0, c1, rows, counts))
+        K = max(int(p[2].shape[1]) for p in parts)              # the tails' row blocks may differ in size: one block, the rest zero
+        slot_rows = torch.zeros(batch.slots, K, 6, dtype=torch.float32, device=batch.device)
+        for c0, c1, rows, _ in parts:
+            slot_rows[c0:c1, :rows.shape[1]] = rows
+        slot_counts = torch.cat([p[3] for p in parts])
+        rows, counts, _, overflow = render.merge_tiles(slot_rows, slot_counts, batch.slot_map, batch.frame_hw, match, match_threshold, class_agnostic,
+                                                       max_det, overflow)
         if draw:
             render.draw_detections(frames, rows, counts, batch=batch)
         if sync:

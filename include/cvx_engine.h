@@ -755,6 +755,41 @@ int cvx_draw_detections(const cvx_frame_job* jobs, int32_t batch, int32_t max_h,
 int cvx_seg_overlay(const cvx_frame_job* jobs, int32_t batch, int32_t max_h, int32_t max_w, const float* logits_rows, int32_t ld, int32_t nc, int32_t lh,
                     int32_t lw, int32_t net_h, int32_t net_w, const uint8_t* lut, int32_t bgr_out, void* hip_stream);
 
+/* ---- tiled prediction for large frames (csrc/tiles.hip) -----------------------------------------------------------
+ * A frame larger than the network input is cut into overlapping tiles at network size (zoom 1), the tiles run as one batch, and the rows
+ * of all tiles of a frame are merged across the tile borders.  Both entries are one launch, asynchronous on hip_stream, with their tables
+ * in device memory, and read nothing back.  The reference predicts one letterboxed image at a time and has no counterpart: the rules are
+ * the project's own, restated in numpy in tests/tiled_restatement.py.  40 bytes per job. */
+typedef struct cvx_tile_job {
+  const uint8_t* src;
+  int32_t h, w, stride, y0, x0, th, tw, out;
+} cvx_tile_job;
+/* Slot `out` of out_nchw (slots, 3, H, W) fp32 receives the crop [y0, y0 + th) x [x0, x0 + tw) of the uint8 HWC frame `src` (h x w, row
+ * pitch `stride` bytes: padded rows are read in place), anchored top-left.  Each value is (float)byte / 255.0f, a true fp32 division as in
+ * cvx_letterbox_u8_to_nchw; everything outside the crop, and any pixel a bad job would read outside the frame, is 128.0f / 255.0f.
+ * swap_rb != 0 swaps the first and third channel.  No resampling.  Any positive H, W; 16-byte stores where W % 4 == 0. */
+int cvx_tiles_u8_to_nchw(const cvx_tile_job* jobs, int32_t n_jobs, int32_t swap_rb, float* out_nchw, int32_t H, int32_t W, void* hip_stream);
+/* Greedy suppression across the slots of each frame, one workgroup per frame.  rows (slots, max_det_in, 6) fp32 [x1, y1, x2, y2, score,
+ * cls] and counts (slots) int32 as cvx_det_to_image leaves them: boxes in the slot's own pixels.  slot_map (slots, 4) int32 [frame, x0,
+ * y0, reserved], frame_hw (frames, 2) int32 [h, w].  Per frame f:
+ *   candidates  the rows r < counts[s] of every slot with slot_map[s].frame == f; ordinal s * max_det_in + r.  A count below 0 or above
+ *               max_det_in contributes nothing and adds 1 to *overflow (1 int32, device, cleared by the caller).
+ *   boxes       x + (float)x0, y + (float)y0 -- one fp32 add -- then fminf(fmaxf(v, 0), w or h); score and class are copied.
+ *   order       score descending, then ordinal ascending (the 64-bit key of cvx_nms, the ordinal in the low word).
+ *   greedy      candidate i is dropped when an earlier kept j, of the same class unless class_agnostic, has metric(i, j) > threshold.
+ *               metric 0: inter / (area_i + area_j - inter), cvx_nms's IoU to the bit; metric 1 (IoS): inter / fminf(area_i, area_j).
+ *               fp32, every operation rounded on its own; a NaN (0 / 0 of a degenerate box) never suppresses.  Stops at max_det_out kept.
+ *   outputs     out_rows (frames, max_det_out, 6) the kept rows in order, the rest zero; out_counts (frames); out_source (frames,
+ *               max_det_out) the ordinal of each kept row, -1 past the count.
+ *   capacity    8192 candidates per frame: beyond it out_counts[f] = -1, the frame's rows are zero and *overflow grows by 1 -- flagged,
+ *               never truncated.
+ * workspace: cvx_det_merge_workspace_bytes(frames) bytes of device memory (8 MB of suppression masks per frame). */
+int64_t cvx_det_merge_workspace_bytes(int32_t frames);
+int cvx_det_merge_tiles(const float* rows, const int32_t* counts, int32_t slots, int32_t max_det_in, const int32_t* slot_map,
+                        const int32_t* frame_hw, int32_t frames, int32_t metric, float threshold, int32_t class_agnostic, int32_t max_det_out,
+                        float* out_rows, int32_t* out_counts, int32_t* out_source, int32_t* overflow, void* workspace, int64_t workspace_bytes,
+                        void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 

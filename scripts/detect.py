@@ -7,17 +7,18 @@ import torch
 from computervision.pytorch_amd._lib import CvxError
 
 
-def detect_frames(algorithm, model, frames, batch_size):
+def detect_frames(algorithm, model, frames, batch_size, tiled=None):
     """Generator over any iterable of uint8 HWC RGB device frames: yields the drawn frames (the same tensors, painted in place) as one list
     per batch of ``batch_size``.  ``algorithm`` is one of the five algorithm objects; each batch is its ``predict_batch(..., draw=True,
-    sync=False)``, so the loop never waits on the host."""
-    return algorithm.detect_frames(model, frames, batch_size)
+    sync=False)``, so the loop never waits on the host.  ``tiled``: a dict of ``predict_tiled`` keywords for footage much larger than the
+    network input (the four detectors): each batch is then cut into tiles, detected and merged on the device."""
+    return algorithm.detect_frames(model, frames, batch_size, tiled=tiled)
 
 
-def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8):
+def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8, tiled=None):
     """The reference's signature: ``decode_fn`` is the bound ``predict`` of an algorithm object (as the reference passes it) or the algorithm
     object itself.  Reads ``src_video_path`` frame by frame, draws the predictions on the device and writes ``dst_video_path`` with the
-    source's frame rate and size."""
+    source's frame rate and size.  ``tiled`` as in ``detect_frames``."""
     algorithm = getattr(decode_fn, "__self__", decode_fn)
     if not hasattr(algorithm, "predict_batch"):
         raise CvxError("detect_video: decode_fn is an algorithm object or its bound predict method")
@@ -42,7 +43,7 @@ def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8)
             yield torch.from_numpy(cv2.cvtColor(bgr, cv2.COLOR_BGR2RGB)).to(device, non_blocking=True)
 
     try:
-        for batch in detect_frames(algorithm, model, decoded(), batch_size):
+        for batch in detect_frames(algorithm, model, decoded(), batch_size, tiled=tiled):
             for frame in batch:                                   # the host read of a finished batch: the only wait
                 writer.write(cv2.cvtColor(frame.cpu().numpy(), cv2.COLOR_RGB2BGR))
     finally:
