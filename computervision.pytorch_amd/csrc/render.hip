@@ -19,6 +19,7 @@
 // Every fp32 step is one rounded operation, so the file is compiled with contraction off (bilinear.h spells its fused steps out).
 #include "bilinear.h"
 #include "det_common.h"
+#include "pixel_blend.h"
 #include "../../include/cvx_engine.h"
 
 #pragma clang fp contract(off)
@@ -230,11 +231,6 @@ __global__ __launch_bounds__(256) void draw_kernel(const cvx_frame_job* __restri
 }
 
 // ---- segmentation overlay -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned blend_half(unsigned a, unsigned b) {  // (a + b) / 2, ties to even
-  const unsigned s = a + b;
-  return (s >> 1) + (s & (s >> 1) & 1u);
-}
-
 __global__ __launch_bounds__(256) void seg_overlay_kernel(const cvx_frame_job* __restrict__ jobs, const float* __restrict__ logits, int ld, int nc,
                                                           int lh, int lw, int NH, int NW, const uint8_t* __restrict__ lut, int bgr_out) {
   const cvx_frame_job jb = jobs[blockIdx.z];

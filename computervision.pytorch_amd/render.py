@@ -6,7 +6,9 @@ none of this waits on the host.  There is no CPU path: frames that are not in GP
 
 Tiled prediction for frames much larger than the network input (csrc/tiles.hip): ``tile_grid`` is the host geometry,
 ``TileBatch`` the ``FrameBatch`` idea for tiles (``cvx_tiles_u8_to_nchw`` crops every tile of every frame into the batch in one launch), and
-``merge_tiles`` suppresses the duplicates across tile borders (``cvx_det_merge_tiles``, one workgroup per frame).
+``merge_tiles`` suppresses the duplicates across tile borders (``cvx_det_merge_tiles``, one workgroup per frame).  For segmentation the tiles'
+logits are stitched instead (csrc/seg_tiles.hip): ``stitch_segmentation`` blends the up-sampled logits of every tile
+that covers a pixel and writes the label, the overlay and the confusion counts in one ``cvx_seg_stitch`` launch.
 
 ``palette``, ``format_label`` and ``FONT`` are the host statement of the drawing rules, shared with the tests'
 restatement (tests/render_restatement.py)."""
@@ -198,6 +200,9 @@ def det_to_image(rows: torch.Tensor, counts: torch.Tensor, box_map: Optional[tor
 TILE_JOB_DTYPE = np.dtype([("src", "<u8"), ("h", "<i4"), ("w", "<i4"), ("stride", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("th", "<i4"), ("tw", "<i4"),
                            ("out", "<i4")])
 assert TILE_JOB_DTYPE.itemsize == 40                 # struct cvx_tile_job, include/cvx_engine.h
+SEG_TILE_FRAME_DTYPE = np.dtype([("first_slot", "<i4"), ("ny", "<i4"), ("nx", "<i4"), ("y_off", "<i4"), ("x_off", "<i4"), ("reserved", "<i4")])
+SEG_MAP_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<i4"), ("reserved", "<i4")])
+assert SEG_TILE_FRAME_DTYPE.itemsize == 24 and SEG_MAP_DTYPE.itemsize == 16      # struct cvx_seg_tile_frame / cvx_seg_map, include/cvx_engine.h
 MERGE_CAP = 8192                                     # candidates per frame cvx_det_merge_tiles sorts
 MERGE_METRICS = {"iou": 0, "ios": 1}
 
@@ -235,7 +240,9 @@ class TileBatch:
     holds the whole picture at network size (letterboxed, or stretched when ``letterbox`` is false -- the input ``predict_batch`` builds).
     ``tile_jobs`` (``cvx_tile_job`` rows, slot order), ``slot_map`` (slots, 4) int32 [frame, x0, y0, 0], ``frame_hw`` (n, 2) int32,
     ``image_hw`` (slots, 2) int32 -- ``input_hw`` for a tile slot, so the class's own box map is the identity there, and the frame's size
-    for a full-frame slot -- and ``frame_jobs`` for the painters.  ``tiles[f]`` is the frame's grid, ``slot_frame`` the frame of each slot."""
+    for a full-frame slot -- and ``frame_jobs`` for the painters.  ``tiles[f]`` is the frame's grid, ``slot_frame`` the frame of each slot.
+    ``seg_frames`` (``cvx_seg_tile_frame`` rows) and ``seg_axes`` (``n_axes`` int32: the per-axis tile starts and extents) are the grid as
+    ``cvx_seg_stitch`` reads it; they lie at the blob's end."""
 
     def __init__(self, frames: Sequence[torch.Tensor], input_hw, tile_overlap: float = 0.2, full_frame: bool = True, letterbox: bool = True):
         self.device = _check_frames(frames)
@@ -268,7 +275,18 @@ class TileBatch:
         o_in = _align(o_hw + 8 * S)
         o_js = _align(o_in + (24 if letterbox else 64) * F)
         o_full = _align(o_js + 4 * (F + 1))
-        total = _align(o_full + 8 * F)
+        # the stitch's view of the grid (cvx_seg_tile_frame): a frame's tiles are the product of its y tiles and its x tiles
+        seg_frames, axes, first = [], [], 0
+        for f, grid in enumerate(self.tiles):
+            ys, xs = sorted({(y0, th) for y0, _, th, _ in grid}), sorted({(x0, tw) for _, x0, _, tw in grid})
+            assert [(y0, x0, th, tw) for y0, th in ys for x0, tw in xs] == grid
+            seg_frames.append((first, len(ys), len(xs), len(axes), len(axes) + 2 * len(ys), 0))
+            axes += [v for pair in ys + xs for v in pair]
+            first += len(grid) + (1 if full_frame else 0)
+        A = self.n_axes = len(axes)
+        o_seg = _align(o_full + 8 * F)
+        o_axes = _align(o_seg + 24 * F)
+        total = _align(o_axes + 4 * A)
         host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
         hv[:] = 0
@@ -291,6 +309,8 @@ class TileBatch:
                     dtype=AUG_JOB_DTYPE)
                 hv[o_js:o_js + 4 * (F + 1)].view(np.int32)[:] = np.arange(F + 1)
             hv[o_full:o_full + 8 * F].view(np.int64)[:] = full_slots
+        hv[o_seg:o_seg + 24 * F].view(SEG_TILE_FRAME_DTYPE)[:] = np.array(seg_frames, dtype=SEG_TILE_FRAME_DTYPE)
+        hv[o_axes:o_axes + 4 * A].view(np.int32)[:] = axes
         self.blob = torch.empty(total, dtype=torch.uint8, device=self.device)
         self.blob.copy_(host, non_blocking=True)
         self._host = host                                     # alive until the copy has run
@@ -301,6 +321,7 @@ class TileBatch:
         self.slot_map = self.blob[o_map:o_map + 16 * S].view(torch.int32).view(S, 4)
         self.image_hw = self.blob[o_hw:o_hw + 8 * S].view(torch.int32).view(S, 2)
         self.full_slots = self.blob[o_full:o_full + 8 * F].view(torch.int64) if full_frame else None
+        self.seg_frames, self.seg_axes = P(base + o_seg), P(base + o_axes)
 
     def network_input(self, swap_rb: bool = False) -> torch.Tensor:
         """The (slots, 3, H, W) fp32 batch in [0, 1]: one ``cvx_tiles_u8_to_nchw`` launch for every tile of every frame and, with
@@ -421,6 +442,92 @@ def seg_overlay(frames, logits_rows: torch.Tensor, nc: int, level_hw, net_hw, lu
         L.check(L.load().cvx_seg_overlay(fb.frame_jobs, fb.n, fb.max_h, fb.max_w, L.ptr(logits_rows), int(logits_rows.shape[2]), int(nc), lh, lw,
                                          int(net_hw[0]), int(net_hw[1]), L.ptr(lut), int(bool(bgr)), L.stream_ptr(fb.device)), "cvx_seg_overlay")
     return fb.frames
+
+
+def slot_chunks(slots: int, batch_size: int):
+    """``[(c0, c1), ...]``: ``slots`` cut into the fewest chunks of at most ``batch_size``, of one size ``ceil(slots / n)`` with at most one shorter chunk at
+    the end.  The engine re-plans its per-batch buffers, and waits for its streams, whenever a forward's batch size
+    differs from the previous one; 30 slots at ``batch_size`` 16 are 15 + 15, not 16 + 14."""
+    slots, batch_size = int(slots), int(batch_size)
+    if slots <= 0 or batch_size <= 0:
+        raise ValueError("slots and batch_size are positive")
+    n = -(-slots // batch_size)
+    size = -(-slots // n)
+    return [(c0, min(c0 + size, slots)) for c0 in range(0, slots, size)]
+
+
+STITCH_WEIGHTS = {"mean": 0, "linear": 1}
+STITCH_COUNT_MAX_NC = 128                            # cvx_seg_stitch counts through an nc x nc int32 histogram in LDS
+
+
+def stitch_segmentation(frames, logits_rows: torch.Tensor, nc: int, level_hw, net_hw, tile_batch: TileBatch, weight: str = "linear",
+                        labels: bool = True, draw: bool = False, bgr: bool = False, targets=None, counts: Optional[torch.Tensor] = None, lut=None):
+    """``cvx_seg_stitch``: logits_rows (slots, lh * lw, ld) fp32 as ``forward_rows`` leaves them for the slots of
+    ``tile_batch`` (a ``TileBatch`` of ``frames`` at ``net_hw`` with ``full_frame=False``) -> per frame pixel the logits of every covering
+    tile, up-sampled by the taps of ``cvx_resize_bilinear_rows_to_nchw`` and blended (``weight``: ``"mean"``, every tile counts 1, or
+    ``"linear"``, the product of the distances to the tile's borders), and their arg max.  ``labels``: returns the list of (h, w) uint8
+    label maps on the device (else None); ``draw``: the class colours blended 50/50 into the frames in place, as ``seg_overlay`` (``bgr``,
+    ``lut``); ``targets`` (a list of (h, w) uint8 device maps, rows may be padded) with ``counts`` ((nc, nc) int64 on the device):
+    ``counts[target][label] += 1`` where ``target < nc``.  One launch for all frames, no host read."""
+    lh, lw = int(level_hw[0]), int(level_hw[1])
+    NH, NW = int(net_hw[0]), int(net_hw[1])
+    nc = int(nc)
+    if weight not in STITCH_WEIGHTS:
+        raise ValueError(f"weight: one of {sorted(STITCH_WEIGHTS)}, got {weight!r}")
+    if not 1 <= nc <= 256:
+        raise ValueError(f"nc {nc}: labels are bytes, 1 <= nc <= 256")
+    if lh <= 0 or lw <= 0 or NH <= 0 or NW <= 0:
+        raise ValueError("level_hw and net_hw are positive")
+    if not torch.is_tensor(logits_rows) or logits_rows.dim() != 3 or logits_rows.shape[1] != lh * lw or logits_rows.shape[2] < nc \
+            or logits_rows.dtype != torch.float32:
+        raise ValueError(f"logits_rows: (slots, {lh * lw}, >= {nc}) float32, got "
+                         f"{tuple(logits_rows.shape) if torch.is_tensor(logits_rows) else type(logits_rows).__name__} {getattr(logits_rows, 'dtype', '')}")
+    if (targets is None) != (counts is None):
+        raise ValueError("targets and counts come together")
+    if targets is not None and nc > STITCH_COUNT_MAX_NC:
+        raise ValueError(f"the confusion counts are kept for nc <= {STITCH_COUNT_MAX_NC}")
+    frames = list(frames)
+    dev = _check_frames(frames)
+    if not isinstance(tile_batch, TileBatch) or tile_batch.full_frame or tile_batch.input_hw != (NH, NW):
+        raise ValueError(f"tile_batch: the TileBatch of the frames at {(NH, NW)} with full_frame=False")
+    if len(frames) != tile_batch.n or any(a is not b for a, b in zip(frames, tile_batch.frames)):
+        raise ValueError("tile_batch was built for other frames")
+    if logits_rows.device != dev or logits_rows.shape[0] != tile_batch.slots:
+        raise ValueError(f"logits_rows: {tile_batch.slots} slots on {dev}, got {tuple(logits_rows.shape)} on {logits_rows.device}")
+    logits_rows = logits_rows.contiguous()
+    F = tile_batch.n
+    sizes = [(int(t.shape[0]), int(t.shape[1])) for t in frames]
+    if targets is not None:
+        targets = list(targets)
+        if len(targets) != F:
+            raise ValueError(f"targets: one (h, w) uint8 map per frame, got {len(targets)} for {F} frames")
+        for t, (h, w) in zip(targets, sizes):
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or t.device != dev or t.stride(1) != 1 or t.stride(0) < w:
+                raise ValueError(f"targets: a ({h}, {w}) uint8 map on {dev} with unit pixel stride per frame")
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (nc, nc) or counts.device != dev or not counts.is_contiguous():
+            raise ValueError(f"counts: ({nc}, {nc}) int64, contiguous, on {dev}")
+    if draw:
+        lut = _device_lut(nc, dev, lut)
+        if lut.shape[0] < nc or lut.device != dev:
+            raise ValueError(f"lut: at least {nc} colours on {dev}")
+    out = [torch.empty(h, w, dtype=torch.uint8, device=dev) for h, w in sizes] if labels else None
+    label_maps = target_maps = None
+    if labels or targets is not None:                         # the per-call pointer tables: one pinned blob, one asynchronous copy
+        maps = ([(t.data_ptr(), t.stride(0), 0) for t in out] if labels else []) + \
+               ([(t.data_ptr(), t.stride(0), 0) for t in targets] if targets is not None else [])
+        host = torch.empty(16 * len(maps), dtype=torch.uint8, pin_memory=True)
+        host.numpy().view(SEG_MAP_DTYPE)[:] = np.array(maps, dtype=SEG_MAP_DTYPE)
+        blob = torch.empty(16 * len(maps), dtype=torch.uint8, device=dev)
+        blob.copy_(host, non_blocking=True)
+        tile_batch._stitch_host = host                        # alive until the copy has run
+        label_maps = blob.data_ptr() if labels else None
+        target_maps = (blob.data_ptr() + (16 * F if labels else 0)) if targets is not None else None
+    with torch.cuda.device(dev):
+        L.check(L.load().cvx_seg_stitch(L.ptr(logits_rows), tile_batch.slots, int(logits_rows.shape[2]), nc, lh, lw, NH, NW, tile_batch.seg_frames,
+                                        tile_batch.seg_axes, tile_batch.n_axes, tile_batch.frame_jobs, F, tile_batch.max_h, tile_batch.max_w,
+                                        L.C.c_void_p(label_maps), L.C.c_void_p(target_maps), L.ptr(counts), L.ptr(lut) if draw else L.C.c_void_p(0),
+                                        STITCH_WEIGHTS[weight], int(bool(draw)), int(bool(bgr)), L.stream_ptr(dev)), "cvx_seg_stitch")
+    return out
 
 
 def read_detections(rows: torch.Tensor, counts: torch.Tensor, overflow: torch.Tensor) -> List[tuple]:

@@ -109,6 +109,71 @@ class DeeplabV3PlusA(FramePredictor):
             torch.cuda.synchronize(rows.device)
         return rows
 
+    def segment_tiled(self, model, frames, overlap=0.2, weight="linear", batch_size=16, draw=True, bgr=False, targets=None, metrics=None,
+                      sync=False):
+        """Sliding-window segmentation for frames much larger than the network input, where ``predict_batch``'s stretch loses the thin
+        structures and the aspect ratio: every frame is cut into tiles of ``cfg.arch.input_size`` that overlap by
+        ``overlap`` (``render.tile_grid``; zoom 1, no whole-picture slot), one ``cvx_tiles_u8_to_nchw`` launch builds all slots (/ 255, no
+        mean / std: ``predict_batch``'s feed), ``forward_rows`` runs them in chunks of at most ``batch_size`` (``render.slot_chunks``: equal chunks, so the
+        engine keeps one plan) into one (slots, h * w, nc_pad) block on the device, and one ``cvx_seg_stitch`` launch blends the up-sampled logits of the tiles that cover each pixel (``weight``:
+        ``"linear"``, the distance to the tile's borders, or ``"mean"``), takes the arg max and, with ``draw``, blends the class colours
+        50/50 into the frames in place (``bgr`` as in ``predict_batch``).  ``targets`` (one (h, w) uint8 device map per frame; values
+        >= num_classes are ignored) with ``metrics`` (a ``SegmentationMetrics``) adds the exact confusion counts to ``metrics.counts``;
+        ``fold()`` / ``get_results()`` then work as after ``add_rows``.  Returns the list of (h, w) uint8 label maps on the device;
+        nothing waits on the host unless ``sync``."""
+        from computervision.pytorch_amd import render
+        self._need_gpu("segment_tiled")
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size is positive")
+        if (targets is None) != (metrics is None):
+            raise ValueError("targets and metrics come together")
+        frames = list(frames)
+        net_hw = tuple(int(v) for v in self.cfg.arch.input_size[1:])
+        batch = render.TileBatch(frames, net_hw, overlap, full_frame=False)
+        x = batch.network_input()
+        model.eval()
+        block = None
+        with torch.no_grad():
+            for c0, c1 in render.slot_chunks(batch.slots, batch_size):
+                chunk = x[c0:c1]
+                if chunk.data_ptr() % 8:                          # the engine reads 8-byte aligned images: an odd slot size at an odd c0
+                    chunk = chunk.clone()
+                rows = model.forward_rows(chunk)
+                if block is None:
+                    block = torch.empty(batch.slots, rows.shape[1], rows.shape[2], dtype=torch.float32, device=rows.device)
+                block[c0:c0 + rows.shape[0]].copy_(rows)
+        counts = metrics.add_labels_counts(block.device) if metrics is not None else None
+        labels = render.stitch_segmentation(frames, block, self.num_classes, model._last_engine.graph.level_hw[0], net_hw, batch, weight=weight,
+                                            labels=True, draw=draw, bgr=bgr, targets=targets, counts=counts)
+        if sync:
+            torch.cuda.synchronize(block.device)
+        return labels
+
+    def segment_frames(self, model, frames, batch_size, **tiled):
+        """``detect_frames`` for ``segment_tiled``: a generator over any iterable of uint8 HWC RGB device frames that yields the list of
+        drawn frames of each batch of ``batch_size`` (the last one may be short).  Each batch is one ``segment_tiled(..., draw=True,
+        sync=False, **tiled)``, so nothing inside the loop waits on the host.  ``batch_size`` counts frames; the slots per forward stay at
+        ``segment_tiled``'s default.  (``detect_frames(..., tiled=...)`` stays the detectors'.)"""
+        self._need_gpu("segment_frames")
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size is positive")
+        if {"draw", "sync"} & set(tiled):
+            raise ValueError("segment_frames draws and does not wait: it takes neither draw nor sync")
+
+        def batches():
+            batch = []
+            for frame in frames:
+                batch.append(frame)
+                if len(batch) == int(batch_size):
+                    self.segment_tiled(model, batch, draw=True, sync=False, **tiled)
+                    yield batch
+                    batch = []
+            if batch:
+                self.segment_tiled(model, batch, draw=True, sync=False, **tiled)
+                yield batch
+
+        return batches()
+
     def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None):
         """Reference :115-166: the validation metrics of ``model`` over VOC-``subset``, printed and written to
         ``results_out_root/DeepLabV3Plus/DeepLabV3Plus_<dataset>_<time>.txt`` as four lines (Overall Acc, Mean Acc, FreqW Acc, Mean IoU).

@@ -67,6 +67,14 @@ class SegmentationMetrics:
             self.counts.zero_()
         return self.confusion_matrix
 
+    def add_labels_counts(self, device):
+        """The exact int64 ``counts`` on ``device``, created on first use (and again when the device changes): what a kernel that counts
+        labels itself -- ``cvx_seg_stitch`` behind ``DeeplabV3PlusA.segment_tiled`` -- adds to."""
+        device = torch.device(device)
+        if self.counts is None or self.counts.device != device:
+            self.counts = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64, device=device)
+        return self.counts
+
     def add_rows(self, rows, targets, hw, criterion, loss_slot):
         """One validation batch from the logits rows ``(B, lh*lw, ld)`` fp32 of ``model.forward_rows`` and the targets ``(B, H, W)`` int64:
         ``confusion[target][argmax of the upsampled logits] += 1`` and ``criterion``'s (a ``SegLoss``) value of the batch into

@@ -790,6 +790,37 @@ int cvx_det_merge_tiles(const float* rows, const int32_t* counts, int32_t slots,
                         float* out_rows, int32_t* out_counts, int32_t* out_source, int32_t* overflow, void* workspace, int64_t workspace_bytes,
                         void* hip_stream);
 
+/* ---- sliding-window segmentation for large frames (csrc/seg_tiles.hip) ----------------------------------------------
+ * The tiles of a frame (render.tile_grid, cvx_tiles_u8_to_nchw with full_frame off) run through the DeepLab engine as slots of one batch;
+ * cvx_seg_stitch blends their up-sampled logits per frame pixel and writes the label, the overlay and the confusion counts.  One launch
+ * for all frames, asynchronous on hip_stream, tables in device memory, nothing read back, no full-resolution logits in memory.  The
+ * reference has no counterpart: the rules are the project's own, restated in numpy in tests/seg_tiled_restatement.py.
+ * The tile grid of a frame is the product of ny tiles along y and nx tiles along x: tile (ty, tx) is slot first_slot + ty * nx + tx,
+ * and tile_axes holds (start, extent) int32 pairs -- ny of them from y_off, nx of them from x_off (offsets in int32 elements).  24 bytes. */
+typedef struct cvx_seg_tile_frame {
+  int32_t first_slot, ny, nx, y_off, x_off, reserved;
+} cvx_seg_tile_frame;
+/* A uint8 (h, w) map of a frame -- labels out, targets in -- with its row pitch in bytes; data NULL: this frame has none.  16 bytes. */
+typedef struct cvx_seg_map {
+  uint8_t* data;
+  int32_t pitch, reserved;
+} cvx_seg_map;
+/* logits_rows (slots, lh * lw, ld) fp32 as the engine's forward leaves them for a (net_h, net_w) input; tile_frames / jobs / label_maps /
+ * target_maps have one entry per frame; (max_h, max_w): the largest frame (the grid).  Per frame pixel (y, x), over the tiles that cover
+ * it (y0 <= y < y0 + th and x0 <= x < x0 + tw) in row-major order, ty outer:
+ *   z_k[c]  the logit at the tile-local pixel (y - y0, x - x0) by the taps of cvx_resize_bilinear_rows_to_nchw at scale lh / net_h,
+ *           lw / net_w (a slot is a full network input whatever the tile's extent), bit-identical to that entry's output;
+ *   w_k     weight_mode 0 ("mean"): 1.0f; 1 ("linear"): (float)(min(dy + 1, th - dy) * min(dx + 1, tw - dx)), an integer below 2^24;
+ *   acc[c]  = fmaf(w_k, z_k[c], acc[c]) from 0.0f -- one rounding per tile, no division by the weight sum;
+ *   label   the arg max of acc, the lowest class winning a tie.
+ * Outputs, each optional: label_maps[f] receives the label byte; draw != 0 blends lut[label] (nc x 3 bytes, RGB) 50/50 into the frame in
+ * place as cvx_seg_overlay does (bgr_out != 0 writes B, G, R); with target_maps and confusion (nc x nc int64, added to, never cleared)
+ * confusion[target][label] += 1 where target < nc (a per-workgroup LDS histogram: nc <= 128 on this path).  nc <= 256: labels are bytes. */
+int cvx_seg_stitch(const float* logits_rows, int32_t slots, int32_t ld, int32_t nc, int32_t lh, int32_t lw, int32_t net_h, int32_t net_w,
+                   const cvx_seg_tile_frame* tile_frames, const int32_t* tile_axes, int32_t n_axes, const cvx_frame_job* jobs, int32_t frames,
+                   int32_t max_h, int32_t max_w, const cvx_seg_map* label_maps, const cvx_seg_map* target_maps, int64_t* confusion,
+                   const uint8_t* lut, int32_t weight_mode, int32_t draw, int32_t bgr_out, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 

@@ -15,13 +15,17 @@ def detect_frames(algorithm, model, frames, batch_size, tiled=None):
     return algorithm.detect_frames(model, frames, batch_size, tiled=tiled)
 
 
-def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8, tiled=None):
-    """The reference's signature: ``decode_fn`` is the bound ``predict`` of an algorithm object (as the reference passes it) or the algorithm
-    object itself.  Reads ``src_video_path`` frame by frame, draws the predictions on the device and writes ``dst_video_path`` with the
-    source's frame rate and size.  ``tiled`` as in ``detect_frames``."""
-    algorithm = getattr(decode_fn, "__self__", decode_fn)
-    if not hasattr(algorithm, "predict_batch"):
-        raise CvxError("detect_video: decode_fn is an algorithm object or its bound predict method")
+def segment_frames(algorithm, model, frames, batch_size, **tiled):
+    """``detect_frames`` for sliding-window segmentation: ``algorithm`` is the DeepLab algorithm object, each batch is its
+    ``segment_tiled(..., draw=True, sync=False, **tiled)`` -- tiles at network size, logits stitched on the device, the class colours
+    blended into the frames in place."""
+    if not hasattr(algorithm, "segment_frames"):
+        raise CvxError(f"{type(algorithm).__name__} has no sliding-window segmentation")
+    return algorithm.segment_frames(model, frames, batch_size, **tiled)
+
+
+def _run_video(src_video_path, dst_video_path, device, batches_of):
+    """decode -> ``batches_of(frames on the device)`` -> encode, with the source's frame rate and size"""
     try:
         import cv2
     except ImportError as e:  # pragma: no cover
@@ -33,7 +37,6 @@ def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8,
     fps = capture.get(cv2.CAP_PROP_FPS)
     size = (int(capture.get(cv2.CAP_PROP_FRAME_WIDTH)), int(capture.get(cv2.CAP_PROP_FRAME_HEIGHT)))
     writer = cv2.VideoWriter(dst_video_path, cv2.VideoWriter_fourcc(*"mp4v"), fps, size)
-    device = torch.device(algorithm.device)
 
     def decoded():
         while True:
@@ -43,9 +46,31 @@ def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8,
             yield torch.from_numpy(cv2.cvtColor(bgr, cv2.COLOR_BGR2RGB)).to(device, non_blocking=True)
 
     try:
-        for batch in detect_frames(algorithm, model, decoded(), batch_size, tiled=tiled):
+        for batch in batches_of(decoded()):
             for frame in batch:                                   # the host read of a finished batch: the only wait
                 writer.write(cv2.cvtColor(frame.cpu().numpy(), cv2.COLOR_RGB2BGR))
     finally:
         capture.release()
         writer.release()
+
+
+def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8, tiled=None):
+    """The reference's signature: ``decode_fn`` is the bound ``predict`` of an algorithm object (as the reference passes it) or the algorithm
+    object itself.  Reads ``src_video_path`` frame by frame, draws the predictions on the device and writes ``dst_video_path`` with the
+    source's frame rate and size.  ``tiled`` as in ``detect_frames``."""
+    algorithm = getattr(decode_fn, "__self__", decode_fn)
+    if not hasattr(algorithm, "predict_batch"):
+        raise CvxError("detect_video: decode_fn is an algorithm object or its bound predict method")
+    _run_video(src_video_path, dst_video_path, torch.device(algorithm.device),
+               lambda frames: detect_frames(algorithm, model, frames, batch_size, tiled=tiled))
+
+
+def segment_video(model, src_video_path, dst_video_path, decode_fn, batch_size=2, **tiled):
+    """``detect_video`` for full-resolution segmentation: every frame goes through ``segment_tiled`` (``tiled``: its keywords ``overlap``,
+    ``weight``, ``bgr``; ``batch_size`` is the frames per call, the slots per forward stay at its default) instead of being stretched to
+    the network input."""
+    algorithm = getattr(decode_fn, "__self__", decode_fn)
+    if not hasattr(algorithm, "segment_frames"):
+        raise CvxError("segment_video: decode_fn is the DeepLab algorithm object or its bound predict method")
+    _run_video(src_video_path, dst_video_path, torch.device(algorithm.device),
+               lambda frames: segment_frames(algorithm, model, frames, batch_size, **tiled))
