@@ -121,6 +121,9 @@ PROTOTYPES = {
     "cvx_tiles_u8_to_nchw": (_I32, [_P, _I32, _I32, _P, _I32, _I32, _P]),
     "cvx_det_merge_workspace_bytes": (_I64, [_I32]),
     "cvx_det_merge_tiles": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _I32, _F, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
+    "cvx_track_state_bytes": (_I64, [_I32]),
+    "cvx_track_update": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "cvx_draw_tracks": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_seg_stitch": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_aug_images": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _P]),
     "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),

@@ -20,6 +20,15 @@ __device__ __forceinline__ bool iou_gt(const float4& a, float area_a, const floa
   const float ovr = inter / (sum - inter);
   return ovr > thr;
 }
+// the value iou_gt compares: the same operations in the same order (the tracker ranks its pairs by it, track.hip)
+__device__ __forceinline__ float iou_value(const float4& a, float area_a, const float4& b, float area_b) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
+  const float h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+  const float inter = w * h;
+  const float sum = area_a + area_b;
+  return inter / (sum - inter);
+}
 // intersection over the smaller box, the same `inter`: a box cut by a tile border lies inside the whole box of the neighbouring tile
 __device__ __forceinline__ bool ios_gt(const float4& a, float area_a, const float4& b, float area_b, float thr) {
 #pragma clang fp contract(off)

@@ -1,5 +1,5 @@
 // Output side of batched prediction on gfx950: NMS rows -> original-image coordinates (cvx_det_to_image), the detections painted into the
-// uint8 frames (cvx_draw_detections) and the segmentation result coloured and blended into them (cvx_seg_overlay).  Nothing is read by the
+// uint8 frames (cvx_draw_detections; cvx_draw_tracks for rows with track ids) and the segmentation result coloured and blended into them (cvx_seg_overlay).  Nothing is read by the
 // host; every frame of a batch has its own size and row stride (cvx_frame_job).
 //
 //   K1 det_to_image   one thread per row: mode 1 is det_undo_letterbox (det_common.h), the function cvx_det_match maps its boxes with, so
@@ -113,13 +113,36 @@ __device__ __forceinline__ int draw_label(int cls, float score, unsigned char* c
   return n;
 }
 
+// "{id % 1000000}:{cls}": digits and the colon only
+__device__ __forceinline__ int draw_track_label(int id, int cls, unsigned char* ch) {
+  int n = 0;
+  unsigned char tmp[6];
+  int k = 0, v = id % 1000000;
+  do {
+    tmp[k++] = (unsigned char)(v % 10);
+    v /= 10;
+  } while (v > 0);
+  while (k > 0) ch[n++] = tmp[--k];
+  ch[n++] = GLYPH_COLON;
+  v = cls;
+  do {
+    tmp[k++] = (unsigned char)(v % 10);
+    v /= 10;
+  } while (v > 0);
+  while (k > 0) ch[n++] = tmp[--k];
+  return n;
+}
+
 __device__ __forceinline__ bool rects_meet(int ax0, int ay0, int ax1, int ay1, int bx0, int by0, int bx1, int by1) {  // inclusive corners
   return ax0 <= bx1 && bx0 <= ax1 && ay0 <= by1 && by0 <= ay1;
 }
 
+// TRACKS: the rows carry track ids (cvx_draw_tracks) -- a negative id paints nothing, the label spells the id and the class, the colour
+// follows the id; everything else is one body
+template <bool TRACKS>
 __global__ __launch_bounds__(256) void draw_kernel(const cvx_frame_job* __restrict__ jobs, const float* __restrict__ rows,
-                                                   const int* __restrict__ counts, int max_det, const uint8_t* __restrict__ lut, int n_lut,
-                                                   int thick, int fs) {
+                                                   const int* __restrict__ counts, int max_det, const int* __restrict__ ids,
+                                                   const uint8_t* __restrict__ lut, int n_lut, int thick, int fs) {
   __shared__ DrawBox list[LIST];
   __shared__ int wave_tot[4];
   const cvx_frame_job jb = jobs[blockIdx.y];
@@ -146,7 +169,9 @@ __global__ __launch_bounds__(256) void draw_kernel(const cvx_frame_job* __restri
     const int j = n - 1 - (start + tid);           // this thread's box of the chunk, last box first
     bool hit = false;
     DrawBox d;
-    if (j >= 0) {
+    int track = 0;
+    if constexpr (TRACKS) track = j >= 0 ? ids[(long long)blockIdx.y * max_det + j] : -1;
+    if (j >= 0 && track >= 0) {
       const float* row = rows + ((long long)blockIdx.y * max_det + j) * 6;
       const float fx0 = row[0], fy0 = row[1], fx1 = row[2], fy1 = row[3];
       if (fx0 == fx0 && fy0 == fy0 && fx1 == fx1 && fy1 == fy1) {   // a NaN coordinate paints nothing
@@ -154,14 +179,14 @@ __global__ __launch_bounds__(256) void draw_kernel(const cvx_frame_job* __restri
         if (d.x1 >= d.x0 && d.y1 >= d.y0) {                         // an inverted box paints nothing
           int cls = draw_coord(row[5]);
           cls = cls < 0 ? 0 : (cls > 9999 ? 9999 : cls);
-          d.nch = draw_label(cls, row[4], d.ch);
+          d.nch = TRACKS ? draw_track_label(track, cls, d.ch) : draw_label(cls, row[4], d.ch);
           d.tw = (6 * d.nch + 1) * fs;
           d.tx = d.x0;
           d.ty = d.y0 - tag_h >= 0 ? d.y0 - tag_h : d.y0;           // above the box where it fits, else inside it
           hit = rects_meet(d.x0 - grow, d.y0 - grow, d.x1 + grow, d.y1 + grow, X0, Y0, X1, Y1) ||
                 rects_meet(d.tx, d.ty, d.tx + d.tw - 1, d.ty + tag_h - 1, X0, Y0, X1, Y1);
           if (hit) {
-            const uint8_t* c = lut + 3 * ((cls + 1) % n_lut);
+            const uint8_t* c = lut + 3 * (TRACKS ? (int)(((long long)track + 1) % n_lut) : (cls + 1) % n_lut);
             const unsigned r = c[0], g = c[1], b = c[2];
             d.colour = r | g << 8 | b << 16;
             d.tag = (r * 7 / 10) | (g * 7 / 10) << 8 | (b * 7 / 10) << 16;
@@ -324,8 +349,22 @@ extern "C" int cvx_draw_detections(const cvx_frame_job* jobs, int32_t batch, int
   CVX_CHECK(thickness >= 1 && thickness <= 64 && font_scale >= 1 && font_scale <= 16, "thickness 1 .. 64, font_scale 1 .. 16");
   const long long tiles = (long long)cvx_cdiv(max_w, TW) * cvx_cdiv(max_h, TH);
   CVX_CHECK(tiles <= 0x7FFFFFFF, "frame too large");
-  hipLaunchKernelGGL(draw_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream, jobs, rows, counts, max_det, lut,
-                     lut_entries, thickness, font_scale);
+  hipLaunchKernelGGL(draw_kernel<false>, dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream, jobs, rows, counts, max_det,
+                     (const int*)nullptr, lut, lut_entries, thickness, font_scale);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int cvx_draw_tracks(const cvx_frame_job* jobs, int32_t batch, int32_t max_h, int32_t max_w, const float* rows, const int32_t* counts,
+                               int32_t max_det, const int32_t* ids, const uint8_t* lut, int32_t lut_entries, int32_t thickness, int32_t font_scale,
+                               void* hip_stream) {
+  CVX_CHECK(jobs && rows && counts && ids && lut, "null arguments");
+  CVX_CHECK(batch > 0 && batch <= 65535 && max_h > 0 && max_w > 0 && max_det > 0 && lut_entries > 0, "bad sizes");
+  CVX_CHECK(thickness >= 1 && thickness <= 64 && font_scale >= 1 && font_scale <= 16, "thickness 1 .. 64, font_scale 1 .. 16");
+  const long long tiles = (long long)cvx_cdiv(max_w, TW) * cvx_cdiv(max_h, TH);
+  CVX_CHECK(tiles <= 0x7FFFFFFF, "frame too large");
+  hipLaunchKernelGGL(draw_kernel<true>, dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream, jobs, rows, counts, max_det, ids,
+                     lut, lut_entries, thickness, font_scale);
   CVX_HIP(hipGetLastError());
   return 0;
 }

@@ -10,6 +10,9 @@ Tiled prediction for frames much larger than the network input (DESIGN.md sectio
 logits are stitched instead (csrc/seg_tiles.hip): ``stitch_segmentation`` blends the up-sampled logits of every tile
 that covers a pixel and writes the label, the overlay and the confusion counts in one ``cvx_seg_stitch`` launch.
 
+``draw_tracks`` paints rows that carry track ids (``track.py``; ``cvx_draw_tracks``, one kernel body with
+``cvx_draw_detections``).
+
 ``palette``, ``format_label`` and ``FONT`` are the host statement of the drawing rules, shared with the tests'
 restatement (tests/render_restatement.py)."""
 from __future__ import annotations
@@ -426,6 +429,26 @@ def draw_detections(frames, rows: torch.Tensor, counts: torch.Tensor, lut=None, 
     return fb.frames
 
 
+def draw_tracks(frames, rows: torch.Tensor, ids: torch.Tensor, counts: torch.Tensor, lut=None, thickness: int = 2, font_scale: int = 2,
+                batch: FrameBatch = None):
+    """``cvx_draw_tracks``: ``draw_detections`` for rows with track ids (``track.Tracker.update``).  ``ids``: (B, K)
+    int32 on the device; a row whose id is negative is not painted, the label is ``"{id % 1000000}:{cls}"`` and the colour entry
+    ``(id + 1) % len(lut)``, so an object keeps its colour while it keeps its id."""
+    fb = batch if batch is not None else FrameBatch(frames)
+    if rows.dim() != 3 or rows.shape[0] != fb.n or rows.shape[2] != 6 or rows.dtype != torch.float32 or rows.device != fb.device:
+        raise ValueError(f"rows: ({fb.n}, K, 6) float32 on {fb.device}")
+    if counts.dtype != torch.int32 or counts.numel() != fb.n or counts.device != fb.device:
+        raise ValueError("counts: (B) int32 on the frames' device")
+    if ids.dtype != torch.int32 or tuple(ids.shape) != tuple(rows.shape[:2]) or ids.device != fb.device:
+        raise ValueError("ids: (B, K) int32 on the frames' device")
+    rows, counts, ids = rows.contiguous(), counts.contiguous(), ids.contiguous()
+    lut = _device_lut(256, fb.device, lut)
+    with torch.cuda.device(fb.device):
+        L.check(L.load().cvx_draw_tracks(fb.frame_jobs, fb.n, fb.max_h, fb.max_w, L.ptr(rows), L.ptr(counts), int(rows.shape[1]), L.ptr(ids),
+                                         L.ptr(lut), int(lut.shape[0]), int(thickness), int(font_scale), L.stream_ptr(fb.device)), "cvx_draw_tracks")
+    return fb.frames
+
+
 def seg_overlay(frames, logits_rows: torch.Tensor, nc: int, level_hw, net_hw, lut=None, bgr: bool = False, batch: FrameBatch = None):
     """``cvx_seg_overlay``: logits_rows (B, lh * lw, ld) fp32 as ``forward_rows`` leaves them for a ``net_hw`` input -> class colours
     blended 50/50 into the RGB frames, in place; ``bgr`` writes B, G, R.  ``lut``: (nc, 3) uint8 RGB on the device, default the VOC palette."""
@@ -530,14 +553,22 @@ def stitch_segmentation(frames, logits_rows: torch.Tensor, nc: int, level_hw, ne
     return out
 
 
-def read_detections(rows: torch.Tensor, counts: torch.Tensor, overflow: torch.Tensor) -> List[tuple]:
+def read_detections(rows: torch.Tensor, counts: torch.Tensor, overflow: torch.Tensor, ids: Optional[torch.Tensor] = None) -> List[tuple]:
     """ONE host read of (rows, counts, overflow) -> per image ``(boxes (k, 4) float32, scores (k) float32, classes (k) int64)``, the format of
-    ``decode_box``.  Raises ``CvxError`` when an image was dropped (NMS count -1 or a count past its block)."""
+    ``decode_box``.  Raises ``CvxError`` when an image was dropped (NMS count -1 or a count past its block).  With ``ids`` (B, K) int32, a
+    tracker's, the tuples gain ``ids (k) int32`` as a fourth element, -1 where a row has no track."""
     B, K = int(rows.shape[0]), int(rows.shape[1])
-    flat = torch.cat((rows.reshape(-1), counts.view(torch.float32).reshape(-1), overflow.view(torch.float32).reshape(-1))).cpu().numpy()
+    parts = (rows.reshape(-1), counts.view(torch.float32).reshape(-1), overflow.view(torch.float32).reshape(-1))
+    if ids is not None:
+        parts += (ids.contiguous().view(torch.float32).reshape(-1),)
+    flat = torch.cat(parts).cpu().numpy()
     r = flat[:B * K * 6].reshape(B, K, 6)
     tail = flat[B * K * 6:].view(np.int32)
     if int(tail[B]):
         raise L.CvxError(f"predict_batch: {int(tail[B])} image(s) dropped: an NMS count of -1 (more candidates than cvx_nms sorts), a count "
                          f"past its block or, tiled, a frame with more than {MERGE_CAP} candidates; raise the confidence threshold")
-    return [(r[b, :n, :4].copy(), r[b, :n, 4].copy(), r[b, :n, 5].astype(np.int64)) for b, n in enumerate(int(v) for v in tail[:B])]
+    found = [(r[b, :n, :4].copy(), r[b, :n, 4].copy(), r[b, :n, 5].astype(np.int64)) for b, n in enumerate(int(v) for v in tail[:B])]
+    if ids is None:
+        return found
+    track = tail[B + 1:].reshape(B, K)
+    return [t + (track[b, :len(t[1])].copy(),) for b, t in enumerate(found)]

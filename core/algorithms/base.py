@@ -35,16 +35,25 @@ class FramePredictor:
         if torch.device(self.device).type != "cuda":
             raise L.CvxError(f"{what} runs on an MI355X only (device {self.device}): there is no CPU path")
 
-    def detect_frames(self, model, frames, batch_size, tiled=None):
+    def detect_frames(self, model, frames, batch_size, tiled=None, track=None):
         """Generator over any iterable of uint8 HWC RGB device frames: yields the list of drawn frames of each batch of ``batch_size`` (the
         last one may be short).  Each batch is one ``predict_batch(..., draw=True, sync=False)``: nothing inside the loop waits on the
         host, so the caller synchronises (or reads a frame) when it needs the pixels.  ``tiled``: a dict of ``predict_tiled`` keywords
-        (the four detectors) -- each batch is then one ``predict_tiled(..., draw=True, sync=False, **tiled)``."""
+        (the four detectors) -- each batch is then one ``predict_tiled(..., draw=True, sync=False, **tiled)``.  ``track``: a
+        ``track.Tracker``, or a dict of its parameters from which one is created for the generator's lifetime (the four detectors) -- every
+        batch goes through it in order, and the frames are painted with the track ids (``cvx_draw_tracks``); composes with ``tiled``."""
+        if track is not None and not isinstance(self, Detector):
+            raise L.CvxError(f"{type(self).__name__} has no detections to track")
         self._need_gpu("detect_frames")
         if int(batch_size) <= 0:
             raise ValueError("batch_size is positive")
+        more = {}
+        if track is not None:
+            from computervision.pytorch_amd.track import Tracker
+            more["tracker"] = track if isinstance(track, Tracker) else Tracker(self.device, **dict(track))
         if tiled is None:
-            predict = self.predict_batch
+            def predict(model, batch, draw, sync):
+                return self.predict_batch(model, batch, draw=draw, sync=sync, **more)
         else:
             if not hasattr(self, "predict_tiled"):
                 raise L.CvxError(f"{type(self).__name__} has no tiled prediction")
@@ -53,7 +62,7 @@ class FramePredictor:
                 raise ValueError("detect_frames draws and does not wait: tiled= takes neither draw nor sync")
 
             def predict(model, batch, draw, sync):
-                return self.predict_tiled(model, batch, draw=draw, sync=sync, **tiled)
+                return self.predict_tiled(model, batch, draw=draw, sync=sync, **tiled, **more)
 
         def batches():
             batch = []
@@ -79,14 +88,28 @@ class Detector(FramePredictor):
         size = self.input_image_size if hasattr(self, "input_image_size") else self.input_size
         return (int(size[0]), int(size[1])), bool(self.letterbox_image)
 
-    def predict_batch(self, model, frames, conf_threshold=None, draw=False, sync=True):
+    def _tracked(self, tracker, frames, batch, rows, counts, overflow, draw, sync):
+        """The end of ``predict_batch`` / ``predict_tiled`` with a tracker: ids, the tracks painted, the return with its third element"""
+        from computervision.pytorch_amd import render
+        ids = tracker.update(rows, counts)
+        if draw:
+            render.draw_tracks(frames, rows, ids, counts, batch=batch)
+        if sync:
+            return render.read_detections(rows, counts, overflow, ids)
+        return rows, counts, ids
+
+    def predict_batch(self, model, frames, conf_threshold=None, draw=False, sync=True, tracker=None):
         """``predict`` for a batch, on the device: ``frames`` is a list of uint8 HWC RGB device tensors of any sizes.  One launch builds the
         network batch (``cvx_letterbox_batch_u8_to_nchw`` when ``cfg.decode.letterbox_image``, else the bicubic stretch through
         ``cvx_aug_images_plain`` jobs -- the host ``INTER_CUBIC`` resize of ``predict``), one forward, the class's own decode + NMS tail
         (``_evaluation_rows`` at ``conf_threshold``, default the configured one) and ``cvx_det_to_image``.  ``draw=True`` paints the
         detections into the frames, in place (``cvx_draw_detections``).  Returns ``(rows (B, K, 6) [x1, y1, x2, y2, score, cls] in
         original-image pixels, counts (B) int32)`` on the device; with ``sync=True`` one host read turns them into a list of ``(boxes,
-        scores, classes)`` numpy triples in ``decode_box``'s format (and raises ``CvxError`` if an image overflowed the NMS)."""
+        scores, classes)`` numpy triples in ``decode_box``'s format (and raises ``CvxError`` if an image overflowed the NMS).
+        ``tracker``: a ``track.Tracker`` -- the frames are consecutive frames of its stream 0, the rows get track ids after
+        ``cvx_det_to_image`` (``cvx_track_update``, no host read), ``draw`` paints them with ``cvx_draw_tracks``, and the return gains a
+        third element: ``(rows, counts, ids (B, K) int32)``, or with ``sync=True`` ``(boxes, scores, classes, ids)`` per frame, a row
+        without a track with -1.  Without a tracker nothing changes."""
         from computervision.pytorch_amd import render
         self._need_gpu("predict_batch")
         frames = list(frames)
@@ -96,6 +119,8 @@ class Detector(FramePredictor):
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
         rows, counts, box_map = self._evaluation_rows(model)(batch.network_input(), {"image_hw": batch.image_hw}, conf)
         rows, counts, overflow = render.det_to_image(rows, counts, box_map)
+        if tracker is not None:
+            return self._tracked(tracker, frames, batch, rows, counts, overflow, draw, sync)
         if draw:
             render.draw_detections(frames, rows, counts, batch=batch)
         if sync:
@@ -103,7 +128,7 @@ class Detector(FramePredictor):
         return rows, counts
 
     def predict_tiled(self, model, frames, overlap=0.2, full_frame=True, match="ios", match_threshold=0.5, class_agnostic=False, max_det=300,
-                      conf_threshold=None, batch_size=32, draw=False, sync=True):
+                      conf_threshold=None, batch_size=32, draw=False, sync=True, tracker=None):
         """``predict_batch`` for frames much larger than the network input, where shrinking the whole picture loses the small objects: every
         frame is cut into tiles of the network's input size that overlap by ``overlap`` (``render.tile_grid``; no resampling, zoom 1), with
         ``full_frame`` one more slot per frame holds the whole picture as ``predict_batch`` would feed it, and one ``cvx_tiles_u8_to_nchw``
@@ -113,7 +138,8 @@ class Detector(FramePredictor):
         ``"ios"`` intersection over the smaller box, or ``"iou"``; above ``match_threshold``; inside a class unless ``class_agnostic``;
         at most ``max_det`` rows per frame).  ``draw`` and ``sync`` as in ``predict_batch``: returns ``(rows (frames, max_det, 6), counts
         (frames) int32)`` on the device, or with ``sync=True`` the list of ``(boxes, scores, classes)`` triples from one host read, which
-        raises ``CvxError`` when a slot overflowed its NMS or a frame has more than 8192 candidates."""
+        raises ``CvxError`` when a slot overflowed its NMS or a frame has more than 8192 candidates.  ``tracker`` as in ``predict_batch``:
+        the ids are computed on the merged rows."""
         import torch
         from computervision.pytorch_amd import render
         self._need_gpu("predict_tiled")
@@ -139,6 +165,8 @@ class Detector(FramePredictor):
         slot_counts = torch.cat([p[3] for p in parts])
         rows, counts, _, overflow = render.merge_tiles(slot_rows, slot_counts, batch.slot_map, batch.frame_hw, match, match_threshold, class_agnostic,
                                                        max_det, overflow)
+        if tracker is not None:
+            return self._tracked(tracker, frames, batch, rows, counts, overflow, draw, sync)
         if draw:
             render.draw_detections(frames, rows, counts, batch=batch)
         if sync:

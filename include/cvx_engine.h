@@ -821,6 +821,60 @@ int cvx_seg_stitch(const float* logits_rows, int32_t slots, int32_t ld, int32_t 
                    int32_t max_h, int32_t max_w, const cvx_seg_map* label_maps, const cvx_seg_map* target_maps, int64_t* confusion,
                    const uint8_t* lut, int32_t weight_mode, int32_t draw, int32_t bgr_out, void* hip_stream);
 
+/* ---- multi-object tracking on the device video path (csrc/track.hip) ------------------------------------------------
+ * A ByteTrack-style tracker: two association stages by score, constant-velocity prediction with an alpha-beta update, greedy IoU
+ * association.  One launch per batch of frames, the state in device memory, nothing read back.  The rules are the project's own, restated
+ * in numpy in tests/track_restatement.py; the kernel is held to the restatement bit for bit.
+ * Replaces: nothing, the reference has no counterpart.
+ * The state of one stream.  All zero means "no tracks, frame 0, next id 0": creating or resetting a tracker is a memset.  The live tracks
+ * are the entries [0, n_tracks) of every array; their order inside the table is not part of the contract (everything observable is keyed
+ * by the track id), and the entries past n_tracks are unspecified.  cls holds the class as the rows carry it (a float). */
+#define CVX_TRACK_CAP 1024
+typedef struct cvx_track_stream {
+  int32_t frame, next_id, n_tracks, reserved;
+  int32_t id[CVX_TRACK_CAP], hits[CVX_TRACK_CAP], miss[CVX_TRACK_CAP];
+  float cls[CVX_TRACK_CAP];
+  float p[CVX_TRACK_CAP][4]; /* x1, y1, x2, y2 */
+  float v[CVX_TRACK_CAP][4]; /* per frame */
+} cvx_track_stream;
+/* Host memory, read during the call.  Defaults: high 0.5, new_score 0.6, iou_high 0.2, iou_low 0.5, alpha 0.75, beta 0.25, min_hits 3,
+ * max_age 30, class_agnostic 0.  The four thresholds lie in [0, 1], min_hits >= 1, max_age >= 0. */
+typedef struct cvx_track_params {
+  float high, new_score, iou_high, iou_low, alpha, beta;
+  int32_t min_hits, max_age, class_agnostic, reserved;
+} cvx_track_params;
+/* rows (batch, max_det, 6) fp32 [x1, y1, x2, y2, score, cls] and counts (batch) int32 as cvx_det_to_image and cvx_det_merge_tiles leave
+ * them.  The frames are in time order; frame b belongs to stream frame_stream[b] (NULL: all to stream 0), the frames of a stream are
+ * processed in batch order, and the streams are independent (one workgroup each).  state: cvx_track_state_bytes(streams) bytes of device
+ * memory, `streams` cvx_track_stream in a row, carried from call to call.  out_ids (batch, max_det) int32: the track id of each row or -1.
+ * A frame_stream value outside [0, streams) makes the frame a no-op: its ids are -1 and *overflow (1 int32, device, cleared by the caller)
+ * grows by 1.  All arithmetic is fp32, every operation rounded on its own.  Per frame of a stream, n = counts[b]; a count below 0 or above
+ * max_det adds 1 to *overflow and the frame is processed as n = 0:
+ *   1 count     frame += 1; out_ids[b, :] = -1.
+ *   2 predict   every live track: p = p + v per coordinate.
+ *   3 split     a row with a NaN coordinate is ignored throughout (id -1, no match, no birth); high: score >= high; low: the rest of
+ *               the n rows (a NaN score is low).
+ *   4 stage 1   candidate pairs (live track, high row), of the same class unless class_agnostic, with iou(p, box) > iou_high -- the
+ *               IoU of cvx_nms (box_overlap.h:iou_value), a NaN never passes.  Greedy over the pairs sorted by (IoU descending, track id
+ *               ascending, row index ascending): a pair is taken when neither its track nor its row is taken yet.
+ *   5 stage 2   the same with iou_low, between the low rows and the tracks still unmatched with hits >= min_hits and miss == 0.
+ *   6 update    every matched pair: r = z - p; p = p + alpha * r; v = v + beta * r per coordinate (mul, then add); hits += 1; miss = 0;
+ *               cls = the row's class; out_ids[b, d] = id when hits >= min_hits or frame <= min_hits, else it stays -1.
+ *   7 unmatched a track with hits < min_hits is deleted; otherwise miss += 1 and the track is deleted when miss > max_age.
+ *   8 births    in row order, every unmatched high row with score >= new_score: id = next_id++, p = box, v = 0, hits = 1, miss = 0,
+ *               cls = the row's; out_ids[b, d] = id when 1 >= min_hits or frame <= min_hits.  When the stream already holds
+ *               CVX_TRACK_CAP tracks the row is skipped, next_id does not move and *overflow grows by 1: flagged, never evicted. */
+int64_t cvx_track_state_bytes(int32_t streams);
+int cvx_track_update(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, const int32_t* frame_stream, int32_t streams,
+                     const cvx_track_params* params, void* state, int32_t* out_ids, int32_t* overflow, void* hip_stream);
+/* cvx_draw_detections for tracked rows: ids (batch, max_det) int32 as cvx_track_update leaves them.  A row whose id is negative paints
+ * nothing.  The label is "{id % 1000000}:{cls}" and the outline colour entry (id + 1) mod lut_entries, so an object keeps its colour
+ * while it keeps its id; tag and text colours follow from it by cvx_draw_detections's rules, and geometry, painter's order and the
+ * once-written pixels are that entry's (one kernel body).
+ * Replaces: nothing, the reference has no counterpart. */
+int cvx_draw_tracks(const cvx_frame_job* jobs, int32_t batch, int32_t max_h, int32_t max_w, const float* rows, const int32_t* counts, int32_t max_det,
+                    const int32_t* ids, const uint8_t* lut, int32_t lut_entries, int32_t thickness, int32_t font_scale, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 
