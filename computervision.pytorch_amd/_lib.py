@@ -7,6 +7,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB") or os.path.join(_HERE, "lib", "libcvx_engine.so")   # CVX_LIB: A/B runs of two builds on one box
 ABI_VERSION = 4
@@ -125,6 +127,8 @@ PROTOTYPES = {
     "cvx_track_update": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "cvx_draw_tracks": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_seg_stitch": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "cvx_seg_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "cvx_seg_fuse": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_aug_images": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _P]),
     "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_aug_images_plain": (_I32, [_P, _P, _I32, _P, _I32, _I32, _P]),
@@ -185,6 +189,9 @@ PROTOTYPES = {
     "cvx_stem_backward_nchw": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _F, _P, _P, _P, _P]),
     "cvx_stem_backward_recompute_nchw": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P]),
 }
+
+# cvx_seg_view (include/cvx_engine.h): one view of cvx_seg_fuse's host table, 24 bytes
+SEG_VIEW_DTYPE = np.dtype([("rows", "<u8"), ("lh", "<i4"), ("lw", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
 
 _lib = None
 

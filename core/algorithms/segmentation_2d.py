@@ -65,11 +65,30 @@ class DeeplabV3PlusA(FramePredictor):
             raise L.CvxError(f"loss_type {self.loss_type!r}: the reference knows 'ce' and 'focal'")
         return SegLoss(self.loss_type)
 
-    def predict_tensor(self, model, images: torch.Tensor):
-        """(B,3,H,W) normalised images on the device -> (B,H,W,3) class colours (the tensor part of ``predict``)."""
+    def predict_tensor(self, model, images: torch.Tensor, scales=None, flip=False, fuse="prob"):
+        """(B,3,H,W) normalised images on the device -> (B,H,W,3) class colours (the tensor part of ``predict``).  ``scales`` / ``flip``
+        select test-time augmentation (``predict_labels``): the colours of the fused labels."""
+        if scales is None and not flip:
+            model.eval()
+            with torch.no_grad():
+                return postprocess_seg2d(self.dataset_name, model(images), images.device)
+        if self.dataset_name.lower() not in ("voc", "sbd"):
+            raise NotImplementedError(f"不支持{self.dataset_name}数据集")
+        labels = self.predict_labels(model, images, scales=(1.0,) if scales is None else scales, flip=flip, fuse=fuse)
+        return torch.tensor(voc_colormap(), device=labels.device)[labels.long(), :]
+
+    def predict_labels(self, model, images: torch.Tensor, scales=(1.0,), flip=False, fuse="prob", probs=False):
+        """Multi-scale and flip test-time augmentation: the network runs on ``images`` ((B,3,H,W) on the device) at
+        every zoom of ``scales`` (``seg_tta.view_size``) and, with ``flip``, on their mirror image; one ``cvx_seg_fuse`` launch brings the
+        logits of all views to (H, W), fuses them (``fuse``: ``"prob"``, the mean of the views' softmax, or ``"logits"``, the sum of their
+        logits) and takes the arg max.  Returns the (B, H, W) uint8 labels on the device and, with ``probs`` (``"prob"`` only), the
+        (B, num_classes, H, W) mean probabilities as well.  Nothing waits on the host."""
+        from computervision.pytorch_amd.seg_tta import SegTTA
+        tta = SegTTA(scales, flip, fuse)
+        self._need_gpu("predict_labels")
         model.eval()
-        with torch.no_grad():
-            return postprocess_seg2d(self.dataset_name, model(images), images.device)
+        views = tta.run(model, images)
+        return tta.fuse(views, self.num_classes, model.layout.nc_pad, images.shape[2:], probs=probs)
 
     def predict(self, model, image_path, print_on, save_result):
         """Reference :80-113: read, resize to the network size (no letterbox), forward, colour, resize back, blend 50 % with the
@@ -174,23 +193,34 @@ class DeeplabV3PlusA(FramePredictor):
 
         return batches()
 
-    def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None):
+    def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None, scales=None, flip=False, fuse="prob"):
         """Reference :115-166: the validation metrics of ``model`` over VOC-``subset``, printed and written to
         ``results_out_root/DeepLabV3Plus/DeepLabV3Plus_<dataset>_<time>.txt`` as four lines (Overall Acc, Mean Acc, FreqW Acc, Mean IoU).
         Reading VOC from disk is outside the hot path: ``dataloader`` is a ``DeviceSegLoader`` over the pictures with
         ``DeviceSegAugmenter(crop_hw=cfg.arch.crop_size, base_size=max(cfg.arch.input_size[1:]), colormap=voc_colormap(), train=False)``.
-        Each batch is one engine forward and one ``cvx_seg_eval`` launch; the host waits once, at the end.  Returns the path written."""
-        from core.trainer.segmentation_trainer import SegmentationMetrics, fused_evaluation
+        Each batch is one engine forward and one ``cvx_seg_eval`` launch; the host waits once, at the end.  ``scales`` / ``flip`` /
+        ``fuse`` select test-time augmentation (``predict_labels``): each batch is then one forward per scale and
+        one ``cvx_seg_fuse`` launch, still with one host wait at the end.  Returns the path written."""
+        from core.trainer.segmentation_trainer import SegmentationMetrics, fused_evaluation, fused_evaluation_tta
         if subset != "val":
             raise ValueError(f"不支持VOC-{subset}")
         if dataloader is None:
             raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader=DeviceSegLoader(source, batch_size, "
                              "DeviceSegAugmenter(crop_hw, base_size, colormap=voc_colormap(), train=False)) over the VOC-val pictures")
+        tta = None
+        if scales is not None or flip:
+            from computervision.pytorch_amd.seg_tta import SegTTA
+            tta = SegTTA((1.0,) if scales is None else scales, flip, fuse)
+            self._need_gpu("evaluate_on_voc with test-time augmentation")
         model_name = "DeepLabV3Plus"
         results_out_root = os.path.join(results_out_root, model_name)
         os.makedirs(results_out_root, exist_ok=True)
         results_filepath = os.path.join(results_out_root, f"{model_name}_{self.dataset_name}_{time.strftime('%Y-%m-%d-%H-%M-%S')}.txt")
-        r = fused_evaluation(model, self.build_loss(), SegmentationMetrics(num_classes=self.num_classes, device=self.device), dataloader, self.device)
+        metrics = SegmentationMetrics(num_classes=self.num_classes, device=self.device)
+        if tta is None:
+            r = fused_evaluation(model, self.build_loss(), metrics, dataloader, self.device)
+        else:
+            r = fused_evaluation_tta(model, metrics, dataloader, self.device, tta)
         formatted = (f"Overall Acc: {r['Overall Acc']}\n"
                      f"Mean Acc: {r['Mean Acc']}\n"
                      f"FreqW Acc: {r['FreqW Acc']}\n"

@@ -190,3 +190,20 @@ def fused_evaluation(model, criterion, metrics: SegmentationMetrics, dataloader,
     r = metrics.get_results()
     return {"Loss": total / max(n, 1), "Overall Acc": r["Overall Acc"], "Mean Acc": r["Mean Acc"], "FreqW Acc": r["FreqW Acc"],
             "Mean IoU": r["Mean IoU"]}
+
+
+def fused_evaluation_tta(model, metrics: SegmentationMetrics, dataloader, device, tta) -> Dict:
+    """The validation pass under multi-scale / flip test-time augmentation (``tta``: a ``computervision.pytorch_amd.seg_tta.SegTTA``, DESIGN.md
+    section 7n): per batch ``tta.run`` (one input launch and one ``forward_rows`` per scale) and one ``cvx_seg_fuse`` launch that counts
+    into ``metrics.add_labels_counts(device)``; the host synchronises ONCE, when the matrix is read after the last batch.  Returns the
+    four accuracies; the criterion's value is not defined on this path, so there is no "Loss"."""
+    model.eval()
+    metrics.reset()
+    counts = metrics.add_labels_counts(device)
+    with torch.no_grad():
+        for images, targets in dataloader:
+            images = images.to(device, non_blocking=True)
+            views = tta.run(model, images)
+            tta.fuse(views, metrics.num_classes, model.layout.nc_pad, images.shape[2:], targets=targets, counts=counts, labels=False)
+    r = metrics.get_results()
+    return {"Overall Acc": r["Overall Acc"], "Mean Acc": r["Mean Acc"], "FreqW Acc": r["FreqW Acc"], "Mean IoU": r["Mean IoU"]}

@@ -875,6 +875,39 @@ int cvx_track_update(const float* rows, const int32_t* counts, int32_t batch, in
 int cvx_draw_tracks(const cvx_frame_job* jobs, int32_t batch, int32_t max_h, int32_t max_w, const float* rows, const int32_t* counts, int32_t max_det,
                     const int32_t* ids, const uint8_t* lut, int32_t lut_entries, int32_t thickness, int32_t font_scale, void* hip_stream);
 
+/* ---- multi-scale and flip test-time augmentation for segmentation (csrc/seg_tta.hip) --------------------------------
+ * The network runs on the batch at several zooms and on its mirror image; the class scores of all views are fused per pixel at the
+ * picture's size.  Both entries are one launch, asynchronous on hip_stream, and read nothing back.  The reference has no counterpart: the
+ * rules are the project's own, restated in numpy in tests/seg_tta_restatement.py.
+ * cvx_seg_tta_inputs: images (batch, c, h, w) fp32 -> out (batch * (1 + with_flip), c, oh, ow) fp32.  Image b of the output is the
+ * bilinear resize of image b (align_corners = False, no antialiasing: the taps bilinear_src(y, (float)h / (float)oh, h) and
+ * bilinear_src(x, (float)w / (float)ow, w) of csrc/bilinear.h, the value bilinear_mix); with with_flip, image batch + b is the resized
+ * picture mirrored, out[batch + b, :, y, x] = out[b, :, y, ow - 1 - x] -- the resize first, the mirror second.  At (oh, ow) == (h, w) the
+ * plain half is a bit-exact copy (every tap has lam == 0).  batch * c <= 65535, oh <= 65535. */
+int cvx_seg_tta_inputs(const float* images_nchw, int32_t batch, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t with_flip,
+                       float* out_nchw, void* hip_stream);
+/* One view of the fusion: rows (batch, lh * lw, ld) fp32 (device) as the DeepLab engine's forward leaves them for that view's input;
+ * flip != 0: the view saw the mirrored picture.  24 bytes. */
+typedef struct cvx_seg_view {
+  const float* rows;
+  int32_t lh, lw, flip, reserved;
+} cvx_seg_view;
+/* views_host: 1 <= n_views <= 16 entries in HOST memory, read before the call returns and handed to the kernel by value (no device table,
+ * nothing to keep alive).  Per output pixel (b, y, x), over the views in table order:
+ *   xs      flip_k ? ow - 1 - x : x;
+ *   z_k[c]  the logit by the taps bilinear_src(y, (float)lh_k / (float)oh, lh_k) and bilinear_src(xs, (float)lw_k / (float)ow, lw_k), mixed
+ *           with bilinear_mix: bit-identical to cvx_resize_bilinear_rows_to_nchw's output for that view at (oh, ow), read at (y, xs) -- one
+ *           interpolation from the logit level to the output size, as in cvx_seg_eval;
+ *   mode 0  ("logits") acc[c] = acc[c] + z_k[c] from 0.0f, one rounded add per view;
+ *   mode 1  ("prob")   m_k = max_c z_k[c], e = expf(z_k[c] - m_k), acc[c] += e / sum_c e.
+ * Outputs, each optional (at least one): labels (batch, oh, ow) uint8, the arg max of acc with strict > (the lowest class wins a tie;
+ * nc <= 256); with target (batch, oh, ow) int64 and confusion (nc, nc) int64 (added to, never cleared) confusion[target * nc + label] += 1
+ * for targets in [0, nc), others skipped -- an LDS histogram per workgroup for nc <= 90 and direct 64-bit atomics above, as cvx_seg_eval;
+ * probs_nchw (batch, nc, oh, ow) fp32 = acc[c] / n_views, mode 1 only (refused in mode 0).  The padding columns nc .. ld - 1 are never
+ * read as classes.  batch, oh <= 65535. */
+int cvx_seg_fuse(const cvx_seg_view* views_host, int32_t n_views, int32_t ld, int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t mode,
+                 uint8_t* labels, const int64_t* target, int64_t* confusion, float* probs_nchw, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 
