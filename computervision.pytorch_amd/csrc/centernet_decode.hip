@@ -15,11 +15,12 @@
 //   K1 peak_scores   one thread per (b, y, x, c): window max on the LOGITS (sigmoid is monotone: the arg-max is the same,
 //                    and `heat == hmax` is evaluated on the two sigmoid values exactly as the reference does) -> fp32 scores
 //   K2 select        one 1024-thread workgroup per image: 3-pass radix select of the K-th largest score (LDS histograms),
-//                    collection of the candidates, in-LDS bitonic sort, boxes, mask, greedy DIoU-NMS by one wave
+//                    collection of the candidates, in-LDS bitonic sort (lds_sort.h), boxes, mask, greedy DIoU-NMS by one wave
 #include <cstring>
 
 #include "../../include/cvx_engine.h"
 #include "cvx_common.h"
+#include "lds_sort.h"
 
 namespace {
 
@@ -214,32 +215,14 @@ __device__ int topk_sorted(const unsigned* key, long long n, unsigned idx0, int 
       const unsigned k = k4[u];
       if (k >= T && k != 0) {  // zero = suppressed / never a detection (conf > 0): a top-K that reaches into the zeros is cut short
         const unsigned slot = atomicAdd(&sh.ncand, 1u);
-        if (slot < CAND_CAP) sh.cand[slot] = ((unsigned long long)(0xFFFFFFFFu - k) << 32) | (idx0 + (unsigned)(i + u));
+        if (slot < CAND_CAP) sh.cand[slot] = score_key_bits(k, idx0 + (unsigned)(i + u));
       }
     }
   }
   __syncthreads();
   const unsigned ncand = sh.ncand;
   if (ncand > CAND_CAP) return -1;
-  unsigned cap2 = 1;
-  while (cap2 < ncand) cap2 <<= 1;
-  for (unsigned i = ncand + tid; i < cap2; i += SEL_THREADS) sh.cand[i] = ~0ull;
-  __syncthreads();
-  for (unsigned k = 2; k <= cap2; k <<= 1)
-    for (unsigned j = k >> 1; j > 0; j >>= 1) {
-      for (unsigned i = tid; i < cap2; i += SEL_THREADS) {
-        const unsigned l = i ^ j;
-        if (l > i) {
-          const unsigned long long x = sh.cand[i], z = sh.cand[l];
-          const bool up = (i & k) == 0;
-          if ((x > z) == up) {
-            sh.cand[i] = z;
-            sh.cand[l] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  lds_sort_keys<SEL_THREADS>(sh.cand, (int)ncand);
   return (int)ncand;
 }
 
@@ -272,12 +255,10 @@ __global__ __launch_bounds__(SEL_THREADS) void finish_kernel(const float* pred, 
   const long long N = (long long)H * W * C;
   const float* sc = scores + (long long)b * N;
   const int total = S * K;
-  unsigned cap2 = 1;
-  while ((int)cap2 < total) cap2 <<= 1;
   if (tid == 0) s_over = 0;
   __syncthreads();
-  for (unsigned i = tid; i < cap2; i += SEL_THREADS) {
-    const unsigned long long v = (int)i < total ? slice_top[(long long)b * total + i] : ~0ull;
+  for (int i = tid; i < total; i += SEL_THREADS) {
+    const unsigned long long v = slice_top[(long long)b * total + i];
     if (v == 0xFFFFFFFF00000000ull) s_over = 1;
     cand[i] = v;
   }
@@ -286,21 +267,7 @@ __global__ __launch_bounds__(SEL_THREADS) void finish_kernel(const float* pred, 
     if (tid == 0) o.counts[b] = -1;
     return;
   }
-  for (unsigned k = 2; k <= cap2; k <<= 1)
-    for (unsigned j = k >> 1; j > 0; j >>= 1) {
-      for (unsigned i = tid; i < cap2; i += SEL_THREADS) {
-        const unsigned l = i ^ j;
-        if (l > i) {
-          const unsigned long long x = cand[i], z = cand[l];
-          const bool up = (i & k) == 0;
-          if ((x > z) == up) {
-            cand[i] = z;
-            cand[l] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  lds_sort_keys<SEL_THREADS>(cand, total);
   int ncand = 0;  // valid keys come first after the sort
   for (int i = 0; i < K && i < total; ++i)
     if (cand[i] != ~0ull) ++ncand;

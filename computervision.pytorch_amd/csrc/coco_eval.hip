@@ -3,7 +3,7 @@
 // per evaluation (cvx_coco_accumulate) and the twelve means (cvx_coco_summarize).  Nothing is read by the host between the batches.
 //
 //   K1 coco_match   one workgroup per image.  Its ground truth lives in LDS; its rows are ordered there by (class, score descending, row) --
-//                   one 64-bit key per row, bitonic sort -- which puts every class's detections in COCOeval's order; the first 100 of a
+//                   one 64-bit key per row, the bitonic sort of lds_sort.h -- which puts every class's detections in COCOeval's order; the first 100 of a
 //                   class are evaluated.  Then a wave takes one class at a time: its lanes stage the class's boxes (box map, int(), widths
 //                   in fp32, then fp64), and lane a * 10 + t runs evaluateImg's greedy walk for area range a and IoU threshold t over them,
 //                   IoUs computed as it goes (fp64, no contraction).  Nothing crosses lanes: the "ground truth already matched" bits and
@@ -17,6 +17,7 @@
 //                   writes that threshold's precision (searchsorted side='left').
 //   K4 coco_summarize    the twelve means over the entries > -1, partial sums in a fixed tree order
 #include "det_common.h"
+#include "lds_sort.h"
 #include "../../include/cvx_engine.h"
 
 #pragma clang fp contract(off)  // COCOeval's doubles are rounded after every operation
@@ -165,21 +166,7 @@ __global__ __launch_bounds__(DET_THREADS) void coco_match_kernel(const float* __
     }
     keys[r] = key;
   }
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P; i += DET_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long x = keys[i], y = keys[ixj];
-          if ((x > y) == ((i & k) == 0)) {
-            keys[i] = y;
-            keys[ixj] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  lds_sort_keys<DET_THREADS>(keys, P);  // P is a power of two: nothing is padded
 
   // score, class and rank of every record; the records past a class's first 100 take part in nothing
   for (int i = tid; i < n; i += DET_THREADS) {

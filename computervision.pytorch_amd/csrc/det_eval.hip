@@ -14,13 +14,14 @@
 //                   detection maps its box to the original image (mode 1: (x - px) * gx, uncontracted), truncates it, quantises its score
 //                   to the 4 decimals the reference's text keeps and picks its ground truth.  Because that choice ignores `used`, the
 //                   sequential rule is the same as: of the detections of one image that chose ground truth g with IoU >= threshold, the TP
-//                   is the first by (score descending, row ascending) -- an LDS atomic-min on that key.  Pass 2 writes the flags.  Records go
+//                   is the first by (score descending, row ascending) -- an LDS atomic-min on that key (lds_sort.h).  Pass 2 writes the flags.  Records go
 //                   to [cursor + prefix(counts)[image], ...): image order, then row order, whatever order the workgroups run in.
 //   K2 det_cursor   cursor += sum(counts) (a launch of its own: K1 reads the cursor of the previous batch)
 //   K3 det_ap       one workgroup per class over the records in the reference's order: chunked inclusive scans of TP and FP -> precision
 //                   and recall in fp64; a second, backward sweep carries the suffix maximum and sums the change-point terms
 //   K4 det_map      mean of the APs of the classes that have a non-difficult ground truth
 #include "det_common.h"
+#include "lds_sort.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __r
         }
       }
     }
-    const unsigned long long key = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(q)) << 32) | (unsigned)r;
+    const unsigned long long key = score_key(q, (unsigned)r);
     if (m >= 0 && ovmax >= min_overlap) {
       if (gbox[m * 6 + 5])
         m = -2;
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __r
     if (m == -2) {
       flag = FLAG_NEITHER;
     } else if (m >= 0) {
-      const unsigned long long key = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(qscore[r])) << 32) | (unsigned)r;
+      const unsigned long long key = score_key(qscore[r], (unsigned)r);
       flag = best[m] == key ? FLAG_TP : FLAG_FP;
     }
     rec_flag[base + r] = flag;

@@ -21,9 +21,9 @@
 // Evaluation (cvx_seg_eval, the reference's evaluate_loop, segmentation_trainer.py:133-159, and evaluate_on_voc,
 // segmentation_2d.py:146-157): seg_eval_kernel walks the label pixels the same way -- the same taps, the same online softmax, the same
 // loss definitions -- and keeps the arg max instead of a gradient: confusion[target][argmax] += 1 and the batch's criterion value, with
-// no (B, nc, H, W) tensor and no gradient written.  K3 finishes its loss sum.
-#include "bilinear.h"
+// no (B, nc, H, W) tensor and no gradient written.  K3 finishes its loss sum.  The LDS histogram is seg_tail.h's.
 #include "cvx_common.h"
+#include "seg_tail.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void seg_eval_kernel(const float* rows, int ld
   extern __shared__ unsigned int hist[];
   __shared__ double s_sum[4], s_cnt[4];
   if (LDS_HIST) {
-    for (int i = threadIdx.x; i < nc * nc; i += 256) hist[i] = 0u;
+    hist_zero<256>(hist, nc);
     __syncthreads();
   }
   const long long n = (long long)B * OH * OW;
@@ -206,18 +206,11 @@ __global__ __launch_bounds__(256) void seg_eval_kernel(const float* rows, int ld
       my_cnt += 1.0;
     }
     if (in_range) {
-      const int cell = (int)tg * nc + arg;
-      if (LDS_HIST) atomicAdd(&hist[cell], 1u);
-      else atomicAdd(confusion + cell, 1ull);
+      if (LDS_HIST) hist_add(hist, nc, (int)tg, arg);
+      else atomicAdd(confusion + (int)tg * nc + arg, 1ull);
     }
   }
-  if (LDS_HIST) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < nc * nc; i += 256) {
-      const unsigned int v = hist[i];
-      if (v) atomicAdd(confusion + i, (unsigned long long)v);
-    }
-  }
+  if (LDS_HIST) hist_flush<256>(hist, nc, confusion);
   block_pair_to_part(my_loss, my_cnt, s_sum, s_cnt, part);
 }
 

@@ -14,12 +14,14 @@
 // cls * (max coordinate + 1) in fp32, class-agnostic pass over the shifted, re-rounded boxes), plus the library's own
 // switch between them by candidate count.
 //
-// One workgroup per image: the (score,index) keys are sorted with an in-LDS bitonic network
-// (<= 16384 candidates = 128 KB of the CU's 160 KB LDS), the suppression matrix is built as 64-bit
-// row masks in HBM by all 16 waves, and one wave walks it.
+// One workgroup per image: the (score,index) keys are sorted with an in-LDS bitonic network (lds_sort.h;
+// <= 16384 candidates = 128 KB of the CU's 160 KB LDS), the suppression matrix is built as 64-bit
+// row masks in HBM by all 16 waves, and one wave walks it (greedy_walk of mask_nms.h).  The overlap test is iou_gt of box_overlap.h.
 #include <cstring>
 #include "box_overlap.h"
 #include "cvx_common.h"
+#include "lds_sort.h"
+#include "mask_nms.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -163,7 +165,6 @@ __device__ __forceinline__ float4 class_shift(const float4& bx, int cls, float u
   const float off = (float)cls * unit;
   return make_float4(bx.x + off, bx.y + off, bx.z + off, bx.w + off);
 }
-// box_area / iou_gt: box_overlap.h, shared with the tile merge
 
 struct NmsWs {
   float4* box;              // [B][cap] sorted boxes (xyxy)
@@ -181,14 +182,10 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
   extern __shared__ unsigned long long keys[];  // cap2 entries (power of two >= candidates)
   __shared__ int s_n;
   __shared__ unsigned long long s_removed[NMS_CAP / 64];
-  __shared__ int s_nkeep;
   __shared__ float s_wmax[NMS_THREADS / 64];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* yb = y + (long long)b * (4 + nc) * A;
-  if (tid == 0) {
-    s_n = 0;
-    s_nkeep = 0;
-  }
+  if (tid == 0) s_n = 0;
   __syncthreads();
   // ---- 1. candidates: best class score > conf (ultralytics_ops.py:190,225-226) ----
   for (int a0 = 0; a0 < A; a0 += NMS_THREADS) {
@@ -199,7 +196,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
     }
     if (a < A && best > conf_thres) {
       int slot = atomicAdd(&s_n, 1);
-      if (slot < cap) keys[slot] = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(best)) << 32) | (unsigned)a;
+      if (slot < cap) keys[slot] = score_key(best, (unsigned)a);
     }
   }
   __syncthreads();
@@ -208,27 +205,8 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
     return;
   }
   const int n = min(s_n, cap);
-  int cap2 = 1;
-  while (cap2 < n) cap2 <<= 1;
-  for (int i = n + tid; i < cap2; i += NMS_THREADS) keys[i] = ~0ull;
-  __syncthreads();
   // ---- 2. bitonic sort ascending on (inverted score, anchor) = score desc, anchor asc ----
-  for (int k = 2; k <= cap2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < cap2; i += NMS_THREADS) {
-        int l = i ^ j;
-        if (l > i) {
-          unsigned long long x = keys[i], z = keys[l];
-          bool up = (i & k) == 0;
-          if ((x > z) == up) {
-            keys[i] = z;
-            keys[l] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  lds_sort_keys<NMS_THREADS>(keys, n);
   // ---- 3. gather sorted candidates ----
   // torchvision 0.14.1 batched_nms: vanilla when boxes.numel() = 4 n exceeds 20000 (CUDA tensor) / 4000 (CPU tensor)
   const bool offset_mode = variant == CVX_NMS_OFFSET || (variant == CVX_NMS_TV0141_CUDA && 4 * n <= 20000) ||
@@ -300,27 +278,9 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
     }
     mat[(long long)i * nw + wj] = bits;
   }
-  for (int i = tid; i < nw; i += NMS_THREADS) s_removed[i] = 0;
-  __threadfence_block();
-  __syncthreads();
-  // ---- 5. greedy walk by wave 0 ----
-  if (tid < 64) {
-    int nkeep = 0;
-    for (int i = 0; i < n && nkeep < max_det; ++i) {
-      bool dead = (s_removed[i >> 6] >> (i & 63)) & 1ull;  // uniform
-      if (dead) continue;
-      if (tid == 0) out_index[(long long)b * max_det + nkeep] = i;  // the keep list lives in the output's own index column until step 6
-      ++nkeep;
-      for (int wj = tid; wj < nw; wj += 64) s_removed[wj] |= mat[(long long)i * nw + wj];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    if (tid == 0) s_nkeep = nkeep;
-  }
-  __syncthreads();
+  // ---- 5. greedy walk by wave 0 (mask_nms.h): the keep list lives in the output's own index column until step 6 ----
+  const int nk = greedy_walk<NMS_THREADS>(mat, s_removed, n, max_det, out_index + (long long)b * max_det);
   // ---- 6. emit ----
-  const int nk = s_nkeep;
   for (int r = tid; r < nk; r += NMS_THREADS) {
     int i = out_index[(long long)b * max_det + r];  // (each thread reads and rewrites only its own slots)
     float4 bx = box[i];

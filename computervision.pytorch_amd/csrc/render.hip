@@ -14,12 +14,12 @@
 //   K3 seg_overlay    a thread per 4 pixels of a frame row: nearest source pixel at network size (OpenCV's resizeNN index rule, as the
 //                     letterbox kernel has it), the nc logits there from the four feature rows (bilinear.h: the numbers cvx_seg_eval and
 //                     cvx_resize_bilinear_rows_to_nchw see), arg max (strict >: the lowest class wins a tie), palette, 50/50 blend in
-//                     integers with round-half-even (cv2.addWeighted(a, .5, b, .5, 0) on uint8).
+//                     integers with round-half-even (cv2.addWeighted(a, .5, b, .5, 0) on uint8).  The logit chunk, the arg max and the
+//                     pixel quad are seg_tail.h's, shared with seg_tiles.hip and seg_tta.hip.
 // Byte kernels, HBM-bound: 12 bytes per thread go out (and, in K3, come in) as three dwords when the frame's base and stride allow it.
 // Every fp32 step is one rounded operation, so the file is compiled with contraction off (bilinear.h spells its fused steps out).
-#include "bilinear.h"
 #include "det_common.h"
-#include "pixel_blend.h"
+#include "seg_tail.h"
 #include "../../include/cvx_engine.h"
 
 #pragma clang fp contract(off)
@@ -273,60 +273,26 @@ __global__ __launch_bounds__(256) void seg_overlay_kernel(const cvx_frame_job* _
   const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
   const int npx = min(4, w - x0);
   uint8_t* p = jb.data + (long long)y * jb.stride + (long long)x0 * 3;
-  const bool wide = npx == 4 && ((reinterpret_cast<uintptr_t>(jb.data) | (uintptr_t)jb.stride) & 3) == 0;
-  uint8_t px[12];
-  if (wide) {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    const uint32_t a = q[0], b = q[1], c = q[2];
-    for (int k = 0; k < 4; ++k) {
-      px[k] = (uint8_t)(a >> 8 * k);
-      px[4 + k] = (uint8_t)(b >> 8 * k);
-      px[8 + k] = (uint8_t)(c >> 8 * k);
-    }
-  } else {
-    for (int k = 0; k < 3 * npx; ++k) px[k] = p[k];
-  }
+  const bool wide = quad_is_wide(jb.data, jb.stride, npx);
+  pixel_quad px;
+  quad_load(p, npx, wide, px);
+  const float* ra = base + (long long)y0 * lw * ld;
+  const float* rb = base + (long long)y1 * lw * ld;
   for (int k = 0; k < npx; ++k) {
     int sx = (int)floor((double)(x0 + k) * ifx);
     sx = sx < NW - 1 ? sx : NW - 1;
     int xa, xb;
     float lx;
     bilinear_src(sx, (float)lw / (float)NW, lw, &xa, &xb, &lx);
-    const float* r00 = base + ((long long)y0 * lw + xa) * ld;
-    const float* r01 = base + ((long long)y0 * lw + xb) * ld;
-    const float* r10 = base + ((long long)y1 * lw + xa) * ld;
-    const float* r11 = base + ((long long)y1 * lw + xb) * ld;
-    float best = 0.f;
+    float best = 0.f, z[4];
     int arg = 0;
     for (int c0 = 0; c0 < nc; c0 += 4) {
-      float z[4];
-      if (vec && c0 + 4 <= ld) {
-        const f4 a = *reinterpret_cast<const f4*>(r00 + c0), b = *reinterpret_cast<const f4*>(r01 + c0);
-        const f4 c = *reinterpret_cast<const f4*>(r10 + c0), d = *reinterpret_cast<const f4*>(r11 + c0);
-        for (int i = 0; i < 4; ++i) z[i] = bilinear_mix(a[i], b[i], c[i], d[i], lx, ly);
-      } else {
-        for (int i = 0; i < 4; ++i) z[i] = c0 + i < nc ? bilinear_mix(r00[c0 + i], r01[c0 + i], r10[c0 + i], r11[c0 + i], lx, ly) : 0.f;
-      }
-      for (int i = 0; i < 4; ++i)
-        if (c0 + i < nc && (c0 + i == 0 || z[i] > best)) {   // strict >: the lowest class wins a tie, like torch.argmax
-          best = z[i];
-          arg = c0 + i;
-        }
+      logits4(ra + c0, rb + c0, xa, xb, lx, ly, ld, c0, nc, vec, z);
+      argmax4(z, c0, nc, best, arg);
     }
-    const uint8_t* col = lut + 3 * arg;
-    const unsigned r = blend_half(px[3 * k + 0], col[0]), g = blend_half(px[3 * k + 1], col[1]), b = blend_half(px[3 * k + 2], col[2]);
-    px[3 * k + 0] = (uint8_t)(bgr_out ? b : r);
-    px[3 * k + 1] = (uint8_t)g;
-    px[3 * k + 2] = (uint8_t)(bgr_out ? r : b);
+    quad_blend(px, k, lut + 3 * arg, bgr_out);
   }
-  if (wide) {
-    uint32_t* q = reinterpret_cast<uint32_t*>(p);
-    q[0] = px[0] | px[1] << 8 | px[2] << 16 | (uint32_t)px[3] << 24;
-    q[1] = px[4] | px[5] << 8 | px[6] << 16 | (uint32_t)px[7] << 24;
-    q[2] = px[8] | px[9] << 8 | px[10] << 16 | (uint32_t)px[11] << 24;
-  } else {
-    for (int k = 0; k < 3 * npx; ++k) p[k] = px[k];
-  }
+  quad_store(p, npx, wide, px);
 }
 
 }  // namespace

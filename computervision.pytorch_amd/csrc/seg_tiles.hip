@@ -9,7 +9,7 @@
 //                   integer distance-to-border product), acc = fma(w, z, acc).  No division by the weight sum: the arg max (strict >, the
 //                   lowest class wins a tie) does not need it.  Then the label byte, the 50/50 palette blend into the frame in place, and
 //                   confusion[target][label] += 1 through a per-workgroup LDS histogram that is flushed with one 64-bit atomic per
-//                   non-zero entry.
+//                   non-zero entry.  The arg max, the pixel quad and the histogram are seg_tail.h's.
 //                   The y side (covering ty range, taps, row weight) is the same for the whole workgroup: it is worked out once into LDS,
 //                   not per class chunk.  Classes go four at a time with the tile loop inside, so no nc-sized register array exists; 16
 //                   accumulators per thread.  HBM sees 1 label byte + 3 read + 3 written frame bytes per pixel; the taps come from L2
@@ -17,8 +17,7 @@
 //                   costs: 0.55 ms for two 1024 x 2048 frames, with or without the overlay and the counts.
 // Every fp32 step is one rounded operation, so the file is compiled with contraction off (bilinear.h spells its fused steps out) and
 // tests/seg_tiled_restatement.py holds the kernel to the bit.
-#include "bilinear.h"
-#include "pixel_blend.h"
+#include "seg_tail.h"
 #include "../../include/cvx_engine.h"
 
 #pragma clang fp contract(off)
@@ -79,8 +78,7 @@ __global__ __launch_bounds__(STITCH_THREADS) void seg_stitch_kernel(const float*
     }
   }
   if (tid <= ty_hi - ty_lo && tid < Y_STASH) stash[tid] = y_tap(ay, ty_lo + tid, y, tf.first_slot, nx, sy, lh);
-  if (count)
-    for (int i = tid; i < nc * nc; i += STITCH_THREADS) hist[i] = 0u;
+  if (count) hist_zero<STITCH_THREADS>(hist, nc);
   __syncthreads();
 
   const int npx = min(4, w - x0);   // <= 0: this thread has no pixel, it only helps with the histogram
@@ -96,19 +94,9 @@ __global__ __launch_bounds__(STITCH_THREADS) void seg_stitch_kernel(const float*
     }
 
   uint8_t* p = jb.data + (long long)y * jb.stride + (long long)x0 * 3;
-  const bool wide = draw && npx == 4 && ((reinterpret_cast<uintptr_t>(jb.data) | (uintptr_t)jb.stride) & 3) == 0;
-  uint8_t px[12];
-  if (wide) {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    const uint32_t a = q[0], b = q[1], c = q[2];
-    for (int k = 0; k < 4; ++k) {
-      px[k] = (uint8_t)(a >> 8 * k);
-      px[4 + k] = (uint8_t)(b >> 8 * k);
-      px[8 + k] = (uint8_t)(c >> 8 * k);
-    }
-  } else if (draw) {
-    for (int k = 0; k < 3 * npx; ++k) px[k] = p[k];
-  }
+  const bool wide = draw && quad_is_wide(jb.data, jb.stride, npx);
+  pixel_quad px;
+  if (draw) quad_load(p, npx, wide, px);
 
   const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
   const long long slot_stride = (long long)lh * lw * ld;
@@ -136,6 +124,8 @@ __global__ __launch_bounds__(STITCH_THREADS) void seg_stitch_kernel(const float*
           float lx;
           bilinear_src(dx, sx, lw, &xa, &xb, &lx);
           const float wk = linear ? (float)(t.wy * min(dx + 1, tw - dx)) : 1.0f;   // an integer below 2^24: exact
+          // the chunk of seg_tail.h's logits4, kept in line: through the helper this loop compiled to a different schedule that measured
+          // 3.5 % slower (0.57 against 0.55 ms for two 1024 x 2048 frames, profiles/eval_tail_refactor_ab.txt)
           const float *r00 = ra + (long long)xa * ld, *r01 = ra + (long long)xb * ld;
           const float *r10 = rb + (long long)xa * ld, *r11 = rb + (long long)xb * ld;
           float z[4];
@@ -154,13 +144,7 @@ __global__ __launch_bounds__(STITCH_THREADS) void seg_stitch_kernel(const float*
       }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (c0 + i < nc && (c0 + i == 0 || acc[k][i] > best[k])) {   // strict >: the lowest class wins a tie, like torch.argmax
-          best[k] = acc[k][i];
-          arg[k] = c0 + i;
-        }
+    for (int k = 0; k < 4; ++k) argmax4(acc[k], c0, nc, best[k], arg[k]);
   }
 
   if (npx > 0) {
@@ -176,21 +160,8 @@ __global__ __launch_bounds__(STITCH_THREADS) void seg_stitch_kernel(const float*
     }
     // ---- the overlay, in place ----
     if (draw) {
-      for (int k = 0; k < npx; ++k) {
-        const uint8_t* col = lut + 3 * arg[k];
-        const unsigned r = blend_half(px[3 * k + 0], col[0]), g = blend_half(px[3 * k + 1], col[1]), b = blend_half(px[3 * k + 2], col[2]);
-        px[3 * k + 0] = (uint8_t)(bgr_out ? b : r);
-        px[3 * k + 1] = (uint8_t)g;
-        px[3 * k + 2] = (uint8_t)(bgr_out ? r : b);
-      }
-      if (wide) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(p);
-        q[0] = px[0] | px[1] << 8 | px[2] << 16 | (uint32_t)px[3] << 24;
-        q[1] = px[4] | px[5] << 8 | px[6] << 16 | (uint32_t)px[7] << 24;
-        q[2] = px[8] | px[9] << 8 | px[10] << 16 | (uint32_t)px[11] << 24;
-      } else {
-        for (int k = 0; k < 3 * npx; ++k) p[k] = px[k];
-      }
+      for (int k = 0; k < npx; ++k) quad_blend(px, k, lut + 3 * arg[k], bgr_out);
+      quad_store(p, npx, wide, px);
     }
     // ---- the confusion counts of this row segment ----
     if (count) {
@@ -198,17 +169,11 @@ __global__ __launch_bounds__(STITCH_THREADS) void seg_stitch_kernel(const float*
       const uint8_t* q = tm.data + (long long)y * tm.pitch + x0;
       for (int k = 0; k < npx; ++k) {
         const int tg = q[k];
-        if (tg < nc) atomicAdd(&hist[tg * nc + arg[k]], 1u);
+        if (tg < nc) hist_add(hist, nc, tg, arg[k]);
       }
     }
   }
-  if (count) {
-    __syncthreads();
-    for (int i = tid; i < nc * nc; i += STITCH_THREADS) {
-      const unsigned v = hist[i];
-      if (v) atomicAdd(confusion + i, (unsigned long long)v);
-    }
-  }
+  if (count) hist_flush<STITCH_THREADS>(hist, nc, confusion);
 }
 
 }  // namespace

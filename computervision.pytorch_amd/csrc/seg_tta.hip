@@ -11,13 +11,14 @@
 //                      Mode 0: acc += z, one rounded add per view.  Mode 1: acc += softmax(z); a first pass over the taps leaves every
 //                      view's (max, sum of exp) per pixel in LDS, the second pass accumulates.  Then the arg max (strict >, the lowest
 //                      class wins a tie), the label byte, confusion[target][label] += 1 (LDS histogram or direct atomics, the split of
-//                      cvx_seg_eval) and, in mode 1, the mean probabilities.
+//                      cvx_seg_eval) and, in mode 1, the mean probabilities.  The logit chunk, the arg max and the LDS histogram are
+//                      seg_tail.h's, shared with render.hip and seg_tiles.hip.
 //                      The y taps of every view are the same for the whole workgroup: worked out once into LDS.  Classes go four at a time
 //                      with the view loop inside, so no nc-sized register array exists.  PX is 4 in mode 0 and 2 in mode 1, where the
 //                      per-view pairs cost 16 bytes of LDS per pixel and view.
 // Every fp32 step is one rounded operation, so the file is compiled with contraction off (bilinear.h spells its fused steps out) and
 // tests/seg_tta_restatement.py holds K1 and mode 0 of K2 to the bit.
-#include "bilinear.h"
+#include "seg_tail.h"
 #include "../../include/cvx_engine.h"
 
 #pragma clang fp contract(off)
@@ -56,23 +57,6 @@ __global__ __launch_bounds__(TTA_THREADS) void seg_tta_inputs_kernel(const float
   if (with_flip) q[(long long)planes * oh * ow + (ow - 1 - x)] = v;   // the resize first, the mirror second
 }
 
-// The logits of classes c0 .. c0 + 3 of one view at one pixel; classes past nc are 0 on the scalar path and whatever the padding holds
-// on the vector path -- the callers never look at them.
-__device__ __forceinline__ void view_logits(const float* ra, const float* rb, int xa, int xb, float lx, float ly, int ld, int c0, int nc, bool vec,
-                                            float z[4]) {
-  const float *r00 = ra + (long long)xa * ld, *r01 = ra + (long long)xb * ld;
-  const float *r10 = rb + (long long)xa * ld, *r11 = rb + (long long)xb * ld;
-  if (vec && c0 + 4 <= ld) {
-    const f4 a = *reinterpret_cast<const f4*>(r00), b = *reinterpret_cast<const f4*>(r01);
-    const f4 c = *reinterpret_cast<const f4*>(r10), d = *reinterpret_cast<const f4*>(r11);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = bilinear_mix(a[i], b[i], c[i], d[i], lx, ly);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = c0 + i < nc ? bilinear_mix(r00[i], r01[i], r10[i], r11[i], lx, ly) : 0.f;
-  }
-}
-
 template <int MODE>
 __global__ __launch_bounds__(TTA_THREADS) void seg_fuse_kernel(const ViewTable tab, int n_views, int ld, int nc, int oh, int ow, uint8_t* __restrict__ labels,
                                                                const long long* __restrict__ target, unsigned long long* __restrict__ confusion,
@@ -95,8 +79,7 @@ __global__ __launch_bounds__(TTA_THREADS) void seg_fuse_kernel(const ViewTable t
     t.reserved = 0;
     ytap[tid] = t;
   }
-  if (count && lds_hist)
-    for (int i = tid; i < nc * nc; i += TTA_THREADS) hist[i] = 0u;
+  if (count && lds_hist) hist_zero<TTA_THREADS>(hist, nc);
   __syncthreads();
 
   // ---- mode 1, first pass: (max, sum of exp) of every view at every pixel of this thread ----
@@ -115,13 +98,13 @@ __global__ __launch_bounds__(TTA_THREADS) void seg_fuse_kernel(const ViewTable t
         bilinear_src(v.flip ? ow - 1 - (x0 + j) : x0 + j, sx, v.lw, &xa, &xb, &lx);
         float m = -INFINITY, s = 0.f, z[4];
         for (int c0 = 0; c0 < nc; c0 += 4) {
-          view_logits(ra + c0, rb + c0, xa, xb, lx, t.lam, ld, c0, nc, vec, z);
+          logits4(ra + c0, rb + c0, xa, xb, lx, t.lam, ld, c0, nc, vec, z);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             if (c0 + i < nc) m = fmaxf(m, z[i]);
         }
         for (int c0 = 0; c0 < nc; c0 += 4) {
-          view_logits(ra + c0, rb + c0, xa, xb, lx, t.lam, ld, c0, nc, vec, z);
+          logits4(ra + c0, rb + c0, xa, xb, lx, t.lam, ld, c0, nc, vec, z);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             if (c0 + i < nc) s += expf(z[i] - m);
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(TTA_THREADS) void seg_fuse_kernel(const ViewTable t
         int xa, xb;
         float lx, z[4];
         bilinear_src(v.flip ? ow - 1 - (x0 + j) : x0 + j, sx, v.lw, &xa, &xb, &lx);
-        view_logits(ra, rb, xa, xb, lx, t.lam, ld, c0, nc, vec, z);
+        logits4(ra, rb, xa, xb, lx, t.lam, ld, c0, nc, vec, z);
         if (MODE == 0) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) acc[j][i] = acc[j][i] + z[i];
@@ -166,13 +149,7 @@ __global__ __launch_bounds__(TTA_THREADS) void seg_fuse_kernel(const ViewTable t
       }
     }
 #pragma unroll
-    for (int j = 0; j < PX; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (c0 + i < nc && (c0 + i == 0 || acc[j][i] > best[j])) {   // strict >: the lowest class wins a tie, like torch.argmax
-          best[j] = acc[j][i];
-          arg[j] = c0 + i;
-        }
+    for (int j = 0; j < PX; ++j) argmax4(acc[j], c0, nc, best[j], arg[j]);
     if (MODE == 1 && probs != nullptr) {
       const float n = (float)n_views;
 #pragma unroll
@@ -194,18 +171,11 @@ __global__ __launch_bounds__(TTA_THREADS) void seg_fuse_kernel(const ViewTable t
       for (int j = 0; j < npx; ++j) {
         const long long tg = target[at + j];
         if (tg < 0 || tg >= nc) continue;
-        const int cell = (int)tg * nc + arg[j];
-        if (lds_hist) atomicAdd(&hist[cell], 1u);
-        else atomicAdd(confusion + cell, 1ull);
+        if (lds_hist) hist_add(hist, nc, (int)tg, arg[j]);
+        else atomicAdd(confusion + (int)tg * nc + arg[j], 1ull);
       }
   }
-  if (count && lds_hist) {
-    __syncthreads();
-    for (int i = tid; i < nc * nc; i += TTA_THREADS) {
-      const unsigned v = hist[i];
-      if (v) atomicAdd(confusion + i, (unsigned long long)v);
-    }
-  }
+  if (count && lds_hist) hist_flush<TTA_THREADS>(hist, nc, confusion);
 }
 
 }  // namespace

@@ -9,9 +9,12 @@
 //                         base allow it, one pixel otherwise; a capped grid strides over the work.
 //   K2 det_merge_tiles    one workgroup per frame, the shape of nms_kernel (nms.hip): the rows of the frame's slots are moved to frame
 //                         coordinates (one fp32 add, then the clamp to the frame), ordered by (score desc, ordinal asc) with the 64-bit key and
-//                         the in-LDS bitonic network (<= 8192 candidates = 64 KB), the suppression matrix is built as 64-bit row masks in
-//                         the workspace by all 16 waves, and one wave walks it.  The overlap test is iou_gt or ios_gt of box_overlap.h.
+//                         the in-LDS bitonic network of lds_sort.h (<= 8192 candidates = 64 KB), the suppression matrix is built as 64-bit
+//                         row masks in the workspace by all 16 waves, and one wave walks it (greedy_walk of mask_nms.h).  The overlap test is
+//                         iou_gt or ios_gt of box_overlap.h.
 #include "box_overlap.h"
+#include "lds_sort.h"
+#include "mask_nms.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -82,12 +85,12 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const float* __res
                                                               float* __restrict__ out_rows, int* __restrict__ out_counts, int* out_source,
                                                               int* overflow) {
   extern __shared__ unsigned long long keys[];  // cap2 entries (power of two >= candidates)
-  __shared__ int s_n, s_fill, s_nkeep;
+  __shared__ int s_n, s_fill;
   __shared__ unsigned long long s_removed[MERGE_CAP / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   float* orow = out_rows + (long long)f * max_det * 6;
   int* osrc = out_source + (long long)f * max_det;
-  if (tid == 0) s_n = s_fill = s_nkeep = 0;
+  if (tid == 0) s_n = s_fill = 0;
   __syncthreads();
   // ---- 1. how many candidates: the counts of this frame's slots; a count outside [0, max_det_in] contributes nothing and is flagged ----
   for (int s = tid; s < slots; s += MERGE_THREADS) {
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const float* __res
     }
     return;
   }
-  // ---- 2. keys: (score desc, ordinal asc), the key of nms_kernel with the ordinal s * max_det_in + r in the low word ----
+  // ---- 2. keys: (score desc, ordinal asc), the ordinal s * max_det_in + r in the low word; then the sort ----
   const long long cells = (long long)slots * max_det_in;
   for (long long e = tid; e < cells; e += MERGE_THREADS) {
     const int s = (int)(e / max_det_in), r = (int)(e - (long long)s * max_det_in);
@@ -115,28 +118,9 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const float* __res
     const int c = counts[s];
     if (c < 0 || c > max_det_in || r >= c) continue;
     const int at = atomicAdd(&s_fill, 1);
-    keys[at] = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(rows[e * 6 + 4])) << 32) | (unsigned)e;
+    keys[at] = score_key(rows[e * 6 + 4], (unsigned)e);
   }
-  int cap2 = 1;
-  while (cap2 < n) cap2 <<= 1;
-  for (int i = n + tid; i < cap2; i += MERGE_THREADS) keys[i] = ~0ull;
-  __syncthreads();
-  for (int k = 2; k <= cap2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < cap2; i += MERGE_THREADS) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned long long x = keys[i], z = keys[l];
-          const bool up = (i & k) == 0;
-          if ((x > z) == up) {
-            keys[i] = z;
-            keys[l] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  lds_sort_keys<MERGE_THREADS>(keys, n);
   // ---- 3. gather the sorted candidates in frame coordinates ----
   float4* box = ws.box + (long long)f * MERGE_CAP;
   float* score = ws.score + (long long)f * MERGE_CAP;
@@ -175,28 +159,9 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const float* __res
     }
     mat[(long long)i * nw + wj] = bits;
   }
-  for (int i = tid; i < nw; i += MERGE_THREADS) s_removed[i] = 0;
-  __threadfence_block();
-  __syncthreads();
-  // ---- 5. greedy walk by wave 0 ----
-  if (tid < 64) {
-    int nkeep = 0;
-    for (int i = 0; i < n && nkeep < max_det; ++i) {
-      const bool dead = (s_removed[i >> 6] >> (i & 63)) & 1ull;  // uniform
-      if (dead) continue;
-      if (tid == 0) osrc[nkeep] = i;  // the keep list lives in the source column until step 6
-      ++nkeep;
-      for (int wj = tid; wj < nw; wj += 64) s_removed[wj] |= mat[(long long)i * nw + wj];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    if (tid == 0) s_nkeep = nkeep;
-  }
-  __threadfence_block();
-  __syncthreads();
+  // ---- 5. greedy walk by wave 0 (mask_nms.h): the keep list lives in the source column until step 6 ----
+  const int nk = greedy_walk<MERGE_THREADS>(mat, s_removed, n, max_det, osrc);
   // ---- 6. emit: the kept rows in order, zero rows and source -1 past the count ----
-  const int nk = s_nkeep;
   for (int r = tid; r < max_det; r += MERGE_THREADS) {
     float* o = orow + (long long)r * 6;
     if (r < nk) {

@@ -142,30 +142,42 @@ def test_draw_detections_equals_the_restatement(dev, thickness, font_scale):
 
 
 # ---- 4. segmentation overlay ------------------------------------------------------------------------------------------------------------
+OVERLAY_TIES = {21: ((5, 11), (20, 3)), 5: ((1, 3), (4, 2)), 3: ((1, 2), (2, 0))}
+
+
+@pytest.mark.parametrize("nc,ld", [(3, 4), (5, 5), (21, 24)])          # the vector path, the scalar path, the production padding
 @pytest.mark.parametrize("bgr", [False, True])
-def test_seg_overlay_equals_the_restatement(dev, bgr):
-    nc, ld, lh, lw, NH, NW = 21, 24, 9, 9, 33, 33
+def test_seg_overlay_equals_the_restatement(dev, bgr, nc, ld):
+    lh, lw, NH, NW = 9, 9, 33, 33
+    (t0, t1), (t2, t3) = OVERLAY_TIES[nc]
     rng = np.random.RandomState(7)
-    logits = (rng.randint(-64, 64, (2, lh * lw, ld)) / 8.0).astype(np.float32)
-    logits[0, :20, 5] = logits[0, :20, 11] = 9.0                # exact ties between classes 5 and 11 (and with themselves in the mix)
+    logits = (rng.randint(-64, 64, (4, lh * lw, ld)) / 8.0).astype(np.float32)
+    logits[0, :20, t0] = logits[0, :20, t1] = 9.0              # exact ties between two classes (and with themselves in the mix)
     logits[1, 30:60, :nc] = 1.0                                 # every class ties: class 0
-    logits[1, 60:70, 20] = logits[1, 60:70, 3] = 10.0
-    shapes = [(50, 41), (20, 27)]                               # up and down from 33 x 33
+    logits[1, 60:70, t2] = logits[1, 60:70, t3] = 10.0
+    logits[2:, :, nc:] = 100.0                                  # the padding columns are not classes
+    # up and down from 33 x 33 with row strides 123 and 81 (the byte path); stride 132 (three dwords per thread); a thread with one pixel
+    shapes = [(50, 41), (20, 27), (24, 44), (3, 1)]
     host = pictures(shapes, 8)
     host[0][0, :8] = [[0, 1, 2], [3, 4, 5], [128, 129, 130], [131, 255, 254], [7, 6, 5], [64, 65, 66], [67, 192, 193], [194, 195, 0]]
     frames = on(dev, host)
+    assert [f.stride(0) % 4 for f in frames[:3]] == [3, 1, 0] and all(f.data_ptr() % 4 == 0 for f in frames)
     lut = R.palette(nc)
     R.seg_overlay(frames, torch.from_numpy(logits).to(dev), nc, (lh, lw), (NH, NW), bgr=bgr)
     torch.cuda.synchronize()
-    parities = set()
-    for b in range(2):
+    parities, classes = set(), set()
+    for b in range(4):
         want = RS.seg_overlay(host[b], logits[b], nc, lh, lw, NH, NW, lut, bgr=bgr)
         got = frames[b].cpu().numpy()
         assert np.array_equal(got, want), (b, np.argwhere((got != want).any(2))[:5])
         cls = RS.argmax_lowest(RS.logits_at_network_size(logits[b], nc, lh, lw, NH, NW), 0)[RS.nearest_index(shapes[b][0], NH)][:, RS.nearest_index(shapes[b][1], NW)]
         parities |= set(((host[b].astype(int) + lut[cls].astype(int)) % 4).reshape(-1).tolist())
-        assert len(np.unique(cls)) > 3
+        classes |= set(np.unique(cls).tolist())
+        if nc == 21 and b < 2:
+            assert len(np.unique(cls)) > 3
     assert parities == {0, 1, 2, 3}
+    if nc < 21:
+        assert classes == set(range(nc))
 
 
 # ---- 5. YOLOv8 end to end ---------------------------------------------------------------------------------------------------------------

@@ -114,21 +114,25 @@ MERGE_FRAME_HW = np.array([[120, 150], [64, 64], [140, 160]], np.int32)         
 K_IN = 16
 
 
-def merge_case(seed):
-    """7 slots over 3 frames, jittered copies of a few base boxes per frame (in the slots' own pixels), scores from a small set so that ties
-    occur, slot 5 with count 0"""
-    rng = np.random.RandomState(seed)
+def draw_rows(rng, slot_map, counts, k_in):
+    """jittered copies of a few base boxes (in the slots' own pixels), scores from a small set so that ties occur, three classes"""
     base = np.array([[20, 20, 70, 80], [60, 30, 120, 90], [10, 70, 60, 118], [90, 60, 150, 125]], np.float32)
-    rows = np.zeros((7, K_IN, 6), np.float32)
-    counts = np.array([16, 11, 9, 13, 16, 0, 7], np.int32)
-    for s in range(7):
+    rows = np.zeros((len(counts), k_in, 6), np.float32)
+    for s in range(len(counts)):
         for r in range(counts[s]):
             box = base[rng.randint(4)] + rng.randint(-6, 7, 4).astype(np.float32) * np.float32(0.75)
             if rng.rand() < 0.3:                                     # the part of the box a tile border leaves
                 box[2] = box[0] + (box[2] - box[0]) * np.float32(0.4)
-            box[[0, 2]] -= SLOT_MAP[s, 1]
-            box[[1, 3]] -= SLOT_MAP[s, 2]
+            box[[0, 2]] -= slot_map[s, 1]
+            box[[1, 3]] -= slot_map[s, 2]
             rows[s, r] = [*box, rng.choice([0.9, 0.75, 0.5, 0.25]), rng.randint(3)]
+    return rows
+
+
+def merge_case(seed):
+    """7 slots over 3 frames, slot 5 with count 0"""
+    counts = np.array([16, 11, 9, 13, 16, 0, 7], np.int32)
+    rows = draw_rows(np.random.RandomState(seed), SLOT_MAP, counts, K_IN)
     rows[5, :3] = rows[0, :3]                                        # rows past a count are not candidates
     return rows, counts
 
@@ -157,6 +161,32 @@ def test_merge_kernel_equals_the_restatement(dev, merge_inputs, metric, agnostic
     for f in (0, 2):                                                 # the case bites: every non-empty frame suppresses and keeps
         assert 2 <= want[1][f] and everything[f] < candidates[f], (f, want[1], everything, candidates)
     check_merge(R.merge_tiles(d_rows, d_counts, d_map, d_hw, metric, 0.5, agnostic, max_det), want)
+
+
+WORD_SLOT_MAP = np.array([[0, 0, 0, 0], [0, 40, 0, 0], [0, 0, 30, 0]], np.int32)
+WORD_FRAME_HW = np.array([[140, 200]], np.int32)
+WORD_K, WORD_SEED = 64, 11
+
+
+@pytest.mark.parametrize("metric", ["iou", "ios"])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 129])
+def test_merge_kernel_across_a_mask_word_edge(dev, n, metric):
+    """n candidates of one frame, filled slot by slot into three slots of 64: the suppression matrix has one, two and three 64-bit words per
+    row, and a kept candidate of word 0 has to remove a candidate of word 1"""
+    counts = np.array([min(WORD_K, max(0, n - WORD_K * s)) for s in range(3)], np.int32)
+    rows = draw_rows(np.random.RandomState(WORD_SEED), WORD_SLOT_MAP, counts, WORD_K)
+    want = TR.merge(rows, counts, WORD_SLOT_MAP, WORD_FRAME_HW, metric, 0.5, False, 300)
+    ordinals = np.concatenate([s * WORD_K + np.arange(counts[s]) for s in range(3)]).astype(np.uint64)
+    score_bits = rows.reshape(-1, 6)[ordinals.astype(np.int64), 4].view(np.uint32).astype(np.uint64)
+    order = np.argsort(((np.uint64(0xFFFFFFFF) - score_bits) << np.uint64(32)) | ordinals, kind="stable")
+    position = {int(ordinals[o]): i for i, o in enumerate(order)}    # ordinal -> place under (score desc, ordinal asc)
+    kept = sorted(position[int(o)] for o in want[2][0, :want[1][0]])
+    assert want[3] == 0 and 1 <= len(kept) <= n
+    if n == 65:                                                      # the one candidate of word 1 falls to a kept candidate of word 0
+        assert max(kept) < 64, kept
+    if n == 129 and metric == "iou":                                 # and the walk keeps candidates beyond word 0
+        assert max(kept) >= 64, kept
+    check_merge(R.merge_tiles(*on(dev, [rows, counts, WORD_SLOT_MAP, WORD_FRAME_HW]), metric, 0.5, False, 300), want)
 
 
 def test_merge_kernel_flags_a_bad_count(dev, merge_inputs):
