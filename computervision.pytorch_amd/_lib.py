@@ -129,6 +129,8 @@ PROTOTYPES = {
     "cvx_seg_stitch": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_seg_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "cvx_seg_fuse": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "cvx_det_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _F, _P, _P]),
+    "cvx_det_fuse_views": (_I32, [_P, _P, _I32, _P, _P, _I32, _I32, _F, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "cvx_aug_images": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _P]),
     "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_aug_images_plain": (_I32, [_P, _P, _I32, _P, _I32, _I32, _P]),
@@ -192,6 +194,8 @@ PROTOTYPES = {
 
 # cvx_seg_view (include/cvx_engine.h): one view of cvx_seg_fuse's host table, 24 bytes
 SEG_VIEW_DTYPE = np.dtype([("rows", "<u8"), ("lh", "<i4"), ("lw", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
+# cvx_det_view (include/cvx_engine.h): one view of cvx_det_tta_inputs's host table, 24 bytes
+DET_VIEW_DTYPE = np.dtype([("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
 
 _lib = None
 

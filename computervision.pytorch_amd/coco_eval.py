@@ -76,8 +76,10 @@ class CocoEvaluator:
             self.rec_ignored = torch.zeros(cap, dtype=torch.int64, device=dev)
             self.state = torch.zeros(4, dtype=torch.int64, device=dev)
             self.npig = torch.zeros(nc, 4, dtype=torch.int64, device=dev)
-            self.iou_thrs = torch.from_numpy(IOU_THRS).to(dev)
-            self.rec_thrs = torch.from_numpy(REC_THRS).to(dev)
+            # pinned and kept: the two copies do not wait on the host (the first batch of an evaluation allocates here)
+            self._thrs_host = (torch.from_numpy(IOU_THRS).pin_memory(), torch.from_numpy(REC_THRS).pin_memory())
+            self.iou_thrs = self._thrs_host[0].to(dev, non_blocking=True)
+            self.rec_thrs = self._thrs_host[1].to(dev, non_blocking=True)
             self._alloc = True
             self.reset()
 

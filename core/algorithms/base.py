@@ -35,15 +35,21 @@ class FramePredictor:
         if torch.device(self.device).type != "cuda":
             raise L.CvxError(f"{what} runs on an MI355X only (device {self.device}): there is no CPU path")
 
-    def detect_frames(self, model, frames, batch_size, tiled=None, track=None):
+    def detect_frames(self, model, frames, batch_size, tiled=None, track=None, tta=None):
         """Generator over any iterable of uint8 HWC RGB device frames: yields the list of drawn frames of each batch of ``batch_size`` (the
         last one may be short).  Each batch is one ``predict_batch(..., draw=True, sync=False)``: nothing inside the loop waits on the
         host, so the caller synchronises (or reads a frame) when it needs the pixels.  ``tiled``: a dict of ``predict_tiled`` keywords
         (the four detectors) -- each batch is then one ``predict_tiled(..., draw=True, sync=False, **tiled)``.  ``track``: a
         ``track.Tracker``, or a dict of its parameters from which one is created for the generator's lifetime (the four detectors) -- every
-        batch goes through it in order, and the frames are painted with the track ids (``cvx_draw_tracks``); composes with ``tiled``."""
+        batch goes through it in order, and the frames are painted with the track ids (``cvx_draw_tracks``); composes with ``tiled``.
+        ``tta``: a ``det_tta.DetTTA`` (the four detectors) -- every batch is predicted on its views and fused, ``predict_batch(...,
+        tta=tta)``; composes with ``track``, and is refused together with ``tiled``: augmented tiles are not built."""
         if track is not None and not isinstance(self, Detector):
             raise L.CvxError(f"{type(self).__name__} has no detections to track")
+        if tta is not None and not isinstance(self, Detector):
+            raise L.CvxError(f"{type(self).__name__} has no detections to augment")
+        if tta is not None and tiled is not None:
+            raise L.CvxError("detect_frames: tta= together with tiled= is not built (augmentation of tiles); pass one of them")
         self._need_gpu("detect_frames")
         if int(batch_size) <= 0:
             raise ValueError("batch_size is positive")
@@ -52,6 +58,9 @@ class FramePredictor:
             from computervision.pytorch_amd.track import Tracker
             more["tracker"] = track if isinstance(track, Tracker) else Tracker(self.device, **dict(track))
         if tiled is None:
+            if tta is not None:
+                more["tta"] = tta
+
             def predict(model, batch, draw, sync):
                 return self.predict_batch(model, batch, draw=draw, sync=sync, **more)
         else:
@@ -88,6 +97,23 @@ class Detector(FramePredictor):
         size = self.input_image_size if hasattr(self, "input_image_size") else self.input_size
         return (int(size[0]), int(size[1])), bool(self.letterbox_image)
 
+    def _box_map_terms(self, image_hw, input_hw):
+        """float64 (px, py, gx, gy) of the affine map this class's tail reports its boxes through, ``x_rep = (x_net - px) * gx``, for
+        original sizes ``image_hw`` (B, 2) on the device: the arithmetic of ``det_eval.letterbox_box_map`` / ``correct_boxes_device``,
+        plain stretching when the class does not letterbox.  ``det_tta.DetTTA`` builds its view maps from it."""
+        from computervision.pytorch_amd import det_tta
+        return det_tta.box_map_terms(image_hw, input_hw, bool(self.letterbox_image))
+
+    def _augmented(self, model, tta, max_det=None):
+        """``_evaluation_rows(model)``, behind ``tta`` when one is given"""
+        rows_of = self._evaluation_rows(model)
+        if tta is None:
+            return rows_of
+        from computervision.pytorch_amd.det_tta import DetTTA
+        if not isinstance(tta, DetTTA):
+            raise ValueError(f"tta: a det_tta.DetTTA or None, got {type(tta).__name__}")
+        return tta.wrap(self, rows_of, max_det)
+
     def _tracked(self, tracker, frames, batch, rows, counts, overflow, draw, sync):
         """The end of ``predict_batch`` / ``predict_tiled`` with a tracker: ids, the tracks painted, the return with its third element"""
         from computervision.pytorch_amd import render
@@ -98,7 +124,7 @@ class Detector(FramePredictor):
             return render.read_detections(rows, counts, overflow, ids)
         return rows, counts, ids
 
-    def predict_batch(self, model, frames, conf_threshold=None, draw=False, sync=True, tracker=None):
+    def predict_batch(self, model, frames, conf_threshold=None, draw=False, sync=True, tracker=None, tta=None):
         """``predict`` for a batch, on the device: ``frames`` is a list of uint8 HWC RGB device tensors of any sizes.  One launch builds the
         network batch (``cvx_letterbox_batch_u8_to_nchw`` when ``cfg.decode.letterbox_image``, else the bicubic stretch through
         ``cvx_aug_images_plain`` jobs -- the host ``INTER_CUBIC`` resize of ``predict``), one forward, the class's own decode + NMS tail
@@ -109,7 +135,10 @@ class Detector(FramePredictor):
         ``tracker``: a ``track.Tracker`` -- the frames are consecutive frames of its stream 0, the rows get track ids after
         ``cvx_det_to_image`` (``cvx_track_update``, no host read), ``draw`` paints them with ``cvx_draw_tracks``, and the return gains a
         third element: ``(rows, counts, ids (B, K) int32)``, or with ``sync=True`` ``(boxes, scores, classes, ids)`` per frame, a row
-        without a track with -1.  Without a tracker nothing changes."""
+        without a track with -1.  Without a tracker nothing changes.
+        ``tta``: a ``det_tta.DetTTA`` -- the batch runs once per view (the picture at a few zooms and mirrored, every view at the network's
+        own size: one ``cvx_det_tta_inputs`` launch) and one ``cvx_det_fuse_views`` launch fuses the views' rows per frame; the rows are
+        ``(B, tta.max_det, 6)``.  Drawing, ``sync`` and the tracker see the fused rows.  With None nothing changes."""
         from computervision.pytorch_amd import render
         self._need_gpu("predict_batch")
         frames = list(frames)
@@ -117,7 +146,7 @@ class Detector(FramePredictor):
         batch = render.FrameBatch(frames, input_hw, letterbox)
         model.eval()
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
-        rows, counts, box_map = self._evaluation_rows(model)(batch.network_input(), {"image_hw": batch.image_hw}, conf)
+        rows, counts, box_map = self._augmented(model, tta)(batch.network_input(), {"image_hw": batch.image_hw}, conf)
         rows, counts, overflow = render.det_to_image(rows, counts, box_map)
         if tracker is not None:
             return self._tracked(tracker, frames, batch, rows, counts, overflow, draw, sync)
@@ -173,7 +202,7 @@ class Detector(FramePredictor):
             return render.read_detections(rows, counts, overflow)
         return rows, counts
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False, tta=None):
         """The reference's ``evaluate_on_voc``: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
         ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
         images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
@@ -183,7 +212,9 @@ class Detector(FramePredictor):
         An image without detections contributes none (the reference writes one all-zero line of class 0 for it, YOLOv8's writes
         nothing).  Returns ``DetectionEvaluator.results()``.  No plots.
         ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
-        entry of the result."""
+        entry of the result.
+        ``tta``: a ``det_tta.DetTTA`` -- every batch is evaluated on its views and fused (``DetTTA.wrap`` around ``_evaluation_rows``, at
+        most ``min(eval_max_det, 8192)`` rows per image); everything behind the rows is unchanged."""
         if subset not in ("val", "test"):
             raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
         if dataloader is None:
@@ -192,21 +223,23 @@ class Detector(FramePredictor):
         from computervision.pytorch_amd import det_eval
         from configs.dataset_cfg import VOC_CFG
         model.eval()
-        return det_eval.evaluate_detector(self._evaluation_rows(model), dataloader, self.num_classes, self.device, map_out_root,
-                                          det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric)
+        return det_eval.evaluate_detector(self._augmented(model, tta, min(self.eval_max_det, 8192)), dataloader, self.num_classes, self.device,
+                                          map_out_root, det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric)
 
-    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None):
+    def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None, tta=None):
         """The reference's ``evaluate_on_coco``: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and
         scores unrounded.  Reading COCO from disk, category ids and the annotation JSON are outside the hot path: ``dataloader`` yields
         ``(images, meta)`` with images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes,
         gt_coco (B, G, 7) float64 [class index, x, y, w, h, area, iscrowd], gt_counts (B) int32), all on the device, THE IMAGES IN
         SORTED-ID ORDER.
         The rows come from the pass ``evaluate_on_voc`` runs; per batch one ``cvx_coco_match`` launch, and the host reads once, at the end.
-        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``."""
+        Writes the twelve summary lines to ``map_out_root/coco_results.txt``, prints them and returns ``CocoEvaluator.results()``.
+        ``tta`` as in ``evaluate_on_voc``."""
         from computervision.pytorch_amd import coco_eval
         coco_eval.check_coco_arguments(subset, dataloader)
         model.eval()
-        return coco_eval.evaluate_detector_coco(self._evaluation_rows(model), dataloader, self.num_classes, map_out_root, self.eval_max_det, capacity)
+        return coco_eval.evaluate_detector_coco(self._augmented(model, tta, min(self.eval_max_det, 8192)), dataloader, self.num_classes, map_out_root,
+                                                self.eval_max_det, capacity)
 
 
 class NmsDetector(Detector):

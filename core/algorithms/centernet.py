@@ -102,6 +102,11 @@ class CenterNetA(Detector):
 
         return rows_of
 
+    def _box_map_terms(self, image_hw, input_hw):
+        """``evaluate_rows`` undoes a letterbox whatever ``letterbox_image`` says (``reverse_letterbox_device``)"""
+        from computervision.pytorch_amd import det_tta
+        return det_tta.box_map_terms(image_hw, input_hw, True)
+
     def _finish(self, out, b, h, w):
         n = int(out["counts"][b])
         if n < 0:

@@ -908,6 +908,54 @@ typedef struct cvx_seg_view {
 int cvx_seg_fuse(const cvx_seg_view* views_host, int32_t n_views, int32_t ld, int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t mode,
                  uint8_t* labels, const int64_t* target, int64_t* confusion, float* probs_nchw, void* hip_stream);
 
+/* ---- scale and flip test-time augmentation for the detectors (csrc/det_tta.hip) -------------------------------------
+ * The network runs on the batch at a few zooms <= 1 and on its mirror image, every view at the network's own input size, and the boxes of
+ * all views of a frame are mapped back to the picture and fused.  Both entries are one launch, asynchronous on hip_stream, and read nothing
+ * back.  The reference has no counterpart: the rules are the project's own, restated in numpy in tests/det_tta_restatement.py.
+ * One view: the picture resized to (h, w) sits at (top, left) of the (H, W) network input; flip != 0: the whole input is mirrored along x
+ * after that.  24 bytes. */
+typedef struct cvx_det_view {
+  int32_t h, w, top, left, flip, reserved;
+} cvx_det_view;
+/* images (batch, 3, H, W) fp32 -> out ((n_views * batch), 3, H, W) fp32, slot k * batch + b = view k of picture b.  views_host: 1 <=
+ * n_views <= 8 entries in HOST memory, read before the call returns and handed to the kernel by value; every rectangle lies inside the
+ * input.  With xs = flip_k ? W - 1 - x : x, pixel (y, x) of slot k * batch + b is
+ *   inside   top_k <= y < top_k + h_k and left_k <= xs < left_k + w_k: the bilinear resize of the picture to (h_k, w_k) at (y - top_k,
+ *            xs - left_k) -- align_corners = False, no antialiasing: the taps bilinear_src(y - top_k, (float)H / (float)h_k, H) and
+ *            bilinear_src(xs - left_k, (float)W / (float)w_k, W) of csrc/bilinear.h, the value bilinear_mix;
+ *   outside  pad (the letterbox's grey is 128.0f / 255.0f).
+ * The resize first, the mirror second.  A view with (h, w) == (H, W) and no flip is a bit-exact copy (every tap has lam == 0).  Slots
+ * past n_views * batch are not written.  Any positive H, W; 16-byte stores where W % 4 == 0. */
+int cvx_det_tta_inputs(const float* images_nchw, int32_t batch, int32_t H, int32_t W, const cvx_det_view* views_host, int32_t n_views, float pad,
+                       float* out_nchw, void* hip_stream);
+/* Fuses the views of each frame, one workgroup per frame.  rows (views * frames, max_det_in, 6) fp32 [x1, y1, x2, y2, score, cls] and
+ * counts (views * frames) int32 as cvx_det_to_image leaves them, slot s = k * frames + f: what the tail reports for view k of frame f.
+ * view_map (views * frames, 4) fp32 [ax, cx, ay, cy], frame_hw (frames, 2) int32 [h, w].  Per frame f:
+ *   candidates  the rows r < counts[s] of the slots k * frames + f; ordinal s * max_det_in + r.  A count below 0 or above max_det_in
+ *               contributes nothing and adds 1 to *overflow (1 int32, device, cleared by the caller).
+ *   boxes       t1 = x1 * ax + cx, t2 = x2 * ax + cx -- a rounded product, then a rounded add --, x1' = fminf(t1, t2), x2' = fmaxf(t1, t2)
+ *               (a flipped view has ax < 0), then fminf(fmaxf(v, 0), w); likewise y with ay, cy and h.  Score and class are copied.
+ *   order       score descending, then ordinal ascending (the 64-bit key of cvx_nms, the ordinal in the low word).
+ *   greedy      cvx_det_merge_tiles's walk under metric 0: candidate i is dropped when an earlier kept j, of the same class unless
+ *               class_agnostic, has IoU(i, j) > threshold (cvx_nms's IoU to the bit; a NaN never suppresses).  Stops at max_det_out kept.
+ *   members     of a kept row i: itself and every candidate j != i, before or behind it, kept or not, of its class (unless
+ *               class_agnostic) with IoU(i, j) > threshold.
+ *   mode 0      ("nms") the kept rows' own boxes.
+ *   mode 1      ("vote") over the members j in sorted order, from 0.0f: weight w = score_i for j == i, else IoU(i, j) * score_j;
+ *               Wt = Wt + w; X_c = X_c + w * box_j[c] for the four corners -- every operation rounded on its own, in that order -- and
+ *               the box is X_c / Wt.  A kept row without another member, or with Wt not above 0, keeps its own box bit for bit.
+ *   score_mode  0 ("max"): score_i.  1 ("views"): (score_i * (float)m) / (float)views, m the number of distinct views (ordinal /
+ *               max_det_in / frames) among the members.  The rows stay in kept order either way.
+ *   outputs     out_rows (frames, max_det_out, 6), zero past the count; out_counts (frames); out_source (frames, max_det_out) the ordinal
+ *               of each kept row, -1 past the count; out_members (frames, max_det_out) the members of each kept row, 0 past the count.
+ *   capacity    8192 candidates per frame: beyond it out_counts[f] = -1, the frame's rows are zero and *overflow grows by 1 -- flagged,
+ *               never truncated.
+ * workspace: cvx_det_merge_workspace_bytes(frames) bytes of device memory (the layout of cvx_det_merge_tiles). */
+int cvx_det_fuse_views(const float* rows, const int32_t* counts, int32_t max_det_in, const float* view_map, const int32_t* frame_hw,
+                       int32_t frames, int32_t views, float threshold, int32_t class_agnostic, int32_t mode, int32_t score_mode,
+                       int32_t max_det_out, float* out_rows, int32_t* out_counts, int32_t* out_source, int32_t* out_members, int32_t* overflow,
+                       void* workspace, int64_t workspace_bytes, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 

@@ -7,14 +7,15 @@ import torch
 from computervision.pytorch_amd._lib import CvxError
 
 
-def detect_frames(algorithm, model, frames, batch_size, tiled=None, track=None):
+def detect_frames(algorithm, model, frames, batch_size, tiled=None, track=None, tta=None):
     """Generator over any iterable of uint8 HWC RGB device frames: yields the drawn frames (the same tensors, painted in place) as one list
     per batch of ``batch_size``.  ``algorithm`` is one of the five algorithm objects; each batch is its ``predict_batch(..., draw=True,
     sync=False)``, so the loop never waits on the host.  ``tiled``: a dict of ``predict_tiled`` keywords for footage much larger than the
     network input (the four detectors): each batch is then cut into tiles, detected and merged on the device.  ``track``: a
     ``track.Tracker`` or a dict of its parameters (the four detectors): the detections keep an identity from frame to frame, on the device,
-    and are painted with their track ids."""
-    return algorithm.detect_frames(model, frames, batch_size, tiled=tiled, track=track)
+    and are painted with their track ids.  ``tta``: a ``det_tta.DetTTA`` (the four detectors): every batch is predicted at a few zooms and
+    mirrored and the views are fused on the device; not together with ``tiled``."""
+    return algorithm.detect_frames(model, frames, batch_size, tiled=tiled, track=track, tta=tta)
 
 
 def segment_frames(algorithm, model, frames, batch_size, **tiled):
@@ -56,15 +57,15 @@ def _run_video(src_video_path, dst_video_path, device, batches_of):
         writer.release()
 
 
-def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8, tiled=None, track=None):
+def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8, tiled=None, track=None, tta=None):
     """The reference's signature: ``decode_fn`` is the bound ``predict`` of an algorithm object (as the reference passes it) or the algorithm
     object itself.  Reads ``src_video_path`` frame by frame, draws the predictions on the device and writes ``dst_video_path`` with the
-    source's frame rate and size.  ``tiled`` and ``track`` as in ``detect_frames``."""
+    source's frame rate and size.  ``tiled``, ``track`` and ``tta`` as in ``detect_frames``."""
     algorithm = getattr(decode_fn, "__self__", decode_fn)
     if not hasattr(algorithm, "predict_batch"):
         raise CvxError("detect_video: decode_fn is an algorithm object or its bound predict method")
     _run_video(src_video_path, dst_video_path, torch.device(algorithm.device),
-               lambda frames: detect_frames(algorithm, model, frames, batch_size, tiled=tiled, track=track))
+               lambda frames: detect_frames(algorithm, model, frames, batch_size, tiled=tiled, track=track, tta=tta))
 
 
 def segment_video(model, src_video_path, dst_video_path, decode_fn, batch_size=2, **tiled):
