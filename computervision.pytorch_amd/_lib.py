@@ -96,6 +96,9 @@ PROTOTYPES = {
     "cvx_adam_step_dev": (_I32, [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _P, _I32, _F, _P]),
     "cvx_ema_update": (_I32, [_P, _P, _I64, _F, _F, _P]),
     "cvx_adam_ema_step_dev": (_I32, [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _P, _I32, _F, _P, _F, _F, _P]),
+    "cvx_optim_step": (_I32, [_I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _F, _F, _F, _P, _I32, _F, _P, _P, _F, _F, _P]),
+    "cvx_grad_norm_workspace": (_I64, [_I64]),
+    "cvx_grad_norm": (_I32, [_P, _I64, _P, _P, _I32, _F, _F, _P, _P, _P, _I64, _P]),
     "cvx_engine_set_stream": (_I32, [_P, _P]),
     "cvx_engine_exchange_stream": (_P, [_P]),
     "cvx_decode": (_I32, [_P, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_F), _I32, _P, _P]),

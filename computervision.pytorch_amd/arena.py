@@ -268,9 +268,12 @@ class EngineTrainStep:
             eng.backward(dpred, scale)
 
     def _update(self):
-        """GradScaler.step (skip the update when a gradient is not finite), Adam with the mean's 1/world folded in, zeroed gradients."""
+        """GradScaler.step (skip the update when a gradient is not finite), the optimiser step with the mean's 1/world folded in, zeroed
+        gradients.  An optimiser that clips measures the global norm first, and that launch raises ``found_inf`` on a norm that is not
+        finite: no ``check_finite`` of its own then."""
         if self.scaler is not None:
-            check_finite(self.model.flat_grads, self.scaler.found_inf)
+            if getattr(self.optimizer, "clip_grad_norm", None) is None:
+                check_finite(self.model.flat_grads, self.scaler.found_inf)
             self.optimizer.found_inf = self.scaler.found_inf
         self.optimizer.step(zero_grad=True, grad_scale=1.0 / self.world)
         if self.scaler is not None:

@@ -4,6 +4,7 @@
 #include "misc_ops.h"
 #include "bilinear.h"
 #include "bn_common.h"
+#include "optim_core.h"
 
 namespace {
 
@@ -1315,43 +1316,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, float* g, float* m,
   }
 }
 
-// The weight average (ModelEMA.update of the reference): e <- rn(rn(e * d) + rn(omd * p)), three correctly rounded fp32 operations in this
-// order, which is what torch's `v *= d; v += (1 - d) * p` computes.  Contraction is switched off for exactly these three: this toolchain's
-// __fmul_rn / __fadd_rn are plain `*` and `+` that the backend does fuse into an FMA (it did, in the 16-byte path).
-__device__ __forceinline__ float ema_mix(float e, float p, float d, float omd) {
-#pragma clang fp contract(off)
-  const float a = e * d;
-  const float b = omd * p;
-  return a + b;
-}
-
 // adam_kernel (device-resident step state) with the average in the same pass: `e` moves toward the value of p this thread is about to store --
 // toward the unchanged p on a skipped step -- in the same 16-byte vector.  The parameter is in registers already, so the average costs its own
 // read and write and no launch.  p, m and v must come out bit for bit as adam_kernel leaves them (the fused and the two-launch step are
 // interchangeable), and which products the compiler contracts into FMAs is its heuristic's choice -- a copy of adam_kernel's expressions fused
-// differently here.  So the contraction is written out: adam_step4 / adam_step1 spell the FMAs adam_kernel compiles to for gfx950 in its
-// 16-byte path and in its scalar tail (they differ: the tail keeps v and the denominator as multiply + add), with contraction off around them.
+// differently here.  So the contraction is written out: ema_mix, adam_step4 and adam_step1 live in optim_core.h, which optim.hip shares.
 // tests/test_ema_gpu.py compares the two paths on the device.
-__device__ __forceinline__ void adam_step4(float& p, float& m, float& v, float g, float b1, float b2, float eps, float lr_over_bc1,
-                                           float inv_sqrt_bc2) {
-#pragma clang fp contract(off)
-  const float g1 = (1.f - b1) * g, g2 = (1.f - b2) * g;
-  m = __builtin_fmaf(b1, m, g1);
-  v = __builtin_fmaf(b2, v, g2 * g);
-  const float num = lr_over_bc1 * m;
-  p = p - num / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
-}
-__device__ __forceinline__ void adam_step1(float& p, float& m, float& v, float g, float b1, float b2, float eps, float lr_over_bc1,
-                                           float inv_sqrt_bc2) {
-#pragma clang fp contract(off)
-  const float g1 = (1.f - b1) * g, g2 = (1.f - b2) * g;
-  m = __builtin_fmaf(b1, m, g1);
-  const float bv = b2 * v, gg = g2 * g;
-  v = bv + gg;
-  const float num = lr_over_bc1 * m, den = sqrtf(v) * inv_sqrt_bc2;
-  p = p - num / (den + eps);
-}
-
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps,
                                                        const int* found_inf, int zero_grad, const float* state, float gscale, float* e, float d,
                                                        float omd) {

@@ -307,6 +307,53 @@ def check_finite(grads: torch.Tensor, found_inf: torch.Tensor):
     L.check(lib.cvx_check_finite(L.ptr(grads), grads.numel(), L.ptr(found_inf), L.stream_ptr(grads.device)), "cvx_check_finite")
 
 
+# include/cvx_engine.h: optimisers with parameter groups
+OPTIM_SGD, OPTIM_ADAM = 0, 1
+OPTIM_MAX_GROUPS, OPTIM_GROUP_FLOATS, OPTIM_UNMAPPED = 16, 8, 255
+
+
+def _check_group_tables(n, group_map, group_state):
+    if group_map.dtype != torch.uint8 or group_map.numel() != (n + 3) // 4:
+        raise L.CvxError(f"the group map is one uint8 per 16-byte chunk: {(n + 3) // 4} bytes for {n} values, got {group_map.numel()} of {group_map.dtype}")
+    if group_state.dtype != torch.float32 or group_state.dim() != 2 or group_state.shape[1] != OPTIM_GROUP_FLOATS or not group_state.is_contiguous():
+        raise L.CvxError(f"the group table is a contiguous float32 (n_groups, {OPTIM_GROUP_FLOATS}) tensor")
+    return int(group_state.shape[0])
+
+
+def optim_step(kind, params, grads, buf1, buf2, group_map, group_state, state, betas=(0.9, 0.999), eps=1e-8, found_inf=None, zero_grad=True,
+               grad_scale=1.0, clip_state=None, ema_arena=None, d=0.0, one_minus_d=1.0):
+    """One SGD / AdamW step over the flat arenas with per-chunk parameter groups (cvx_optim_step); ``clip_state`` is what ``grad_norm`` wrote,
+    ``ema_arena`` the weight average moved in the same pass.  The caller has validated the ids of ``group_map`` (``FlatOptimizer`` does)."""
+    lib = L.load()
+    _need_gpu(params, "params")
+    n = params.numel()
+    G = _check_group_tables(n, group_map, group_state)
+    if ema_arena is not None:
+        _need_gpu(ema_arena, "ema")
+        if ema_arena.numel() != n:
+            raise L.CvxError(f"the average holds {ema_arena.numel()} values, the parameter arena {n}")
+        _note_param_write(ema_arena)
+    _note_param_write(params)
+    L.check(lib.cvx_optim_step(int(kind), L.ptr(params), L.ptr(grads), L.ptr(buf1), L.ptr(buf2), n, L.ptr(group_map), L.ptr(group_state), G,
+                               L.ptr(state), betas[0], betas[1], eps, L.ptr(found_inf), 1 if zero_grad else 0, float(grad_scale), L.ptr(clip_state),
+                               L.ptr(ema_arena), float(d), float(one_minus_d), L.stream_ptr(params.device)), "cvx_optim_step")
+
+
+def grad_norm_workspace(n: int) -> int:
+    """floats of workspace ``grad_norm`` needs for an arena of n values = the number of first-stage partials"""
+    return int(L.load().cvx_grad_norm_workspace(int(n)))
+
+
+def grad_norm(grads, group_map, group_state, max_norm, clip_state, workspace, grad_scale=1.0, found_inf=None):
+    """clip_state <- [norm, min(1, max_norm / (norm + 1e-6)), non-finite marker] of grad_scale * grads over the live, unfrozen chunks
+    (cvx_grad_norm: deterministic, two launches, no host read); a non-finite norm raises ``found_inf``."""
+    lib = L.load()
+    _need_gpu(grads, "grads")
+    G = _check_group_tables(grads.numel(), group_map, group_state)
+    L.check(lib.cvx_grad_norm(L.ptr(grads), grads.numel(), L.ptr(group_map), L.ptr(group_state), G, float(grad_scale), float(max_norm),
+                              L.ptr(clip_state), L.ptr(found_inf), L.ptr(workspace), workspace.numel(), L.stream_ptr(grads.device)), "cvx_grad_norm")
+
+
 def decode(pred: torch.Tensor, nc: int, level_hw, strides) -> torch.Tensor:
     lib = L.load()
     _need_gpu(pred, "pred")

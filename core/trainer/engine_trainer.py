@@ -7,15 +7,34 @@ from typing import Dict
 
 import torch
 
+from computervision.pytorch_amd.optim import FlatAdamW, FlatSGD
 from computervision.pytorch_amd.train import DynamicLossScale, FlatAdam
 from core.trainer.base import BaseTrainer, LinearWarmup
 
 
-def get_optimizer(optimizer_name, model, initial_lr):
-    """reference core/trainer/lr_scheduler.py:37-43 (Adam only)."""
-    if optimizer_name.lower() == "adam":
+# cfg.optimizer options beyond the reference's `name`, with their defaults; `freeze` is read from cfg.train
+OPTIMIZER_OPTIONS = dict(momentum=0.937, nesterov=True, weight_decay=0.0, groups=None, bias_lr_scale=1.0, clip_grad_norm=None)
+
+
+def get_optimizer(optimizer_name, model, initial_lr, cfg=None):
+    """Without ``cfg`` this is the reference's function (core/trainer/lr_scheduler.py:37-43): Adam only, ``FlatAdam``, any other name raises --
+    the call ``EngineTrainer.set_optimizer`` makes, so the five trainers accept what they accepted before.  With ``cfg`` it also builds
+    ``FlatSGD`` ("sgd") and ``FlatAdamW`` ("adamw") from ``OPTIMIZER_OPTIONS`` in ``cfg.optimizer`` and ``cfg.train.freeze``; "adam" with none
+    of them set is still ``FlatAdam``, with any of them ``FlatAdamW`` with its weight decay (0 by default)."""
+    name = optimizer_name.lower()
+    if name not in (("adam", "adamw", "sgd") if cfg is not None else ("adam",)):
+        raise ValueError(f"{optimizer_name} is not supported")
+    group, train = getattr(cfg, "optimizer", None), getattr(cfg, "train", None)
+    opts = {k: getattr(group, k, d) for k, d in OPTIMIZER_OPTIONS.items()}
+    freeze = tuple(getattr(train, "freeze", ()) or ())
+    asked = freeze or any(hasattr(group, k) for k in OPTIMIZER_OPTIONS)
+    if name == "adam" and not asked:
         return FlatAdam(model, lr=initial_lr)
-    raise ValueError(f"{optimizer_name} is not supported")
+    shared = dict(weight_decay=opts["weight_decay"], groups=opts["groups"], bias_lr_scale=opts["bias_lr_scale"], freeze=freeze,
+                  clip_grad_norm=opts["clip_grad_norm"])
+    if name == "sgd":
+        return FlatSGD(model, lr=initial_lr, momentum=opts["momentum"], nesterov=opts["nesterov"], **shared)
+    return FlatAdamW(model, lr=initial_lr, **shared)
 
 
 class EngineTrainer(BaseTrainer):

@@ -289,6 +289,45 @@ int cvx_adam_ema_step_dev(float* params, float* grads, float* exp_avg, float* ex
                           float* state, const int32_t* found_inf, int32_t zero_grad, float grad_scale, float* ema, float d, float one_minus_d,
                           void* hip_stream);
 
+/* ---- optimisers with parameter groups: SGD, AdamW, frozen groups, clipping by the global norm -----------
+ * group_map: one byte per 16-byte chunk of the arenas, (n + 3) / 4 bytes (arena offsets and sizes are multiples of 4 floats, so a chunk
+ *   belongs to at most one parameter): a group id below n_groups, or CVX_OPTIM_UNMAPPED for "no trainable parameter here: do not touch".
+ *   The caller refuses any other id before it launches (a kernel cannot return a status; an id the caller let through is left alone).
+ * group_state: device float[n_groups][CVX_OPTIM_GROUP_FLOATS], written by the host only when a learning rate changes:
+ *   [0] lr  [1] decay_coupled, the lambda added to the gradient (SGD)  [2] decay_factor, fp32 of the host double 1 - lr * lambda (ADAM kind:
+ *   torch.optim.AdamW's param.mul_(1 - lr * wd))  [3] frozen (non-zero: the group stands still)  [4] momentum  [5] nesterov (SGD)
+ *   [6] lr / (1 - beta1^t), filled by the call itself (ADAM kind)  [7] reserved.
+ * state: device float[4] = [group 0's lr, step count, group 0's lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)], advanced by the call itself and
+ *   only on a step that is not skipped; all groups share the step count.  A one-group ADAM run keeps the state cvx_adam_step_dev keeps.
+ * cvx_optim_step, per element i of group k: g1 = rn(grads[i] * grad_scale); with a clip_state g2 = rn(g1 * clip_state[1]), else g2 = g1.
+ *   Skipped step (found_inf non-zero, or clip_state[2] non-zero), frozen group or unmapped chunk: params and the buffers keep their bits;
+ *   grads[i] is zeroed whenever zero_grad is set, for frozen and unmapped chunks too.
+ *   CVX_OPTIM_SGD (torch.optim.SGD, dampening 0; buf1 = momentum buffer, buf2 unused): g3 = rn(g2 + rn(lambda * p)); b = rn(rn(mu * b) + g3);
+ *   d = nesterov ? rn(g3 + rn(mu * b)) : b; p = rn(p - rn(lr * d)) -- every operation rounded on its own, never contracted.
+ *   CVX_OPTIM_ADAM (torch.optim.AdamW; buf1 = exp_avg, buf2 = exp_avg_sq): p = rn(p * decay_factor), then cvx_adam_step_dev's own arithmetic
+ *   with the group's lr / (1 - beta1^t): one group, decay_factor 1 and a map without holes give cvx_adam_step_dev's bits.
+ *   ema (may be NULL): the weight average in the same pass, ema[i] <- rn(rn(ema[i] * d) + rn(one_minus_d * p)) toward the value of p the
+ *   step stores -- toward the unchanged p on a skipped step and for frozen groups; unmapped chunks are not averaged.
+ *   All arenas 16-byte aligned, ema != params, n_groups <= CVX_OPTIM_MAX_GROUPS.  Two launches: the 1-thread state advance and the update.
+ *   Replaces: torch.optim.SGD / AdamW .step over per-parameter tensors (the reference offers Adam only, core/trainer/lr_scheduler.py:37-43).
+ * cvx_grad_norm: the global L2 norm of grad_scale * grads over the chunks whose group is neither unmapped nor frozen, into
+ *   clip_state = [norm, coef = min(1, max_norm / (norm + 1e-6)), non-finite marker] (torch.nn.utils.clip_grad_norm_'s coefficient).
+ *   Deterministic: one partial per workgroup of a grid that depends on n alone, then one workgroup that adds the partials in a fixed
+ *   tree; no floating-point atomics.  A norm that is not finite sets the marker and raises found_inf (may be NULL): the launch replaces
+ *   cvx_check_finite for a step that clips, and cvx_optim_step skips on the marker -- where torch would scale every gradient by NaN.
+ *   workspace: cvx_grad_norm_workspace(n) floats of device memory (at most 1024); a smaller one is refused.
+ *   Replaces: torch.nn.utils.clip_grad_norm_ (one norm launch per parameter, then a host-visible total). */
+enum { CVX_OPTIM_SGD = 0, CVX_OPTIM_ADAM = 1 };
+#define CVX_OPTIM_MAX_GROUPS 16
+#define CVX_OPTIM_GROUP_FLOATS 8
+#define CVX_OPTIM_UNMAPPED 255
+int cvx_optim_step(int32_t kind, float* params, float* grads, float* buf1, float* buf2, int64_t n, const uint8_t* group_map, float* group_state,
+                   int32_t n_groups, float* state, float beta1, float beta2, float eps, const int32_t* found_inf, int32_t zero_grad,
+                   float grad_scale, const float* clip_state, float* ema, float d, float one_minus_d, void* hip_stream);
+int64_t cvx_grad_norm_workspace(int64_t n);
+int cvx_grad_norm(const float* grads, int64_t n, const uint8_t* group_map, const float* group_state, int32_t n_groups, float grad_scale,
+                  float max_norm, float* clip_state, int32_t* found_inf, float* workspace, int64_t workspace_floats, void* hip_stream);
+
 /* ---- eval tail: DFL decode + sigmoid, then class-aware NMS ---------------------------------------
  * cvx_decode: pred (B,A,no) -> y (B, 4+nc, A) fp32 [cx,cy,w,h (pixels), class scores]
  *   Replaces: Detect eval branch, core/models/yolov8/modules.py:434-446.
