@@ -12,6 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB") or os.path.join(_HERE, "lib", "libcvx_engine.so")   # CVX_LIB: A/B runs of two builds on one box
 ABI_VERSION = 4
+SEG_OPTS_KEY_OFFSET = 4096      # CVX_SEG_OPTS_KEY_OFFSET: where cvx_seg_loss_opts keeps the OHEM key plane in its workspace
 
 
 class CvxError(RuntimeError):
@@ -154,6 +155,9 @@ PROTOTYPES = {
     "cvx_seg_loss": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _F, _P, _P, _P, _P, _P]),
     "cvx_seg_eval_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "cvx_seg_eval": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _P, _P, _P, _P]),
+    "cvx_seg_loss_opts_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
+    "cvx_seg_loss_opts": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _I64, _F, _I64, _F, _P, _P, _P, _P, _P, _P]),
+    "cvx_seg_eval_opts": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _I64, _P, _P, _P, _P]),
     "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
     "cvx_coco_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),

@@ -358,9 +358,17 @@ class SegLoss:
     """``FocalLoss()`` / ``nn.CrossEntropyLoss(reduction="mean")`` of ``DeeplabV3PlusA.build_loss`` (segmentation_2d.py:59-64,
     core/loss/focal_loss.py:6-22) on the engine: ``loss = criterion(preds, targets)`` with ``preds = model(images)``.  Value and
     gradient come from ``cvx_seg_loss`` on the low-resolution rows behind ``preds`` (no autograd tape through the upsampling);
-    ``loss.backward()`` then runs the engine's backward pass."""
+    ``loss.backward()`` then runs the engine's backward pass.
 
-    def __init__(self, loss_type: str = "focal", alpha: float = 0.25, gamma: float = 2.0, ignore_index: int = -100, check_targets: bool = True):
+    Options of ``"ce"`` (not in the reference; ``cvx_seg_loss_opts``, csrc/loss_seg_opts.hip -- the same fused chain):
+    ``class_weights`` (``num_classes`` non-negative floats) and ``label_smoothing`` in [0, 1) are those of
+    ``F.cross_entropy(weight=, label_smoothing=, reduction="mean")``; ``ohem=dict(thresh=t, min_kept=m)`` trains on the hard pixels
+    only: those whose target probability is below ``t``, and at least the ``m * batch`` pixels with the largest cross-entropy (all
+    pixels tied at that rank).  ``last_stats`` is the device tensor (kept pixels, valid pixels, theta_min, sum of target weights) of
+    the last call, ``ohem_keys()`` its per-pixel selection keys.  Without an option the criterion is ``cvx_seg_loss`` as before."""
+
+    def __init__(self, loss_type: str = "focal", alpha: float = 0.25, gamma: float = 2.0, ignore_index: int = -100, check_targets: bool = True,
+                 class_weights=None, label_smoothing: float = 0.0, ohem=None):
         if loss_type not in ("focal", "ce"):
             raise ValueError("loss_type must be 'focal' or 'ce' (segmentation_2d.py:59-64)")
         self.mode = 0 if loss_type == "focal" else 1
@@ -369,10 +377,69 @@ class SegLoss:
         self._ws = None
         self._dpred = None
         self._bad = None
+        self.class_weights = self.ohem = None
+        self.label_smoothing = float(label_smoothing)
+        self.last_stats = None
+        self._weights_dev = self._keys_shape = None
+        self.has_options = class_weights is not None or self.label_smoothing != 0.0 or ohem is not None
+        if not self.has_options:
+            return
+        if self.mode == 0:
+            raise ValueError("class_weights, label_smoothing and ohem are options of loss_type='ce', not of 'focal'")
+        if class_weights is not None:
+            w = torch.as_tensor(class_weights, dtype=torch.float32).detach().cpu().reshape(-1).clone()
+            if w.numel() == 0 or not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not bool((w > 0).any()):
+                raise ValueError("class_weights must be finite, non-negative and not all zero")
+            self.class_weights = w
+        if not 0.0 <= self.label_smoothing < 1.0:          # nan fails too
+            raise ValueError("label_smoothing must lie in [0, 1)")
+        if ohem is not None:
+            thresh, min_kept = float(ohem["thresh"]), ohem["min_kept"]
+            if not 0.0 < thresh <= 1.0:
+                raise ValueError("ohem: thresh must lie in (0, 1]")
+            if int(min_kept) != min_kept or int(min_kept) < 1:
+                raise ValueError("ohem: min_kept must be an integer >= 1")
+            self.ohem = {"thresh": thresh, "min_kept": int(min_kept)}
+            self.ohem_theta = abs(math.log(thresh))         # -ln thresh as a host double (abs: thresh = 1 gives +0.0); fp32 at the call
 
     def bad_targets(self) -> bool:
         """True when the last call saw a label that is neither ignore_index nor a class (synchronises)."""
         return self._bad is not None and int(self._bad.item()) != 0
+
+    def weights_on(self, device, nc: int):
+        """The class weights on ``device`` (copied once), or None; their length is checked against ``nc`` here, where it is known."""
+        if self.class_weights is None:
+            return None
+        if self.class_weights.numel() != nc:
+            raise ValueError(f"class_weights has {self.class_weights.numel()} entries for {nc} classes")
+        if self._weights_dev is None or self._weights_dev.device != device:
+            self._weights_dev = self.class_weights.to(device)
+        return self._weights_dev
+
+    def ohem_keys(self) -> torch.Tensor:
+        """(B, H, W) fp32 view of the last call's selection keys, max(lse - z_t, 0), with -1 at pixels that are not valid.  A view of
+        the workspace: the next call overwrites it.  Does not synchronise."""
+        if self.ohem is None or self._keys_shape is None:
+            raise L.CvxError("ohem_keys: the criterion has no ohem option, or has not been called yet")
+        B, H, W = self._keys_shape
+        return self._ws[L.SEG_OPTS_KEY_OFFSET:L.SEG_OPTS_KEY_OFFSET + B * H * W * 4].view(torch.float32).view(B, H, W)
+
+    def _op_opts(self, lib, rows, target, dims, loss_scale, dpred):
+        B, A, ld, nc, lh, lw, H, W = dims
+        dev = rows.device
+        weights = self.weights_on(dev, nc)
+        need = int(lib.cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, int(self.ohem is not None)))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.last_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, device=dev)
+        theta, k = (self.ohem_theta, self.ohem["min_kept"] * B) if self.ohem is not None else (-1.0, 0)
+        L.check(lib.cvx_seg_loss_opts(L.ptr(rows), ld, B, nc, lh, lw, H, W, L.ptr(target), L.ptr(weights) if weights is not None else None,
+                                      self.label_smoothing, self.ignore_index, theta, k, float(loss_scale), L.ptr(loss), L.ptr(dpred),
+                                      L.ptr(self._bad), L.ptr(self.last_stats), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_loss_opts")
+        self._keys_shape = (B, H, W)
+        return loss
 
     def op(self, rows: torch.Tensor, target: torch.Tensor, hw, loss_scale: float, dpred: Optional[torch.Tensor] = None,
            check: Optional[bool] = None):
@@ -387,6 +454,13 @@ class SegLoss:
         H, W = int(target.shape[1]), int(target.shape[2])
         nc = getattr(self, "nc", None) or ld
         target = target.to(device=rows.device, dtype=torch.long).contiguous()
+        if self.has_options:
+            if dpred is None:
+                dpred = torch.empty(B, A, ld, dtype=torch.float16, device=rows.device)
+            loss = self._op_opts(lib, rows, target, (B, A, ld, nc, lh, lw, H, W), loss_scale, dpred)
+            if (self.check_targets if check is None else check) and self.bad_targets():
+                raise L.CvxError("SegLoss: a target label is neither ignore_index nor in [0, num_classes)")
+            return loss, dpred
         need = int(lib.cvx_seg_loss_workspace_bytes(B, nc, H, W))
         if self._ws is None or self._ws.numel() < need or self._ws.device != rows.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=rows.device)
@@ -410,6 +484,22 @@ class SegLoss:
         if model.training and torch.is_grad_enabled():
             return _SegLossFn.apply(preds, self, rows, model, targets, hw)
         return self.op(rows, targets, hw, model.loss_scale)[0].reshape(())
+
+
+def seg_class_weights(counts, scheme: str = "median_freq") -> torch.Tensor:
+    """Class weights for ``SegLoss(class_weights=)`` from per-class pixel counts (e.g. the row sums of the confusion matrix of one
+    ``cvx_seg_eval`` pass over the training loader).  With f the class frequency among the counted pixels: ``"median_freq"`` gives
+    median(f over the classes that occur) / f_c, ``"enet"`` 1 / ln(1.02 + f_c); a class with count 0 gets weight 0.  Host only."""
+    counts = torch.as_tensor(counts, dtype=torch.float64).reshape(-1)
+    if scheme not in ("median_freq", "enet"):
+        raise ValueError("scheme must be 'median_freq' or 'enet'")
+    if counts.numel() == 0 or bool((counts < 0).any()) or float(counts.sum()) <= 0:
+        raise ValueError("counts must be non-negative with a positive sum")
+    seen = counts > 0
+    f = counts / counts.sum()
+    w = torch.zeros_like(f)
+    w[seen] = torch.quantile(f[seen], 0.5) / f[seen] if scheme == "median_freq" else 1.0 / torch.log(1.02 + f[seen])
+    return w.float()
 
 
 class SegTrainStep(EngineTrainStep):

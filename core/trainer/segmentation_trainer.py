@@ -78,7 +78,9 @@ class SegmentationMetrics:
     def add_rows(self, rows, targets, hw, criterion, loss_slot):
         """One validation batch from the logits rows ``(B, lh*lw, ld)`` fp32 of ``model.forward_rows`` and the targets ``(B, H, W)`` int64:
         ``confusion[target][argmax of the upsampled logits] += 1`` and ``criterion``'s (a ``SegLoss``) value of the batch into
-        ``loss_slot``, a one-element float32 view on the rows' device.  Asynchronous: nothing is read back."""
+        ``loss_slot``, a one-element float32 view on the rows' device.  A criterion with options (class weights, label smoothing) goes
+        through ``cvx_seg_eval_opts``: the weighted, smoothed value over all valid pixels, the same matrix; its OHEM setting is not
+        applied in evaluation.  Asynchronous: nothing is read back."""
         if not (torch.is_tensor(rows) and rows.is_cuda):
             raise L.CvxError("SegmentationMetrics.add_rows runs on an MI355X only (there is no CPU path); add_batch takes host predictions")
         lib = L.load()
@@ -96,6 +98,13 @@ class SegmentationMetrics:
         need = int(lib.cvx_seg_eval_workspace_bytes(B, H, W))
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        if getattr(criterion, "has_options", False):       # weighted / smoothed cross-entropy over all valid pixels; OHEM is a training device
+            weights = criterion.weights_on(dev, self.num_classes)
+            with torch.cuda.device(dev):
+                L.check(lib.cvx_seg_eval_opts(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets),
+                                              L.ptr(weights) if weights is not None else None, criterion.label_smoothing, criterion.ignore_index,
+                                              L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_eval_opts")
+            return
         with torch.cuda.device(dev):
             L.check(lib.cvx_seg_eval(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets), criterion.mode, criterion.alpha,
                                      criterion.gamma, criterion.ignore_index, L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws),

@@ -490,6 +490,32 @@ int64_t cvx_seg_eval_workspace_bytes(int32_t batch, int32_t oh, int32_t ow);
 int cvx_seg_eval(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                  const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, int64_t* confusion, float* loss_out,
                  void* workspace, void* hip_stream);
+/* Cross-entropy with class weights, label smoothing and online hard example mining (OHEM) for the DeepLabv3+ step: cvx_seg_loss's
+ * mode 1 with options, same rows, target, dpred, bad_target and loss_scale.  With z_c the interpolated logits of a label pixel, lse their
+ * log-sum-exp, t the target, w = class_weight (nc floats on the device; null: all ones), W = sum_c w_c, eps = label_smoothing in [0, 1):
+ *   l    = (1 - eps) w_t (lse - z_t) + (eps / nc) sum_c w_c (lse - z_c)
+ *   loss = sum_{i in S} l_i / sum_{i in S} w_{t_i}, S = the valid pixels (target != ignore_index and in [0, nc)) -- torch's
+ *          F.cross_entropy(weight=, ignore_index=, label_smoothing=, reduction="mean"); an empty S gives nan and a zero gradient.
+ * OHEM (ohem_theta >= 0; a negative value turns it off): key = fp32 max(lse - z_t, 0), ohem_theta = fp32(-ln thresh),
+ * K = ohem_min_kept >= 1 counted over the whole batch, theta_min = the K-th largest key of the valid pixels (-inf when there are fewer
+ * than K); S = the valid pixels with key > ohem_theta or key >= theta_min.  Ties at theta_min are all kept.  The selection is a radix
+ * select over the keys' bit patterns: no sort, integer atomics only; every floating-point sum runs in a fixed order, so two calls give
+ * the same bits.  stats_out: 4 doubles (device): pixels in S, valid pixels, theta_min, the denominator sum w_t.  With class_weight null,
+ * eps 0 and OHEM off, loss_out and dpred are cvx_seg_loss's mode 1 to the bit.  workspace: cvx_seg_loss_opts_workspace_bytes() bytes
+ * (ohem != 0: with the key planes); under OHEM the fp32 keys of the last call, (batch, oh, ow) with -1 at pixels that are not valid,
+ * start CVX_SEG_OPTS_KEY_OFFSET bytes into it.  Asynchronous on hip_stream.  Not in the reference: its build_loss has no options. */
+#define CVX_SEG_OPTS_KEY_OFFSET 4096
+int64_t cvx_seg_loss_opts_workspace_bytes(int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t ohem);
+int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                      const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, float ohem_theta,
+                      int64_t ohem_min_kept, float loss_scale, float* loss_out, void* dpred_f16, int32_t* bad_target, double* stats_out,
+                      void* workspace, void* hip_stream);
+/* cvx_seg_eval with cvx_seg_loss_opts's class_weight and label_smoothing: loss_out is the weighted, smoothed cross-entropy over all valid
+ * pixels of the batch (OHEM is never applied in evaluation); the confusion matrix is cvx_seg_eval's, count for count.
+ * workspace: cvx_seg_eval_workspace_bytes() bytes.  Asynchronous on hip_stream. */
+int cvx_seg_eval_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                      const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, int64_t* confusion,
+                      float* loss_out, void* workspace, void* hip_stream);
 /* VOC mAP evaluation of a detector (get_map at IoU min_overlap), accumulated on the device batch by batch.
  * cvx_det_match, once per batch: rows (batch, max_det, 6) [x1,y1,x2,y2,score,cls] fp32 and counts (batch) int32 exactly as cvx_nms /
  * cvx_nms_variant write them; a count of -1 (or one past max_det) adds 1 to the overflow counter and the image contributes nothing.
