@@ -44,12 +44,15 @@ __device__ __forceinline__ void wait_steps_ahead(int ahead) {
   }
 }
 
+// DMA instructions per wave per K-step: the four waves fill 64 stage rows per pass (the last pass is partial when BM + BN % 64 != 0)
+constexpr int dma_passes(int bm, int bn) { return (bm + bn + 63) / 64; }
+
 // compile-time LDS geometry of one tile configuration (shared by kernel and launcher)
 template <int WM, int WN, int MT, int NTW, int STAGES>
 struct Geom {
   static constexpr int BM = 16 * MT * WM, BN = 16 * NTW * WN;
   static constexpr int ROWS = BM + BN;
-  static constexpr int PASSES = (ROWS + 63) / 64;
+  static constexpr int PASSES = dma_passes(BM, BN);
   // a stage holds the real rows plus one 16-row dump piece that every out-of-range DMA piece of the last pass targets
   static constexpr int STAGE_HALVES = (ROWS + 16) * BK;
   static constexpr int RING_BYTES = STAGES * STAGE_HALVES * 2;
@@ -349,7 +352,56 @@ int launch_m4(int NT, const ConvParams& p, hipStream_t st, dim3 grid) {  // 4 wa
   }
 }
 
+// The launcher's choice of a compiled tile configuration: BM tile rows, NT channel tiles per workgroup -- 16-channel tiles (BN = 16 NT)
+// in the 4 x 1-wave families of 64 and 128 rows, 32-channel pairs (BN = 32 NT, the kernel's NTW) in the 2 x 2-wave family of 32 rows --
+// and gy channel blocks (gridDim.y).  M = output pixels of the launch (of the largest phase for merged phases).
+struct DmaPlan {
+  int BM, NT, gy;
+  int BN() const { return (BM == 32 ? 32 : 16) * NT; }
+};
+DmaPlan dma_plan(long long M, int Cin, int Cout, int ntaps) {
+  const int tiles = (Cout + 15) / 16;
+  static const int allowed[] = {1, 2, 3, 4, 5, 6, 8};
+  // tile height by problem size (pixels): big M -> 128 rows; below t128 -> 64 rows; below t64 -> 32 rows
+  static const long long t128 = env_int("CVX_T128", 128 * 1024), t64 = env_int("CVX_T64", 64 * 1024);
+  int BM = 128;
+  if (M < t128) BM = (M >= t64) ? 64 : 32;
+  // heavy weights (>= 512 K elements: ResNet / DLA layers with 256+ channels in 3x3, 1024+ in 1x1): every workgroup streams the
+  // whole [BN][K] weight block from L2, so 32-row tiles re-read it M/32 times -- the L2->LDS path, not the MFMAs, was the limit
+  // (DeepLabv3+ ASPP: 6.4 GB per launch); 64 rows from 8 K pixels on (DeepLabv3+ forward 11.85 -> 10.27 ms)
+  static const long long heavy = env_int("CVX_HEAVY_W", 512 * 1024), t64h = env_int("CVX_T64_HEAVY", 8192);
+  if (BM == 32 && (long long)ntaps * Cin * Cout >= heavy && M >= t64h) BM = 64;
+  if (BM == 32) {
+    // 2x2 waves: BN = 32 * NTW
+    int pairs = (tiles + 1) / 2;
+    int gy = (pairs + 3) / 4;
+    int ntw = (pairs + gy - 1) / gy;  // 1..4
+    gy = (pairs + ntw - 1) / ntw;
+    return DmaPlan{32, ntw, gy};
+  }
+  int gy = (tiles + 7) / 8;
+  int want = (tiles + gy - 1) / gy;
+  int NT = 8;
+  for (int a : allowed)
+    if (a >= want) {
+      NT = a;
+      break;
+    }
+  gy = (tiles + NT - 1) / NT;
+  return DmaPlan{BM, NT, gy};
+}
+
 }  // namespace
+
+extern "C" int cvx_debug_conv_dma_plan(int64_t pixels, int32_t cin, int32_t cout, int32_t ntaps, int32_t* out4) {
+  CVX_CHECK(out4 && pixels > 0 && pixels < (1LL << 31) && cin > 0 && cout > 0 && ntaps > 0 && ntaps <= CVX_MAX_TAPS, "bad arguments");
+  const DmaPlan pl = dma_plan(pixels, cin, cout, ntaps);
+  out4[0] = pl.BM;
+  out4[1] = pl.NT;
+  out4[2] = pl.gy;
+  out4[3] = dma_passes(pl.BM, pl.BN());
+  return 0;
+}
 
 int cvx_conv_igemm_dma_launch(const ConvParams& p, hipStream_t stream) {
   CVX_CHECK(p.zeros && ((uintptr_t)p.zeros % 16) == 0, "conv_igemm_dma: needs a 16-byte aligned zero page");
@@ -362,43 +414,19 @@ int cvx_conv_igemm_dma_launch(const ConvParams& p, hipStream_t stream) {
     for (int q = 0; q < p.nphase; ++q) M = std::max(M, (long long)p.B * p.phase[q].OH2 * p.phase[q].OW2);
   }
   CVX_CHECK(M < (1LL << 31), "conv_igemm_dma: more than 2^31 output pixels per launch");
-  const int tiles = (p.Cout + 15) / 16;
-  static const int allowed[] = {1, 2, 3, 4, 5, 6, 8};
-  // tile height by problem size (pixels): big M -> 128 rows; below t128 -> 64 rows; below t64 -> 32 rows
-  static const long long t128 = env_int("CVX_T128", 128 * 1024), t64 = env_int("CVX_T64", 64 * 1024);
-  int BM = 128;
-  if (M < t128) BM = (M >= t64) ? 64 : 32;
-  // heavy weights (>= 512 K elements: ResNet / DLA layers with 256+ channels in 3x3, 1024+ in 1x1): every workgroup streams the
-  // whole [BN][K] weight block from L2, so 32-row tiles re-read it M/32 times -- the L2->LDS path, not the MFMAs, was the limit
-  // (DeepLabv3+ ASPP: 6.4 GB per launch); 64 rows from 8 K pixels on (DeepLabv3+ forward 11.85 -> 10.27 ms)
-  static const long long heavy = env_int("CVX_HEAVY_W", 512 * 1024), t64h = env_int("CVX_T64_HEAVY", 8192);
-  if (BM == 32 && (long long)p.ntaps * p.Cin * p.Cout >= heavy && M >= t64h) BM = 64;
-  if (BM == 32) {
-    // 2x2 waves: BN = 32 * NTW
-    int pairs = (tiles + 1) / 2;
-    int gy = (pairs + 3) / 4;
-    int ntw = (pairs + gy - 1) / gy;  // 1..4
-    gy = (pairs + ntw - 1) / ntw;
-    dim3 grid(cvx_cdiv(M, 32), gy, nz);
-    switch (ntw) {
+  const DmaPlan pl = dma_plan(M, p.Cin, p.Cout, p.ntaps);
+  dim3 grid(cvx_cdiv(M, pl.BM), pl.gy, nz);
+  if (pl.BM == 32) {
+    switch (pl.NT) {
       case 1: CVX_TRY((launch_cfg<2, 2, 1, 1>(p, stream, grid))); break;
       case 2: CVX_TRY((launch_cfg<2, 2, 1, 2>(p, stream, grid))); break;
       case 3: CVX_TRY((launch_cfg<2, 2, 1, 3>(p, stream, grid))); break;
       default: CVX_TRY((launch_cfg<2, 2, 1, 4>(p, stream, grid))); break;
     }
+  } else if (pl.BM == 128) {
+    CVX_TRY(launch_m4<2>(pl.NT, p, stream, grid));
   } else {
-    int gy = (tiles + 7) / 8;
-    int want = (tiles + gy - 1) / gy;
-    int NT = 8;
-    for (int a : allowed)
-      if (a >= want) {
-        NT = a;
-        break;
-      }
-    gy = (tiles + NT - 1) / NT;
-    dim3 grid(cvx_cdiv(M, BM), gy, nz);
-    if (BM == 128) CVX_TRY(launch_m4<2>(NT, p, stream, grid));
-    else CVX_TRY(launch_m4<1>(NT, p, stream, grid));
+    CVX_TRY(launch_m4<1>(pl.NT, p, stream, grid));
   }
   CVX_HIP(hipGetLastError());
   return 0;

@@ -371,6 +371,13 @@ void fill_conv_dgrad(const ConvGeom& g, const PhaseRt& ph, ViewDesc dy, ViewDesc
   cp->out_ld = gin.ld;
   cp->out_bstride = gin.bstride;
 }
+// the phase classes of a strided data gradient go out as ONE launch when there are 2 ... 4 of them and every one has pixels and taps
+bool phases_mergeable(const DgClass* dg, int n) {
+  if (n < 2 || n > 4) return false;
+  for (int q = 0; q < n; ++q)
+    if (dg[q].ph.OH2 <= 0 || dg[q].ph.OW2 <= 0 || dg[q].ph.ntaps <= 0) return false;
+  return true;
+}
 // ... all n (2 ... 4) phase classes as one launch of the DMA-ring kernel (blockIdx.z selects the phase); *cp was filled for phase 0
 void set_merged_phases(const DgClass* dg, int n, ConvParams* cp) {
   cp->nphase = n;
@@ -2122,9 +2129,7 @@ int backward_op(cvx_engine* e, int i) {
       ViewDesc gin = make_view(e, o.in, true);
       // the phases of a strided data gradient differ only in tap subset and output phase: one launch (blockIdx.z)
       static const bool merge_off = cvx_tune_set("CVX_NO_PHASE_MERGE");
-      bool merged = !merge_off && c.ndg > 1 && c.ndg <= 4;
-      for (int q = 0; q < c.ndg && merged; ++q)
-        if (c.dg[q].ph.OH2 <= 0 || c.dg[q].ph.OW2 <= 0 || c.dg[q].ph.ntaps <= 0) merged = false;
+      const bool merged = !merge_off && phases_mergeable(c.dg, c.ndg);
       // stride > kernel (ResNet's 1x1 stride-2 downsample): input pixels of the tap-less phases receive no gradient -- the first
       // writer of the slice zeroes it, the phases with taps then overwrite their own pixels
       bool empty_phase = false;
@@ -2491,6 +2496,7 @@ extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int
   const int gemm_variant = (mode >> 9) & 15;    // ... and of one particular variant of it (0: the cost model's choice)
   const bool force_tile = (mode & 0x2000) != 0;  // likewise the row-band kernel (conv_tile.hip); 0x4000: never the row-band kernel
   const bool no_tile = (mode & 0x4000) != 0;
+  const bool force_dma = (mode & 0x8000) != 0;  // ... and the LDS-DMA ring kernel (conv_igemm_dma.hip), whose wide tiles serve shapes the dispatcher gives away
   mode &= 0xff;
   const int oh = cvx_conv_out_size(ih, k, stride, pad, dil), ow = cvx_conv_out_size(iw, k, stride, pad, dil);
   const std::vector<ConvTap> taps = cvx_conv_fwd_taps(k, pad, dil);
@@ -2531,6 +2537,11 @@ extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int
     CVX_CHECK(cvx_conv_tile_shape_ok(cp), "shape outside the row-band kernel (3x3 stride 1, cin % 8, cin >= 32)");
     cp.clk = g_cvx_clk;
     rc = cvx_conv_tile_launch(cp, st);
+  } else if (force_dma) {  // the dispatcher's own conditions (cvx_conv_igemm_launch), then straight to the kernel of last resort
+    CVX_CHECK(cin % 8 == 0 && cout % 4 == 0 && oh > 0 && ow > 0 && batch > 0, "shape outside the ring kernel (cin % 8, cout % 4, a non-empty output)");
+    CVX_CHECK(((uintptr_t)x_f16 % 16) == 0 && ((uintptr_t)w_f16 % 16) == 0, "conv: operands must be 16-byte aligned");
+    cp.clk = g_cvx_clk;
+    rc = cvx_conv_igemm_dma_launch(cp, st);
   } else {
     cp.no_tile = no_tile ? 1 : 0;
     rc = cvx_conv_igemm_launch(cp, st);
@@ -2569,7 +2580,26 @@ extern "C" int cvx_conv2d_dgrad_nhwc(const void* dy_f16, int32_t batch, int32_t 
       return rc;
     }
   }
-  // every other shape: one launch per phase class (the engine merges the classes of a strided gradient into one launch of the ring kernel)
+  // a strided gradient whose 2 ... 4 phase classes all have pixels and taps: the engine's route (backward_op) -- one merged launch of the ring kernel
+  if (phases.size() >= 2 && phases.size() <= 4) {
+    DevTemps tmp;
+    DgClass dg[4];
+    const half_t* zeros = nullptr;
+    for (size_t q = 0; q < phases.size(); ++q) {
+      const ConvTap* dt = nullptr;
+      if (!phases[q].taps.empty()) CVX_TRY(tmp.taps(phases[q].taps, &dt, &zeros));
+      dg[q].ph = make_phase(phases[q], dt);
+    }
+    if (phases_mergeable(dg, (int)phases.size())) {
+      ConvParams cp;
+      fill_conv_dgrad(g, dg[0].ph, dy, dx, (const half_t*)wt_f16, zeros, 0, &cp);
+      set_merged_phases(dg, (int)phases.size(), &cp);
+      const int rc = cvx_conv_igemm_launch(cp, st);
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+  }
+  // every other shape: one launch per phase class
   int rc = 0;
   for (size_t q = 0; q < phases.size() && rc == 0; ++q) {
     const DgradPhase& d = phases[q];

@@ -194,6 +194,12 @@ int cvx_debug_clock_buffer(void* buf);
  * workgroups, K-steps per weight chunk, LDS bytes, estimated microseconds x 100.  Returns 0, or -1 when the kernel does not take the
  * shape.  (No reference counterpart: the reference leaves the choice of algorithm to cuDNN behind nn.Conv2d, core/models/yolov8/modules.py:19-33.) */
 int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out8);
+/* Test hook: which of its compiled tile configurations the LDS-DMA ring convolution kernel (csrc/conv_igemm_dma.hip) runs for a launch of
+ * `pixels` output pixels (of the largest phase class for a merged data gradient), cin gathered and cout produced channels and ntaps taps --
+ * out[0..3] = tile rows (128, 64 or 32), channel tiles per workgroup (16-channel tiles for 128 / 64 rows: 1..6 or 8; 32-channel pairs for
+ * 32 rows: 1..4), channel blocks (gridDim.y), DMA passes per K-step.  The launcher calls the same function.  Returns 0, or -1 on bad
+ * arguments.  (No reference counterpart: the reference leaves the choice of algorithm to cuDNN behind nn.Conv2d, core/models/yolov8/modules.py:19-33.) */
+int cvx_debug_conv_dma_plan(int64_t pixels, int32_t cin, int32_t cout, int32_t ntaps, int32_t* out4);
 
 /* Bytes of device memory the engine currently owns (workspaces). */
 int64_t cvx_engine_workspace_bytes(const cvx_engine* e);
@@ -395,12 +401,14 @@ int cvx_centernet_decode(const float* pred, int32_t pred_ld, int32_t batch, int3
  * NHWC fp16 convolution, weights [cout][kh][kw][cin] fp16.  mode 0: out fp16 = conv; mode 1: out fp16 =
  * silu(conv*scale+shift); mode 2: out fp32 = conv + bias; mode 3 (the training epilogue): out fp32 = conv, and the
  * per-channel (sum, sum of squares) are added into `shift` viewed as zeroed fixed-point replica slabs.  mode | 0x100 runs the GEMM-shaped
- * kernel (conv_gemm.hip) whatever the dispatcher would pick (needs cin % 8 == 0, cout % 4 == 0).  Replaces: F.conv2d as used by
- * Conv.forward, core/models/yolov8/modules.py:29-30. */
+ * kernel (conv_gemm.hip) whatever the dispatcher would pick (needs cin % 8 == 0, cout % 4 == 0); mode | 0x8000 likewise the
+ * LDS-DMA ring kernel (conv_igemm_dma.hip).  Replaces: F.conv2d as used by Conv.forward, core/models/yolov8/modules.py:29-30. */
 int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, const void* w_f16, int32_t cout, int32_t k,
                     int32_t stride, int32_t pad, int32_t dil, int32_t mode, const float* scale_or_bias, const float* shift, void* out,
                     void* hip_stream);
-/* data gradient: dx (B,ih,iw,cin) fp16 from dy (B,oh,ow,cout) fp16 and w_t [cin][kh][kw][cout] fp16 */
+/* data gradient: dx (B,ih,iw,cin) fp16 from dy (B,oh,ow,cout) fp16 and w_t [cin][kh][kw][cout] fp16.  A strided gradient takes the
+ * engine's route: the pixel-shuffle GEMM where that applies, else one merged launch of its 2..4 phase classes (one launch per class
+ * when a class has no pixels or no taps). */
 int cvx_conv2d_dgrad_nhwc(const void* dy_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, const void* wt_f16, int32_t cout,
                           int32_t k, int32_t stride, int32_t pad, int32_t dil, void* dx_f16, void* hip_stream);
 /* weight gradient: dw [cout][kh][kw][cin] fp32 (overwritten) from x and dy; workspace >= cvx_conv2d_wgrad_workspace_bytes */
