@@ -140,6 +140,8 @@ PROTOTYPES = {
     "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_aug_images_plain": (_I32, [_P, _P, _I32, _P, _I32, _I32, _P]),
     "cvx_aug_boxes_padded": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "cvx_aug_warp_mix": (_I32, [_P, _P, _I32, _P, _I32, _I32, _P]),
+    "cvx_aug_boxes_warp": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _F, _F, _F, _I32, _P, _I32, _P, _P, _P]),
     "cvx_engine_set_seed": (_I32, [_P, _U64]),
     "cvx_engine_keep_shadows": (_I32, [_P]),
     "cvx_engine_set_fusion": (_I32, [_P, _I32]),

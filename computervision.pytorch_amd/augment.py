@@ -25,6 +25,13 @@ Deliberate deviations from the reference:
 
 The pixel primitives (bicubic resize, RGB<->HSV) follow OpenCV's uint8 algorithms as restated in tests/aug_restatement.py; their parity with
 OpenCV's bytes is not pinned.
+
+Beyond the reference: ``DeviceAugmenter(affine=..., mixup=...)`` runs a second stage of two launches behind the
+first -- ``cvx_aug_warp_mix`` warps every canvas by its own random affine / perspective matrix and mixes a partner canvas of the same batch
+in, ``cvx_aug_boxes_warp`` sends the labels through the same matrices and writes any of the four target formats -- with rules modelled on
+YOLOv5's ``random_perspective``, ``box_candidates`` and ``mixup`` (``draw_warp``, restated in tests/aug_warp_restatement.py), and
+``DeviceAugLoader(close_after=...)`` switches mosaic and MixUp off for the last epochs.  Both options default to off; then nothing new is
+drawn or launched.
 """
 from __future__ import annotations
 
@@ -124,6 +131,107 @@ def _align(n, a=16):
     return (n + a - 1) // a * a
 
 
+# ---- stage 2: affine / perspective warp and MixUp ----
+VIEW_DTYPE = np.dtype([("m", "<f4", (9,)), ("inv", "<f4", (9,)), ("s", "<f4"), ("partner", "<i4"), ("r", "<f4"), ("r1", "<f4"), ("reserved", "<i4", (2,))])
+assert VIEW_DTYPE.itemsize == 96                     # struct cvx_aug_view, include/cvx_engine.h
+
+AFFINE_DEFAULTS = dict(degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0, min_wh=2.0, min_area_ratio=0.1, max_aspect=100.0)
+
+
+def check_affine(affine, input_shape) -> Optional[Dict]:
+    """``affine`` completed with the defaults, or None; refuses unknown keys, ranges the draws cannot take and a perspective that could bring
+    the homogeneous w near 0 inside the picture (``perspective * max(H, W) >= 0.5``)."""
+    if affine is None:
+        return None
+    unknown = set(affine) - set(AFFINE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"affine: unknown option(s) {sorted(unknown)}; known: {sorted(AFFINE_DEFAULTS)}")
+    a = {k: float(affine.get(k, v)) for k, v in AFFINE_DEFAULTS.items()}
+    if not all(np.isfinite(v) for v in a.values()):
+        raise ValueError(f"affine: {a}")
+    if a["degrees"] < 0 or a["translate"] < 0 or a["perspective"] < 0 or not 0 <= a["scale"] < 1 or not 0 <= a["shear"] < 90:
+        raise ValueError(f"affine: degrees, translate, perspective >= 0, 0 <= scale < 1 and 0 <= shear < 90 are needed, got {a}")
+    if a["min_wh"] < 0 or a["min_area_ratio"] < 0 or a["max_aspect"] <= 1:
+        raise ValueError(f"affine: min_wh >= 0, min_area_ratio >= 0 and max_aspect > 1 are needed, got {a}")
+    if abs(a["perspective"]) * max(int(input_shape[0]), int(input_shape[1])) >= 0.5:
+        raise ValueError(f"affine: perspective {a['perspective']} times the longer side of {tuple(input_shape)} reaches 0.5: the homogeneous w "
+                         "would come near 0 inside the picture")
+    return a
+
+
+def warp_matrix(eight, input_shape) -> np.ndarray:
+    """``M = T . Sh . R . P . C`` in float64 from the eight drawn numbers ``(p_x, p_y, angle in degrees, zoom s, shear_x in degrees, shear_y in
+    degrees, t_x, t_y)``, YOLOv5's random_perspective: C moves the canvas centre to the origin, P carries the perspective terms, R is
+    cv2.getRotationMatrix2D(angle, (0, 0), s), Sh the shears' tangents, T the translation by ``(t_x W, t_y H)``."""
+    h, w = int(input_shape[0]), int(input_shape[1])
+    px, py, angle, zoom, shx, shy, tx, ty = (float(v) for v in eight)
+    C, P, R, Sh, T = (np.eye(3) for _ in range(5))
+    C[0, 2], C[1, 2] = -w / 2, -h / 2
+    P[2, 0], P[2, 1] = px, py
+    ca, sa = zoom * np.cos(np.deg2rad(angle)), zoom * np.sin(np.deg2rad(angle))
+    R[0, 0], R[0, 1], R[1, 0], R[1, 1] = ca, sa, -sa, ca
+    Sh[0, 1], Sh[1, 0] = np.tan(np.deg2rad(shx)), np.tan(np.deg2rad(shy))
+    T[0, 2], T[1, 2] = tx * w, ty * h
+    return T @ Sh @ R @ P @ C
+
+
+def draw_warp(rng: np.random.RandomState, B: int, input_shape, affine=None, mixup=0.0) -> Optional[Dict]:
+    """The host side of stage 2 for a batch of ``B`` outputs, drawn AFTER the batch's ``draw_params`` draws, in a fixed order:
+
+    1. with ``affine``: per canvas the eight numbers in YOLOv5's order, always all eight -- ``uniform(-perspective, perspective)`` twice,
+       ``uniform(-degrees, degrees)``, ``uniform(1 - scale, 1 + scale)``, ``uniform(-shear, shear)`` twice, ``uniform(0.5 - translate,
+       0.5 + translate)`` twice;
+    2. with ``mixup > 0`` and ``B > 1``: per output ``rand() < mixup``, then the partner ``j = randint(B - 1)``, ``p = j + (j >= i)``, then
+       ``beta(32, 32)``, always all three.
+
+    With both off nothing is drawn and None is returned.  Otherwise ``{"M", "Minv": (B, 3, 3) float64, "s": (B,) float64, "partner": (B,)
+    int (-1: none), "r", "r1": (B,) float32}`` -- what ``DeviceAugmenter.apply(warp=...)`` takes."""
+    a = check_affine(affine, input_shape)
+    mixup = float(mixup)
+    if not 0.0 <= mixup <= 1.0:
+        raise ValueError(f"mixup is a probability, got {mixup}")
+    mix = mixup > 0 and B > 1
+    if a is None and not mix:
+        return None
+    M, s = np.tile(np.eye(3), (B, 1, 1)), np.ones(B)
+    if a is not None:
+        for i in range(B):
+            e = [rng.uniform(-a["perspective"], a["perspective"]), rng.uniform(-a["perspective"], a["perspective"]),
+                 rng.uniform(-a["degrees"], a["degrees"]), rng.uniform(1 - a["scale"], 1 + a["scale"]),
+                 rng.uniform(-a["shear"], a["shear"]), rng.uniform(-a["shear"], a["shear"]),
+                 rng.uniform(0.5 - a["translate"], 0.5 + a["translate"]), rng.uniform(0.5 - a["translate"], 0.5 + a["translate"])]
+            M[i], s[i] = warp_matrix(e, input_shape), e[3]
+    partner, r = np.full(B, -1, np.int64), np.ones(B, np.float32)
+    if mix:
+        for i in range(B):
+            take = rng.rand() < mixup
+            j = int(rng.randint(B - 1))
+            ratio = np.float32(rng.beta(32.0, 32.0))
+            if take:
+                partner[i], r[i] = j + (j >= i), ratio
+    return {"M": M, "Minv": np.linalg.inv(M), "s": s, "partner": partner, "r": r, "r1": np.float32(1) - r}
+
+
+def view_table(warp: Dict, B: int) -> np.ndarray:
+    """``warp`` (a ``draw_warp`` result, or a hand-made one: ``M`` is needed, ``Minv`` defaults to the float64 inverse, ``s`` to 1, ``partner``
+    to none, ``r`` to 1, ``r1`` to ``fp32(1) - r``) as ``B`` ``cvx_aug_view`` records, everything rounded to fp32 here."""
+    M = np.asarray(warp["M"], np.float64).reshape(-1, 3, 3)
+    Minv = np.asarray(warp["Minv"], np.float64).reshape(-1, 3, 3) if warp.get("Minv") is not None else np.linalg.inv(M)
+    s = np.asarray(warp.get("s", np.ones(B)), np.float64).reshape(-1)
+    partner = np.asarray(warp.get("partner", np.full(B, -1)), np.int64).reshape(-1)
+    r = np.asarray(warp.get("r", np.ones(B)), np.float32).reshape(-1)
+    r1 = np.asarray(warp["r1"], np.float32).reshape(-1) if warp.get("r1") is not None else np.float32(1) - r
+    if not (len(M) == len(Minv) == len(s) == len(partner) == len(r) == len(r1) == B):
+        raise ValueError(f"warp: every entry needs one value per output image ({B})")
+    if not (np.isfinite(M).all() and np.isfinite(Minv).all() and np.isfinite(s).all() and (s > 0).all() and np.isfinite(r).all() and np.isfinite(r1).all()):
+        raise ValueError("warp: matrices, zooms and mixing weights must be finite, zooms positive")
+    if ((partner < -1) | (partner >= B) | (partner == np.arange(B))).any():
+        raise ValueError(f"warp: a partner is another output of the batch (0 .. {B - 1}) or -1, got {partner.tolist()}")
+    v = np.zeros(B, VIEW_DTYPE)
+    v["m"], v["inv"], v["s"], v["partner"], v["r"], v["r1"] = M.reshape(B, 9), Minv.reshape(B, 9), s, partner, r, r1
+    return v
+
+
 class SsdTargetSpec(NamedTuple):
     """What ``fmt="ssd"`` needs of the algorithm object: ``priors`` (A, 4) fp32 corner boxes (numpy or tensor), the class count without
     background, the matching threshold and the two variances."""
@@ -170,11 +278,23 @@ class DeviceAugmenter:
     of one image in the batch, so nothing can overflow; for CenterNet K = max_num_boxes, longer lists are cut to their first K boxes.  The
     per-image counts stay on the device in ``last_count`` and the overflow word (non-zero when an image was cut) in ``last_overflow``.
 
-    ``train=False`` is the validation path (module docstring): no mosaic, no flip, no colour transform, no random numbers, all four formats."""
+    ``train=False`` is the validation path (module docstring): no mosaic, no flip, no colour transform, no random numbers, all four formats.
 
-    def __init__(self, input_shape, mosaic=False, mosaic_prob=0.5, seed=None, jitter=0.3, hue=0.1, sat=0.7, val=0.4, train=True, target=None):
+    ``affine`` (None, or a dict of any of ``AFFINE_DEFAULTS``' keys: degrees, translate, scale, shear, perspective and the box tests min_wh,
+    min_area_ratio, max_aspect) and ``mixup`` (the probability that an output takes a partner from its own batch) are training options and
+    off by default; with either on, ``draw_warp`` draws after the batch's ``draw_params`` draws and ``apply`` runs stage 2.  The warp last
+    applied (None without stage 2) stays in ``last_warp``.  ``__call__(..., mixup=0.0)`` overrides the probability for one batch."""
+
+    def __init__(self, input_shape, mosaic=False, mosaic_prob=0.5, seed=None, jitter=0.3, hue=0.1, sat=0.7, val=0.4, train=True, target=None,
+                 affine=None, mixup=0.0):
         self.input_shape = (int(input_shape[0]), int(input_shape[1]))
         self.train = bool(train)
+        self.affine, self.mixup = check_affine(affine, self.input_shape), float(mixup)
+        if not 0.0 <= self.mixup <= 1.0:
+            raise ValueError(f"mixup is a probability, got {mixup}")
+        if not self.train and (self.affine is not None or self.mixup > 0):
+            raise ValueError("affine and mixup are training options: validation pictures are not warped or mixed")
+        self.last_warp = None
         self.mosaic, self.mosaic_prob = bool(mosaic) and self.train, float(mosaic_prob)
         self.rng = np.random.RandomState(seed)
         self.gains = dict(jitter=jitter, hue=hue, sat=sat, val=val)
@@ -196,7 +316,7 @@ class DeviceAugmenter:
             raise ValueError(f'fmt="{fmt}" with a {type(spec).__name__}')
         return spec
 
-    def __call__(self, images, boxes, fmt="yolo8", exact=True):
+    def __call__(self, images, boxes, fmt="yolo8", exact=True, mixup=None):
         groups = [list(e) if isinstance(e, (list, tuple)) else [e] for e in images]
         bgroups = [list(b) if isinstance(b, (list, tuple)) else [b] for b in boxes]
         params = []
@@ -205,17 +325,23 @@ class DeviceAugmenter:
                 raise ValueError("an output image takes one picture, or four for a mosaic, and as many box arrays")
             params.append(draw_params(self.rng, [tuple(t.shape[:2]) for t in g], self.input_shape, len(g) == 4,
                                       nboxes=[len(np.asarray(b).reshape(-1, 5)) for b in bg], train=self.train, **self.gains))
-        return self.apply(params, groups, bgroups, fmt=fmt, exact=exact)
+        warp = draw_warp(self.rng, len(params), self.input_shape, self.affine, self.mixup if mixup is None else mixup)
+        return self.apply(params, groups, bgroups, fmt=fmt, exact=exact, warp=warp)
 
-    def apply(self, params: List[Dict], sources: List[List[torch.Tensor]], boxes: List[List], fmt="yolo8", exact=True, max_boxes=None):
+    def apply(self, params: List[Dict], sources: List[List[torch.Tensor]], boxes: List[List], fmt="yolo8", exact=True, max_boxes=None, warp=None):
         """Runs the launches for drawn parameters (``draw_params`` results, or hand-made ones of the same form).  ``fmt="padded"`` stops
         after the padded box kernel and returns ``(images, (labels (B, capacity, 5), counts (B)))`` with capacity ``max_boxes``, or
-        without it the largest number of source boxes of one image."""
+        without it the largest number of source boxes of one image.  ``warp``: a ``draw_warp`` result or hand-made matrices and partners
+        (``view_table``); with it stage 1 writes into scratch and the two stage-2 launches write the batch and the targets, without it
+        (None) exactly the stage-1 launches run."""
         if fmt not in YOLO_FORMATS + TARGET_FORMATS:
             raise ValueError(fmt)
         spec = self._spec(fmt) if fmt in ("ssd", "centernet") else None
         H, W = self.input_shape
         B = len(params)
+        if warp is not None and not self.train:
+            raise ValueError("the warp and MixUp are training options")
+        views = None if warp is None else view_table(warp, B)
         flat_src = [t for g in sources for t in g]
         if B == 0 or not all(torch.is_tensor(t) and t.is_cuda for t in flat_src):
             raise L.CvxError("DeviceAugmenter takes uint8 pictures in GPU memory (there is no CPU path)")
@@ -241,13 +367,14 @@ class DeviceAugmenter:
                 box_start.append(box_start[-1] + len(b))
             job_start.append(len(jobs))
         J, N = len(jobs), box_start[-1]
-        # one pinned blob: jobs | job_start | job_box_start | luts | boxes
+        # one pinned blob: jobs | job_start | job_box_start | luts | boxes | views (stage 2 only)
         o_jobs = 0
         o_js = _align(o_jobs + J * 64)
         o_bs = _align(o_js + 4 * (B + 1))
         o_lut = _align(o_bs + 4 * (J + 1))
         o_box = _align(o_lut + 768 * B)
-        total = _align(o_box + 20 * N)
+        o_view = _align(o_box + 20 * N)
+        total = o_view if views is None else _align(o_view + 96 * B)
         host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
         hv[o_jobs:o_jobs + J * 64].view(JOB_DTYPE)[:] = np.array(jobs, dtype=JOB_DTYPE)
@@ -256,8 +383,14 @@ class DeviceAugmenter:
         hv[o_lut:o_lut + 768 * B].reshape(B, 3, 256)[:] = np.stack([np.asarray(p["lut"], np.uint8).reshape(3, 256) for p in params])
         if N:
             hv[o_box:o_box + 20 * N].view(np.float32).reshape(N, 5)[:] = np.concatenate(box_rows, 0)
+        if views is not None:
+            hv[o_view:o_view + 96 * B].view(VIEW_DTYPE)[:] = views
         blob = torch.empty(total, dtype=torch.uint8, device=dev)
         blob.copy_(host, non_blocking=True)
+        self.last_warp = warp
+        if views is not None:
+            n_src = [box_start[job_start[i + 1]] - box_start[job_start[i]] for i in range(B)]
+            return self._apply_warp(fmt, spec, blob, (o_jobs, o_js, o_bs, o_lut, o_box), o_view, views["partner"].tolist(), n_src, N, exact, max_boxes)
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
         if fmt in TARGET_FORMATS:
             most = max(box_start[job_start[i + 1]] - box_start[job_start[i]] for i in range(B))
@@ -275,6 +408,16 @@ class DeviceAugmenter:
     def _targets(self, fmt, spec, blob, offsets, B, N, out, most_boxes, max_boxes):
         """``fmt="ssd"`` / ``"centernet"`` / ``"padded"``: image launch, padded box launch, target kernel -- nothing is read back"""
         dev = blob.device
+        cap = self._capacity(fmt, spec, most_boxes, max_boxes, dev)
+        labels = torch.empty(B, cap, 5, dtype=torch.float32, device=dev)
+        counts = torch.empty(B, dtype=torch.int32, device=dev)
+        overflow = torch.empty(1, dtype=torch.int32, device=dev)
+        self._launch_padded(blob, offsets, B, N, out, labels, counts, overflow)
+        self.last_count, self.last_overflow = counts, overflow
+        return self._finish(fmt, spec, labels, counts)
+
+    def _capacity(self, fmt, spec, most_boxes, max_boxes, dev):
+        """rows per image of the padded labels, known on the host; caches SSD's priors on ``dev`` and checks CenterNet's feature size"""
         if fmt == "padded":
             cap = max(most_boxes, 1) if max_boxes is None else int(max_boxes)
         elif fmt == "ssd":
@@ -287,11 +430,9 @@ class DeviceAugmenter:
             ratio = self.input_shape[0] // fh if fh > 0 else 0
             if ratio <= 0 or (self.input_shape[0] // ratio, self.input_shape[1] // ratio) != (fh, fw):
                 raise ValueError(f"CenterNet feature size {tuple(spec.feature_hw)} does not belong to a {self.input_shape} input")
-        labels = torch.empty(B, cap, 5, dtype=torch.float32, device=dev)
-        counts = torch.empty(B, dtype=torch.int32, device=dev)
-        overflow = torch.empty(1, dtype=torch.int32, device=dev)
-        self._launch_padded(blob, offsets, B, N, out, labels, counts, overflow)
-        self.last_count, self.last_overflow = counts, overflow
+        return cap
+
+    def _finish(self, fmt, spec, labels, counts):
         if fmt == "padded":
             return labels, counts
         if fmt == "ssd":
@@ -328,6 +469,47 @@ class DeviceAugmenter:
             L.check(lib.cvx_aug_boxes_padded(P(base + o_jobs), P(base + o_js), P(base + o_bs), B, P(base + o_box), N, H, W, int(labels.shape[1]),
                                              L.ptr(labels), L.ptr(counts), L.ptr(overflow), stream), "cvx_aug_boxes_padded")
 
+    def _apply_warp(self, fmt, spec, blob, offsets, o_view, partner, n_src, N, exact, max_boxes):
+        """Stage 1 into scratch (image launch + ``cvx_aug_boxes_padded`` with a row for every source box, so it cannot overflow), then
+        ``cvx_aug_warp_mix`` and ``cvx_aug_boxes_warp``.  Output i can carry the boxes of its canvas and of its partner's, so the
+        capacities count both: the compact rows their sum over the batch, SSD the largest pair."""
+        dev, B, (H, W) = blob.device, len(n_src), self.input_shape
+        pair = [n + (n_src[p] if p >= 0 else 0) for n, p in zip(n_src, partner)]
+        canvases = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+        labels1 = torch.empty(B, max(max(n_src), 1), 5, dtype=torch.float32, device=dev)
+        counts1 = torch.empty(B, dtype=torch.int32, device=dev)
+        overflow1 = torch.empty(1, dtype=torch.int32, device=dev)
+        self._launch_padded(blob, offsets, B, N, canvases, labels1, counts1, overflow1)
+        if fmt in YOLO_FORMATS:
+            rows = torch.empty(max(sum(pair), 1), 6, dtype=torch.float32, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            self._launch_warp(blob, o_view, canvases, out, labels1, counts1, True, rows, count, None)
+            self.last_count = count
+            t = rows[:int(count.item()) if exact else sum(pair)]
+            if fmt == "yolo7":
+                return out, t
+            return out, {"batch_idx": t[:, 0], "cls": t[:, 1:2], "bboxes": t[:, 2:6]}
+        cap = self._capacity(fmt, spec, max(pair), max_boxes, dev)
+        labels = torch.empty(B, cap, 5, dtype=torch.float32, device=dev)
+        counts = torch.empty(B, dtype=torch.int32, device=dev)
+        overflow = torch.empty(1, dtype=torch.int32, device=dev)
+        self._launch_warp(blob, o_view, canvases, out, labels1, counts1, False, labels, counts, overflow)
+        self.last_count, self.last_overflow = counts, overflow
+        return out, self._finish(fmt, spec, labels, counts)
+
+    def _launch_warp(self, blob, o_view, canvases, out, labels1, counts1, compact, rows, counts, overflow):
+        """the two stage-2 launches on the current stream of the blob's device (tools/aug_warp_cost.py times this behind ``_launch_padded``)"""
+        H, W = self.input_shape
+        c = self.affine or AFFINE_DEFAULTS
+        views, lib = L.C.c_void_p(blob.data_ptr() + o_view), L.load()
+        with torch.cuda.device(blob.device):
+            stream = L.stream_ptr(blob.device)
+            L.check(lib.cvx_aug_warp_mix(L.ptr(canvases), views, int(canvases.shape[0]), L.ptr(out), H, W, stream), "cvx_aug_warp_mix")
+            L.check(lib.cvx_aug_boxes_warp(L.ptr(labels1), L.ptr(counts1), int(labels1.shape[1]), views, int(canvases.shape[0]), H, W, c["min_wh"],
+                                           c["min_area_ratio"], c["max_aspect"], int(compact), L.ptr(rows), int(rows.shape[-2]), L.ptr(counts),
+                                           L.ptr(overflow), stream), "cvx_aug_boxes_warp")
+
 
 class DeviceAugLoader:
     """Iterable of augmented batches over any indexable ``source`` of ``(uint8 HWC image tensor, (n, 5) boxes)``: what ``DetectionDataset`` +
@@ -338,11 +520,19 @@ class DeviceAugLoader:
     Training (``augmenter.train``): ``length`` batches; items are taken in order, wrapping around; a mosaic item takes three further random
     items and shuffles the four, like mosaic_for_voc (:292-298).  Validation (``DeviceAugmenter(train=False)``): the source is walked once,
     in order; ``drop_last=True`` (the reference's DataLoader setting) leaves out a short last batch, ``drop_last=False`` yields it;
-    ``length`` is not needed."""
+    ``length`` is not needed.
 
-    def __init__(self, source, batch_size, augmenter: DeviceAugmenter, length: Optional[int] = None, fmt="yolo8", device="cuda", drop_last=True):
+    ``close_after=E`` ("close mosaic", YOLOv8): every ``__iter__`` call is an epoch, counted in ``epoch`` (settable, for a resumed run); from
+    epoch ``E`` on no mosaic is asked for and the augmenter is called with ``mixup=0``, while its ``affine`` stays on."""
+
+    def __init__(self, source, batch_size, augmenter: DeviceAugmenter, length: Optional[int] = None, fmt="yolo8", device="cuda", drop_last=True,
+                 close_after: Optional[int] = None):
         self.source, self.batch_size, self.augmenter, self.fmt = source, int(batch_size), augmenter, fmt
         self.device, self.drop_last = torch.device(device), bool(drop_last)
+        if close_after is not None and (int(close_after) < 0 or not augmenter.train):
+            raise ValueError("close_after is a number of training epochs")
+        self.close_after = None if close_after is None else int(close_after)
+        self.epoch = 0                                   # __iter__ calls so far; settable, for a resumed run
         if fmt not in YOLO_FORMATS + ("ssd", "centernet"):
             raise ValueError(fmt)
         if augmenter.train:
@@ -361,6 +551,13 @@ class DeviceAugLoader:
         return image.to(self.device, non_blocking=True), box
 
     def __iter__(self):
+        """One epoch.  The loader counts these calls in ``epoch``; from epoch ``close_after`` on ("close mosaic", YOLOv8) it asks for no
+        mosaic -- ``want_mosaic`` is not called, so its draw is not made -- and passes ``mixup=0``; ``affine`` stays on."""
+        closed = self.close_after is not None and self.epoch >= self.close_after
+        self.epoch += 1
+        return self._batches(closed)
+
+    def _batches(self, closed):
         n, aug = len(self.source), self.augmenter
         if not aug.train:
             for k in range(self.length):
@@ -371,7 +568,7 @@ class DeviceAugLoader:
         for _ in range(self.length):
             images, boxes = [], []
             for _ in range(self.batch_size):
-                if aug.want_mosaic():
+                if not closed and aug.want_mosaic():
                     ids = list(aug.rng.choice(n, 3, replace=n < 3)) + [item % n]
                     aug.rng.shuffle(ids)
                     picked = [self._item(i) for i in ids]
@@ -382,4 +579,4 @@ class DeviceAugLoader:
                     images.append(image)
                     boxes.append(box)
                 item += 1
-            yield aug(images, boxes, fmt=self.fmt)
+            yield aug(images, boxes, fmt=self.fmt, mixup=0.0 if closed else None)

@@ -383,3 +383,267 @@ extern "C" int cvx_aug_boxes_padded(const cvx_aug_job* jobs, const int32_t* job_
   CVX_HIP(hipGetLastError());
   return 0;
 }
+
+// ---- stage 2: affine / perspective warp, MixUp inside the batch, and the boxes that go with them ---------------------
+// Stage 1 above writes its canvases and padded labels into scratch; two further launches turn them into the batch and the targets.  The
+// rules are the project's own, modelled on YOLOv5's random_perspective / box_candidates / mixup, and tests/aug_warp_restatement.py holds
+// both kernels to the bit.  The fp32 operation order, every step rounded on its own (contraction is off for the whole file):
+//
+//   pixel (x, y), integer coordinates, no half-pixel shift:
+//     u' = (i0 * x + i1 * y) + i2,  v' = (i3 * x + i4 * y) + i5,  w = (i6 * x + i7 * y) + i8      (i = M^-1, row-major)
+//     u = u' / w,  v = v' / w                                       (always divided)
+//     if not (-1 < u < W and -1 < v < H): no tap can lie on the canvas, the value is the grey 128 / 255 itself
+//     x0 = floor(u), lx = u - x0, y0 = floor(v), ly = v - y0; a tap outside the canvas is the grey
+//     top = v00 * (1 - lx) + v01 * lx,  bot = v10 * (1 - lx) + v11 * lx,  value = top * (1 - ly) + bot * ly
+//   MixUp: out = own * r + partner * r1 (both products rounded, then the sum); an output without a partner is `own` untouched
+//   box [cls, cx, cy, w, h]: pcx = cx * W, pw = w * W, x1 = pcx - pw / 2, x2 = pcx + pw / 2 (y alike with H); the corners (x1, y1), (x2, y2),
+//     (x1, y2), (x2, y1) through M as above ((m0 * x + m1 * y) + m2, ... , divided by the third row's value); min / max of the four,
+//     clipped to [0, W] x [0, H]; w2 = X2 - X1, h2 = Y2 - Y1, w1 = x2 - x1, h1 = y2 - y1; kept iff w2 > min_wh and h2 > min_wh and
+//     (w2 * h2) / ((w1 * s) * (h1 * s)) > min_area_ratio and fmax(w2 / h2, h2 / w2) < max_aspect; then the tail of box_row():
+//     X / W, Y / H, bw = X2 - X1, cx = X1 + bw / 2.
+namespace {
+
+static_assert(sizeof(cvx_aug_view) == 96, "cvx_aug_view is 96 bytes on both sides of the ABI");
+
+__device__ __forceinline__ void project(const float* __restrict__ m, float x, float y, float* px, float* py) {
+  const float a = (m[0] * x + m[1] * y) + m[2];
+  const float b = (m[3] * x + m[4] * y) + m[5];
+  const float w = (m[6] * x + m[7] * y) + m[8];
+  *px = a / w;
+  *py = b / w;
+}
+
+// the three planes of output pixel (x, y) of one canvas seen through inv = M^-1
+__device__ __forceinline__ void warp_pixel(const float* __restrict__ canvas, size_t plane, const float* __restrict__ inv, int x, int y, int H, int W,
+                                           float* o) {
+  const float grey = 128.0f / 255.0f;
+  float u, v;
+  project(inv, (float)x, (float)y, &u, &v);
+  if (!(u > -1.0f && u < (float)W && v > -1.0f && v < (float)H)) {   // also every NaN
+    o[0] = o[1] = o[2] = grey;
+    return;
+  }
+  const float xf = floorf(u), yf = floorf(v);
+  const float lx = u - xf, ly = v - yf, omx = 1.0f - lx, omy = 1.0f - ly;
+  const int x0 = (int)xf, y0 = (int)yf;                              // -1 .. W - 1, -1 .. H - 1
+  const bool xa = x0 >= 0, xb = x0 + 1 < W, ya = y0 >= 0, yb = y0 + 1 < H;
+  const long long at = (long long)y0 * W + x0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* p = canvas + c * plane;
+    const float v00 = (xa && ya) ? p[at] : grey, v01 = (xb && ya) ? p[at + 1] : grey;
+    const float v10 = (xa && yb) ? p[at + W] : grey, v11 = (xb && yb) ? p[at + W + 1] : grey;
+    const float top = v00 * omx + v01 * lx, bot = v10 * omx + v11 * lx;
+    o[c] = top * omy + bot * ly;
+  }
+}
+
+// The tile and the thread -> pixel map of aug_images_kernel: a wave stores 256 contiguous bytes per plane.  The view of an output is the
+// same for the whole workgroup, so its matrix arrives through scalar loads and the partner branch never diverges.
+__global__ __launch_bounds__(256) void aug_warp_mix_kernel(const float* __restrict__ canvases, const cvx_aug_view* __restrict__ views, int batch,
+                                                           float* __restrict__ out, int H, int W) {
+  const int tid = threadIdx.x, img = blockIdx.z;
+  const int x = blockIdx.x * TW + (tid & 63), ty0 = blockIdx.y * TH;
+  if (x >= W) return;
+  const size_t plane = (size_t)H * W;
+  const cvx_aug_view& vw = views[img];
+  const int p = vw.partner;
+  const bool mix = p >= 0 && p < batch;
+  const float r = vw.r, r1 = vw.r1;
+  for (int ly = tid >> 6; ly < TH; ly += 4) {
+    const int y = ty0 + ly;
+    if (y >= H) break;
+    float a[3];
+    warp_pixel(canvases + (size_t)img * 3 * plane, plane, vw.inv, x, y, H, W, a);
+    if (mix) {
+      float b[3];
+      warp_pixel(canvases + (size_t)p * 3 * plane, plane, views[p].inv, x, y, H, W, b);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a[c] = a[c] * r + b[c] * r1;
+    }
+    float* o = out + (size_t)img * 3 * plane + (size_t)y * W + x;
+    o[0] = a[0];
+    o[plane] = a[1];
+    o[2 * plane] = a[2];
+  }
+}
+
+// One stage-1 label l = [cls, cx, cy, w, h] through the view of its canvas -> o in the same form; returns whether the box is kept.
+__device__ __forceinline__ bool warp_box_row(const cvx_aug_view& vw, const float* __restrict__ l, float fW, float fH, float min_wh, float min_area,
+                                             float max_aspect, float* o) {
+  const float pcx = l[1] * fW, pcy = l[2] * fH, pw = l[3] * fW, ph = l[4] * fH;
+  const float x1 = pcx - pw / 2.0f, x2 = pcx + pw / 2.0f, y1 = pcy - ph / 2.0f, y2 = pcy + ph / 2.0f;
+  float ax, ay, bx, by, cx, cy, dx, dy;
+  project(vw.m, x1, y1, &ax, &ay);
+  project(vw.m, x2, y2, &bx, &by);
+  project(vw.m, x1, y2, &cx, &cy);
+  project(vw.m, x2, y1, &dx, &dy);
+  float X1 = fminf(fminf(ax, bx), fminf(cx, dx)), X2 = fmaxf(fmaxf(ax, bx), fmaxf(cx, dx));
+  float Y1 = fminf(fminf(ay, by), fminf(cy, dy)), Y2 = fmaxf(fmaxf(ay, by), fmaxf(cy, dy));
+  X1 = fminf(fmaxf(X1, 0.0f), fW);
+  X2 = fminf(fmaxf(X2, 0.0f), fW);
+  Y1 = fminf(fmaxf(Y1, 0.0f), fH);
+  Y2 = fminf(fmaxf(Y2, 0.0f), fH);
+  const float w2 = X2 - X1, h2 = Y2 - Y1, w1 = x2 - x1, h1 = y2 - y1;
+  const float ratio = (w2 * h2) / ((w1 * vw.s) * (h1 * vw.s));
+  const float aspect = fmaxf(w2 / h2, h2 / w2);
+  const bool keep = w2 > min_wh && h2 > min_wh && ratio > min_area && aspect < max_aspect;
+  const float nx1 = X1 / fW, nx2 = X2 / fW, ny1 = Y1 / fH, ny2 = Y2 / fH;
+  const float bw = nx2 - nx1, bh = ny2 - ny1;
+  o[0] = l[0];
+  o[1] = nx1 + bw / 2.0f;
+  o[2] = ny1 + bh / 2.0f;
+  o[3] = bw;
+  o[4] = bh;
+  return keep;
+}
+
+// Output b takes the kept boxes of its own canvas in stage-1 order, then those of its partner's canvas, each through the view of the
+// canvas it came from.  The padded form, one workgroup per output: labels[b] (cap_out, 5), counts[b] and the overflow word, the shape of
+// aug_boxes_padded_kernel with its scan (chunk_rank), no atomics.
+__global__ __launch_bounds__(256) void aug_boxes_warp_padded_kernel(const float* __restrict__ labels_in, const int32_t* __restrict__ counts_in,
+                                                                    int cap_in, const cvx_aug_view* __restrict__ views, int batch, int H, int W,
+                                                                    float min_wh, float min_area, float max_aspect, float* __restrict__ out,
+                                                                    int cap_out, int32_t* __restrict__ counts, int32_t* __restrict__ overflow) {
+  __shared__ int wave_tot[4];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const float fW = (float)W, fH = (float)H;
+  const int partner = views[b].partner;
+  float* lab_out = out + (size_t)b * cap_out * 5;
+  int base = 0;
+  for (int seg = 0; seg < 2; ++seg) {
+    const int c = seg ? partner : b;
+    if (c < 0 || c >= batch) break;
+    const cvx_aug_view vw = views[c];
+    const int n = min(counts_in[c], cap_in);
+    const float* lab = labels_in + (size_t)c * cap_in * 5;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+      const int i = c0 + tid;
+      bool keep = false;
+      float o[5] = {0, 0, 0, 0, 0};
+      if (i < n) keep = warp_box_row(vw, lab + (size_t)i * 5, fW, fH, min_wh, min_area, max_aspect, o);
+      int total;
+      const int pos = base + chunk_rank(keep, wave_tot, &total);
+      if (keep && pos < cap_out) {
+        float* t = lab_out + (size_t)pos * 5;
+        t[0] = o[0]; t[1] = o[1]; t[2] = o[2]; t[3] = o[3]; t[4] = o[4];
+      }
+      base += total;
+    }
+  }
+  const int kept = min(base, cap_out);
+  for (int i = kept * 5 + tid; i < cap_out * 5; i += 256) lab_out[i] = 0.0f;
+  if (tid == 0) {
+    counts[b] = kept;
+    if (base > cap_out) *overflow = 1;
+  }
+}
+
+// The compact form, rows [image, cls, cx, cy, w, h] in image order from row 0 on, the rest of the cap_out rows with image -1, and the row
+// count: the form of aug_boxes_kernel.  The rows of all outputs share one numbering, so one workgroup makes them, but not output after
+// output (a batch of 32 with partners is 64 short lists, and a walk with two barriers per list took 50 - 90 us): each of its 16 waves
+// takes every 16th output and walks that output's lists 64 boxes at a time with a ballot, once to count the kept boxes, and, after an
+// integer scan of the counts in LDS, a second time to write them at their place.  The order is fixed by construction, no atomics.
+constexpr int COMPACT_THREADS = 1024, COMPACT_MAX_BATCH = 4096;
+
+// One pass over the lists of output b by one wave.  WRITE: rows from `base` on.  Returns the number of kept boxes.
+template <bool WRITE>
+__device__ __forceinline__ int compact_walk(const float* __restrict__ labels_in, const int32_t* __restrict__ counts_in, int cap_in,
+                                            const cvx_aug_view* __restrict__ views, int batch, int b, float fW, float fH, float min_wh, float min_area,
+                                            float max_aspect, float* __restrict__ out, int cap_out, int base) {
+  const int lane = threadIdx.x & 63;
+  const int partner = views[b].partner;
+  int kept = 0;
+  for (int seg = 0; seg < 2; ++seg) {
+    const int c = seg ? partner : b;
+    if (c < 0 || c >= batch) break;
+    const cvx_aug_view vw = views[c];
+    const int n = min(counts_in[c], cap_in);
+    const float* lab = labels_in + (size_t)c * cap_in * 5;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+      const int i = c0 + lane;
+      bool keep = false;
+      float o[5] = {0, 0, 0, 0, 0};
+      if (i < n) keep = warp_box_row(vw, lab + (size_t)i * 5, fW, fH, min_wh, min_area, max_aspect, o);
+      const unsigned long long m = __ballot(keep);
+      if (WRITE) {
+        const int pos = base + kept + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && pos < cap_out) {
+          float* t = out + (size_t)pos * 6;
+          t[0] = (float)b; t[1] = o[0]; t[2] = o[1]; t[3] = o[2]; t[4] = o[3]; t[5] = o[4];
+        }
+      }
+      kept += __popcll(m);
+    }
+  }
+  return kept;
+}
+
+__global__ __launch_bounds__(COMPACT_THREADS) void aug_boxes_warp_compact_kernel(const float* __restrict__ labels_in, const int32_t* __restrict__ counts_in,
+                                                                                 int cap_in, const cvx_aug_view* __restrict__ views, int batch, int H,
+                                                                                 int W, float min_wh, float min_area, float max_aspect,
+                                                                                 float* __restrict__ out, int cap_out, int32_t* __restrict__ count) {
+  __shared__ int start[COMPACT_MAX_BATCH + 1];               // start[b]: first row of output b; start[batch]: the number of rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = COMPACT_THREADS / 64;
+  const float fW = (float)W, fH = (float)H;
+  for (int b = wave; b < batch; b += waves) {
+    const int kept = compact_walk<false>(labels_in, counts_in, cap_in, views, batch, b, fW, fH, min_wh, min_area, max_aspect, out, cap_out, 0);
+    if (lane == 0) start[b + 1] = kept;
+  }
+  __syncthreads();
+  if (wave == 0) {                                            // inclusive scan of the counts, 64 at a time
+    int carry = 0;
+    for (int c0 = 0; c0 < batch; c0 += 64) {
+      int x = c0 + lane < batch ? start[c0 + lane + 1] : 0;
+      for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+      }
+      if (c0 + lane < batch) start[c0 + lane + 1] = carry + x;
+      carry += __shfl(x, 63);
+    }
+    if (lane == 0) start[0] = 0;
+  }
+  __syncthreads();
+  for (int b = wave; b < batch; b += waves)
+    compact_walk<true>(labels_in, counts_in, cap_in, views, batch, b, fW, fH, min_wh, min_area, max_aspect, out, cap_out, start[b]);
+  const int kept = min(start[batch], cap_out);
+  for (int i = kept + tid; i < cap_out; i += COMPACT_THREADS) {   // unused rows: image -1
+    float* t = out + (size_t)i * 6;
+    t[0] = -1.0f; t[1] = 0.0f; t[2] = 0.0f; t[3] = 0.0f; t[4] = 0.0f; t[5] = 0.0f;
+  }
+  if (tid == 0) *count = kept;
+}
+
+}  // namespace
+
+extern "C" int cvx_aug_warp_mix(const float* canvases, const cvx_aug_view* views, int32_t batch, float* out_nchw, int32_t H, int32_t W,
+                                void* hip_stream) {
+  CVX_CHECK(canvases && views && out_nchw && canvases != out_nchw, "null pointer, or the warp in place");
+  CVX_CHECK(batch > 0 && batch <= 65535 && H > 0 && W > 0 && (long long)H * W * 3 < (1ll << 31), "bad shape");
+  const dim3 grid(cvx_cdiv(W, TW), cvx_cdiv(H, TH), batch);
+  CVX_CHECK(grid.y <= 65535, "output too tall");
+  hipLaunchKernelGGL(aug_warp_mix_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, canvases, views, batch, out_nchw, H, W);
+  CVX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int cvx_aug_boxes_warp(const float* labels_in, const int32_t* counts_in, int32_t cap_in, const cvx_aug_view* views, int32_t batch,
+                                  int32_t H, int32_t W, float min_wh, float min_area_ratio, float max_aspect, int32_t compact, float* out,
+                                  int32_t cap_out, int32_t* counts, int32_t* overflow, void* hip_stream) {
+  CVX_CHECK(labels_in && counts_in && views && out && counts, "null pointer");
+  CVX_CHECK(batch > 0 && H > 0 && W > 0 && cap_in > 0 && cap_out > 0 && (long long)cap_in * 5 < (1ll << 31) && (long long)cap_out * 6 < (1ll << 31),
+            "bad arguments");
+  if (compact) {
+    CVX_CHECK(batch <= COMPACT_MAX_BATCH, "the compact form takes a batch of at most 4096");
+    hipLaunchKernelGGL(aug_boxes_warp_compact_kernel, dim3(1), dim3(COMPACT_THREADS), 0, (hipStream_t)hip_stream, labels_in, counts_in, cap_in, views,
+                       batch, H, W, min_wh, min_area_ratio, max_aspect, out, cap_out, counts);
+  } else {
+    CVX_CHECK(overflow, "the padded form needs the overflow word");
+    CVX_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t), (hipStream_t)hip_stream));
+    hipLaunchKernelGGL(aug_boxes_warp_padded_kernel, dim3(batch), dim3(256), 0, (hipStream_t)hip_stream, labels_in, counts_in, cap_in, views, batch, H,
+                       W, min_wh, min_area_ratio, max_aspect, out, cap_out, counts, overflow);
+  }
+  CVX_HIP(hipGetLastError());
+  return 0;
+}

@@ -748,6 +748,38 @@ int cvx_aug_images_plain(const cvx_aug_job* jobs, const int32_t* job_start, int3
  * function cvx_aug_boxes uses, so the rows of image b are bit-identical to cvx_aug_boxes' rows with image index b. */
 int cvx_aug_boxes_padded(const cvx_aug_job* jobs, const int32_t* job_start, const int32_t* job_box_start, int32_t batch, const float* boxes,
                          int32_t n_boxes, int32_t H, int32_t W, int32_t max_boxes, float* labels, int32_t* counts, int32_t* overflow, void* hip_stream);
+/* Stage 2 of the training augmentation: a random affine / perspective warp of every canvas and MixUp inside the
+ * batch, behind the launches above, which then write into scratch.  One view per output image b, in device memory.  m: the matrix M
+ * (row-major, canvas pixel -> output pixel) of canvas b; inv: its inverse (inverted in float64 on the host, then rounded); s: the zoom
+ * drawn for M, used by the area test of the boxes; partner: the output whose warped canvas is mixed into output b, or -1; r, r1: the
+ * weights of the own and the partner's canvas (r1 = 1 - r in fp32, taken on the host).  96 bytes. */
+typedef struct cvx_aug_view {
+  float m[9], inv[9], s;
+  int32_t partner;
+  float r, r1;
+  int32_t reserved[2];
+} cvx_aug_view;
+/* The image half of stage 2, one launch, asynchronous.  canvases: (batch, 3, H, W) fp32, what cvx_aug_images / cvx_aug_images_plain wrote;
+ * out_nchw: the final batch, same shape, another buffer.  Output pixel (x, y), integer coordinates without a half-pixel shift (as
+ * cv2.warpPerspective): (u', v', w) = inv . (x, y, 1), u = u' / w, v = v' / w (always divided), x0 = floor(u), lx = u - x0, likewise y,
+ * the four taps mixed bilinearly, a tap outside the canvas being the canvas grey 128 / 255.  With a partner p (0 <= p < batch):
+ * out_b = warp_b(canvas_b) * r + warp_p(canvas_p) * r1, each canvas through its own matrix.  Every fp32 operation is rounded on its own,
+ * in the order written at the head of the stage-2 part of csrc/augment.hip; the identity matrix returns the canvas bit for bit.
+ * Modelled on YOLOv5's random_perspective (cv2.warpPerspective, borderValue 114 there) and mixup; the reference has neither. */
+int cvx_aug_warp_mix(const float* canvases, const cvx_aug_view* views, int32_t batch, float* out_nchw, int32_t H, int32_t W, void* hip_stream);
+/* The box half of stage 2, one launch, asynchronous.  labels_in (batch, cap_in, 5) / counts_in (batch): what cvx_aug_boxes_padded wrote
+ * for the canvases.  A label goes back to pixel corners, its four corners through m with the divide, the new box is their min / max
+ * clipped to [0, W] x [0, H]; it is kept iff w2 > min_wh, h2 > min_wh, w2 h2 / (w1 s h1 s) > min_area_ratio and
+ * max(w2 / h2, h2 / w2) < max_aspect (YOLOv5's box_candidates without its epsilon).  Output b carries the kept boxes of its own canvas in
+ * stage-1 order, then those of its partner's canvas (through the partner's own view), ordered by a scan, no atomics.
+ * compact != 0 (one workgroup): out (cap_out, 6) rows [image, cls, cx, cy, w, h] in image order from row 0, the other rows with
+ * image = -1; counts: 1 int32, the number of rows; overflow is not touched.
+ * compact == 0 (one workgroup per output): out (batch, cap_out, 5), zero rows after the kept ones; counts (batch) = min(kept, cap_out);
+ * overflow: 1 int32, cleared on the stream first, non-zero when an output kept more than cap_out (its first cap_out survive) -- the form
+ * cvx_ssd_encode_targets / cvx_centernet_draw_targets read in place. */
+int cvx_aug_boxes_warp(const float* labels_in, const int32_t* counts_in, int32_t cap_in, const cvx_aug_view* views, int32_t batch, int32_t H,
+                       int32_t W, float min_wh, float min_area_ratio, float max_aspect, int32_t compact, float* out, int32_t cap_out,
+                       int32_t* counts, int32_t* overflow, void* hip_stream);
 
 /* ---- device-side segmentation input pipeline (csrc/seg_pipeline.hip) ------------------------------------------------------------------
  * One job per output image.  image: uint8 HWC (ih, iw, 3) in device memory; mask: its label picture, uint8 (ih, iw, 3) colour coded
