@@ -167,6 +167,7 @@ PROTOTYPES = {
     "cvx_coco_accumulate": (_I32, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "cvx_coco_summarize": (_I32, [_P, _P, _I32, _P, _P]),
     "cvx_seg_pipeline": (_I32, [_P, _I32, _P, _I32, _I32, C.POINTER(_F), C.POINTER(_F), _P, _P, _I32, _I32, _P]),
+    "cvx_seg_pipeline_aug": (_I32, [_P, _I32, _P, _I32, _I32, _I32, _I32, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _P, _I32, _I32, _P]),
     "cvx_resize_bilinear_nchw_grad_to_rows": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _I32, _P]),
     "cvx_maxpool3_train_nhwc": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_maxpool3_bwd_nhwc": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P]),

@@ -803,6 +803,57 @@ typedef struct cvx_seg_job {
 int cvx_seg_pipeline(const cvx_seg_job* jobs, int32_t batch, const uint8_t* colours, int32_t n_colours, int32_t label_mode, const float* mean3,
                      const float* std3, float* out_nchw, int64_t* targets, int32_t H, int32_t W, void* hip_stream);
 
+/* The training recipe on top of it: zoom, rotation, padding, photometric distortion and Gaussian blur, one job per output image.  The
+ * first 48 bytes are cvx_seg_job's fields up to mask_channels; (rh, rw) is the size after Resize(base) AND the zoom, and the origin (i, j)
+ * may be negative or exceed rh - H / rw - W: what lies outside the picture is padding.  cos / sin: the rotation about the crop's centre,
+ * rounded to fp32 by the host.  flags: CVX_SEG_AUG_* bits; beta (added, in [0, 1] units), alpha (contrast factor), sat (saturation
+ * factor), hue (degrees, |hue| <= 360) are read only when their bit is set.  blur_k: 0, 3, 5, 7 or 9 taps, read when CVX_SEG_AUG_BLUR is
+ * set; taps[t], t < blur_k.  128 bytes. */
+#define CVX_SEG_AUG_BRIGHTNESS 1
+#define CVX_SEG_AUG_CONTRAST 2
+#define CVX_SEG_AUG_CONTRAST_LAST 4 /* contrast after the HSV step instead of before it */
+#define CVX_SEG_AUG_SATURATION 8
+#define CVX_SEG_AUG_HUE 16
+#define CVX_SEG_AUG_BLUR 32
+typedef struct cvx_seg_aug_job {
+  const uint8_t* image;
+  const uint8_t* mask;
+  int32_t ih, iw, rh, rw, i, j, flip, mask_channels;
+  float cos, sin;
+  int32_t flags;
+  float beta, alpha, sat, hue;
+  int32_t blur_k;
+  float taps[9];
+  int32_t reserved[3];
+} cvx_seg_aug_job;
+/* One launch for the whole batch, asynchronous on hip_stream; jobs, colours, mean3, std3, out_nchw, targets, label_mode as
+ * cvx_seg_pipeline; fill3: 3 HOST floats, the padding colour in 0 ... 255.  Every fp32 operation below is rounded on its own, in the
+ * order written.  Per output pixel (x, y):
+ *  1. geometry: x' = flip ? W - 1 - x : x; px = (x' + 0.5) - W/2, py = (y + 0.5) - H/2; u = ((cos px + sin py) + W/2) + j,
+ *     v = ((cos py - sin px) + H/2) + i: the continuous coordinate in the resized picture; inside iff 0 <= u < rw and 0 <= v < rh.
+ *     Source coordinate max((iw / rw) u - 0.5, 0), taps and clamps as cvx_seg_pipeline; nearest is floor((u - 0.5) (iw / rw)) clamped to
+ *     [0, iw - 1].  With cos = 1, sin = 0 u is the half-integer x' + j + 0.5, so a job without rotation, colour, blur and padding gives
+ *     cvx_seg_pipeline's result bit for bit.
+ *  2. outside: the image takes fill[c] / 255, the target ignore_index.
+ *  3. photometric, on inside pixels only, on the [0, 1] value after the bilinear mix, each only when its bit is set: clip(v + beta);
+ *     clip(v alpha) here unless CONTRAST_LAST; the hexcone HSV step when SATURATION or HUE is set (mx / mn = max / min of r, g, b,
+ *     d = mx - mn, S = mx > 0 ? d / mx : 0; H = 0 if d = 0, else 60 ((g - b) / d) (+ 360 if negative) when mx = r, else
+ *     60 ((b - r) / d) + 120 when mx = g, else 60 ((r - g) / d) + 240; S = clip(S sat); H = H + hue, - 360 if >= 360, then + 360 if
+ *     < 0; hh = H / 60, sector = int(hh), f = hh - sector, sector 6 counts as 0; p = mx (1 - S), q = mx (1 - S f),
+ *     t = mx (1 - S (1 - f)); (r, g, b) = (mx,t,p) (q,mx,p) (p,mx,t) (p,q,mx) (t,p,mx) (mx,p,q) for sectors 0 ... 5); clip(v alpha) here
+ *     when CONTRAST_LAST.  clip is to [0, 1].
+ *  4. blur (BLUR set, blur_k = 2 r + 1): horizontal pass sum_t taps[t] c(x + t - r, y), then the vertical pass over its results, both
+ *     accumulated in tap order from the first product.  c beyond the crop's edge is what steps 1-3 give at that position of the
+ *     extended plane, not a reflection.
+ *  5. out = (c - mean) / std.  Targets come from steps 1-2 alone and follow label_mode.
+ * unlisted_mode 0: a mask colour that is not in the table is class 0; 1: it is ignore_index (label_mode 1 only: an ignore value
+ * cannot be mixed as a float).  32 x 16 output pixels per workgroup; a blurred image holds the tile with its halo and the horizontal
+ * pass in LDS (20736 bytes), an image without blur does not touch it.
+ * The reference has no such stage (its transforms end at RandomHorizontalFlip, core/data/segmentation_dataset.py:268-273). */
+int cvx_seg_pipeline_aug(const cvx_seg_aug_job* jobs, int32_t batch, const uint8_t* colours, int32_t n_colours, int32_t label_mode,
+                         int32_t unlisted_mode, int32_t ignore_index, const float* fill3, const float* mean3, const float* std3,
+                         float* out_nchw, int64_t* targets, int32_t H, int32_t W, void* hip_stream);
+
 /* ---- data-parallel gradient exchange over RCCL (csrc/comm.hip), SURVEY.md section 8(b) / 8(e) --------------------------------------
  * One process per GPU.  Rank 0 calls cvx_comm_unique_id (128 bytes, ncclGetUniqueId), ships them to every rank by any means, all ranks
  * call cvx_comm_create (ncclCommInitRank; RCCL is dlopen'ed on first use).  `comm` below is the ncclComm_t.
