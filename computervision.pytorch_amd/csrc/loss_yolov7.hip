@@ -468,6 +468,19 @@ extern "C" int64_t cvx_yolo7_loss_workspace_bytes(int32_t batch, int32_t anchors
   return (int64_t)y7_layout(batch, anchors, ld, n_targets, (long long)batch * 3 * anchors).total;
 }
 
+// host only, launches nothing: where the assignment's lists lie inside the workspace, from the same y7_layout the launcher uses
+extern "C" int cvx_debug_yolo7_loss_layout(int32_t batch, int32_t anchors, int32_t ld, int32_t n_targets, int64_t* offsets) {
+  CVX_CHECK(offsets && batch > 0 && anchors > 0 && ld > 0 && n_targets >= 0, "bad arguments");
+  const Y7Layout l = y7_layout(batch, anchors, ld, n_targets, (long long)batch * 3 * anchors);
+  offsets[0] = (int64_t)l.cand;
+  offsets[1] = (int64_t)l.matched;
+  offsets[2] = (int64_t)l.mcount;
+  offsets[3] = (int64_t)l.state;
+  offsets[4] = (int64_t)std::max(15 * n_targets, 1);
+  offsets[5] = (int64_t)Y7_CMAX;
+  return 0;
+}
+
 extern "C" int cvx_yolo7_loss(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, const int32_t* level_hw, const float* anchors_px,
                               const float* strides, const float* targets, int32_t n_targets, float img_size, float box_ratio, float obj_ratio,
                               float cls_ratio, float label_smoothing, float loss_scale, float* loss_items, void* dpred_f16, int32_t* bad,

@@ -615,6 +615,14 @@ int64_t cvx_yolo7_loss_workspace_bytes(int32_t batch, int32_t anchors, int32_t l
 int cvx_yolo7_loss(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, const int32_t* level_hw, const float* anchors_px, const float* strides,
                    const float* targets, int32_t n_targets, float img_size, float box_ratio, float obj_ratio, float cls_ratio, float label_smoothing,
                    float loss_scale, float* loss_items, void* dpred_f16, int32_t* bad, void* workspace, void* hip_stream);
+/* Test hook, host only (launches nothing): where cvx_yolo7_loss keeps its assignment inside a workspace of
+ * cvx_yolo7_loss_workspace_bytes(batch, anchors, ld, n_targets) bytes, from the launcher's own layout function.  offsets[0..3] = byte
+ * offsets of: the candidate lists, int32 [3 levels][cap][5] = image, anchor, gj, gi, target row, in list order; the matched lists, int32
+ * [3 levels][batch][cmax][4] = anchor, gj, gi, target row, in list order; their lengths, int32 [batch][3]; the state block, whose first
+ * seven int32 are the candidate count per level, the matched count per level and the overflow bits.  offsets[4] = cap (candidate slots
+ * per level), offsets[5] = cmax (2880).  Returns 0, or -1 on bad arguments.  (No reference counterpart: find_3_positive / build_targets
+ * return their lists as Python objects, core/loss/yolo7_loss.py:129-398.) */
+int cvx_debug_yolo7_loss_layout(int32_t batch, int32_t anchors, int32_t ld, int32_t n_targets, int64_t* offsets);
 /* CenterNet target drawing on the device: what centernet_collate does per image on the CPU.  labels: (batch, max_boxes, 5) fp32 rows
  * [class id, cx, cy, w, h] (normalised), counts (batch) valid rows (<= max_boxes = cfg.train.max_num_boxes).  Outputs in the reference's
  * formats: heatmap (batch, fh, fw, nc) -- per object a (2r+1)^2 Gaussian, r the CornerNet radius of its integer size, merged by maximum;

@@ -319,9 +319,13 @@ def loss_candidates(targets, level_hw, threshold: float = 4.0):
     return out
 
 
-def simota_assign(preds, targets, cands, img_size: float, nc: int):
+def simota_assign(preds, targets, cands, img_size: float, nc: int, dtype=torch.float32, ties: str = "topk"):
     """build_targets (:129-338): per image, among its candidates of all levels, the SimOTA assignment.  Returns per level the ordered list of
-    matched (image, anchor, gj, gi, target row)."""
+    matched (image, anchor, gj, gi, target row).  ``dtype``: the precision of the cost matrices -- float32 as in the reference, or float64
+    with float64 ``preds`` for the seeded sweeps (tests/loss_sweep_cases.py).  ``ties``: two candidates of an image that name the same cell
+    have bit-identical cost columns; when such a pair straddles a ground truth's k, ``torch.topk`` ("topk", the reference) leaves open
+    which one it takes, and the choice reaches the loss (the two may end with different ground truths, and the later entry sets the cell's
+    objectness target).  "lower" takes the lower list index, the rule of csrc/loss_yolov7.hip; without such a pair the two are the same."""
     matched = [[] for _ in preds]
     B = preds[0].shape[0]
     for b in range(B):
@@ -329,7 +333,7 @@ def simota_assign(preds, targets, cands, img_size: float, nc: int):
         if not rows:
             continue
         tgt = targets[rows]
-        txywh = tgt[:, 2:6] * img_size                                        # imgs[b].shape[1] for all four coordinates
+        txywh = tgt[:, 2:6].to(dtype) * img_size                             # imgs[b].shape[1] for all four coordinates
         txyxy = torch.cat((txywh[:, :2] - txywh[:, 2:] / 2, txywh[:, :2] + txywh[:, 2:] / 2), 1)
         entries, boxes, p_obj, p_cls = [], [], [], []
         for lv, p in enumerate(preds):
@@ -356,13 +360,16 @@ def simota_assign(preds, targets, cands, img_size: float, nc: int):
         iou = inter / (area_t + area_p - inter)
         topv, _ = torch.topk(iou, min(20, C), dim=1)
         dyn_k = torch.clamp(topv.sum(1).int(), min=1)
-        onehot = F.one_hot(tgt[:, 1].long(), nc).float()[:, None, :].expand(G, C, nc)
-        y = (p_cls.float().sigmoid()[None] * p_obj.sigmoid()[None]).expand(G, C, nc).sqrt()
+        onehot = F.one_hot(tgt[:, 1].long(), nc).to(dtype)[:, None, :].expand(G, C, nc)
+        y = (p_cls.to(dtype).sigmoid()[None] * p_obj.sigmoid()[None]).expand(G, C, nc).sqrt()
         cls_cost = F.binary_cross_entropy_with_logits(torch.log(y / (1 - y)), onehot, reduction="none").sum(-1)
         cost = cls_cost + 3.0 * (-torch.log(iou + 1e-8))
         match = torch.zeros_like(cost)
         for g in range(G):
-            _, pos = torch.topk(cost[g], k=int(dyn_k[g]), largest=False)
+            if ties == "lower":
+                pos = torch.argsort(cost[g], stable=True)[:int(dyn_k[g])]
+            else:
+                _, pos = torch.topk(cost[g], k=int(dyn_k[g]), largest=False)
             match[g][pos] = 1.0
         multi = match.sum(0) > 1
         if int(multi.sum()) > 0:
@@ -397,16 +404,18 @@ def _ciou_xywh(box, tbox, eps: float = 1e-7):
     return iou - (rho2 / c2 + v * alpha)
 
 
-def yolo7_loss(outs, targets, img_size: float, nc: int, input_hw=(640, 640), label_smoothing: float = 0.0):
+def yolo7_loss(outs, targets, img_size: float, nc: int, input_hw=(640, 640), label_smoothing: float = 0.0, dtype=torch.float32, ties: str = "topk"):
     """Yolo7Loss.__call__ (:38-127): outs = the three (B, 3*(5+nc), h, w) maps, coarsest first; targets (N, 6) [image, class, cx, cy, w, h]
-    normalised; img_size = imgs[b].shape[1].  Returns (total, box, obj, cls) with the reference's ratios applied."""
+    normalised; img_size = imgs[b].shape[1].  Returns (total, box, obj, cls) with the reference's ratios applied.  ``dtype=torch.float64`` with
+    float64 ``outs`` runs the assignment and the three terms in float64 (the candidate generation stays float32, as in the reference); ``ties``
+    as in simota_assign."""
     preds = [o.reshape(o.shape[0], 3, -1, o.shape[2], o.shape[3]).permute(0, 1, 3, 4, 2) for o in outs]
     level_hw = [(p.shape[2], p.shape[3]) for p in preds]
     with torch.no_grad():
         cands = loss_candidates(targets, level_hw)
-        matched = simota_assign([p.detach() for p in preds], targets, cands, img_size, nc)
+        matched = simota_assign([p.detach() for p in preds], targets, cands, img_size, nc, dtype, ties)
     cp, cn = 1.0 - 0.5 * label_smoothing, 0.5 * label_smoothing
-    box_loss, obj_loss, cls_loss = torch.zeros(1), torch.zeros(1), torch.zeros(1)
+    box_loss, obj_loss, cls_loss = torch.zeros(1, dtype=dtype), torch.zeros(1, dtype=dtype), torch.zeros(1, dtype=dtype)
     for lv, p in enumerate(preds):
         h, w = level_hw[lv]
         tobj = torch.zeros_like(p[..., 0])
