@@ -31,6 +31,21 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
+// LDS bytes of a workgroup of `hv` tile streams with TH = th output rows, wm wave rows, bn output channels and cin gathered channels:
+// 2 patch buffers per tile stream (+1 dump piece) | all weights of the workgroup's bn channels | stat scratch.  Plain integers, so that
+// HaloGeom (device side) and halo_plan (the launcher's choice, host side) read ONE formula.
+constexpr int halo_lds(int th, int wm, int bn, int cin, int hv) {
+  const int pieces = ((th + 2) * HW * (cin >> 3) + 63) / 64;
+  const int nsteps = (9 * cin + BK - 1) / BK;
+  return (2 * hv * pieces + 1) * 1024 + nsteps * bn * BK * 2 + hv * wm * bn * 2 * 4;
+}
+constexpr int HALO_LDS_MAX = 160 * 1024;
+// Two tile streams per workgroup when only ONE single-stream workgroup would fit a CU (heavy weight slices) and the two-stream layout
+// does; the register budget halves (256 per wave), so only the moderate register tiles (mt x ntw accumulator tiles per wave).
+constexpr bool halo_two_streams(int lds1, int lds2, int mt, int ntw) {
+  return lds2 <= HALO_LDS_MAX && 2 * lds1 > HALO_LDS_MAX && mt * ntw <= 8 && ntw <= 4;
+}
+
 template <int WM, int WN, int MT, int NTW, int CIN_, int HV_ = 1>
 struct HaloGeom {
   static constexpr int HV = HV_;                  // tile streams per workgroup (4 waves each) sharing the resident weights
@@ -46,8 +61,8 @@ struct HaloGeom {
   static constexpr int UNITS = (TH + 2) * HW * P;  // 16-byte units of the patch
   static constexpr int PATCH_PIECES = (UNITS + 63) / 64;
   static constexpr int STAT_BYTES = HV_ * WM * BN * 2 * 4;
-  // 2 patch buffers per tile stream (+1 dump piece) | all weights of the workgroup's BN channels | stat scratch
-  static constexpr int LDS_BYTES = (2 * HV_ * PATCH_PIECES + 1) * 1024 + NSTEPS * STEP_HALVES * 2 + STAT_BYTES;
+  static constexpr int LDS_BYTES = halo_lds(TH, WM, BN, CIN_, HV_);
+  static_assert(LDS_BYTES == (2 * HV_ * PATCH_PIECES + 1) * 1024 + NSTEPS * STEP_HALVES * 2 + STAT_BYTES, "halo_lds and the kernel's LDS carve-up differ");
 };
 
 // P 16-byte chunks per pixel.  Power-of-two P (2, 4, 8, 16): XOR swizzle that spreads 16 consecutive columns of one
@@ -294,45 +309,44 @@ int launch_halo_hv(const ConvParams& p, hipStream_t stream, int gy) {
 }
 
 template <int WM, int WN, int MT, int NTW, int CIN>
-int launch_halo_c(const ConvParams& p, hipStream_t stream, int gy) {
+int launch_halo_c(const ConvParams& p, hipStream_t stream, int gy, int hv) {
   using G1 = HaloGeom<WM, WN, MT, NTW, CIN, 1>;
   using G2 = HaloGeom<WM, WN, MT, NTW, CIN, 2>;
-  if constexpr (G1::LDS_BYTES > 160 * 1024) {
+  if constexpr (G1::LDS_BYTES > HALO_LDS_MAX) {
     CVX_CHECK(false, "conv_halo: weight slice does not fit in LDS (launcher bug)");
   } else {
-    // two tile streams per workgroup when only ONE single-stream workgroup would fit a CU (heavy weight slices) and the
-    // two-stream layout does; register budget halves (256 per wave), so only the moderate register tiles
-    static const bool hv2 = cvx_tune_int("CVX_HALO_HV", 2) != 1;
-    if constexpr (G2::LDS_BYTES <= 160 * 1024 && 2 * G1::LDS_BYTES > 160 * 1024 && MT * NTW <= 8 && NTW <= 4) {
-      if (hv2) return launch_halo_hv<WM, WN, MT, NTW, CIN, 2>(p, stream, gy);
+    // the two-stream form is compiled exactly where halo_plan may choose it (halo_two_streams)
+    if constexpr (halo_two_streams(G1::LDS_BYTES, G2::LDS_BYTES, MT, NTW)) {
+      if (hv == 2) return launch_halo_hv<WM, WN, MT, NTW, CIN, 2>(p, stream, gy);
     }
+    CVX_CHECK(hv == 1, "conv_halo: two tile streams planned for a configuration without them (launcher bug)");
     return launch_halo_hv<WM, WN, MT, NTW, CIN, 1>(p, stream, gy);
   }
   return 0;
 }
 
 template <int WM, int WN, int MT, int NTW>
-int launch_halo(const ConvParams& p, hipStream_t stream, int gy, int) {
+int launch_halo(const ConvParams& p, hipStream_t stream, int gy, int hv) {
   switch (p.Cin) {
-    case 16: return launch_halo_c<WM, WN, MT, NTW, 16>(p, stream, gy);
-    case 32: return launch_halo_c<WM, WN, MT, NTW, 32>(p, stream, gy);
-    case 64: return launch_halo_c<WM, WN, MT, NTW, 64>(p, stream, gy);
-    case 80: return launch_halo_c<WM, WN, MT, NTW, 80>(p, stream, gy);
-    case 128: return launch_halo_c<WM, WN, MT, NTW, 128>(p, stream, gy);
-    default: return launch_halo_c<WM, WN, MT, NTW, 144>(p, stream, gy);
+    case 16: return launch_halo_c<WM, WN, MT, NTW, 16>(p, stream, gy, hv);
+    case 32: return launch_halo_c<WM, WN, MT, NTW, 32>(p, stream, gy, hv);
+    case 64: return launch_halo_c<WM, WN, MT, NTW, 64>(p, stream, gy, hv);
+    case 80: return launch_halo_c<WM, WN, MT, NTW, 80>(p, stream, gy, hv);
+    case 128: return launch_halo_c<WM, WN, MT, NTW, 128>(p, stream, gy, hv);
+    default: return launch_halo_c<WM, WN, MT, NTW, 144>(p, stream, gy, hv);
   }
 }
 
 template <int WM, int MT>
-int launch_m(int NT, const ConvParams& p, hipStream_t st, int gy, int l2) {
+int launch_m(int NT, const ConvParams& p, hipStream_t st, int gy, int hv) {
   switch (NT) {
-    case 1: return launch_halo<WM, 1, MT, 1>(p, st, gy, l2);
-    case 2: return launch_halo<WM, 1, MT, 2>(p, st, gy, l2);
-    case 3: return launch_halo<WM, 1, MT, 3>(p, st, gy, l2);
-    case 4: return launch_halo<WM, 1, MT, 4>(p, st, gy, l2);
-    case 5: return launch_halo<WM, 1, MT, 5>(p, st, gy, l2);
-    case 6: return launch_halo<WM, 1, MT, 6>(p, st, gy, l2);
-    default: return launch_halo<WM, 1, MT, 8>(p, st, gy, l2);
+    case 1: return launch_halo<WM, 1, MT, 1>(p, st, gy, hv);
+    case 2: return launch_halo<WM, 1, MT, 2>(p, st, gy, hv);
+    case 3: return launch_halo<WM, 1, MT, 3>(p, st, gy, hv);
+    case 4: return launch_halo<WM, 1, MT, 4>(p, st, gy, hv);
+    case 5: return launch_halo<WM, 1, MT, 5>(p, st, gy, hv);
+    case 6: return launch_halo<WM, 1, MT, 6>(p, st, gy, hv);
+    default: return launch_halo<WM, 1, MT, 8>(p, st, gy, hv);
   }
 }
 
@@ -355,17 +369,19 @@ static int halo_tile_cap(int cin) {
   return cap < 1 ? 1 : (cap > 8 ? 8 : cap);
 }
 
-// LDS bytes of HaloGeom<.., TH rows, BN channels, cin> (mirrors HaloGeom::LDS_BYTES)
-static int halo_lds_bytes(int th, int wm, int bn, int cin) {
-  const int pieces = ((th + 2) * HW * (cin / 8) + 63) / 64;
-  const int nsteps = (9 * cin + BK - 1) / BK;
-  return (2 * pieces + 1) * 1024 + nsteps * bn * BK * 2 + wm * bn * 2 * 4;
-}
-
-int cvx_conv_halo_launch(const ConvParams& p, hipStream_t stream) {
-  const int tiles = (p.Cout + 15) / 16;
-  const int cap = halo_tile_cap(p.Cin);
-  const long long hw = (long long)p.IH * p.IW;
+namespace {
+// The launcher's choice of a compiled instantiation: TH output rows per tile (8 and 4: 4 x 1 waves, NT 16-channel tiles per workgroup,
+// BN = 16 NT; 2: 2 x 2 waves, NT 32-channel pairs -- the kernel's NTW --, BN = 32 NT), gy channel blocks (gridDim.y) and HV tile streams.
+struct HaloPlan {
+  int TH, NT, gy, HV;
+  int WM() const { return TH == 2 ? 2 : 4; }
+  int MT() const { return TH == 8 ? 2 : 1; }
+  int BN() const { return (TH == 2 ? 32 : 16) * NT; }
+};
+HaloPlan halo_plan(int B, int IH, int IW, int Cin, int Cout) {
+  const int tiles = (Cout + 15) / 16;
+  const int cap = halo_tile_cap(Cin);
+  const long long hw = (long long)IH * IW;
   static const int allowed[] = {1, 2, 3, 4, 5, 6, 8};
   auto pick = [&](int th, int* gy_out) {  // fewest channel blocks within the cap and the LDS, then the smallest allowed tile count
     int gy = (tiles + cap - 1) / cap, want = (tiles + gy - 1) / gy;
@@ -377,18 +393,12 @@ int cvx_conv_halo_launch(const ConvParams& p, hipStream_t stream) {
       }
     while (NT > cap) --NT;  // 7 is not compiled: cap 7 -> 6
     if (NT == 7) NT = 6;
-    while (NT > 1 && halo_lds_bytes(th, 4, NT * 16, p.Cin) > 160 * 1024) NT = (NT == 8) ? 6 : NT - 1;
+    while (NT > 1 && halo_lds(th, 4, NT * 16, Cin, 1) > HALO_LDS_MAX) NT = (NT == 8) ? 6 : NT - 1;
     *gy_out = (tiles + NT - 1) / NT;
     return NT;
   };
-  int th = (hw >= 80 * 80 || hw * p.B >= 128 * 1024) ? 8 : ((hw >= 40 * 40 || cap < 2) ? 4 : 2);
-  if (th == 8 && halo_lds_bytes(8, 4, (cap < 2 ? 1 : 2) * 16, p.Cin) > 160 * 1024) th = 4;  // wide channels: the 10-row patches do not fit twice
-  // LDS bytes of the two-stream (HV = 2) form of HaloGeom<4, 1, th/4, NT, cin>: four patch buffers instead of two
-  auto lds_hv2 = [&](int th_, int nt) {
-    const int pieces = ((th_ + 2) * HW * (p.Cin / 8) + 63) / 64;
-    const int nsteps = (9 * p.Cin + BK - 1) / BK;
-    return (4 * pieces + 1) * 1024 + nsteps * nt * 16 * BK * 2 + 2 * 4 * nt * 16 * 2 * 4;
-  };
+  int th = (hw >= 80 * 80 || hw * B >= 128 * 1024) ? 8 : ((hw >= 40 * 40 || cap < 2) ? 4 : 2);
+  if (th == 8 && halo_lds(8, 4, (cap < 2 ? 1 : 2) * 16, Cin, 1) > HALO_LDS_MAX) th = 4;  // wide channels: the 10-row patches do not fit twice
   // 8-row tiles whose patches only fit a CU once run as ONE 4-wave workgroup per CU -- one wave per SIMD, nobody hides its LDS and MFMA
   // latencies (80 x 80, 64 -> 64: 80 us for 15 GFLOP).  The 4-row tile of the same layer fits with two tile streams (8 waves) and
   // measured ahead on every inference bench (tools/sweeps/ab_hv1.sh: SSD -3.7 %, YOLOv7 -2.4 %, CenterNet -2 %, YOLOv8-n eval -1.6 %,
@@ -397,40 +407,69 @@ int cvx_conv_halo_launch(const ConvParams& p, hipStream_t stream) {
   int nt_force = 0;
   if (th == 8 && hv1_mode != 0) {
     int gy0, NT0 = pick(8, &gy0);
-    const bool one_stream = lds_hv2(8, NT0) > 160 * 1024 && 2 * halo_lds_bytes(8, 4, NT0 * 16, p.Cin) > 160 * 1024;
+    const bool one_stream = halo_lds(8, 4, NT0 * 16, Cin, 2) > HALO_LDS_MAX && 2 * halo_lds(8, 4, NT0 * 16, Cin, 1) > HALO_LDS_MAX;
     if (one_stream && hv1_mode == 1) {
       int gy4, NT4 = pick(4, &gy4);
-      if (lds_hv2(4, NT4) <= 160 * 1024 || 2 * halo_lds_bytes(4, 4, NT4 * 16, p.Cin) <= 160 * 1024) th = 4;  // only if the 4-row form does get its 8 waves
+      if (halo_lds(4, 4, NT4 * 16, Cin, 2) <= HALO_LDS_MAX || 2 * halo_lds(4, 4, NT4 * 16, Cin, 1) <= HALO_LDS_MAX) th = 4;  // only if the 4-row form does get its 8 waves
     }
     if (one_stream && hv1_mode == 2) {
       int nt = NT0;
-      while (nt > 2 && lds_hv2(8, nt) > 160 * 1024) --nt;
-      if (lds_hv2(8, nt) <= 160 * 1024) nt_force = nt;
+      while (nt > 2 && halo_lds(8, 4, nt * 16, Cin, 2) > HALO_LDS_MAX) --nt;
+      if (halo_lds(8, 4, nt * 16, Cin, 2) <= HALO_LDS_MAX) nt_force = nt;
     }
   }
+  HaloPlan pl{th, 0, 0, 1};
   if (th == 8) {
-    int gy, NT = pick(8, &gy);
+    pl.NT = pick(8, &pl.gy);
     if (nt_force) {
-      NT = nt_force;
-      gy = (tiles + NT - 1) / NT;
+      pl.NT = nt_force;
+      pl.gy = (tiles + pl.NT - 1) / pl.NT;
     }
-    CVX_TRY((launch_m<4, 2>(NT, p, stream, gy, 0)));
   } else if (th == 4) {
-    int gy, NT = pick(4, &gy);
-    CVX_TRY((launch_m<4, 1>(NT, p, stream, gy, 0)));
+    pl.NT = pick(4, &pl.gy);
   } else {  // TH = 2, 2x2 waves, BN = 32 * NTW
     const int pairs = (tiles + 1) / 2, pcap = cap / 2;
     int gy = (pairs + pcap - 1) / pcap;
     int ntw = (pairs + gy - 1) / gy;
     if (ntw > 4) ntw = 4;
-    gy = (pairs + ntw - 1) / ntw;
-    switch (ntw) {
-      case 1: CVX_TRY((launch_halo<2, 2, 1, 1>(p, stream, gy, 0))); break;
-      case 2: CVX_TRY((launch_halo<2, 2, 1, 2>(p, stream, gy, 0))); break;
-      case 3: CVX_TRY((launch_halo<2, 2, 1, 3>(p, stream, gy, 0))); break;
-      default: CVX_TRY((launch_halo<2, 2, 1, 4>(p, stream, gy, 0))); break;
+    pl.NT = ntw;
+    pl.gy = (pairs + ntw - 1) / ntw;
+  }
+  static const bool hv2 = cvx_tune_int("CVX_HALO_HV", 2) != 1;
+  if (hv2 && halo_two_streams(halo_lds(th, pl.WM(), pl.BN(), Cin, 1), halo_lds(th, pl.WM(), pl.BN(), Cin, 2), pl.MT(), pl.NT)) pl.HV = 2;
+  return pl;
+}
+bool halo_cin_ok(int cin) { return cin == 16 || cin == 32 || cin == 64 || cin == 80 || cin == 128 || cin == 144; }
+}  // namespace
+
+extern "C" int cvx_debug_conv_halo_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out4) {
+  CVX_CHECK(out4 && batch > 0 && h > 0 && w > 0 && cout > 0, "bad arguments");
+  CVX_CHECK(halo_cin_ok(cin), "conv_halo: gathered channels must be 16, 32, 64, 80, 128 or 144");
+  const HaloPlan pl = halo_plan(batch, h, w, cin, cout);
+  CVX_CHECK(halo_lds(pl.TH, pl.WM(), pl.BN(), cin, 1) <= HALO_LDS_MAX, "conv_halo: weight slice does not fit in LDS (launcher bug)");
+  out4[0] = pl.TH;
+  out4[1] = pl.NT;
+  out4[2] = pl.gy;
+  out4[3] = pl.HV;
+  return 0;
+}
+
+int cvx_conv_halo_launch(const ConvParams& p, hipStream_t stream) {
+  CVX_CHECK(halo_cin_ok(p.Cin), "conv_halo: gathered channels must be 16, 32, 64, 80, 128 or 144");
+  const HaloPlan pl = halo_plan(p.B, p.IH, p.IW, p.Cin, p.Cout);
+  if (pl.TH == 8) {
+    CVX_TRY((launch_m<4, 2>(pl.NT, p, stream, pl.gy, pl.HV)));
+  } else if (pl.TH == 4) {
+    CVX_TRY((launch_m<4, 1>(pl.NT, p, stream, pl.gy, pl.HV)));
+  } else {
+    switch (pl.NT) {
+      case 1: CVX_TRY((launch_halo<2, 2, 1, 1>(p, stream, pl.gy, pl.HV))); break;
+      case 2: CVX_TRY((launch_halo<2, 2, 1, 2>(p, stream, pl.gy, pl.HV))); break;
+      case 3: CVX_TRY((launch_halo<2, 2, 1, 3>(p, stream, pl.gy, pl.HV))); break;
+      default: CVX_TRY((launch_halo<2, 2, 1, 4>(p, stream, pl.gy, pl.HV))); break;
     }
   }
   CVX_HIP(hipGetLastError());
   return 0;
 }
+

@@ -12,6 +12,13 @@
 unsigned long long* g_cvx_clk = nullptr;
 int g_cvx_grid_div = 1;
 
+extern "C" int cvx_debug_conv_grid_div(int32_t div) {
+  CVX_CHECK(div >= 1, "the grid divisor is at least 1");
+  const int prev = g_cvx_grid_div;
+  g_cvx_grid_div = div;
+  return prev;
+}
+
 int cvx_conv_igemm_launch(const ConvParams& p_in, hipStream_t stream) {
   ConvParams p = p_in;
   p.clk = g_cvx_clk;

@@ -191,11 +191,15 @@ bool cvx_conv_pw_supported(const ConvParams& p) {
   return p.Cin <= 512;
 }
 
-int cvx_conv_pw_launch(const ConvParams& p, hipStream_t stream) {
-  const long long M = (long long)p.B * p.OH2 * p.OW2;
-  CVX_CHECK(M < (1LL << 31), "conv_pw: more than 2^31 output pixels per launch");
-  CVX_CHECK(((uintptr_t)p.in % 16) == 0 && p.in_ld % 8 == 0 && p.in_bstride % 8 == 0, "conv_pw: 16-byte aligned pixel rows needed");
-  const int nsteps = (p.Cin + BK - 1) / BK;  // 1..16
+namespace {
+// The launcher's choice of a compiled instantiation: NS 32-wide K-steps (the smallest compiled count that holds Cin), NT 16-channel tiles
+// per workgroup, gy channel blocks (gridDim.y) and MT 16-pixel groups per wave tile.  M (output pixels) does not enter the choice yet.
+struct PwPlan {
+  int NS, NT, gy, MT;
+};
+PwPlan pw_plan(long long M, int Cin, int Cout) {
+  (void)M;
+  const int nsteps = (Cin + BK - 1) / BK;  // 1..16
   static const int steps_allowed[] = {1, 2, 3, 4, 6, 8, 12, 16};
   int NS = 16;
   for (int a : steps_allowed)
@@ -205,7 +209,7 @@ int cvx_conv_pw_launch(const ConvParams& p, hipStream_t stream) {
     }
   // channel tiles per workgroup: fewest channel blocks whose weights (NT*16 x NS*32 fp16 = NT*NS KiB) fit the budget
   static const int kb = cvx_tune_int("CVX_PW_WKB", 64);
-  const int tiles = (p.Cout + 15) / 16;
+  const int tiles = (Cout + 15) / 16;
   int cap = kb / NS;
   cap = cap < 1 ? 1 : (cap > 8 ? 8 : cap);
   static const int allowed[] = {1, 2, 3, 4, 5, 6, 8};
@@ -219,7 +223,30 @@ int cvx_conv_pw_launch(const ConvParams& p, hipStream_t stream) {
   while (NT > cap) --NT;
   if (NT == 7) NT = 6;
   gy = (tiles + NT - 1) / NT;
-  switch (NS) {
+  return PwPlan{NS, NT, gy, NS <= 8 ? 2 : 1};
+}
+}  // namespace
+
+extern "C" int cvx_debug_conv_pw_plan(int64_t pixels, int32_t cin, int32_t cout, int32_t* out4) {
+  CVX_CHECK(out4 && pixels > 0 && pixels < (1LL << 31) && cout > 0, "bad arguments");
+  CVX_CHECK(cin > 0 && cin <= 512 && cin % 8 == 0, "conv_pw: gathered channels must be a multiple of 8, at most 512");
+  const PwPlan pl = pw_plan(pixels, cin, cout);
+  CVX_CHECK(1024 + pl.NS * pl.NT * 16 * BK * 2 + 4 * pl.NT * 16 * 2 * 4 <= 160 * 1024, "conv_pw: weight slice does not fit in LDS (launcher bug)");  // PwGeom::LDS_BYTES
+  out4[0] = pl.NS;
+  out4[1] = pl.NT;
+  out4[2] = pl.gy;
+  out4[3] = pl.MT;
+  return 0;
+}
+
+int cvx_conv_pw_launch(const ConvParams& p, hipStream_t stream) {
+  const long long M = (long long)p.B * p.OH2 * p.OW2;
+  CVX_CHECK(M < (1LL << 31), "conv_pw: more than 2^31 output pixels per launch");
+  CVX_CHECK(((uintptr_t)p.in % 16) == 0 && p.in_ld % 8 == 0 && p.in_bstride % 8 == 0, "conv_pw: 16-byte aligned pixel rows needed");
+  CVX_CHECK(p.Cin > 0 && p.Cin <= 512, "conv_pw: at most 512 gathered channels");
+  const PwPlan pl = pw_plan(M, p.Cin, p.Cout);
+  const int NT = pl.NT, gy = pl.gy;
+  switch (pl.NS) {  // MT = 2 up to 8 K-steps, 1 beyond (PwPlan::MT): the activation registers of a wave tile
     case 1: CVX_TRY((launch_pw_n<2, 1>(NT, p, stream, gy))); break;
     case 2: CVX_TRY((launch_pw_n<2, 2>(NT, p, stream, gy))); break;
     case 3: CVX_TRY((launch_pw_n<2, 3>(NT, p, stream, gy))); break;
@@ -232,3 +259,4 @@ int cvx_conv_pw_launch(const ConvParams& p, hipStream_t stream) {
   CVX_HIP(hipGetLastError());
   return 0;
 }
+

@@ -2497,6 +2497,8 @@ extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int
   const bool force_tile = (mode & 0x2000) != 0;  // likewise the row-band kernel (conv_tile.hip); 0x4000: never the row-band kernel
   const bool no_tile = (mode & 0x4000) != 0;
   const bool force_dma = (mode & 0x8000) != 0;  // ... and the LDS-DMA ring kernel (conv_igemm_dma.hip), whose wide tiles serve shapes the dispatcher gives away
+  const bool force_halo = (mode & 0x10000) != 0;  // ... the 3x3 halo kernel (conv_halo.hip) and the pointwise kernel (conv_pw.hip), whose
+  const bool force_pw = (mode & 0x20000) != 0;    // wider instantiations the dispatcher gives to the GEMM-shaped kernel
   mode &= 0xff;
   const int oh = cvx_conv_out_size(ih, k, stride, pad, dil), ow = cvx_conv_out_size(iw, k, stride, pad, dil);
   const std::vector<ConvTap> taps = cvx_conv_fwd_taps(k, pad, dil);
@@ -2542,6 +2544,17 @@ extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int
     CVX_CHECK(((uintptr_t)x_f16 % 16) == 0 && ((uintptr_t)w_f16 % 16) == 0, "conv: operands must be 16-byte aligned");
     cp.clk = g_cvx_clk;
     rc = cvx_conv_igemm_dma_launch(cp, st);
+  } else if (force_halo || force_pw) {  // the kernel's own conditions and the dispatcher's (cvx_conv_igemm_launch); outside them an error, never a launch
+    CVX_CHECK(cin % 8 == 0 && cout % 4 == 0 && oh > 0 && ow > 0 && batch > 0, "shape outside the kernel (cin % 8, cout % 4, a non-empty output)");
+    CVX_CHECK(((uintptr_t)x_f16 % 16) == 0 && ((uintptr_t)w_f16 % 16) == 0, "conv: operands must be 16-byte aligned");
+    cp.clk = g_cvx_clk;
+    if (force_halo) {
+      CVX_CHECK(cvx_conv_halo_supported(cp), "shape outside the halo kernel (3x3, stride 1, pad 1, dilation 1, cin 16 / 32 / 64 / 80 / 128 / 144)");
+      rc = cvx_conv_halo_launch(cp, st);
+    } else {
+      CVX_CHECK(cvx_conv_pw_supported(cp), "shape outside the pointwise kernel (1x1, stride 1, pad 0, cin <= 512)");
+      rc = cvx_conv_pw_launch(cp, st);
+    }
   } else {
     cp.no_tile = no_tile ? 1 : 0;
     rc = cvx_conv_igemm_launch(cp, st);

@@ -200,6 +200,18 @@ int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, i
  * 32 rows: 1..4), channel blocks (gridDim.y), DMA passes per K-step.  The launcher calls the same function.  Returns 0, or -1 on bad
  * arguments.  (No reference counterpart: the reference leaves the choice of algorithm to cuDNN behind nn.Conv2d, core/models/yolov8/modules.py:19-33.) */
 int cvx_debug_conv_dma_plan(int64_t pixels, int32_t cin, int32_t cout, int32_t ntaps, int32_t* out4);
+/* Test hooks, likewise for the two persistent kernels with LDS-resident weights; the launchers call the same functions.
+ * 3x3 / stride 1 halo kernel (csrc/conv_halo.hip) on a batch x h x w map, cin gathered (16, 32, 64, 80, 128 or 144: anything else is an
+ * error) and cout produced channels -- out[0..3] = output rows per tile TH (8, 4 or 2), channel tiles per workgroup (16-channel tiles for
+ * TH 8 / 4: 1..6 or 8; 32-channel pairs for TH 2: 1..4), channel blocks (gridDim.y), tile streams per workgroup (1 or 2).
+ * 1x1 / stride 1 pointwise kernel (csrc/conv_pw.hip) on `pixels` pixels, cin gathered (a multiple of 8, at most 512: anything else is an
+ * error) and cout produced channels -- out[0..3] = 32-wide K-steps (1, 2, 3, 4, 6, 8, 12 or 16), 16-channel tiles per workgroup (1..6 or
+ * 8), channel blocks, 16-pixel groups per wave tile (2 or 1).  Both return 0, or -1 on bad arguments.  (No reference counterpart, as above.) */
+int cvx_debug_conv_halo_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out4);
+int cvx_debug_conv_pw_plan(int64_t pixels, int32_t cin, int32_t cout, int32_t* out4);
+/* Test hook: the persistent convolution kernels size their grids for 1 / div of the chip (1: all of it), so that every workgroup walks
+ * many tiles of a small map.  Returns the previous divisor, or -1 for div < 1 (nothing changes).  Process-wide: restore it. */
+int cvx_debug_conv_grid_div(int32_t div);
 
 /* Bytes of device memory the engine currently owns (workspaces). */
 int64_t cvx_engine_workspace_bytes(const cvx_engine* e);
@@ -402,7 +414,8 @@ int cvx_centernet_decode(const float* pred, int32_t pred_ld, int32_t batch, int3
  * silu(conv*scale+shift); mode 2: out fp32 = conv + bias; mode 3 (the training epilogue): out fp32 = conv, and the
  * per-channel (sum, sum of squares) are added into `shift` viewed as zeroed fixed-point replica slabs.  mode | 0x100 runs the GEMM-shaped
  * kernel (conv_gemm.hip) whatever the dispatcher would pick (needs cin % 8 == 0, cout % 4 == 0); mode | 0x8000 likewise the
- * LDS-DMA ring kernel (conv_igemm_dma.hip).  Replaces: F.conv2d as used by Conv.forward, core/models/yolov8/modules.py:29-30. */
+ * LDS-DMA ring kernel (conv_igemm_dma.hip), mode | 0x10000 the 3x3 halo kernel (conv_halo.hip) and mode | 0x20000 the pointwise kernel
+ * (conv_pw.hip); a shape outside the forced kernel is an error and launches nothing.  Replaces: F.conv2d as used by Conv.forward, core/models/yolov8/modules.py:29-30. */
 int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, const void* w_f16, int32_t cout, int32_t k,
                     int32_t stride, int32_t pad, int32_t dil, int32_t mode, const float* scale_or_bias, const float* shift, void* out,
                     void* hip_stream);
