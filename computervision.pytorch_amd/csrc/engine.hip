@@ -2390,36 +2390,6 @@ extern "C" int cvx_nchw_grad_to_dpred(const float* grad_nchw, int32_t batch, int
                                       float scale, void* dpred_f16, void* hip_stream) {
   return cvx_nchw_to_pred_f16(grad_nchw, batch, anchors, no, a_off, h, w, scale, (half_t*)dpred_f16, (hipStream_t)hip_stream);
 }
-extern "C" int cvx_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
-                             float eps, int32_t step, const int32_t* found_inf, int32_t zero_grad, void* hip_stream) {
-  CVX_CHECK(params && grads && exp_avg && exp_avg_sq && n > 0, "bad arguments");
-  CVX_CHECK(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 && ((uintptr_t)exp_avg_sq % 16) == 0,
-            "adam arenas must be 16-byte aligned");
-  return cvx_adam(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, found_inf, zero_grad, (hipStream_t)hip_stream);
-}
-extern "C" int cvx_adam_step_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1, float beta2, float eps,
-                                 float* state, const int32_t* found_inf, int32_t zero_grad, float grad_scale, void* hip_stream) {
-  CVX_CHECK(params && grads && exp_avg && exp_avg_sq && state && n > 0, "bad arguments");
-  return cvx_adam_dev(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, state, found_inf, zero_grad, grad_scale,
-                      (hipStream_t)hip_stream);
-}
-extern "C" int cvx_ema_update(float* ema, const float* src, int64_t n, float d, float one_minus_d, void* hip_stream) {
-  CVX_CHECK(ema && src && n > 0, "bad arguments");
-  CVX_CHECK(ema != src, "the average must not be the arena it follows");
-  CVX_CHECK(((uintptr_t)ema % 16) == 0 && ((uintptr_t)src % 16) == 0, "ema arenas must be 16-byte aligned");
-  return cvx_ema_update_launch(ema, src, n, d, one_minus_d, (hipStream_t)hip_stream);
-}
-extern "C" int cvx_adam_ema_step_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1, float beta2,
-                                     float eps, float* state, const int32_t* found_inf, int32_t zero_grad, float grad_scale, float* ema, float d,
-                                     float one_minus_d, void* hip_stream) {
-  CVX_CHECK(params && grads && exp_avg && exp_avg_sq && state && ema && n > 0, "bad arguments");
-  CVX_CHECK(ema != params, "the average must not be the arena it follows");
-  CVX_CHECK(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 && ((uintptr_t)exp_avg_sq % 16) == 0 &&
-                ((uintptr_t)ema % 16) == 0,
-            "adam arenas must be 16-byte aligned");
-  return cvx_adam_ema_dev(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, state, found_inf, zero_grad, grad_scale, ema, d, one_minus_d,
-                          (hipStream_t)hip_stream);
-}
 extern "C" int cvx_engine_set_stream(cvx_engine* e, void* hip_stream) {
   CVX_CHECK(e, "null engine");
   e->stream = (hipStream_t)hip_stream;
@@ -2444,11 +2414,6 @@ extern "C" void* cvx_engine_exchange_stream(cvx_engine* e) {
     return nullptr;
   }
   return (void*)s;
-}
-
-extern "C" int cvx_check_finite(const float* grads, int64_t n, int32_t* found_inf, void* hip_stream) {
-  CVX_CHECK(grads && found_inf, "bad arguments");
-  return cvx_check_finite_launch(grads, n, found_inf, (hipStream_t)hip_stream);
 }
 
 // ---- single-op entry points: the engine's geometry (conv_plan.h) and fillers on dense caller tensors ------------------------------

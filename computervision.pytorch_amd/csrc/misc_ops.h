@@ -1,4 +1,4 @@
-// Layout, pooling, resampling, weight-packing, gradient-slab reduction and Adam kernels.
+// Layout, pooling, resampling, weight-packing, and gradient-slab reduction kernels.
 #pragma once
 #include "bn_act.h"
 
@@ -101,18 +101,3 @@ static inline int cvx_slab_lanes(int nsplit) {
 }
 int cvx_reduce_slabs(const float* slabs, float* grads, float inv_scale, const SlabDesc* descs, const BlockRef* blocks, int nblocks,
                      hipStream_t st);
-
-// Adam (torch.optim.Adam defaults semantics, no weight decay / amsgrad), fp32 state; optionally skipped
-// when *found_inf != 0; zeroes the gradient arena afterwards when zero_grad != 0.
-int cvx_adam(float* p, float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step, const int* found_inf,
-             int zero_grad, hipStream_t st);
-// same update with the step state on the device (state[0]=lr, [1]=step, [2],[3] derived): replayable from a hipGraph
-int cvx_adam_dev(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps, float* state, const int* found_inf,
-                 int zero_grad, float grad_scale, hipStream_t st);
-// cvx_adam_dev plus the weight average in the same pass: e <- rn(rn(e * d) + rn(omd * p_new)); on a skipped step e moves toward the unchanged p
-int cvx_adam_ema_dev(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps, float* state, const int* found_inf,
-                     int zero_grad, float grad_scale, float* e, float d, float omd, hipStream_t st);
-// the average alone: e <- rn(rn(e * d) + rn(omd * p)) over n floats
-int cvx_ema_update_launch(float* e, const float* p, long long n, float d, float omd, hipStream_t st);
-// sets *found_inf = 1 if any gradient is non-finite
-int cvx_check_finite_launch(const float* g, long long n, int* found_inf, hipStream_t st);

@@ -1,10 +1,9 @@
 // HBM-bound helper kernels (gfx950): layout change, SPPF max-pool, nearest upsample, weight shadow
-// packing, gradient-slab reduction, fused Adam.  16-byte accesses wherever the layout allows.
+// packing, gradient-slab reduction.  16-byte accesses wherever the layout allows.
 #include <algorithm>
 #include "misc_ops.h"
 #include "bilinear.h"
 #include "bn_common.h"
-#include "optim_core.h"
 
 namespace {
 
@@ -1265,132 +1264,6 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* slabs, f
   if (rl == 0 && e < total) grads[d.dst_off + e] += sred[col] * inv_scale;
 }
 
-// ---- Adam ---------------------------------------------------------------------------------------
-// state[0] = lr (host-written), state[1] = step count, state[2] = lr/(1-b1^t), state[3] = 1/sqrt(1-b2^t)
-__global__ void adam_advance_kernel(float* state, float b1, float b2, const int* found_inf) {
-  if (found_inf && *found_inf != 0) return;  // a skipped step does not advance the bias correction
-  const float t = state[1] + 1.f;
-  state[1] = t;
-  state[2] = state[0] / (1.f - powf(b1, t));
-  state[3] = rsqrtf(1.f - powf(b2, t));
-}
-
-__global__ __launch_bounds__(256) void adam_kernel(float* p, float* g, float* m, float* v, long long n, float lr_over_bc1, float b1, float b2,
-                                                   float eps, float inv_sqrt_bc2, const int* found_inf, int zero_grad, const float* state, float gscale) {
-  const bool skip = found_inf && *found_inf != 0;
-  if (state) {  // device-resident step state (hipGraph replay: no host-side arguments change between steps)
-    lr_over_bc1 = state[2];
-    inv_sqrt_bc2 = state[3];
-  }
-  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= n) return;
-  if (i + 4 <= n) {
-    f4 gg = *reinterpret_cast<f4*>(g + i);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) gg[k] *= gscale;  // 1/world_size after a SUM all-reduce (1 otherwise)
-    if (!skip) {
-      f4 pp = *reinterpret_cast<f4*>(p + i), mm = *reinterpret_cast<f4*>(m + i), vv = *reinterpret_cast<f4*>(v + i);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-        vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-        pp[k] -= lr_over_bc1 * mm[k] / (sqrtf(vv[k]) * inv_sqrt_bc2 + eps);
-      }
-      *reinterpret_cast<f4*>(p + i) = pp;
-      *reinterpret_cast<f4*>(m + i) = mm;
-      *reinterpret_cast<f4*>(v + i) = vv;
-    }
-    if (zero_grad) *reinterpret_cast<f4*>(g + i) = f4{0.f, 0.f, 0.f, 0.f};
-  } else {
-    for (; i < n; ++i) {
-      float gg = g[i] * gscale;
-      if (!skip) {
-        float mm = b1 * m[i] + (1.f - b1) * gg;
-        float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm;
-        v[i] = vv;
-        p[i] -= lr_over_bc1 * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
-      }
-      if (zero_grad) g[i] = 0.f;
-    }
-  }
-}
-
-// adam_kernel (device-resident step state) with the average in the same pass: `e` moves toward the value of p this thread is about to store --
-// toward the unchanged p on a skipped step -- in the same 16-byte vector.  The parameter is in registers already, so the average costs its own
-// read and write and no launch.  p, m and v must come out bit for bit as adam_kernel leaves them (the fused and the two-launch step are
-// interchangeable), and which products the compiler contracts into FMAs is its heuristic's choice -- a copy of adam_kernel's expressions fused
-// differently here.  So the contraction is written out: ema_mix, adam_step4 and adam_step1 live in optim_core.h, which optim.hip shares.
-// tests/test_ema_gpu.py compares the two paths on the device.
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps,
-                                                       const int* found_inf, int zero_grad, const float* state, float gscale, float* e, float d,
-                                                       float omd) {
-  const bool skip = found_inf && *found_inf != 0;
-  const float lr_over_bc1 = state[2], inv_sqrt_bc2 = state[3];
-  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= n) return;
-  if (i + 4 <= n) {
-    f4 pp = *reinterpret_cast<f4*>(p + i), ee = *reinterpret_cast<f4*>(e + i);
-    if (!skip) {
-      f4 gg = *reinterpret_cast<f4*>(g + i), mm = *reinterpret_cast<f4*>(m + i), vv = *reinterpret_cast<f4*>(v + i);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float pk = pp[k], mk = mm[k], vk = vv[k];
-        adam_step4(pk, mk, vk, gg[k] * gscale, b1, b2, eps, lr_over_bc1, inv_sqrt_bc2);
-        pp[k] = pk;
-        mm[k] = mk;
-        vv[k] = vk;
-      }
-      *reinterpret_cast<f4*>(p + i) = pp;
-      *reinterpret_cast<f4*>(m + i) = mm;
-      *reinterpret_cast<f4*>(v + i) = vv;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ee[k] = ema_mix(ee[k], pp[k], d, omd);
-    *reinterpret_cast<f4*>(e + i) = ee;
-    if (zero_grad) *reinterpret_cast<f4*>(g + i) = f4{0.f, 0.f, 0.f, 0.f};
-  } else {
-    for (; i < n; ++i) {
-      float pp = p[i];
-      if (!skip) {
-        float mm = m[i], vv = v[i];
-        adam_step1(pp, mm, vv, g[i] * gscale, b1, b2, eps, lr_over_bc1, inv_sqrt_bc2);
-        m[i] = mm;
-        v[i] = vv;
-        p[i] = pp;
-      }
-      e[i] = ema_mix(e[i], pp, d, omd);
-      if (zero_grad) g[i] = 0.f;
-    }
-  }
-}
-
-// The average as a pass of its own (BatchNorm statistics; parameters when no optimiser step is fused with it): 16-byte vectors, scalar tail.
-__global__ __launch_bounds__(256) void ema_update_kernel(float* e, const float* p, long long n, float d, float omd) {
-  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= n) return;
-  if (i + 4 <= n) {
-    f4 ee = *reinterpret_cast<f4*>(e + i);
-    const f4 pp = *reinterpret_cast<const f4*>(p + i);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ee[k] = ema_mix(ee[k], pp[k], d, omd);
-    *reinterpret_cast<f4*>(e + i) = ee;
-  } else {
-    for (; i < n; ++i) e[i] = ema_mix(e[i], p[i], d, omd);
-  }
-}
-
-__global__ __launch_bounds__(256) void check_finite_kernel(const float* g, long long n, int* found_inf) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  long long stride = (long long)gridDim.x * blockDim.x;
-  bool bad = false;
-  for (; i < n; i += stride) {
-    float x = g[i];
-    bad |= !(fabsf(x) <= 3.0e38f);
-  }
-  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) *found_inf = 1;
-}
-
 template <typename K, typename... Args>
 int launch1d(K kern, long long n, hipStream_t st, Args... args) {
   if (n <= 0) return 0;
@@ -1611,33 +1484,6 @@ int cvx_reduce_slabs(const float* slabs, float* grads, float inv_scale, const Sl
                      hipStream_t st) {
   if (nblocks <= 0) return 0;
   hipLaunchKernelGGL(reduce_slabs_kernel, dim3(nblocks), dim3(256), 0, st, slabs, grads, inv_scale, descs, blocks);
-  CVX_HIP(hipGetLastError());
-  return 0;
-}
-int cvx_adam(float* p, float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step, const int* found_inf,
-             int zero_grad, hipStream_t st) {
-  CVX_CHECK(step >= 1, "adam: step starts at 1");
-  double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-  return launch1d(adam_kernel, (n + 3) / 4, st, p, g, m, v, n, (float)(lr / bc1), b1, b2, eps, (float)(1.0 / sqrt(bc2)), found_inf, zero_grad,
-                  (const float*)nullptr, 1.0f);
-}
-int cvx_adam_dev(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps, float* state, const int* found_inf,
-                 int zero_grad, float grad_scale, hipStream_t st) {
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, state, b1, b2, found_inf);
-  return launch1d(adam_kernel, (n + 3) / 4, st, p, g, m, v, n, 0.f, b1, b2, eps, 0.f, found_inf, zero_grad, (const float*)state, grad_scale);
-}
-int cvx_adam_ema_dev(float* p, float* g, float* m, float* v, long long n, float b1, float b2, float eps, float* state, const int* found_inf,
-                     int zero_grad, float grad_scale, float* e, float d, float omd, hipStream_t st) {
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, state, b1, b2, found_inf);
-  return launch1d(adam_ema_kernel, (n + 3) / 4, st, p, g, m, v, n, b1, b2, eps, found_inf, zero_grad, (const float*)state, grad_scale, e, d, omd);
-}
-int cvx_ema_update_launch(float* e, const float* p, long long n, float d, float omd, hipStream_t st) {
-  return launch1d(ema_update_kernel, (n + 3) / 4, st, e, p, n, d, omd);
-}
-int cvx_check_finite_launch(const float* g, long long n, int* found_inf, hipStream_t st) {
-  if (n <= 0) return 0;
-  int blocks = (int)std::min<long long>(1024, (n + 255) / 256);
-  hipLaunchKernelGGL(check_finite_kernel, dim3(blocks), dim3(256), 0, st, g, n, found_inf);
   CVX_HIP(hipGetLastError());
   return 0;
 }

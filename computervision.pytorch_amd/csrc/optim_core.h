@@ -1,5 +1,6 @@
-// The per-element arithmetic the optimiser kernels of misc_ops.hip (adam_ema_kernel, ema_update_kernel) and optim.hip (optim_kernel) share.
-// Every function here fixes its own rounding: contraction is off inside it and the FMAs it wants are written out.
+// The per-element arithmetic of the optimiser kernels of optim.hip (optim_step_kernel, ema_update_kernel): the weight average and the Adam
+// recurrence are spelled here and nowhere else.  Every function fixes its own rounding: contraction is off inside it and the FMAs it wants
+// are written out, so what a kernel fuses around a call, or a compiler upgrade, does not move a bit.
 #pragma once
 #include "cvx_common.h"
 
@@ -13,10 +14,11 @@ __device__ __forceinline__ float ema_mix(float e, float p, float d, float omd) {
   return a + b;
 }
 
-// adam_kernel's arithmetic with the contraction written out: adam_step4 / adam_step1 spell the FMAs adam_kernel (misc_ops.hip) compiles to for
-// gfx950 in its 16-byte path and in its scalar tail (they differ: the tail keeps v and the denominator as multiply + add), with contraction off
-// around them, so that a kernel which calls them leaves p, m and v bit for bit as adam_kernel does whatever else it fuses into the pass.
-// tests/test_ema_gpu.py and tests/test_optim_gpu.py compare the paths on the device.
+// The Adam arithmetic of this library (torch.optim.Adam without weight decay or amsgrad; g arrives scaled, lr_over_bc1 = lr/(1-b1^t),
+// inv_sqrt_bc2 = 1/sqrt(1-b2^t)): adam_step4 for the elements of a 16-byte chunk, adam_step1 for the scalar tail of n % 4 != 0.  Which
+// products are FMAs is part of the definition.  The two differ -- the tail keeps v and the denominator as multiply + add -- and stay
+// different because checkpoints and fixtures hold those bits: tests/golden/adam_trace.npz pins both (tests/test_optim_gpu.py), and
+// tests/test_ema_gpu.py and tests/test_optim_gpu.py compare the instantiations of the step kernel with each other on the device.
 __device__ __forceinline__ void adam_step4(float& p, float& m, float& v, float g, float b1, float b2, float eps, float lr_over_bc1,
                                            float inv_sqrt_bc2) {
 #pragma clang fp contract(off)

@@ -119,10 +119,70 @@ def _torch_group_defaults(cls) -> dict:
     return g
 
 
-class FlatOptimizer(torch.optim.Optimizer):
-    """What ``FlatSGD`` and ``FlatAdamW`` share: the grouping, the device tables, the step, the checkpoint layout.  It keeps ``FlatAdam``'s
-    surface -- ``step(closure=None, zero_grad=False, grad_scale=1.0)``, ``sync_lr()``, ``found_inf``, ``attach_ema``, ``ema_fused``,
-    ``zero_grad``, ``device_step()``.
+class FlatStep(torch.optim.Optimizer):
+    """The surface and the step skeleton of every optimiser over a model's flat arenas (``FlatAdam`` in train.py, ``FlatSGD`` and
+    ``FlatAdamW`` here): ``step(closure=None, zero_grad=False, grad_scale=1.0)``, ``found_inf``, ``attach_ema``, ``ema_fused``,
+    ``zero_grad``, ``device_step()``.  A subclass supplies ``_ensure_state`` (device buffers and ``_state``, whose [1] is the step count),
+    ``sync_lr`` and ``_launch``."""
+
+    def __init__(self, model, params, defaults):
+        self.model = model
+        super().__init__(params, defaults)
+        self._step = 0
+        self._state = None          # device step state: the step advances on the device
+        self.found_inf: Optional[torch.Tensor] = None
+        self._ema = None            # attach_ema: a ModelEMA whose average moves with every step()
+        self.ema_fused = True       # False: the average as launches of its own after the step (tools/ema_cost.py, tools/optim_cost.py time both)
+
+    def attach_ema(self, ema):
+        """Every ``step()`` from now on also moves ``ema`` (a ``ModelEMA`` of this optimiser's model; None detaches it): the parameters inside
+        the step kernel, the BatchNorm statistics with one ``cvx_ema_update`` launch, ``ema.updates`` + 1 -- what ``ema.update(model)`` after
+        ``optimizer.step()`` does in the reference's loop shape, a step skipped by ``found_inf`` included."""
+        if ema is not None:
+            ema.check(self.model)
+        self._ema = ema
+
+    def _ensure_state(self):
+        raise NotImplementedError
+
+    def sync_lr(self):
+        """Push what a scheduler changed in ``param_groups`` to the device (call outside graph capture)."""
+        raise NotImplementedError
+
+    def _launch(self, zero_grad, grad_scale, ema_arena, d, omd):
+        """the step's launches; ``ema_arena``: the average of the parameters to move in the same pass, or None"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def step(self, closure=None, zero_grad: bool = False, grad_scale: float = 1.0):
+        self._ensure_state()
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()               # a scheduler (or GradScaler.step -> optimizer.step) may have changed param_groups["lr"]
+        m = self.model
+        self._step += 1                  # host mirror only; the authoritative count lives in the device state
+        ema = self._ema
+        fused = ema is not None and self.ema_fused
+        d = omd = 0.0
+        if fused:
+            ema.check(m)
+            ema.updates += 1
+            d, omd = ema.factors()
+        self._launch(zero_grad, grad_scale, ema.ema.flat_params if fused else None, d, omd)
+        if fused:
+            E.ema_update(ema.ema.flat_stats, m.flat_stats, d, omd)
+        elif ema is not None:
+            ema.update(m)
+
+    def zero_grad(self, set_to_none: bool = True):
+        self.model.flat_grads.zero_()
+
+    def device_step(self) -> int:
+        """Steps actually applied: read from the device state (skipped steps and graph replays are counted there)."""
+        return self._step if self._state is None else int(self._state[1].item())
+
+
+class FlatOptimizer(FlatStep):
+    """What ``FlatSGD`` and ``FlatAdamW`` share: the grouping, the device tables, the launches of a step, the checkpoint layout.
 
     ``groups``: None (one group, uniform decay -- torch's meaning of a plain parameter list) or ``"no_decay_norm_bias"`` (``classify``);
     ``bias_lr_scale`` multiplies the bias group's learning rate.  ``freeze``: state_dict key prefixes; the matching parameters get
@@ -138,7 +198,6 @@ class FlatOptimizer(torch.optim.Optimizer):
     def __init__(self, model, hyper: dict, weight_decay: float, groups, bias_lr_scale: float, freeze, clip_grad_norm):
         if clip_grad_norm is not None and not float(clip_grad_norm) > 0:
             raise ValueError(f"clip_grad_norm: None or a positive max norm, got {clip_grad_norm}")
-        self.model = model
         self.plan = GroupPlan(model, groups, freeze)
         self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
         named = dict(model.named_parameters())
@@ -148,16 +207,12 @@ class FlatOptimizer(torch.optim.Optimizer):
             glr = lr * bias_lr_scale if name == "bias" else lr
             wd = weight_decay if name in ("all", "weights") else 0.0
             entries.append(dict(hyper, params=[named[k] for k in keys], lr=glr, initial_lr=glr, weight_decay=wd, name=name, frozen=g == self.plan.frozen))
-        super().__init__(entries, dict(hyper, weight_decay=weight_decay))
+        super().__init__(model, entries, dict(hyper, weight_decay=weight_decay))
         self._buf1 = self._buf2 = None
-        self._step = 0
-        self._state = None          # device [group 0's lr, step, group 0's lr/(1-b1^t), 1/sqrt(1-b2^t)]: the step advances on the device
+        # _state: device [group 0's lr, step, group 0's lr/(1-b1^t), 1/sqrt(1-b2^t)]
         self._gs = None             # device (n_groups, 8) group table
         self._rows_on_device = None
         self._map = self._clip = self._ws = None
-        self.found_inf: Optional[torch.Tensor] = None
-        self._ema = None
-        self.ema_fused = True       # False: the average as launches of its own after the step (tools/optim_cost.py times both)
 
     # ---- per-kind pieces ----------------------------------------------------------------------------------------------------------------
     def _row(self, g) -> List[float]:
@@ -168,13 +223,6 @@ class FlatOptimizer(torch.optim.Optimizer):
         return (0.0, 0.0), 0.0
 
     # ---- device state ---------------------------------------------------------------------------------------------------------------------
-    def attach_ema(self, ema):
-        """Every ``step()`` from now on also moves ``ema`` (a ``ModelEMA`` of this optimiser's model; None detaches it): the parameters inside
-        the step kernel, the BatchNorm statistics with one ``cvx_ema_update`` launch, ``ema.updates`` + 1, a skipped step included."""
-        if ema is not None:
-            ema.check(self.model)
-        self._ema = ema
-
     def _rows(self):
         return [[float(v) for v in self._row(g)] for g in self.param_groups]
 
@@ -207,38 +255,15 @@ class FlatOptimizer(torch.optim.Optimizer):
         """The norm the last clipping step measured, on the device (None without clipping or before the first step)."""
         return None if self.clip_grad_norm is None or self._clip is None else self._clip[0]
 
-    @torch.no_grad()
-    def step(self, closure=None, zero_grad: bool = False, grad_scale: float = 1.0):
-        self._ensure_state()
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_lr()
+    def _launch(self, zero_grad, grad_scale, ema_arena, d, omd):
         m = self.model
-        self._step += 1                  # host mirror only; the authoritative count lives in the device state
         clip = None
         if self.clip_grad_norm is not None:
             E.grad_norm(m.flat_grads, self._map, self._gs, self.clip_grad_norm, self._clip, self._ws, grad_scale, self.found_inf)
             clip = self._clip
-        ema = self._ema
-        fused = ema is not None and self.ema_fused
-        d = omd = 0.0
-        if fused:
-            ema.check(m)
-            ema.updates += 1
-            d, omd = ema.factors()
         betas, eps = self._betas_eps()
         E.optim_step(self.kind, m.flat_params, m.flat_grads, self._buf1, self._buf2, self._map, self._gs, self._state, betas, eps, self.found_inf,
-                     zero_grad, grad_scale, clip, ema.ema.flat_params if fused else None, d, omd)
-        if fused:
-            E.ema_update(ema.ema.flat_stats, m.flat_stats, d, omd)
-        elif ema is not None:
-            ema.update(m)
-
-    def zero_grad(self, set_to_none: bool = True):
-        self.model.flat_grads.zero_()
-
-    def device_step(self) -> int:
-        """Steps actually applied: read from the device state (skipped steps and graph replays are counted there)."""
-        return self._step if self._state is None else int(self._state[1].item())
+                     zero_grad, grad_scale, clip, ema_arena, d, omd)
 
     # ---- checkpoint interchange: the installed torch optimiser's state_dict layout ------------------------------------------------------------
     def _buffers(self):

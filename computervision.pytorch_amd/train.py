@@ -2,8 +2,9 @@
 
 * ``V8DetectionLoss`` -- the reference's ``Loss(cfg, model)`` callable (core/algorithms/yolo_v8.py:25-124):
   ``loss, items = criterion(preds, batch)``; value and gradient come from ``cvx_loss_v8``.
-* ``FlatAdam`` -- ``torch.optim.Optimizer``-shaped wrapper over ``cvx_adam_step`` on the flat arenas
-  (the reference builds ``torch.optim.Adam`` over all parameters, core/trainer/lr_scheduler.py:37-43).
+* ``FlatAdam`` -- ``torch.optim.Optimizer``-shaped wrapper over ``cvx_adam_step_dev`` (csrc/optim.hip) on the flat arenas
+  (the reference builds ``torch.optim.Adam`` over all parameters, core/trainer/lr_scheduler.py:37-43); the step skeleton it shares
+  with ``FlatSGD`` / ``FlatAdamW`` is ``optim.FlatStep``.
 * ``FusedTrainStep`` -- zero_grad -> forward -> loss -> backward -> [all-reduce] -> Adam as five C-ABI
   calls with no per-parameter Python work (the reference's ``train_loop``,
   core/trainer/yolo8_train.py:93-111).
@@ -19,9 +20,10 @@ import os
 
 from . import _lib as L
 from .arena import EngineTrainStep
-from .engine import V8LossOp, _note_param_write, adam_ema_step_dev, adam_step, adam_step_dev, ema_update
+from .engine import V8LossOp, _note_param_write, adam_ema_step_dev, adam_step, adam_step_dev
 from .graph import STRIDES
 from .model import PredList, Yolo8
+from .optim import FlatStep
 
 
 def flatten_targets(batch: Dict[str, torch.Tensor], device) -> torch.Tensor:
@@ -87,29 +89,17 @@ class V8DetectionLoss:
         return loss, self.last_items.detach()
 
 
-class FlatAdam(torch.optim.Optimizer):
-    """Adam over the model's flat arenas; ``param_groups`` keeps torch's shape so LR schedulers work."""
+class FlatAdam(FlatStep):
+    """Adam over the model's flat arenas; ``param_groups`` keeps torch's shape so LR schedulers work.  The surface and the step skeleton
+    are ``FlatStep``'s (optim.py); the launch is ``cvx_adam_step_dev``, or ``cvx_adam_ema_step_dev`` with an average attached."""
 
     def __init__(self, model: Yolo8, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        self.model = model
         params = [p for p in model.parameters() if p.requires_grad]
-        super().__init__([{"params": params, "initial_lr": lr}], dict(lr=lr, betas=betas, eps=eps))
+        super().__init__(model, [{"params": params, "initial_lr": lr}], dict(lr=lr, betas=betas, eps=eps))
         self._m = None
         self._v = None
-        self._step = 0
-        self._state = None          # device [lr, step, lr/(1-b1^t), 1/sqrt(1-b2^t)]: the step advances on the device
+        # _state: device [lr, step, lr/(1-b1^t), 1/sqrt(1-b2^t)]
         self._lr_on_device = None
-        self.found_inf: Optional[torch.Tensor] = None
-        self._ema = None            # attach_ema: a ModelEMA whose average moves with every step()
-        self.ema_fused = True       # False: the average as launches of its own after the Adam kernel (tools/ema_cost.py times both)
-
-    def attach_ema(self, ema):
-        """Every ``step()`` from now on also moves ``ema`` (a ``ModelEMA`` of this optimiser's model; None detaches it): the parameter average
-        inside the Adam kernel (``cvx_adam_ema_step_dev``), the BatchNorm statistics with one ``cvx_ema_update`` launch, ``ema.updates`` + 1 --
-        what ``ema.update(model)`` after ``optimizer.step()`` does in the reference's loop shape, a step skipped by ``found_inf`` included."""
-        if ema is not None:
-            ema.check(self.model)
-        self._ema = ema
 
     def _ensure_state(self):
         p = self.model.flat_params
@@ -126,33 +116,13 @@ class FlatAdam(torch.optim.Optimizer):
             self._state[0:1].fill_(lr)
             self._lr_on_device = lr
 
-    @torch.no_grad()
-    def step(self, closure=None, zero_grad: bool = False, grad_scale: float = 1.0):
-        self._ensure_state()
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_lr()               # a scheduler (or GradScaler.step -> optimizer.step) may have changed param_groups["lr"]
-        g = self.param_groups[0]
-        self._step += 1                  # host mirror only; the authoritative count lives in the device state
-        ema = self._ema
-        if ema is None or not self.ema_fused:
-            adam_step_dev(self.model.flat_params, self.model.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, self.found_inf,
-                          zero_grad, grad_scale)
-            if ema is not None:
-                ema.update(self.model)
-            return
-        ema.check(self.model)
-        ema.updates += 1
-        d, omd = ema.factors()
-        adam_ema_step_dev(self.model.flat_params, self.model.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, ema.ema.flat_params,
-                          d, omd, self.found_inf, zero_grad, grad_scale)
-        ema_update(ema.ema.flat_stats, self.model.flat_stats, d, omd)
-
-    def zero_grad(self, set_to_none: bool = True):
-        self.model.flat_grads.zero_()
-
-    def device_step(self) -> int:
-        """Steps actually applied: read from the device state (overflow-skipped steps and graph replays are counted there)."""
-        return self._step if self._state is None else int(self._state[1].item())
+    def _launch(self, zero_grad, grad_scale, ema_arena, d, omd):
+        g, m = self.param_groups[0], self.model
+        if ema_arena is None:
+            adam_step_dev(m.flat_params, m.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, self.found_inf, zero_grad, grad_scale)
+        else:
+            adam_ema_step_dev(m.flat_params, m.flat_grads, self._m, self._v, g["betas"], g["eps"], self._state, ema_arena, d, omd, self.found_inf,
+                              zero_grad, grad_scale)
 
     # ---- checkpoint interchange: torch.optim.Adam's state_dict layout (what the reference saves and loads, core/utils/ckpt.py:41-66) ----
     def _all_params(self):

@@ -1,6 +1,7 @@
-"""numpy fp32 restatement of what csrc/optim.hip adds around the existing Adam arithmetic: the SGD step, AdamW's decay multiply, the clip
+"""numpy fp32 restatement of what csrc/optim.hip puts around the Adam arithmetic: the SGD step, AdamW's decay multiply, the clip
 coefficient and the group map.  Every operation is one correctly rounded fp32 operation, in the order include/cvx_engine.h gives
-(numpy never contracts a multiply and an add).  The Adam core is NOT restated: it is defined as cvx_adam_step_dev's output.
+(numpy never contracts a multiply and an add).  The Adam core is NOT restated: csrc/optim_core.h (adam_step4 / adam_step1) defines it,
+and tests/golden/adam_trace.npz, a trace recorded on the device, pins its bits (tests/test_optim_gpu.py).
 
 tests/test_optim_cpu.py pins these against torch.optim / torch.nn.utils on the CPU; tests/test_optim_gpu.py compares the kernels with them bit for bit."""
 import numpy as np

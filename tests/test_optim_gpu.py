@@ -2,7 +2,9 @@
 
 The kernel comparisons are bit-exact (``torch.equal``): SGD, the decay multiply and the clip coefficient against tests/optim_restatement.py
 (numpy fp32, one rounding per operation; tests/test_optim_cpu.py pins it against torch), the ADAM kind against ``cvx_adam_step_dev`` --
-the Adam core is defined as that kernel's output --, the fused average against the two-launch form.  Clipped steps are fed the norm the
+the ungrouped instantiation of the same kernel body; the Adam core is csrc/optim_core.h's, and every Adam entry point replays
+tests/golden/adam_trace.npz, recorded on the device before the kernels were folded into one --, the fused average against the two-launch
+form.  Clipped steps are fed the norm the
 device measured, so the reduction order is not part of the bit-exact claim; the norm itself is held to 1e-5 of the fp64 norm (a tree sum
 of n <= 2^22 fp32 squares is bounded by about log2(n) 2^-24 = 1.3e-6; the rest is room for the square root and the partition)."""
 import numpy as np
@@ -196,6 +198,54 @@ def test_adam_kind_two_groups_equal_one_group_runs(dev, n):
             want = torch.where(gid == 0, singles[0][i][j], singles[1][i][j])
             assert np.array_equal(bits(got[i][j]), bits(want)), f"step {i}: {name}"
         assert float(got[i][4][1]) == float(singles[0][i][4][1])
+
+
+# ---- 2b. the Adam bits against the recorded trace -------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def adam_trace(gold):
+    return gold("adam_trace.npz")
+
+
+@pytest.mark.parametrize("path", ["dev", "ema", "host", "grouped"])
+@pytest.mark.parametrize("n", [3, 4, 1027, 1028])
+def test_adam_entry_points_replay_the_recorded_trace(dev, adam_trace, n, path):
+    """tests/golden/adam_trace.npz (tools/make_adam_golden.py) holds what cvx_adam_step_dev, cvx_adam_ema_step_dev and cvx_adam_step left
+    behind over PLAN on the build its ``commit`` names.  Every entry point, and cvx_optim_step(ADAM, one group, a map without holes, no
+    decay) against the ``dev`` leg, leaves the same bits in p, m, v, g, the state and the average after every step, and the guards alone."""
+    T = adam_trace
+    leg = "dev" if path == "grouped" else path
+    lr, betas, eps, gscale, d = float(T["lr"]), tuple(float(x) for x in T["betas"]), float(T["eps"]), float(T["grad_scale"]), float(T["d"])
+    A = Arenas(n, dev, 0)
+    A.p.copy_(torch.from_numpy(T[f"n{n}_p0"]))
+    A.e.copy_(torch.from_numpy(T[f"n{n}_e0"]))
+    grads = T[f"n{n}_grads"]
+    state0 = torch.tensor([lr, 0.0, 0.0, 0.0], device=dev)
+    state = state0.clone()
+    found = torch.zeros(1, dtype=torch.int32, device=dev)
+    gs = table([dict(lr=lr, wd=0.0, frozen=0.0)], E.OPTIM_ADAM, dev)
+    dmap = torch.zeros((n + 3) // 4, dtype=torch.uint8, device=dev)
+    arenas = dict(p=A.p, m=A.a, v=A.b, g=A.g, state=state, **({"e": A.e} if path == "ema" else {}))
+    for i, st in enumerate(PLAN):
+        A.g.copy_(torch.from_numpy(grads[i]))
+        found.fill_(st["inf"])
+        if path == "dev":
+            E.adam_step_dev(A.p, A.g, A.a, A.b, betas, eps, state, found, st["zg"], gscale)
+        elif path == "ema":
+            E.adam_ema_step_dev(A.p, A.g, A.a, A.b, betas, eps, state, A.e, d, 1.0 - d, found, st["zg"], gscale)
+        elif path == "host":
+            E.adam_step(A.p, A.g, A.a, A.b, lr, betas, eps, i + 1, found, st["zg"])
+        else:
+            E.optim_step(E.OPTIM_ADAM, A.p, A.g, A.a, A.b, dmap, gs, state, betas, eps, found, st["zg"], gscale)
+        torch.cuda.synchronize()
+        for name, t in arenas.items():
+            key = f"n{n}_{leg}_{name}"
+            if key in T.files:
+                assert np.array_equal(bits(t), T[key][i].view(np.uint32)), f"step {i}: {name}"
+        assert A.guards_intact()
+    if path != "ema":
+        assert np.array_equal(bits(A.e), T[f"n{n}_e0"].view(np.uint32))
+    if path == "host":
+        assert torch.equal(state, state0)
 
 
 # ---- 3. the fused average -----------------------------------------------------------------------------------------------------------

@@ -33,7 +33,7 @@ def one_step(path, counter):
         if r["Counter_Name"] == counter:
             per[int(r["Dispatch_Id"])] = (r["Kernel_Name"], float(r["Counter_Value"]))
     ids = list(per)
-    adam = [i for i in ids if "adam_kernel" in per[i][0]]
+    adam = [i for i in ids if "optim_step_kernel" in per[i][0]]
     a, b = adam[2], adam[3]
     agg = collections.defaultdict(lambda: [0.0, 0])
     for i in ids:

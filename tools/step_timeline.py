@@ -21,7 +21,7 @@ def short(n):
 
 df = pd.read_csv(sys.argv[1])
 df["name"] = df["Kernel_Name"].map(short)
-adam = df[df["name"].str.contains("adam_kernel")].sort_values("Start_Timestamp")
+adam = df[df["name"].str.contains("optim_step_kernel")].sort_values("Start_Timestamp")
 a0, a1 = adam.iloc[2]["End_Timestamp"], adam.iloc[3]["End_Timestamp"]
 st = df[(df["Start_Timestamp"] >= a0) & (df["End_Timestamp"] <= a1)].sort_values("Start_Timestamp").copy()
 st["dur"] = (st["End_Timestamp"] - st["Start_Timestamp"]) / 1e3
