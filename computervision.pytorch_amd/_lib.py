@@ -165,6 +165,10 @@ PROTOTYPES = {
     "cvx_seg_loss_opts_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "cvx_seg_loss_opts": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _I64, _F, _I64, _F, _P, _P, _P, _P, _P, _P]),
     "cvx_seg_eval_opts": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _I64, _P, _P, _P, _P]),
+    # Dice / Tversky region loss in the fused criterion chain: replaces F.interpolate + softmax + a one-hot region loss + autograd
+    "cvx_seg_loss_region_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "cvx_seg_loss_region": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _P, _F, _I64, _F, _I64, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, C.c_double, C.c_double, _I32, _I32, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
     "cvx_coco_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),

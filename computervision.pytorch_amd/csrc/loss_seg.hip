@@ -26,6 +26,7 @@
 // The taps, the class loop, the block sums, K2 and K3 live in seg_loss_core.h, which loss_seg_opts.hip (class weights, label smoothing,
 // hard-pixel mining) includes too.
 #include "seg_loss_core.h"
+#include "seg_loss_chain.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -154,6 +155,20 @@ extern "C" int64_t cvx_seg_loss_workspace_bytes(int32_t batch, int32_t nc, int32
   return 64 + seg_pixel_blocks((long long)batch * oh * ow) * 16 + (int64_t)batch * nc * oh * ow * 4;
 }
 
+// The chain half of cvx_seg_loss (seg_loss_chain.h): K1 and K3, which leave the gradient plane and its normaliser on the device.
+void seg_plain_chain(const float* rows_f32, int ld, int batch, int nc, int ih, int iw, int oh, int ow, const int64_t* target, int mode, float alpha,
+                     float gamma, int64_t ignore_index, float* loss_out, int32_t* bad_target, void* workspace, hipStream_t st, SegChainOut* out) {
+  const long long npix = (long long)batch * oh * ow;
+  const long long nblk = seg_pixel_blocks(npix);
+  double* acc = (double*)workspace;
+  double* part = (double*)((char*)workspace + 64);
+  float* dlogits = (float*)((char*)workspace + 64 + nblk * 16);
+  hipLaunchKernelGGL(seg_loss_pixel_kernel, dim3((unsigned)nblk), dim3(256), 0, st, rows_f32, ld, batch, nc, ih, iw, oh, ow,
+                     (const long long*)target, mode, alpha, gamma, (long long)ignore_index, dlogits, part, bad_target);
+  hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nblk, acc, mode, (double)npix, loss_out);
+  *out = SegChainOut{dlogits, acc, mode, (double)npix};
+}
+
 extern "C" int cvx_seg_loss(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                             const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, float loss_scale,
                             float* loss_out, void* dpred_f16, int32_t* bad_target, void* workspace, void* hip_stream) {
@@ -162,19 +177,13 @@ extern "C" int cvx_seg_loss(const float* rows_f32, int32_t ld, int32_t batch, in
   CVX_CHECK(mode == 0 || mode == 1, "mode: 0 focal, 1 cross-entropy");
   CVX_CHECK(loss_scale > 0.f, "loss_scale must be positive");
   hipStream_t st = (hipStream_t)hip_stream;
-  const long long npix = (long long)batch * oh * ow;
-  const long long nblk = seg_pixel_blocks(npix);
-  double* acc = (double*)workspace;
-  double* part = (double*)((char*)workspace + 64);
-  float* dlogits = (float*)((char*)workspace + 64 + nblk * 16);
-  CVX_CHECK(nblk < (1LL << 31) && ld <= 4096, "too many pixels / columns");
+  CVX_CHECK(seg_pixel_blocks((long long)batch * oh * ow) < (1LL << 31) && ld <= 4096, "too many pixels / columns");
   CVX_HIP(hipMemsetAsync(bad_target, 0, 4, st));
-  hipLaunchKernelGGL(seg_loss_pixel_kernel, dim3((unsigned)nblk), dim3(256), 0, st, rows_f32, ld, batch, nc, ih, iw, oh, ow,
-                     (const long long*)target, mode, alpha, gamma, (long long)ignore_index, dlogits, part, bad_target);
-  hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nblk, acc, mode, (double)npix, loss_out);
+  SegChainOut ch;
+  seg_plain_chain(rows_f32, ld, batch, nc, ih, iw, oh, ow, target, mode, alpha, gamma, ignore_index, loss_out, bad_target, workspace, st, &ch);
   const long long nlow = (long long)batch * ih * iw;
-  hipLaunchKernelGGL(resize_grad_rows_kernel, dim3((unsigned)cvx_cdiv(nlow, RG_PIX)), dim3(256), (size_t)RG_PIX * ld * 2, st, dlogits, batch, nc, ih, iw, oh,
-                     ow, loss_scale, mode, (double)npix, acc, (half_t*)dpred_f16, ld);
+  hipLaunchKernelGGL(resize_grad_rows_kernel, dim3((unsigned)cvx_cdiv(nlow, RG_PIX)), dim3(256), (size_t)RG_PIX * ld * 2, st, ch.dlogits, batch, nc, ih, iw, oh,
+                     ow, loss_scale, ch.norm_mode, ch.norm_const, ch.acc, (half_t*)dpred_f16, ld);
   CVX_HIP(hipGetLastError());
   return 0;
 }

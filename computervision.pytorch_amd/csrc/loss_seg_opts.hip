@@ -34,6 +34,7 @@
 #include <algorithm>
 
 #include "seg_loss_core.h"
+#include "seg_loss_chain.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -314,21 +315,13 @@ extern "C" int64_t cvx_seg_loss_opts_workspace_bytes(int32_t batch, int32_t nc, 
   return n + (int64_t)batch * nc * oh * ow * 4;
 }
 
-extern "C" int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                                 const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, float ohem_theta,
-                                 int64_t ohem_min_kept, float loss_scale, float* loss_out, void* dpred_f16, int32_t* bad_target, double* stats_out,
-                                 void* workspace, void* hip_stream) {
-  CVX_CHECK(rows_f32 && target && loss_out && dpred_f16 && bad_target && stats_out && workspace, "null arguments");
-  CVX_CHECK(batch > 0 && nc > 0 && nc <= SEG_MAX_NC && nc <= ld && ih > 0 && iw > 0 && oh > 0 && ow > 0, "bad sizes");
-  CVX_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "label_smoothing in [0, 1)");
-  CVX_CHECK(loss_scale > 0.f, "loss_scale must be positive");
+// The chain half of cvx_seg_loss_opts (seg_loss_chain.h): K1 .. K5, which leave the gradient plane and its normaliser on the device.
+void seg_opts_chain(const float* rows_f32, int ld, int batch, int nc, int ih, int iw, int oh, int ow, const int64_t* target, const float* class_weight,
+                    float label_smoothing, int64_t ignore_index, float ohem_theta, int64_t ohem_min_kept, float* loss_out, int32_t* bad_target,
+                    double* stats_out, void* workspace, hipStream_t st, SegChainOut* out) {
   const bool ohem = !(ohem_theta < 0.f);  // -ln thresh >= 0; negative: off
-  CVX_CHECK(!ohem || (ohem_min_kept >= 1 && isfinite(ohem_theta)), "OHEM: thresh in (0, 1], min_kept >= 1");
-  hipStream_t st = (hipStream_t)hip_stream;
   const long long npix = (long long)batch * oh * ow;
   const long long nblk = pixel_blocks(npix), nks = kept_sum_blocks(npix);
-  CVX_CHECK(nblk < (1LL << 31) && ld <= 4096, "too many pixels / columns");
-  CVX_CHECK(!ohem || npix < (1LL << 31), "OHEM counts pixels in 32 bits");
   char* w = (char*)workspace;
   double* acc = (double*)w;
   SegSelect* sel = (SegSelect*)(w + 64);
@@ -346,16 +339,10 @@ extern "C" int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batc
   w += al16((size_t)nks * 24);
   float* dlogits = (float*)w;
   const long long* tg = (const long long*)target;
-  const long long nlow = (long long)batch * ih * iw;
-  const unsigned gblocks = (unsigned)cvx_cdiv(nlow, RG_PIX);
-  const size_t glds = (size_t)RG_PIX * ld * 2;
-  CVX_HIP(hipMemsetAsync(bad_target, 0, 4, st));
   if (!ohem) {
     hipLaunchKernelGGL(seg_opts_pixel_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, st, rows_f32, ld, batch, nc, ih, iw, oh, ow, tg, class_weight,
                        label_smoothing, (long long)ignore_index, dlogits, part, bad_target, key, lplane);
     hipLaunchKernelGGL(seg_opts_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nblk, (const SegSelect*)nullptr, acc, loss_out, stats_out);
-    hipLaunchKernelGGL(resize_grad_rows_kernel, dim3(gblocks), dim3(256), glds, st, dlogits, batch, nc, ih, iw, oh, ow, loss_scale, 1, 1.0, acc,
-                       (half_t*)dpred_f16, ld);
   } else {
     const float theta = ohem_theta == 0.f ? 0.f : ohem_theta;  // -0.0 (thresh = 1) has the sign bit set
     hipLaunchKernelGGL(seg_opts_pixel_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, st, rows_f32, ld, batch, nc, ih, iw, oh, ow, tg, class_weight,
@@ -369,9 +356,31 @@ extern "C" int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batc
     hipLaunchKernelGGL(seg_opts_kept_sum_kernel, dim3((unsigned)nks), dim3(256), 0, st, (const unsigned*)key, lplane, tg, class_weight, npix, sel,
                        part_kept, dlogits, nc, (long long)oh * ow);
     hipLaunchKernelGGL(seg_opts_finalize_kernel, dim3(1), dim3(256), 0, st, part_kept, (int)nks, (const SegSelect*)sel, acc, loss_out, stats_out);
-    hipLaunchKernelGGL(resize_grad_rows_kernel, dim3(gblocks), dim3(256), glds, st, dlogits, batch, nc, ih, iw, oh, ow, loss_scale, 1, 1.0, acc,
-                       (half_t*)dpred_f16, ld);
   }
+  *out = SegChainOut{dlogits, acc, 1, 1.0};
+}
+
+extern "C" int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                                 const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, float ohem_theta,
+                                 int64_t ohem_min_kept, float loss_scale, float* loss_out, void* dpred_f16, int32_t* bad_target, double* stats_out,
+                                 void* workspace, void* hip_stream) {
+  CVX_CHECK(rows_f32 && target && loss_out && dpred_f16 && bad_target && stats_out && workspace, "null arguments");
+  CVX_CHECK(batch > 0 && nc > 0 && nc <= SEG_MAX_NC && nc <= ld && ih > 0 && iw > 0 && oh > 0 && ow > 0, "bad sizes");
+  CVX_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "label_smoothing in [0, 1)");
+  CVX_CHECK(loss_scale > 0.f, "loss_scale must be positive");
+  const bool ohem = !(ohem_theta < 0.f);  // -ln thresh >= 0; negative: off
+  CVX_CHECK(!ohem || (ohem_min_kept >= 1 && isfinite(ohem_theta)), "OHEM: thresh in (0, 1], min_kept >= 1");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long npix = (long long)batch * oh * ow;
+  CVX_CHECK(pixel_blocks(npix) < (1LL << 31) && ld <= 4096, "too many pixels / columns");
+  CVX_CHECK(!ohem || npix < (1LL << 31), "OHEM counts pixels in 32 bits");
+  CVX_HIP(hipMemsetAsync(bad_target, 0, 4, st));
+  SegChainOut ch;
+  seg_opts_chain(rows_f32, ld, batch, nc, ih, iw, oh, ow, target, class_weight, label_smoothing, ignore_index, ohem_theta, ohem_min_kept, loss_out,
+                 bad_target, stats_out, workspace, st, &ch);
+  const long long nlow = (long long)batch * ih * iw;
+  hipLaunchKernelGGL(resize_grad_rows_kernel, dim3((unsigned)cvx_cdiv(nlow, RG_PIX)), dim3(256), (size_t)RG_PIX * ld * 2, st, ch.dlogits, batch, nc, ih, iw,
+                     oh, ow, loss_scale, ch.norm_mode, ch.norm_const, ch.acc, (half_t*)dpred_f16, ld);
   CVX_HIP(hipGetLastError());
   return 0;
 }

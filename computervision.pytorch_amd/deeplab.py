@@ -365,10 +365,20 @@ class SegLoss:
     ``F.cross_entropy(weight=, label_smoothing=, reduction="mean")``; ``ohem=dict(thresh=t, min_kept=m)`` trains on the hard pixels
     only: those whose target probability is below ``t``, and at least the ``m * batch`` pixels with the largest cross-entropy (all
     pixels tied at that rank).  ``last_stats`` is the device tensor (kept pixels, valid pixels, theta_min, sum of target weights) of
-    the last call, ``ohem_keys()`` its per-pixel selection keys.  Without an option the criterion is ``cvx_seg_loss`` as before."""
+    the last call, ``ohem_keys()`` its per-pixel selection keys.  Without an option the criterion is ``cvx_seg_loss`` as before.
+
+    ``region=dict(kind="dice" | "tversky", ...)`` (see ``seg_region_defaults``; ``cvx_seg_loss_region``, csrc/loss_seg_region.hip) adds a
+    region loss to either loss type, with or without the options: the value is ``base_weight * base + weight * region`` with ``base``
+    what the criterion computes without ``region``.  Over the valid pixels of the batch (``per_image``: of each image, then the mean
+    over the images), with p the softmax and y the one-hot target: ``T_c = (I_c + smooth) / (I_c + alpha FP_c + beta FN_c + smooth)``,
+    ``I = sum p y``, ``FP = sum p (1 - y)``, ``FN = sum (1 - p) y``; the loss is the (``class_weights``-weighted) mean of
+    ``(1 - T_c)^gamma`` over the classes, those without a target pixel left out under ``skip_absent``.  Dice is ``alpha = beta = 0.5``.
+    ``base_weight = 0`` trains on the region loss alone (the base chain is skipped).  OHEM selects pixels for the base term only.
+    ``region_stats`` is the float64 device tensor ``(G, nc, 4)`` = I, P = sum p, Y = sum y, T of the last call (G = batch under
+    ``per_image``, else 1).  Data parallel: every rank takes the sums over its own shard, like OHEM and the weighted denominators."""
 
     def __init__(self, loss_type: str = "focal", alpha: float = 0.25, gamma: float = 2.0, ignore_index: int = -100, check_targets: bool = True,
-                 class_weights=None, label_smoothing: float = 0.0, ohem=None):
+                 class_weights=None, label_smoothing: float = 0.0, ohem=None, region=None):
         if loss_type not in ("focal", "ce"):
             raise ValueError("loss_type must be 'focal' or 'ce' (segmentation_2d.py:59-64)")
         self.mode = 0 if loss_type == "focal" else 1
@@ -381,6 +391,11 @@ class SegLoss:
         self.label_smoothing = float(label_smoothing)
         self.last_stats = None
         self._weights_dev = self._keys_shape = None
+        self.region = seg_region_defaults(**region) if region is not None else None
+        self.has_region = self.region is not None
+        self.region_stats = None
+        self._region_weights_dev = None
+        self._keys_base = 0
         self.has_options = class_weights is not None or self.label_smoothing != 0.0 or ohem is not None
         if not self.has_options:
             return
@@ -422,7 +437,8 @@ class SegLoss:
         if self.ohem is None or self._keys_shape is None:
             raise L.CvxError("ohem_keys: the criterion has no ohem option, or has not been called yet")
         B, H, W = self._keys_shape
-        return self._ws[L.SEG_OPTS_KEY_OFFSET:L.SEG_OPTS_KEY_OFFSET + B * H * W * 4].view(torch.float32).view(B, H, W)
+        o = self._keys_base + L.SEG_OPTS_KEY_OFFSET        # with a region term the base chain's workspace sits behind the region's own
+        return self._ws[o:o + B * H * W * 4].view(torch.float32).view(B, H, W)
 
     def _op_opts(self, lib, rows, target, dims, loss_scale, dpred):
         B, A, ld, nc, lh, lw, H, W = dims
@@ -441,6 +457,59 @@ class SegLoss:
         self._keys_shape = (B, H, W)
         return loss
 
+    def _region_call(self, lib, rows, target, dims, loss_scale, dpred, base_value, loss):
+        """``cvx_seg_loss_region``: training when ``dpred`` is a tensor, value only (``base_value``: the device float that holds the
+        base's value, or None) when it is None.  The workspace, the flag and the statistics are allocated by the first call of a
+        shape and kept."""
+        B, A, ld, nc, lh, lw, H, W = dims
+        dev, r = rows.device, self.region
+        value_only = dpred is None
+        with_base = base_value is not None if value_only else r["base_weight"] > 0.0
+        base = 0 if not with_base else (3 if self.has_options else (1 if self.mode == 0 else 2))
+        weights = self.weights_on(dev, nc) if base == 3 else None
+        rw = r["class_weights"]
+        if rw is not None:
+            if rw.numel() != nc:
+                raise ValueError(f"region class_weights has {rw.numel()} entries for {nc} classes")
+            if self._region_weights_dev is None or self._region_weights_dev.device != dev:
+                self._region_weights_dev = rw.to(dev)
+        ohem = base == 3 and self.ohem is not None and not value_only
+        G = B if r["per_image"] else 1
+        need = int(lib.cvx_seg_loss_region_workspace_bytes(B, nc, H, W, base, int(ohem), int(r["per_image"]), int(value_only)))
+        if need <= 0:
+            raise L.CvxError("cvx_seg_loss_region_workspace_bytes: bad sizes")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        if self._bad is None or self._bad.device != dev:
+            self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.last_stats is None or self.last_stats.device != dev:
+            self.last_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        if self.region_stats is None or self.region_stats.device != dev or tuple(self.region_stats.shape) != (G, nc, 4):
+            self.region_stats = torch.zeros(G, nc, 4, dtype=torch.float64, device=dev)
+        theta, k = (self.ohem_theta, self.ohem["min_kept"] * B) if ohem else (-1.0, 0)
+        with torch.cuda.device(dev):
+            L.check(lib.cvx_seg_loss_region(
+                L.ptr(rows), ld, B, nc, lh, lw, H, W, L.ptr(target), base, self.alpha, self.gamma, L.ptr(weights) if weights is not None else None,
+                self.label_smoothing, self.ignore_index, theta, k, r["base_weight"] if with_base else 0.0, r["weight"], r["alpha"], r["beta"],
+                r["gamma"], r["smooth"], int(r["per_image"]), int(r["skip_absent"]), L.ptr(self._region_weights_dev) if rw is not None else None,
+                float(loss_scale), L.ptr(base_value) if base_value is not None else None, L.ptr(loss), L.ptr(dpred) if dpred is not None else None,
+                L.ptr(self._bad), L.ptr(self.last_stats), L.ptr(self.region_stats), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_loss_region")
+        if ohem:
+            self._keys_shape = (B, H, W)
+            self._keys_base = need - int(lib.cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, 1))
+
+    def region_value(self, rows: torch.Tensor, target: torch.Tensor, hw, loss_slot: torch.Tensor, nc=None):
+        """Validation: ``loss_slot`` (one float32 on the rows' device) holds the base's value of the batch, e.g. what ``cvx_seg_eval``
+        wrote, and receives ``base_weight * base + weight * region``.  No gradient plane, no adjoint, nothing read back."""
+        if not self.has_region:
+            raise L.CvxError("region_value: the criterion has no region term")
+        B, A, ld = rows.shape
+        nc = nc or getattr(self, "nc", None) or ld
+        target = target.to(device=rows.device, dtype=torch.long).contiguous()
+        dims = (B, A, ld, nc, int(hw[0]), int(hw[1]), int(target.shape[1]), int(target.shape[2]))
+        base_value = loss_slot if self.region["base_weight"] > 0.0 else None
+        self._region_call(L.load(), rows, target, dims, 1.0, None, base_value, loss_slot)
+
     def op(self, rows: torch.Tensor, target: torch.Tensor, hw, loss_scale: float, dpred: Optional[torch.Tensor] = None,
            check: Optional[bool] = None):
         """rows (B, lh*lw, ld) fp32, target (B, H, W) int64, hw = (lh, lw) -> (loss (1,), dpred (B, lh*lw, ld) fp16)."""
@@ -454,6 +523,14 @@ class SegLoss:
         H, W = int(target.shape[1]), int(target.shape[2])
         nc = getattr(self, "nc", None) or ld
         target = target.to(device=rows.device, dtype=torch.long).contiguous()
+        if self.has_region:
+            if dpred is None:
+                dpred = torch.empty(B, A, ld, dtype=torch.float16, device=rows.device)
+            loss = torch.empty(1, device=rows.device)     # as the other two paths: a block of the caching allocator, no device allocation
+            self._region_call(lib, rows, target, (B, A, ld, nc, lh, lw, H, W), loss_scale, dpred, None, loss)
+            if (self.check_targets if check is None else check) and self.bad_targets():
+                raise L.CvxError("SegLoss: a target label is neither ignore_index nor in [0, num_classes)")
+            return loss, dpred
         if self.has_options:
             if dpred is None:
                 dpred = torch.empty(B, A, ld, dtype=torch.float16, device=rows.device)
@@ -484,6 +561,44 @@ class SegLoss:
         if model.training and torch.is_grad_enabled():
             return _SegLossFn.apply(preds, self, rows, model, targets, hw)
         return self.op(rows, targets, hw, model.loss_scale)[0].reshape(())
+
+
+_REGION_KEYS = ("kind", "weight", "base_weight", "alpha", "beta", "gamma", "smooth", "per_image", "skip_absent", "class_weights")
+
+
+def seg_region_defaults(kind: str = "dice", **kw) -> dict:
+    """The filled-in ``region=`` dict of ``SegLoss``: ``kind`` "dice" (alpha = beta = 0.5, fixed) or "tversky" (alpha 0.3, beta 0.7 by
+    default), ``weight`` 1, ``base_weight`` 1, ``gamma`` 1 (another value: focal Tversky), ``smooth`` 1, ``per_image`` False,
+    ``skip_absent`` True, ``class_weights`` None.  Raises ``ValueError`` for an unknown kind or key and for a value outside its range."""
+    if kind not in ("dice", "tversky"):
+        raise ValueError("region: kind must be 'dice' or 'tversky'")
+    unknown = sorted(set(kw) - set(_REGION_KEYS))
+    if unknown:
+        raise ValueError(f"region: unknown keys {unknown}")
+    if kind == "dice":
+        if any(kw.get(k) is not None and float(kw[k]) != 0.5 for k in ("alpha", "beta")):
+            raise ValueError("region: kind 'dice' is alpha = beta = 0.5; use kind 'tversky' for other values")
+        a, b = 0.5, 0.5
+    else:
+        a = 0.3 if kw.get("alpha") is None else float(kw["alpha"])
+        b = 0.7 if kw.get("beta") is None else float(kw["beta"])
+
+    def num(key, default):
+        return default if kw.get(key) is None else float(kw[key])
+
+    r = {"kind": kind, "weight": num("weight", 1.0), "base_weight": num("base_weight", 1.0), "alpha": a, "beta": b, "gamma": num("gamma", 1.0),
+         "smooth": num("smooth", 1.0), "per_image": bool(kw.get("per_image", False)),
+         "skip_absent": True if kw.get("skip_absent") is None else bool(kw["skip_absent"]), "class_weights": None}
+    if not all(math.isfinite(r[k]) for k in ("weight", "base_weight", "alpha", "beta", "gamma", "smooth")):
+        raise ValueError("region: every value must be finite")
+    if r["weight"] <= 0 or r["base_weight"] < 0 or r["alpha"] < 0 or r["beta"] < 0 or r["gamma"] <= 0 or r["smooth"] < 0:
+        raise ValueError("region: weight > 0, base_weight >= 0, alpha >= 0, beta >= 0, gamma > 0 and smooth >= 0")
+    if kw.get("class_weights") is not None:
+        w = torch.as_tensor(kw["class_weights"], dtype=torch.float32).detach().cpu().reshape(-1).clone()
+        if w.numel() == 0 or not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not bool((w > 0).any()):
+            raise ValueError("region: class_weights must be finite, non-negative and not all zero")
+        r["class_weights"] = w
+    return r
 
 
 def seg_class_weights(counts, scheme: str = "median_freq") -> torch.Tensor:

@@ -80,7 +80,9 @@ class SegmentationMetrics:
         ``confusion[target][argmax of the upsampled logits] += 1`` and ``criterion``'s (a ``SegLoss``) value of the batch into
         ``loss_slot``, a one-element float32 view on the rows' device.  A criterion with options (class weights, label smoothing) goes
         through ``cvx_seg_eval_opts``: the weighted, smoothed value over all valid pixels, the same matrix; its OHEM setting is not
-        applied in evaluation.  Asynchronous: nothing is read back."""
+        applied in evaluation.  A criterion with a region term (``SegLoss(region=)``) then runs ``cvx_seg_loss_region`` in its value-only
+        mode (no gradient plane, no adjoint), so that the slot holds ``base_weight * base + weight * region`` of the batch; the matrix is the
+        eval launch's.  Asynchronous: nothing is read back."""
         if not (torch.is_tensor(rows) and rows.is_cuda):
             raise L.CvxError("SegmentationMetrics.add_rows runs on an MI355X only (there is no CPU path); add_batch takes host predictions")
         lib = L.load()
@@ -104,11 +106,13 @@ class SegmentationMetrics:
                 L.check(lib.cvx_seg_eval_opts(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets),
                                               L.ptr(weights) if weights is not None else None, criterion.label_smoothing, criterion.ignore_index,
                                               L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_eval_opts")
-            return
-        with torch.cuda.device(dev):
-            L.check(lib.cvx_seg_eval(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets), criterion.mode, criterion.alpha,
-                                     criterion.gamma, criterion.ignore_index, L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws),
-                                     L.stream_ptr(dev)), "cvx_seg_eval")
+        else:
+            with torch.cuda.device(dev):
+                L.check(lib.cvx_seg_eval(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets), criterion.mode, criterion.alpha,
+                                         criterion.gamma, criterion.ignore_index, L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws),
+                                         L.stream_ptr(dev)), "cvx_seg_eval")
+        if getattr(criterion, "has_region", False):        # the slot holds the base's value: base_weight * base + weight * region replaces it
+            criterion.region_value(rows, targets, (lh, lw), loss_slot, nc=self.num_classes)
 
     def add_batch(self, predictions, gts):
         predictions, gts = torch.as_tensor(predictions).reshape(-1), torch.as_tensor(gts).reshape(-1)

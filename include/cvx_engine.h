@@ -537,6 +537,32 @@ int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t 
 int cvx_seg_eval_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                       const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, int64_t* confusion,
                       float* loss_out, void* workspace, void* hip_stream);
+/* Dice / Tversky / focal-Tversky region loss added to the fused criterion chain of the DeepLabv3+ step:
+ *   loss = base_weight * base + weight * region.
+ * base: 0 none (base_weight must be 0), 1 cvx_seg_loss mode 0 (focal_alpha, focal_gamma), 2 cvx_seg_loss mode 1, 3 cvx_seg_loss_opts
+ * (class_weight, label_smoothing, ohem_theta, ohem_min_kept; base_stats_out = its 4 doubles); the base's kernels run unchanged, its OHEM
+ * selects pixels for the base term only.  region, over the valid pixels (cvx_seg_loss's rule) of a group -- the batch, or each image when
+ * per_image != 0 -- with p = softmax of the interpolated logits and y the one-hot target:
+ *   I_c = sum p_c y_c, P_c = sum p_c, Y_c = sum y_c, D_c = (1 - alpha - beta) I_c + alpha P_c + beta Y_c + smooth,
+ *   T_c = (I_c + smooth) / D_c (1 when D_c == 0), L_c = (1 - T_c)^gamma, group loss = sum_c m_c v_c L_c / sum_c m_c v_c (0 when that is 0),
+ *   m_c = [Y_c > 0] when skip_absent != 0, else 1; v = region_class_weight (nc floats on the device; null: ones);
+ *   region = mean of the group losses.  alpha = beta = 0.5 is the Dice loss, gamma != 1 the focal Tversky loss.
+ * Training (dpred_f16 not null): dpred = loss_scale * d loss / d rows as for cvx_seg_loss; base_value is not read.  Value only (dpred_f16
+ * null): no base chain, no gradient plane, no adjoint; base_value (1 device float, e.g. what cvx_seg_eval wrote; may be loss_out itself;
+ * null: no base term) is the base's value and the base arguments are not read.  region_stats_out: (G, nc, 4) doubles on the device,
+ * G = per_image ? batch : 1: I, P, Y, T.  Every floating-point sum runs in a fixed order (per-workgroup trees, then the partials in index
+ * order; no floating-point atomics): two calls give the same bits.  nc <= 1024.  workspace: cvx_seg_loss_region_workspace_bytes() bytes
+ * with the same base, ohem (base 3 with OHEM), per_image and value_only.  Asynchronous on hip_stream, no host read.
+ * Replaces: F.interpolate + softmax + a one-hot Dice / Tversky loss (e.g. segmentation_models_pytorch's DiceLoss / TverskyLoss) added to
+ * the criterion + loss.backward() down to the classifier's output; not in the reference, whose build_loss has no region loss. */
+int64_t cvx_seg_loss_region_workspace_bytes(int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t base, int32_t ohem, int32_t per_image,
+                                            int32_t value_only);
+int cvx_seg_loss_region(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                        const int64_t* target, int32_t base, float focal_alpha, float focal_gamma, const float* class_weight, float label_smoothing,
+                        int64_t ignore_index, float ohem_theta, int64_t ohem_min_kept, double base_weight, double weight, double alpha, double beta,
+                        double gamma, double smooth, int32_t per_image, int32_t skip_absent, const float* region_class_weight, float loss_scale,
+                        const float* base_value, float* loss_out, void* dpred_f16, int32_t* bad_target, double* base_stats_out,
+                        double* region_stats_out, void* workspace, void* hip_stream);
 /* VOC mAP evaluation of a detector (get_map at IoU min_overlap), accumulated on the device batch by batch.
  * cvx_det_match, once per batch: rows (batch, max_det, 6) [x1,y1,x2,y2,score,cls] fp32 and counts (batch) int32 exactly as cvx_nms /
  * cvx_nms_variant write them; a count of -1 (or one past max_det) adds 1 to the overflow counter and the image contributes nothing.

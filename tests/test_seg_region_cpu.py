@@ -1,0 +1,188 @@
+"""The region-loss rules (tests/seg_region_restatement.py) against an independent one-hot + torch.autograd float64 formulation, their
+edge rules, and the host side of ``SegLoss(region=)``: the refusals, ``build_loss`` and the C ABI's new entries.  No GPU."""
+import ctypes
+import math
+import os
+import re
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import builder
+from computervision.pytorch_amd import CvxError
+from computervision.pytorch_amd import _lib as L
+from computervision.pytorch_amd.deeplab import SegLoss, seg_region_defaults
+import seg_region_restatement as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def autograd_region(logits, target, al, be, gamma, smooth, per_image, skip_absent, weights):
+    """One-hot TP / FP / FN formulation with autograd; (value, d value / d logits).  For inputs without D_c == 0 and 1 - T_c == 0."""
+    x = logits.double().clone().requires_grad_(True)
+    B, C, H, W = x.shape
+    mask = ((target != -100) & (target >= 0) & (target < C))[:, None].double()
+    y = F.one_hot(target.clamp(0, C - 1), C).permute(0, 3, 1, 2).double() * mask
+    p = torch.softmax(x, dim=1)
+    dims = (2, 3) if per_image else (0, 2, 3)
+    tp, fp, fn = (p * y).sum(dims), (p * (1 - y) * mask).sum(dims), ((1 - p) * y).sum(dims)
+    tversky = (tp + smooth) / (tp + al * fp + be * fn + smooth)
+    per_class = ((1 - tversky) ** gamma).reshape(-1, C)
+    v = torch.ones(C, dtype=torch.float64) if weights is None else weights.double()
+    m = v[None] * ((y.sum(dims).reshape(-1, C) > 0).double() if skip_absent else 1.0)
+    value = ((m * per_class).sum(1) / m.sum(1)).mean()
+    return value.detach(), torch.autograd.grad(value, x)[0]
+
+
+@pytest.mark.parametrize("name", list(R.CONFIGS))
+@pytest.mark.parametrize("shape", R.SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_restatement_against_autograd(shape, name):
+    rows, t, w = R.case(shape)
+    assert int((t == 2).sum()) == 0 and int((t == 3).sum()) > 0
+    cfg = seg_region_defaults(**R.config(name, w))
+    logits = R.upsample(R.low_res_nchw(rows, shape), shape)
+    got = R.region(logits, t, **cfg)
+    want_v, want_g = autograd_region(logits, t, cfg["alpha"], cfg["beta"], cfg["gamma"], cfg["smooth"], cfg["per_image"], cfg["skip_absent"],
+                                     cfg["class_weights"])
+    verr = abs(float(got["value"]) - float(want_v)) / abs(float(want_v))
+    gerr = float((got["grad"] - want_g).abs().max() / want_g.abs().max())
+    print(f"{name} {shape}: value {float(got['value']):.12f}, relative error {verr:.3g}; gradient relative error {gerr:.3g}")
+    assert verr <= 1e-12 and gerr <= 1e-12
+    G = shape[0] if cfg["per_image"] else 1
+    assert tuple(got["stats"].shape) == (G, shape[5], 4)
+    assert float(got["stats"][:, 2, 2].abs().max()) == 0.0                      # Y of the absent class
+    assert float(got["stats"][..., 2].sum()) == float(got["valid"].sum())
+    assert bool((got["grad"][~got["valid"][:, None].expand_as(got["grad"])] == 0).all())
+
+
+def test_combination_with_a_base():
+    shape = R.SHAPES[1]
+    rows, t, w = R.case(shape)
+    logits = R.upsample(R.low_res_nchw(rows, shape), shape)
+    reg, base = R.region(logits, t), R.criterion(logits, t)
+    v, g = R.combine(base["loss"], base["grad"], reg, weight=0.5, base_weight=2.0)
+    assert abs(float(v) - (2.0 * float(base["loss"]) + 0.5 * float(reg["value"]))) < 1e-15
+    assert torch.equal(g, 2.0 * base["grad"] + 0.5 * reg["grad"])
+    v0, g0 = R.combine(base["loss"], base["grad"], reg, weight=3.0, base_weight=0.0)
+    assert float(v0) == 3.0 * float(reg["value"]) and torch.equal(g0, 3.0 * reg["grad"])
+    # the focal restatement against autograd through F.cross_entropy, as the reference's FocalLoss computes it
+    x = logits.clone().requires_grad_(True)
+    ce = F.cross_entropy(x, t, ignore_index=-100, reduction="none")
+    fl = (0.25 * (1 - torch.exp(-ce)) ** 2 * ce).mean()
+    fv, fg = R.focal(logits, t)
+    assert abs(float(fv) - float(fl)) <= 1e-12 * float(fl)
+    assert float((fg - torch.autograd.grad(fl, x)[0]).abs().max()) <= 1e-12 * float(fg.abs().max())
+
+
+def test_edge_rules():
+    shape = R.SHAPES[1]
+    B, ih, iw, H, W, nc = (2,) + shape[1:]
+    rows, t, _ = R.make_case((B,) + shape[1:], 7)
+    logits = R.upsample(R.low_res_nchw(rows, (B,) + shape[1:]), (B,) + shape[1:])
+    # an image whose pixels are all ignored, under per_image: it contributes 0 and still counts
+    t1 = t.clone()
+    t1[1] = -100
+    both, alone = R.region(logits, t1, per_image=True), R.region(logits[:1], t1[:1], per_image=True)
+    assert abs(float(both["value"]) - 0.5 * float(alone["value"])) < 1e-15
+    assert float(both["grad"][1].abs().max()) == 0.0
+    assert float((both["grad"][0] - 0.5 * alone["grad"][0]).abs().max()) < 1e-18
+    # a batch with no valid pixel: value 0, gradient 0, no nan (skip_absent on and off, smooth 0 and 1)
+    for kw in (dict(), dict(skip_absent=False), dict(smooth=0.0), dict(smooth=0.0, skip_absent=False, kind="tversky", gamma=0.5)):
+        r = R.region(logits, torch.full_like(t, -100), **kw)
+        assert float(r["value"]) == 0.0, kw                         # no counted class, or every T_c = 1 (D_c == 0, or smooth / smooth)
+        assert float(r["grad"].abs().max()) == 0.0 and bool(torch.isfinite(r["stats"]).all()), kw
+    # D_c == 0 with smooth = 0: a class that no pixel has and whose probability is exactly zero
+    z = logits.clone()
+    z[:, 4] = -2000.0
+    t2 = torch.where(t == 4, torch.full_like(t, 1), t)
+    r = R.region(z, t2, smooth=0.0, skip_absent=False)
+    assert r["stats"][0, 4].tolist() == [0.0, 0.0, 0.0, 1.0] and bool(torch.isfinite(r["grad"]).all()) and math.isfinite(float(r["value"]))
+    assert float(r["grad"][:, 4].abs().max()) == 0.0
+    # 1 - T_c == 0 with gamma < 1: zero gradient, not inf
+    zc = torch.full((1, 2, 4, 4), -1000.0, dtype=torch.float64)
+    tt = torch.zeros(1, 4, 4, dtype=torch.long)
+    tt[0, 2:] = 1
+    zc.scatter_(1, tt[:, None], 1000.0)
+    r = R.region(zc, tt, kind="tversky", alpha=0.5, beta=0.5, gamma=0.5, smooth=0.0)
+    assert r["stats"][0, :, 3].tolist() == [1.0, 1.0] and float(r["value"]) == 0.0
+    assert float(r["grad"].abs().max()) == 0.0
+    # nc = 2
+    g = torch.Generator().manual_seed(3)
+    z2, t2c = torch.randn(2, 2, 6, 5, generator=g, dtype=torch.float64), torch.randint(0, 2, (2, 6, 5), generator=g)
+    r = R.region(z2, t2c, kind="tversky", gamma=0.75)
+    wv, wg = autograd_region(z2, t2c, 0.3, 0.7, 0.75, 1.0, False, True, None)
+    assert abs(float(r["value"]) - float(wv)) <= 1e-12 * float(wv) and float((r["grad"] - wg).abs().max()) <= 1e-12 * float(wg.abs().max())
+
+
+BAD_REGIONS = [
+    dict(kind="lovasz"), dict(kind="dice", sigma=1.0), dict(kind="dice", weight=0.0), dict(kind="dice", weight=-1.0),
+    dict(kind="dice", base_weight=-0.5), dict(kind="tversky", alpha=-0.1), dict(kind="tversky", beta=-0.1), dict(kind="dice", gamma=0.0),
+    dict(kind="dice", gamma=-1.0), dict(kind="dice", smooth=-1e-3), dict(kind="dice", weight=float("nan")), dict(kind="dice", base_weight=float("inf")),
+    dict(kind="tversky", alpha=float("nan")), dict(kind="tversky", beta=float("inf")), dict(kind="dice", gamma=float("inf")),
+    dict(kind="dice", smooth=float("nan")), dict(kind="dice", class_weights=[1.0, -1.0, 1.0]), dict(kind="dice", class_weights=[1.0, float("nan")]),
+    dict(kind="dice", class_weights=[0.0, 0.0, 0.0]),
+]
+
+
+@pytest.mark.parametrize("bad", BAD_REGIONS, ids=lambda b: ",".join(f"{k}={v}" for k, v in b.items()))
+def test_constructor_refusals(bad):
+    for loss_type in ("ce", "focal"):
+        with pytest.raises(ValueError):
+            SegLoss(loss_type, region=bad)
+
+
+def test_constructor_and_config_surface():
+    d = seg_region_defaults("dice")
+    assert (d["alpha"], d["beta"], d["gamma"], d["smooth"], d["weight"], d["base_weight"]) == (0.5, 0.5, 1.0, 1.0, 1.0, 1.0)
+    assert d["per_image"] is False and d["skip_absent"] is True and d["class_weights"] is None
+    tv = seg_region_defaults("tversky")
+    assert (tv["alpha"], tv["beta"]) == (0.3, 0.7)
+    assert not SegLoss("ce").has_region and not SegLoss("focal").has_region and SegLoss("ce").region_stats is None
+    crit = SegLoss("ce", region=dict(kind="tversky", gamma=0.75, base_weight=0.0))
+    assert crit.has_region and not crit.has_options and crit.region["gamma"] == 0.75 and crit.region["base_weight"] == 0.0
+    both = SegLoss("ce", class_weights=[1.0, 2.0], label_smoothing=0.1, ohem=dict(thresh=0.7, min_kept=10), region=dict(kind="dice"))
+    assert both.has_region and both.has_options
+    # region under "focal" is accepted, the cross-entropy options under "focal" still are not
+    assert SegLoss("focal", region=dict(kind="dice")).has_region and SegLoss("focal", region=dict(kind="dice")).mode == 0
+    with pytest.raises(ValueError):
+        SegLoss("focal", class_weights=[1.0, 2.0])
+    with pytest.raises(ValueError):
+        SegLoss("focal", class_weights=[1.0, 2.0], region=dict(kind="dice"))
+    with pytest.raises(ValueError):
+        SegLoss("dice")
+    with pytest.raises(CvxError):                                               # no CPU path
+        crit.op(torch.zeros(1, 4, 24), torch.zeros(1, 8, 8, dtype=torch.long), (2, 2), 1.0)
+
+
+def test_build_loss_reads_the_region_config():
+    cfg, algo_cls, _ = builder.export_from_registry("deeplabv3plus")
+    crit = algo_cls(cfg, torch.device("cpu")).build_loss()
+    assert crit.has_region is False and crit.has_options is False
+    cfg.loss.region = dict(kind="tversky", alpha=0.4, beta=0.6, weight=0.5)
+    crit = algo_cls(cfg, torch.device("cpu")).build_loss()
+    assert crit.has_region and crit.mode == 0 and (crit.region["alpha"], crit.region["beta"], crit.region["weight"]) == (0.4, 0.6, 0.5)
+    cfg.loss.loss_type = "ce"
+    assert algo_cls(cfg, torch.device("cpu")).build_loss().mode == 1
+    cfg.loss.region = dict(kind="dice", gamma=0.0)
+    with pytest.raises(ValueError):
+        algo_cls(cfg, torch.device("cpu")).build_loss()
+    cfg.loss.region = None
+    cfg.loss.loss_type = "dice"
+    with pytest.raises(CvxError):
+        algo_cls(cfg, torch.device("cpu")).build_loss()
+
+
+def test_the_new_entries_are_declared_bound_and_exported():
+    header = open(os.path.join(ROOT, "include", "cvx_engine.h")).read()
+    declared = set(re.findall(r"\b(cvx_[a-z0-9_]+)\s*\(", header))
+    lib = ctypes.CDLL(os.environ.get("CVX_LIB", os.path.join(ROOT, "computervision.pytorch_amd", "lib", "libcvx_engine.so")))
+    for name in ("cvx_seg_loss_region", "cvx_seg_loss_region_workspace_bytes"):
+        assert name in declared and name in L.PROTOTYPES and hasattr(lib, name)
+    # value only: the partials and sums, no gradient plane; training without a base: plus exactly one plane
+    ws = L.load().cvx_seg_loss_region_workspace_bytes
+    B, nc, H, W = 16, 21, 513, 513
+    small = int(ws(B, nc, H, W, 0, 0, 0, 1))
+    assert 0 < small < 8 * 2 ** 20
+    assert int(ws(B, nc, H, W, 0, 0, 0, 0)) == small + B * nc * H * W * 4
+    assert int(ws(B, nc, H, W, 3, 1, 0, 0)) == small + int(L.load().cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, 1))

@@ -7,6 +7,9 @@ rows 129 x 129 with 24 columns.
              ohem       OHEM thresh 0.7, min_kept 100000 per image (13 launches)
              all        weights + smoothing + OHEM
              ohem_few   OHEM thresh 1e-4: the rank decides, 100000 pixels per image are kept and the gradients of the rest are zeroed
+             dice       the Dice region loss alone, cvx_seg_loss_region without a base (5 launches)
+             ce_dice    cross-entropy + Dice (7 launches: the plain chain's two, the region's four, the adjoint)
+             all_tversky   weights + smoothing + OHEM + focal Tversky (0.3 / 0.7, gamma 0.75) per image
 
 Every arm has its own criterion (workspace) and gradient buffer and the same rows and targets.  The arms are interleaved in blocks; each
 block times `--reps` back-to-back calls of every arm between two device events after a warm-up of every arm, and an arm's figure is the
@@ -14,7 +17,9 @@ median over the blocks of the time per call, with the smallest and the largest b
 move: the fp32 rows and int64 targets read once, the (B, nc, H, W) fp32 per-pixel gradients written once and read once by the adjoint,
 the fp16 row gradients written once; under OHEM a 4-byte key plane and a 4-byte loss plane written once, the keys read by the four
 histogram passes and the masked sum (with the loss plane and the targets), which also writes nc zeros for every valid pixel that is not
-kept (counted from the arm's own kept / valid figures).
+kept (counted from the arm's own kept / valid figures).  A region term reads the rows and the targets once more for its sums and, in
+its gradient pass, a third time; with a base that pass reads and rewrites the gradient plane, without one it writes the plane (then
+the rows and targets are read twice in all, by the two region passes).  The partial sums (3 nc doubles per 2048 pixels) are not counted.
 
     python tools/seg_loss_cost.py --blocks 9 --reps 20 --out profiles/seg_loss_cost.json
 """
@@ -59,6 +64,11 @@ def main():
     arms = {"plain": (SegLoss("ce"), base), "weights": (SegLoss("ce", class_weights=weights, label_smoothing=0.1), base),
             "ohem": (SegLoss("ce", ohem=ohem), mined), "all": (SegLoss("ce", class_weights=weights, label_smoothing=0.1, ohem=ohem), mined),
             "ohem_few": (SegLoss("ce", ohem=dict(thresh=1e-4, min_kept=ohem["min_kept"])), mined)}
+    again = nlow * ld * 4 + npix * 8                       # one more read of the rows and the targets
+    arms.update({"dice": (SegLoss("ce", region=dict(kind="dice", base_weight=0.0)), base + again),
+                 "ce_dice": (SegLoss("ce", region=dict(kind="dice")), base + 2 * again + 2 * npix * nc * 4),
+                 "all_tversky": (SegLoss("ce", class_weights=weights, label_smoothing=0.1, ohem=ohem,
+                                         region=dict(kind="tversky", gamma=0.75, per_image=True)), mined + 2 * again + 2 * npix * nc * 4)})
     runs, values = {}, {}
     for name, (crit, _) in arms.items():
         crit.nc = nc
