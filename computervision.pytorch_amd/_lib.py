@@ -11,8 +11,8 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB") or os.path.join(_HERE, "lib", "libcvx_engine.so")   # CVX_LIB: A/B runs of two builds on one box
-ABI_VERSION = 4
-SEG_OPTS_KEY_OFFSET = 4096      # CVX_SEG_OPTS_KEY_OFFSET: where cvx_seg_loss_opts keeps the OHEM key plane in its workspace
+ABI_VERSION = 5
+SEG_OPTS_KEY_OFFSET = 4096      # CVX_SEG_OPTS_KEY_OFFSET: where cvx_seg_criterion_loss keeps the OHEM key plane in its workspace
 
 
 class CvxError(RuntimeError):
@@ -38,6 +38,20 @@ class OpDesc(C.Structure):
         ("rmean_off", C.c_int64), ("rvar_off", C.c_int64),
         ("lane", C.c_int32), ("flags", C.c_int32),
     ]
+
+
+class SegDims(C.Structure):
+    """cvx_seg_dims"""
+    _fields_ = [(k, C.c_int32) for k in ("ld", "batch", "nc", "ih", "iw", "oh", "ow")]
+
+
+class SegCriterion(C.Structure):
+    """cvx_seg_criterion; base: 0 none, 1 focal, 2 cross-entropy"""
+    _fields_ = [("base", C.c_int32), ("focal_alpha", C.c_float), ("focal_gamma", C.c_float), ("class_weight", C.c_void_p),
+                ("label_smoothing", C.c_float), ("ignore_index", C.c_int64), ("ohem_theta", C.c_float), ("ohem_min_kept", C.c_int64),
+                ("region", C.c_int32), ("base_weight", C.c_double), ("weight", C.c_double), ("alpha", C.c_double), ("beta", C.c_double),
+                ("gamma", C.c_double), ("smooth", C.c_double), ("per_image", C.c_int32), ("skip_absent", C.c_int32),
+                ("region_class_weight", C.c_void_p)]
 
 
 BUF_ACT_F16, BUF_PRED_F32 = 0, 1
@@ -158,17 +172,10 @@ PROTOTYPES = {
     "cvx_ssd_encode_targets": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I32, _F, _F, _F, _P, _P, _P]),
     "cvx_multibox_loss_workspace_bytes": (_I64, [_I32, _I32]),
     "cvx_multibox_loss": (_I32, [_P, _P, _P, _I32, _I32, _I32, _F, _F, _F, _P, _P, _P, _P, _P]),
-    "cvx_seg_loss_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
-    "cvx_seg_loss": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _F, _P, _P, _P, _P, _P]),
-    "cvx_seg_eval_workspace_bytes": (_I64, [_I32, _I32, _I32]),
-    "cvx_seg_eval": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _I64, _P, _P, _P, _P]),
-    "cvx_seg_loss_opts_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
-    "cvx_seg_loss_opts": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _I64, _F, _I64, _F, _P, _P, _P, _P, _P, _P]),
-    "cvx_seg_eval_opts": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _I64, _P, _P, _P, _P]),
-    # Dice / Tversky region loss in the fused criterion chain: replaces F.interpolate + softmax + a one-hot region loss + autograd
-    "cvx_seg_loss_region_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
-    "cvx_seg_loss_region": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _F, _F, _P, _F, _I64, _F, _I64, C.c_double, C.c_double,
-                                    C.c_double, C.c_double, C.c_double, C.c_double, _I32, _I32, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the fused segmentation criterion (focal / cross-entropy with options, plus a Dice / Tversky region term): training and validation
+    "cvx_seg_criterion_workspace_bytes": (_I64, [C.POINTER(SegDims), C.POINTER(SegCriterion), _I32]),
+    "cvx_seg_criterion_loss": (_I32, [_P, C.POINTER(SegDims), _P, C.POINTER(SegCriterion), _F, _P, _P, _P, _P, _P, _P, _P]),
+    "cvx_seg_criterion_eval": (_I32, [_P, C.POINTER(SegDims), _P, C.POINTER(SegCriterion), _P, _P, _P, _P, _P]),
     "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
     "cvx_coco_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),

@@ -17,7 +17,7 @@ __device__ __forceinline__ void bilinear_src(int d, float scale, int in_size, in
 }
 
 // One value from its four taps: along x in both rows, then along y.  The roundings are spelled out -- a product, then one fused
-// multiply-add, at both levels -- because callers compare results to the bit (cvx_seg_eval's arg max against the arg max of
+// multiply-add, at both levels -- because callers compare results to the bit (cvx_seg_criterion_eval's arg max against the arg max of
 // cvx_resize_bilinear_rows_to_nchw's output) and the compiler's own contraction of a * b + c * d differs from one inlining site to the
 // next.  Pinning it is a choice, not a restatement of what each site compiled to before: a site where the compiler had contracted the
 // other product may differ from the previous build by one ulp of the result, inside the tolerances its tests hold it to.

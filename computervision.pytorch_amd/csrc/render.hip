@@ -12,7 +12,7 @@
 //                     spelled out, then every thread walks the list for its pixels that are still open.  A tile no box meets writes
 //                     nothing.
 //   K3 seg_overlay    a thread per 4 pixels of a frame row: nearest source pixel at network size (OpenCV's resizeNN index rule, as the
-//                     letterbox kernel has it), the nc logits there from the four feature rows (bilinear.h: the numbers cvx_seg_eval and
+//                     letterbox kernel has it), the nc logits there from the four feature rows (bilinear.h: the numbers cvx_seg_criterion_eval and
 //                     cvx_resize_bilinear_rows_to_nchw see), arg max (strict >: the lowest class wins a tie), palette, 50/50 blend in
 //                     integers with round-half-even (cv2.addWeighted(a, .5, b, .5, 0) on uint8).  The logit chunk, the arg max and the
 //                     pixel quad are seg_tail.h's, shared with seg_tiles.hip and seg_tta.hip.

@@ -11,7 +11,7 @@
 //                      Mode 0: acc += z, one rounded add per view.  Mode 1: acc += softmax(z); a first pass over the taps leaves every
 //                      view's (max, sum of exp) per pixel in LDS, the second pass accumulates.  Then the arg max (strict >, the lowest
 //                      class wins a tie), the label byte, confusion[target][label] += 1 (LDS histogram or direct atomics, the split of
-//                      cvx_seg_eval) and, in mode 1, the mean probabilities.  The logit chunk, the arg max and the LDS histogram are
+//                      cvx_seg_criterion_eval) and, in mode 1, the mean probabilities.  The logit chunk, the arg max and the LDS histogram are
 //                      seg_tail.h's, shared with render.hip and seg_tiles.hip.
 //                      The y taps of every view are the same for the whole workgroup: worked out once into LDS.  Classes go four at a time
 //                      with the view loop inside, so no nc-sized register array exists.  PX is 4 in mode 0 and 2 in mode 1, where the
@@ -27,7 +27,7 @@ namespace {
 
 constexpr int TTA_THREADS = 256;
 constexpr int MAX_VIEWS = 16;
-constexpr int HIST_LDS_CELLS = 8192;   // nc * nc uint32 cells a workgroup counts in (32 KB, nc <= 90): cvx_seg_eval's split
+constexpr int HIST_LDS_CELLS = 8192;   // nc * nc uint32 cells a workgroup counts in (32 KB, nc <= 90): cvx_seg_criterion_eval's split
 constexpr int YTAP_BYTES = MAX_VIEWS * 16;
 
 struct ViewTable {

@@ -28,6 +28,7 @@ in three launches).  ``SegTrainStep`` is the reference's ``train_loop`` (segment
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Optional
 
@@ -357,17 +358,17 @@ class _SegLossFn(torch.autograd.Function):
 class SegLoss:
     """``FocalLoss()`` / ``nn.CrossEntropyLoss(reduction="mean")`` of ``DeeplabV3PlusA.build_loss`` (segmentation_2d.py:59-64,
     core/loss/focal_loss.py:6-22) on the engine: ``loss = criterion(preds, targets)`` with ``preds = model(images)``.  Value and
-    gradient come from ``cvx_seg_loss`` on the low-resolution rows behind ``preds`` (no autograd tape through the upsampling);
+    gradient come from ``cvx_seg_criterion_loss`` on the low-resolution rows behind ``preds`` (no autograd tape through the upsampling);
     ``loss.backward()`` then runs the engine's backward pass.
 
-    Options of ``"ce"`` (not in the reference; ``cvx_seg_loss_opts``, csrc/loss_seg_opts.hip -- the same fused chain):
+    Options of ``"ce"`` (not in the reference; the same entry, the same fused chain):
     ``class_weights`` (``num_classes`` non-negative floats) and ``label_smoothing`` in [0, 1) are those of
     ``F.cross_entropy(weight=, label_smoothing=, reduction="mean")``; ``ohem=dict(thresh=t, min_kept=m)`` trains on the hard pixels
     only: those whose target probability is below ``t``, and at least the ``m * batch`` pixels with the largest cross-entropy (all
     pixels tied at that rank).  ``last_stats`` is the device tensor (kept pixels, valid pixels, theta_min, sum of target weights) of
-    the last call, ``ohem_keys()`` its per-pixel selection keys.  Without an option the criterion is ``cvx_seg_loss`` as before.
+    the last call, ``ohem_keys()`` its per-pixel selection keys.  Without an option the criterion runs the option-free kernel.
 
-    ``region=dict(kind="dice" | "tversky", ...)`` (see ``seg_region_defaults``; ``cvx_seg_loss_region``, csrc/loss_seg_region.hip) adds a
+    ``region=dict(kind="dice" | "tversky", ...)`` (see ``seg_region_defaults``; the same entry again) adds a
     region loss to either loss type, with or without the options: the value is ``base_weight * base + weight * region`` with ``base``
     what the criterion computes without ``region``.  Over the valid pixels of the batch (``per_image``: of each image, then the mean
     over the images), with p the softmax and y the one-hot target: ``T_c = (I_c + smooth) / (I_c + alpha FP_c + beta FN_c + smooth)``,
@@ -384,7 +385,7 @@ class SegLoss:
         self.mode = 0 if loss_type == "focal" else 1
         self.alpha, self.gamma, self.ignore_index = float(alpha), float(gamma), int(ignore_index)
         self.check_targets = check_targets           # False: skip the host check of the bad-label flag (no sync in the step)
-        self._ws = None
+        self._ws = self._ws_eval = None
         self._dpred = None
         self._bad = None
         self.class_weights = self.ohem = None
@@ -395,7 +396,6 @@ class SegLoss:
         self.has_region = self.region is not None
         self.region_stats = None
         self._region_weights_dev = None
-        self._keys_base = 0
         self.has_options = class_weights is not None or self.label_smoothing != 0.0 or ohem is not None
         if not self.has_options:
             return
@@ -437,117 +437,77 @@ class SegLoss:
         if self.ohem is None or self._keys_shape is None:
             raise L.CvxError("ohem_keys: the criterion has no ohem option, or has not been called yet")
         B, H, W = self._keys_shape
-        o = self._keys_base + L.SEG_OPTS_KEY_OFFSET        # with a region term the base chain's workspace sits behind the region's own
+        o = L.SEG_OPTS_KEY_OFFSET                          # the same offset whatever else the criterion holds
         return self._ws[o:o + B * H * W * 4].view(torch.float32).view(B, H, W)
 
-    def _op_opts(self, lib, rows, target, dims, loss_scale, dpred):
-        B, A, ld, nc, lh, lw, H, W = dims
-        dev = rows.device
-        weights = self.weights_on(dev, nc)
-        need = int(lib.cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, int(self.ohem is not None)))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.last_stats = torch.zeros(4, dtype=torch.float64, device=dev)
-        loss = torch.empty(1, device=dev)
-        theta, k = (self.ohem_theta, self.ohem["min_kept"] * B) if self.ohem is not None else (-1.0, 0)
-        L.check(lib.cvx_seg_loss_opts(L.ptr(rows), ld, B, nc, lh, lw, H, W, L.ptr(target), L.ptr(weights) if weights is not None else None,
-                                      self.label_smoothing, self.ignore_index, theta, k, float(loss_scale), L.ptr(loss), L.ptr(dpred),
-                                      L.ptr(self._bad), L.ptr(self.last_stats), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_loss_opts")
-        self._keys_shape = (B, H, W)
-        return loss
+    def _criterion_struct(self, dev, nc: int, batch: int) -> L.SegCriterion:
+        """``cvx_seg_criterion`` of this criterion for ``nc`` classes and ``batch`` images, its weights on ``dev`` (copied once; their
+        lengths are checked here, where ``nc`` is known).  ``base_weight = 0`` drops the base term and its options with it."""
+        r = self.region
+        with_base = r is None or r["base_weight"] > 0.0
+        c = L.SegCriterion(base=(1 if self.mode == 0 else 2) if with_base else 0, focal_alpha=self.alpha, focal_gamma=self.gamma,
+                           ignore_index=self.ignore_index, ohem_theta=-1.0, region=int(r is not None))
+        if with_base and self.has_options:
+            weights = self.weights_on(dev, nc)
+            c.class_weight = weights.data_ptr() if weights is not None else None
+            c.label_smoothing = self.label_smoothing
+            if self.ohem is not None:
+                c.ohem_theta, c.ohem_min_kept = self.ohem_theta, self.ohem["min_kept"] * batch
+        if r is not None:
+            rw = r["class_weights"]
+            if rw is not None:
+                if rw.numel() != nc:
+                    raise ValueError(f"region class_weights has {rw.numel()} entries for {nc} classes")
+                if self._region_weights_dev is None or self._region_weights_dev.device != dev:
+                    self._region_weights_dev = rw.to(dev)
+                c.region_class_weight = self._region_weights_dev.data_ptr()
+            c.base_weight, c.weight, c.alpha, c.beta, c.gamma, c.smooth = (r[k] for k in ("base_weight", "weight", "alpha", "beta", "gamma", "smooth"))
+            c.per_image, c.skip_absent = int(r["per_image"]), int(r["skip_absent"])
+        return c
 
-    def _region_call(self, lib, rows, target, dims, loss_scale, dpred, base_value, loss):
-        """``cvx_seg_loss_region``: training when ``dpred`` is a tensor, value only (``base_value``: the device float that holds the
-        base's value, or None) when it is None.  The workspace, the flag and the statistics are allocated by the first call of a
-        shape and kept."""
-        B, A, ld, nc, lh, lw, H, W = dims
-        dev, r = rows.device, self.region
-        value_only = dpred is None
-        with_base = base_value is not None if value_only else r["base_weight"] > 0.0
-        base = 0 if not with_base else (3 if self.has_options else (1 if self.mode == 0 else 2))
-        weights = self.weights_on(dev, nc) if base == 3 else None
-        rw = r["class_weights"]
-        if rw is not None:
-            if rw.numel() != nc:
-                raise ValueError(f"region class_weights has {rw.numel()} entries for {nc} classes")
-            if self._region_weights_dev is None or self._region_weights_dev.device != dev:
-                self._region_weights_dev = rw.to(dev)
-        ohem = base == 3 and self.ohem is not None and not value_only
-        G = B if r["per_image"] else 1
-        need = int(lib.cvx_seg_loss_region_workspace_bytes(B, nc, H, W, base, int(ohem), int(r["per_image"]), int(value_only)))
+    def _ensure_buffers(self, lib, dev, dims: L.SegDims, crit: L.SegCriterion, for_eval: bool = False) -> torch.Tensor:
+        """The workspace of this call (training and validation each keep their own), with the bad-label flag, ``last_stats`` (a
+        criterion with options or a region term) and ``region_stats`` (one with a region term) next to it: allocated by the first call of a shape and kept."""
+        need = int(lib.cvx_seg_criterion_workspace_bytes(C.byref(dims), C.byref(crit), int(for_eval)))
         if need <= 0:
-            raise L.CvxError("cvx_seg_loss_region_workspace_bytes: bad sizes")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            raise L.CvxError("cvx_seg_criterion_workspace_bytes: bad sizes, or a criterion the library refuses")
+        name = "_ws_eval" if for_eval else "_ws"
+        ws = getattr(self, name)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            setattr(self, name, ws)
         if self._bad is None or self._bad.device != dev:
             self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        if self.last_stats is None or self.last_stats.device != dev:
+        if (self.has_options or self.has_region) and (self.last_stats is None or self.last_stats.device != dev):   # zeros without an option
             self.last_stats = torch.zeros(4, dtype=torch.float64, device=dev)
-        if self.region_stats is None or self.region_stats.device != dev or tuple(self.region_stats.shape) != (G, nc, 4):
-            self.region_stats = torch.zeros(G, nc, 4, dtype=torch.float64, device=dev)
-        theta, k = (self.ohem_theta, self.ohem["min_kept"] * B) if ohem else (-1.0, 0)
-        with torch.cuda.device(dev):
-            L.check(lib.cvx_seg_loss_region(
-                L.ptr(rows), ld, B, nc, lh, lw, H, W, L.ptr(target), base, self.alpha, self.gamma, L.ptr(weights) if weights is not None else None,
-                self.label_smoothing, self.ignore_index, theta, k, r["base_weight"] if with_base else 0.0, r["weight"], r["alpha"], r["beta"],
-                r["gamma"], r["smooth"], int(r["per_image"]), int(r["skip_absent"]), L.ptr(self._region_weights_dev) if rw is not None else None,
-                float(loss_scale), L.ptr(base_value) if base_value is not None else None, L.ptr(loss), L.ptr(dpred) if dpred is not None else None,
-                L.ptr(self._bad), L.ptr(self.last_stats), L.ptr(self.region_stats), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_loss_region")
-        if ohem:
-            self._keys_shape = (B, H, W)
-            self._keys_base = need - int(lib.cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, 1))
-
-    def region_value(self, rows: torch.Tensor, target: torch.Tensor, hw, loss_slot: torch.Tensor, nc=None):
-        """Validation: ``loss_slot`` (one float32 on the rows' device) holds the base's value of the batch, e.g. what ``cvx_seg_eval``
-        wrote, and receives ``base_weight * base + weight * region``.  No gradient plane, no adjoint, nothing read back."""
-        if not self.has_region:
-            raise L.CvxError("region_value: the criterion has no region term")
-        B, A, ld = rows.shape
-        nc = nc or getattr(self, "nc", None) or ld
-        target = target.to(device=rows.device, dtype=torch.long).contiguous()
-        dims = (B, A, ld, nc, int(hw[0]), int(hw[1]), int(target.shape[1]), int(target.shape[2]))
-        base_value = loss_slot if self.region["base_weight"] > 0.0 else None
-        self._region_call(L.load(), rows, target, dims, 1.0, None, base_value, loss_slot)
+        shape = (dims.batch if crit.per_image else 1, dims.nc, 4)
+        if self.has_region and (self.region_stats is None or self.region_stats.device != dev or tuple(self.region_stats.shape) != shape):
+            self.region_stats = torch.zeros(shape, dtype=torch.float64, device=dev)
+        return ws
 
     def op(self, rows: torch.Tensor, target: torch.Tensor, hw, loss_scale: float, dpred: Optional[torch.Tensor] = None,
            check: Optional[bool] = None):
         """rows (B, lh*lw, ld) fp32, target (B, H, W) int64, hw = (lh, lw) -> (loss (1,), dpred (B, lh*lw, ld) fp16)."""
         if rows.device.type != "cuda":
             raise L.CvxError("SegLoss runs on an MI355X only (there is no CPU path)")
-        lib = L.load()
+        lib, dev = L.load(), rows.device
         B, A, ld = rows.shape
-        lh, lw = hw
         if target.dim() != 3 or target.shape[0] != B:
             raise ValueError("targets must have shape (B, H, W)")
-        H, W = int(target.shape[1]), int(target.shape[2])
         nc = getattr(self, "nc", None) or ld
-        target = target.to(device=rows.device, dtype=torch.long).contiguous()
-        if self.has_region:
-            if dpred is None:
-                dpred = torch.empty(B, A, ld, dtype=torch.float16, device=rows.device)
-            loss = torch.empty(1, device=rows.device)     # as the other two paths: a block of the caching allocator, no device allocation
-            self._region_call(lib, rows, target, (B, A, ld, nc, lh, lw, H, W), loss_scale, dpred, None, loss)
-            if (self.check_targets if check is None else check) and self.bad_targets():
-                raise L.CvxError("SegLoss: a target label is neither ignore_index nor in [0, num_classes)")
-            return loss, dpred
-        if self.has_options:
-            if dpred is None:
-                dpred = torch.empty(B, A, ld, dtype=torch.float16, device=rows.device)
-            loss = self._op_opts(lib, rows, target, (B, A, ld, nc, lh, lw, H, W), loss_scale, dpred)
-            if (self.check_targets if check is None else check) and self.bad_targets():
-                raise L.CvxError("SegLoss: a target label is neither ignore_index nor in [0, num_classes)")
-            return loss, dpred
-        need = int(lib.cvx_seg_loss_workspace_bytes(B, nc, H, W))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != rows.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=rows.device)
-            self._bad = torch.zeros(1, dtype=torch.int32, device=rows.device)
+        target = target.to(device=dev, dtype=torch.long).contiguous()
+        dims = L.SegDims(ld, B, nc, int(hw[0]), int(hw[1]), int(target.shape[1]), int(target.shape[2]))
+        crit = self._criterion_struct(dev, nc, B)
+        ws = self._ensure_buffers(lib, dev, dims, crit)
         if dpred is None:
-            dpred = torch.empty(B, A, ld, dtype=torch.float16, device=rows.device)
-        loss = torch.empty(1, device=rows.device)
-        L.check(lib.cvx_seg_loss(L.ptr(rows), ld, B, nc, lh, lw, H, W, L.ptr(target), self.mode, self.alpha, self.gamma, self.ignore_index,
-                                 float(loss_scale), L.ptr(loss), L.ptr(dpred), L.ptr(self._bad), L.ptr(self._ws), L.stream_ptr(rows.device)),
-                "cvx_seg_loss")
+            dpred = torch.empty(B, A, ld, dtype=torch.float16, device=dev)
+        loss = torch.empty(1, device=dev)                   # a block of the caching allocator, no device allocation
+        with torch.cuda.device(dev):
+            L.check(lib.cvx_seg_criterion_loss(L.ptr(rows), C.byref(dims), L.ptr(target), C.byref(crit), float(loss_scale), L.ptr(loss), L.ptr(dpred),
+                                               L.ptr(self._bad), L.ptr(self.last_stats), L.ptr(self.region_stats), L.ptr(ws), L.stream_ptr(dev)),
+                    "cvx_seg_criterion_loss")
+        if crit.ohem_theta >= 0.0:
+            self._keys_shape = (B, dims.oh, dims.ow)
         if (self.check_targets if check is None else check) and self.bad_targets():
             raise L.CvxError("SegLoss: a target label is neither ignore_index nor in [0, num_classes)")
         return loss, dpred
@@ -603,7 +563,7 @@ def seg_region_defaults(kind: str = "dice", **kw) -> dict:
 
 def seg_class_weights(counts, scheme: str = "median_freq") -> torch.Tensor:
     """Class weights for ``SegLoss(class_weights=)`` from per-class pixel counts (e.g. the row sums of the confusion matrix of one
-    ``cvx_seg_eval`` pass over the training loader).  With f the class frequency among the counted pixels: ``"median_freq"`` gives
+    ``cvx_seg_criterion_eval`` pass over the training loader).  With f the class frequency among the counted pixels: ``"median_freq"`` gives
     median(f over the classes that occur) / f_c, ``"enet"`` 1 / ln(1.02 + f_c); a class with count 0 gets weight 0.  Host only."""
     counts = torch.as_tensor(counts, dtype=torch.float64).reshape(-1)
     if scheme not in ("median_freq", "enet"):
@@ -619,7 +579,7 @@ def seg_class_weights(counts, scheme: str = "median_freq") -> torch.Tensor:
 
 class SegTrainStep(EngineTrainStep):
     """One optimisation step of the reference's ``DeeplabV3PlusTrainer.train_loop`` (segmentation_trainer.py:114-131:
-    zero_grad -> forward -> criterion -> backward -> Adam under AMP) as C-ABI calls: engine forward (training), ``cvx_seg_loss``,
+    zero_grad -> forward -> criterion -> backward -> Adam under AMP) as C-ABI calls: engine forward (training), ``cvx_seg_criterion_loss``,
     engine backward, [gradient all-reduce over RCCL], fused Adam with the inf/nan check of GradScaler.step.  Returns the loss (1,).
     Data parallel: the flat gradient arena is summed over the ranks in a few large slices on a side stream after the backward
     pass (the mean's 1/world is folded into Adam); BatchNorm statistics stay per rank, as in the reference."""

@@ -5,7 +5,7 @@ as ONE HIP launch per batch (``csrc/seg_pipeline.hip``: ``cvx_seg_pipeline``).
     validation  ToTensor -> RGB2idx -> Resize((H, W)) -> Normalize                                               (:280-291)
 
 A batch of uint8 HWC pictures and their label pictures (uint8 ``(h, w, 3)`` colour coded, or uint8 ``(h, w)`` class indices) already in
-device memory becomes the fp32 ``(B, 3, H, W)`` normalised batch and the int64 ``(B, H, W)`` targets ``SegTrainStep`` / ``cvx_seg_loss``
+device memory becomes the fp32 ``(B, 3, H, W)`` normalised batch and the int64 ``(B, H, W)`` targets ``SegTrainStep`` / ``cvx_seg_criterion_loss``
 take.  The random draws are made on the host by ``draw_seg_params`` in the reference's order -- per item the crop origin ``i``, ``j`` from a
 ``torch.Generator`` (``RandomCrop.get_params``), then the flip from a ``random.Random`` (``RandomHorizontalFlip``) --; the job table and the
 colour table go up in ONE pinned copy per batch, and nothing is read back.  There is no CPU fallback: pictures that are not on a GPU raise

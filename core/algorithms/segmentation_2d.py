@@ -204,7 +204,7 @@ class DeeplabV3PlusA(FramePredictor):
         ``results_out_root/DeepLabV3Plus/DeepLabV3Plus_<dataset>_<time>.txt`` as four lines (Overall Acc, Mean Acc, FreqW Acc, Mean IoU).
         Reading VOC from disk is outside the hot path: ``dataloader`` is a ``DeviceSegLoader`` over the pictures with
         ``DeviceSegAugmenter(crop_hw=cfg.arch.crop_size, base_size=max(cfg.arch.input_size[1:]), colormap=voc_colormap(), train=False)``.
-        Each batch is one engine forward and one ``cvx_seg_eval`` launch; the host waits once, at the end.  ``scales`` / ``flip`` /
+        Each batch is one engine forward and one ``cvx_seg_criterion_eval`` launch; the host waits once, at the end.  ``scales`` / ``flip`` /
         ``fuse`` select test-time augmentation (``predict_labels``): each batch is then one forward per scale and
         one ``cvx_seg_fuse`` launch, still with one host wait at the end.  Returns the path written."""
         from core.trainer.segmentation_trainer import SegmentationMetrics, fused_evaluation, fused_evaluation_tta

@@ -1,16 +1,17 @@
 """``DeeplabV3PlusTrainer`` -- registered as ``trainer_deeplabv3plus`` like the reference's
 (core/trainer/segmentation_trainer.py:21-159).  ``train_loop`` keeps the reference's step semantics (zero_grad -> forward ->
 criterion -> backward -> Adam under AMP, :114-131) and runs it as the engine's fused step (``SegTrainStep``: engine forward,
-``cvx_seg_loss``, engine backward, fused Adam with GradScaler's skip-on-overflow); with ``torch.distributed`` initialised the step
+``cvx_seg_criterion_loss``, engine backward, fused Adam with GradScaler's skip-on-overflow); with ``torch.distributed`` initialised the step
 also sums the gradients over the ranks (RCCL).  ``evaluate_loop`` reports the reference's numbers (loss, Overall / Mean / FreqW
 accuracy, Mean IoU, :133-159) from a confusion matrix accumulated on the device.  The VOC / Cityscapes / SBD readers are outside
 the hot path: a dataloader is injected, or seeded synthetic batches stand in.  The input side is the device
 pipeline: ``dataloader=`` / ``val_dataloader=`` take a ``DeviceSegLoader`` (computervision.pytorch_amd/seg_pipeline.py, the reference's
 segmentation transforms as one launch per batch).  With ``val_dataloader=`` given, ``evaluate_loop`` is the fused pass: engine forward to
-the low-resolution logits rows, then ``cvx_seg_eval`` (upsampling + arg max + confusion matrix + criterion in one launch, no
+the low-resolution logits rows, then ``cvx_seg_criterion_eval`` (upsampling + arg max + confusion matrix + criterion in one launch, no
 full-resolution logits, no gradient), one host synchronisation after the last batch; without it the unfused loop runs on the training
 loader as before.
 """
+import ctypes
 from typing import Dict, List
 
 import torch
@@ -46,14 +47,13 @@ class SyntheticSegmentationLoader:
 
 class SegmentationMetrics:
     """core/metrics/seg_metrics.py:4-44 with the confusion matrix kept on the device: ``add_batch`` takes predictions (one bincount per
-    batch, into the float64 ``confusion_matrix``), ``add_rows`` the engine's low-resolution logits rows (``cvx_seg_eval``: one launch, into
+    batch, into the float64 ``confusion_matrix``), ``add_rows`` the engine's low-resolution logits rows (``cvx_seg_criterion_eval``: one launch, into
     the exact int64 ``counts``).  ``fold()`` adds ``counts`` into ``confusion_matrix`` and clears them; ``get_results`` folds first."""
 
     def __init__(self, num_classes, device="cpu"):
         self.num_classes = num_classes
         self.confusion_matrix = torch.zeros(num_classes, num_classes, dtype=torch.float64, device=device)
         self.counts = None                  # (nc, nc) int64 on the rows' device, created by the first add_rows
-        self._ws = None
 
     def reset(self):
         self.confusion_matrix.zero_()
@@ -78,10 +78,10 @@ class SegmentationMetrics:
     def add_rows(self, rows, targets, hw, criterion, loss_slot):
         """One validation batch from the logits rows ``(B, lh*lw, ld)`` fp32 of ``model.forward_rows`` and the targets ``(B, H, W)`` int64:
         ``confusion[target][argmax of the upsampled logits] += 1`` and ``criterion``'s (a ``SegLoss``) value of the batch into
-        ``loss_slot``, a one-element float32 view on the rows' device.  A criterion with options (class weights, label smoothing) goes
-        through ``cvx_seg_eval_opts``: the weighted, smoothed value over all valid pixels, the same matrix; its OHEM setting is not
-        applied in evaluation.  A criterion with a region term (``SegLoss(region=)``) then runs ``cvx_seg_loss_region`` in its value-only
-        mode (no gradient plane, no adjoint), so that the slot holds ``base_weight * base + weight * region`` of the batch; the matrix is the
+        ``loss_slot``, a one-element float32 view on the rows' device, in one ``cvx_seg_criterion_eval`` call.  A criterion with options
+        (class weights, label smoothing) gives the weighted, smoothed value over all valid pixels and the same matrix; its OHEM setting
+        is not applied in evaluation.  With a region term (``SegLoss(region=)``) the value-only region chain follows (no gradient plane,
+        no adjoint), so that the slot holds ``base_weight * base + weight * region`` of the batch; the matrix is the
         eval launch's.  Asynchronous: nothing is read back."""
         if not (torch.is_tensor(rows) and rows.is_cuda):
             raise L.CvxError("SegmentationMetrics.add_rows runs on an MI355X only (there is no CPU path); add_batch takes host predictions")
@@ -93,26 +93,16 @@ class SegmentationMetrics:
             raise ValueError("rows must be contiguous fp32 (B, lh*lw, ld) and targets (B, H, W)")
         if loss_slot.dtype != torch.float32 or loss_slot.numel() != 1 or loss_slot.device != dev:
             raise ValueError("loss_slot: one float32 element on the rows' device")
-        H, W = int(targets.shape[1]), int(targets.shape[2])
         targets = targets.to(device=dev, dtype=torch.long).contiguous()
         if self.counts is None or self.counts.device != dev:
             self.counts = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64, device=dev)
-        need = int(lib.cvx_seg_eval_workspace_bytes(B, H, W))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        if getattr(criterion, "has_options", False):       # weighted / smoothed cross-entropy over all valid pixels; OHEM is a training device
-            weights = criterion.weights_on(dev, self.num_classes)
-            with torch.cuda.device(dev):
-                L.check(lib.cvx_seg_eval_opts(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets),
-                                              L.ptr(weights) if weights is not None else None, criterion.label_smoothing, criterion.ignore_index,
-                                              L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws), L.stream_ptr(dev)), "cvx_seg_eval_opts")
-        else:
-            with torch.cuda.device(dev):
-                L.check(lib.cvx_seg_eval(L.ptr(rows), ld, B, self.num_classes, lh, lw, H, W, L.ptr(targets), criterion.mode, criterion.alpha,
-                                         criterion.gamma, criterion.ignore_index, L.ptr(self.counts), L.ptr(loss_slot), L.ptr(self._ws),
-                                         L.stream_ptr(dev)), "cvx_seg_eval")
-        if getattr(criterion, "has_region", False):        # the slot holds the base's value: base_weight * base + weight * region replaces it
-            criterion.region_value(rows, targets, (lh, lw), loss_slot, nc=self.num_classes)
+        dims = L.SegDims(ld, B, self.num_classes, lh, lw, int(targets.shape[1]), int(targets.shape[2]))
+        crit = criterion._criterion_struct(dev, self.num_classes, B)
+        ws = criterion._ensure_buffers(lib, dev, dims, crit, for_eval=True)
+        with torch.cuda.device(dev):
+            L.check(lib.cvx_seg_criterion_eval(L.ptr(rows), ctypes.byref(dims), L.ptr(targets), ctypes.byref(crit), L.ptr(self.counts),
+                                               L.ptr(loss_slot), L.ptr(criterion.region_stats), L.ptr(ws), L.stream_ptr(dev)),
+                    "cvx_seg_criterion_eval")
 
     def add_batch(self, predictions, gts):
         predictions, gts = torch.as_tensor(predictions).reshape(-1), torch.as_tensor(gts).reshape(-1)
@@ -142,7 +132,7 @@ class DeeplabV3PlusTrainer(EngineTrainer):
             # ``device`` attribute is taken at its word, and host batches it yields are moved by evaluate_loop
             on = [torch.device(device)] + ([torch.device(val_dataloader.device)] if hasattr(val_dataloader, "device") else [])
             if any(d.type != "cuda" for d in on):
-                raise L.CvxError("val_dataloader= selects the fused evaluation (cvx_seg_eval), which runs on an MI355X only: the trainer's "
+                raise L.CvxError("val_dataloader= selects the fused evaluation (cvx_seg_criterion_eval), which runs on an MI355X only: the trainer's "
                                  f"device and the loader's (here {', '.join(str(d) for d in on)}) must be GPUs, "
                                  "e.g. DeviceSegLoader(..., device='cuda')")
         super().__init__(cfg, device, dataloader, val_dataloader)

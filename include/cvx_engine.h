@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define CVX_ABI_VERSION 4
+#define CVX_ABI_VERSION 5
 
 const char* cvx_last_error(void);
 int cvx_abi_version(void);
@@ -481,88 +481,80 @@ int cvx_l2norm_nhwc(const void* x_f16, const float* weight, int32_t batch, int32
  * Replaces: F.interpolate(x, size=input_shape, mode="bilinear", align_corners=False), core/models/deeplabv3plus.py:147. */
 int cvx_resize_bilinear_rows_to_nchw(const float* rows_f32, int32_t ld, int32_t batch, int32_t c, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                                      float* out_nchw, void* hip_stream);
-/* Segmentation loss with its gradient, for the DeepLabv3+ step.  rows: the engine's fp32 logits rows (batch, ih*iw, ld) at decoder
- * resolution; target: (batch, oh, ow) int64 class indices at label resolution (= the network input size).  Per label pixel the nc
- * logits are interpolated bilinearly (align_corners = False, deeplabv3plus.py:147), then
- *   mode 0: focal loss  alpha * (1 - pt)^gamma * ce, pt = exp(-ce), mean over ALL batch*oh*ow pixels (focal_loss.py:14-22;
- *           ignored pixels contribute 0 to the sum and count in the mean, like the reference's .mean());
- *   mode 1: cross-entropy, mean over the non-ignored pixels (nn.CrossEntropyLoss(reduction="mean"), segmentation_2d.py:61).
- * loss_out: 1 float (device).  dpred: (batch, ih*iw, ld) fp16 = loss_scale * dLoss/drows (columns nc..ld-1 zero) -- the operand of
- * cvx_engine_backward.  bad_target: 1 int32 (device), set non-zero when a label is neither ignore_index nor in [0, nc) (torch
- * raises a device assert there; the pixel is skipped).  workspace: cvx_seg_loss_workspace_bytes() bytes.  Asynchronous on hip_stream.
+/* The fused segmentation criterion of the DeepLabv3+ step: loss = base (no region term), or base_weight * base + weight * region.
+ * Both structs are plain host data, passed by pointer and read before the call returns.
+ * rows: the engine's fp32 logits rows (batch, ih*iw, ld) at decoder resolution; target: (batch, oh, ow) int64 class indices at label
+ * resolution (= the network input size).  Per label pixel the nc logits are interpolated bilinearly (align_corners = False,
+ * deeplabv3plus.py:147) with the device function cvx_resize_bilinear_rows_to_nchw uses (bit-identical values): z_c, lse their
+ * log-sum-exp, p their softmax, t the target.  Valid pixels: t != ignore_index and t in [0, nc).
+ * base 1, focal loss: alpha * (1 - pt)^gamma * ce, ce = lse - z_t, pt = exp(-ce), mean over ALL batch*oh*ow pixels (focal_loss.py:14-22;
+ *   ignored pixels contribute 0 to the sum and count in the mean, like the reference's .mean()).
+ * base 2, cross-entropy: mean over the valid pixels (nn.CrossEntropyLoss(reduction="mean"), segmentation_2d.py:61).  Its options, in use
+ *   when class_weight != NULL || label_smoothing > 0 || ohem_theta >= 0 (not in the reference), with w = class_weight (nc floats on
+ *   the device; null: all ones), W = sum_c w_c, eps = label_smoothing in [0, 1):
+ *     l    = (1 - eps) w_t (lse - z_t) + (eps / nc) sum_c w_c (lse - z_c)
+ *     loss = sum_{i in S} l_i / sum_{i in S} w_{t_i}, S = the valid pixels -- torch's F.cross_entropy(weight=, ignore_index=,
+ *            label_smoothing=, reduction="mean"); an empty S gives nan and a zero gradient.
+ *   OHEM (ohem_theta >= 0; a negative value turns it off): key = fp32 max(lse - z_t, 0), ohem_theta = fp32(-ln thresh),
+ *   K = ohem_min_kept >= 1 counted over the whole batch, theta_min = the K-th largest key of the valid pixels (-inf when there are fewer
+ *   than K); S = the valid pixels with key > ohem_theta or key >= theta_min.  Ties at theta_min are all kept.  The selection is a radix
+ *   select over the keys' bit patterns: no sort, integer atomics only.  Without an option the value and the gradient are those of the
+ *   option-free kernel to the bit (unit weights and eps 0 through the options kernel give the same bits, too).
+ * base 0: no base term; takes region != 0 and base_weight 0 (and a base term takes base_weight > 0 when there is a region term).
+ * region != 0, the Dice / Tversky / focal-Tversky loss over the valid pixels of a group -- the batch, or each image when per_image != 0 --
+ *   with y the one-hot target:
+ *     I_c = sum p_c y_c, P_c = sum p_c, Y_c = sum y_c, D_c = (1 - alpha - beta) I_c + alpha P_c + beta Y_c + smooth,
+ *     T_c = (I_c + smooth) / D_c (1 when D_c == 0), L_c = (1 - T_c)^gamma, group loss = sum_c m_c v_c L_c / sum_c m_c v_c (0 when that is 0),
+ *     m_c = [Y_c > 0] when skip_absent != 0, else 1; v = region_class_weight (nc floats on the device; null: ones);
+ *     region = mean of the group losses.  alpha = beta = 0.5 is the Dice loss, gamma != 1 the focal Tversky loss.  nc <= 1024.
+ *   OHEM selects pixels for the base term only.
+ * Every floating-point sum runs in a fixed order (per-workgroup trees, then the partials in index order; no floating-point atomics): two
+ * calls give the same bits.
+ * cvx_seg_criterion_loss: loss_out: 1 float (device).  dpred: (batch, ih*iw, ld) fp16 = loss_scale * dLoss/drows (columns nc..ld-1 zero) --
+ *   the operand of cvx_engine_backward.  bad_target: 1 int32 (device), set non-zero when a label is neither ignore_index nor in [0, nc)
+ *   (torch raises a device assert there; the pixel is skipped).  stats_out: 4 doubles (device), written by base 2 with options: pixels in
+ *   S, valid pixels, theta_min, the denominator sum w_t (may be null otherwise).  region_stats_out: (G, nc, 4) doubles (device),
+ *   G = per_image ? batch : 1: I, P, Y, T (may be null without a region term).  Launches: 3 (13 under OHEM), plus 4 for a region term;
+ *   5 for a region term alone.
+ * cvx_seg_criterion_eval, one validation batch: the arg max of the interpolated logits is taken (the lowest class wins a tie, like
+ *   torch.argmax) and confusion[target * nc + argmax] += 1 for targets in [0, nc); other targets are left out, as SegmentationMetrics
+ *   does.  confusion: (nc, nc) int64 (device) that ACCUMULATES over calls -- the caller zeroes it.  loss_out: the criterion's value of this
+ *   batch over all valid pixels (OHEM is never applied in evaluation; a label that is neither ignore_index nor a class contributes
+ *   nothing); with a region term the value-only region chain follows and loss_out holds base_weight * base + weight * region (with
+ *   base 0 the pass still counts the matrix).  No gradient and no full-resolution tensor is written.  A workgroup counts in LDS for
+ *   nc <= 90 (nc * nc uint32 cells, 32 KB) and adds its non-zero cells to the matrix with 64-bit atomics; larger nc goes to the matrix
+ *   directly.
+ * workspace: cvx_seg_criterion_workspace_bytes(dims, crit, for_eval) bytes (0: bad arguments).  After a training call with OHEM the fp32
+ * keys of that call, (batch, oh, ow) with -1 at pixels that are not valid, start CVX_SEG_OPTS_KEY_OFFSET bytes into it, whatever else
+ * the criterion holds.  Asynchronous on hip_stream, no host read.
  * Replaces: F.interpolate + FocalLoss.forward / nn.CrossEntropyLoss + loss.backward() down to the classifier's output,
- * core/trainer/segmentation_trainer.py:121-130. */
-int64_t cvx_seg_loss_workspace_bytes(int32_t batch, int32_t nc, int32_t oh, int32_t ow);
-int cvx_seg_loss(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                 const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, float loss_scale, float* loss_out,
-                 void* dpred_f16, int32_t* bad_target, void* workspace, void* hip_stream);
-/* Segmentation evaluation of one batch in one pass, for the DeepLabv3+ validation loop.  rows, target, mode, alpha, gamma,
- * ignore_index as for cvx_seg_loss.  Per label pixel the nc logits are interpolated with the device function
- * cvx_resize_bilinear_rows_to_nchw uses (bit-identical values), their arg max is taken (the lowest class wins a tie, like torch.argmax) and
- * confusion[target * nc + argmax] += 1 for targets in [0, nc); other targets are left out, as SegmentationMetrics does.  confusion:
- * (nc, nc) int64 (device) that ACCUMULATES over calls -- the caller zeroes it.  loss_out: 1 float (device) = the criterion's value of
- * this batch, cvx_seg_loss's definitions (a target that is neither ignore_index nor a class contributes nothing).  No gradient and no
- * full-resolution tensor is written.  A workgroup counts in LDS for nc <= 90 (nc * nc uint32 cells, 32 KB) and adds its non-zero cells
- * to the matrix with 64-bit atomics; larger nc goes to the matrix directly.  workspace: cvx_seg_eval_workspace_bytes() bytes.
- * Asynchronous on hip_stream.
- * Replaces: F.interpolate + criterion(preds, targets) + torch.argmax(preds, dim=1) + SegmentationMetrics.add_batch,
- * core/trainer/segmentation_trainer.py:141-150 and core/algorithms/segmentation_2d.py:154-157. */
-int64_t cvx_seg_eval_workspace_bytes(int32_t batch, int32_t oh, int32_t ow);
-int cvx_seg_eval(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                 const int64_t* target, int32_t mode, float alpha, float gamma, int64_t ignore_index, int64_t* confusion, float* loss_out,
-                 void* workspace, void* hip_stream);
-/* Cross-entropy with class weights, label smoothing and online hard example mining (OHEM) for the DeepLabv3+ step: cvx_seg_loss's
- * mode 1 with options, same rows, target, dpred, bad_target and loss_scale.  With z_c the interpolated logits of a label pixel, lse their
- * log-sum-exp, t the target, w = class_weight (nc floats on the device; null: all ones), W = sum_c w_c, eps = label_smoothing in [0, 1):
- *   l    = (1 - eps) w_t (lse - z_t) + (eps / nc) sum_c w_c (lse - z_c)
- *   loss = sum_{i in S} l_i / sum_{i in S} w_{t_i}, S = the valid pixels (target != ignore_index and in [0, nc)) -- torch's
- *          F.cross_entropy(weight=, ignore_index=, label_smoothing=, reduction="mean"); an empty S gives nan and a zero gradient.
- * OHEM (ohem_theta >= 0; a negative value turns it off): key = fp32 max(lse - z_t, 0), ohem_theta = fp32(-ln thresh),
- * K = ohem_min_kept >= 1 counted over the whole batch, theta_min = the K-th largest key of the valid pixels (-inf when there are fewer
- * than K); S = the valid pixels with key > ohem_theta or key >= theta_min.  Ties at theta_min are all kept.  The selection is a radix
- * select over the keys' bit patterns: no sort, integer atomics only; every floating-point sum runs in a fixed order, so two calls give
- * the same bits.  stats_out: 4 doubles (device): pixels in S, valid pixels, theta_min, the denominator sum w_t.  With class_weight null,
- * eps 0 and OHEM off, loss_out and dpred are cvx_seg_loss's mode 1 to the bit.  workspace: cvx_seg_loss_opts_workspace_bytes() bytes
- * (ohem != 0: with the key planes); under OHEM the fp32 keys of the last call, (batch, oh, ow) with -1 at pixels that are not valid,
- * start CVX_SEG_OPTS_KEY_OFFSET bytes into it.  Asynchronous on hip_stream.  Not in the reference: its build_loss has no options. */
+ * core/trainer/segmentation_trainer.py:121-130; F.interpolate + criterion(preds, targets) + torch.argmax(preds, dim=1) +
+ * SegmentationMetrics.add_batch, segmentation_trainer.py:141-150 and core/algorithms/segmentation_2d.py:154-157. */
 #define CVX_SEG_OPTS_KEY_OFFSET 4096
-int64_t cvx_seg_loss_opts_workspace_bytes(int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t ohem);
-int cvx_seg_loss_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                      const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, float ohem_theta,
-                      int64_t ohem_min_kept, float loss_scale, float* loss_out, void* dpred_f16, int32_t* bad_target, double* stats_out,
-                      void* workspace, void* hip_stream);
-/* cvx_seg_eval with cvx_seg_loss_opts's class_weight and label_smoothing: loss_out is the weighted, smoothed cross-entropy over all valid
- * pixels of the batch (OHEM is never applied in evaluation); the confusion matrix is cvx_seg_eval's, count for count.
- * workspace: cvx_seg_eval_workspace_bytes() bytes.  Asynchronous on hip_stream. */
-int cvx_seg_eval_opts(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                      const int64_t* target, const float* class_weight, float label_smoothing, int64_t ignore_index, int64_t* confusion,
-                      float* loss_out, void* workspace, void* hip_stream);
-/* Dice / Tversky / focal-Tversky region loss added to the fused criterion chain of the DeepLabv3+ step:
- *   loss = base_weight * base + weight * region.
- * base: 0 none (base_weight must be 0), 1 cvx_seg_loss mode 0 (focal_alpha, focal_gamma), 2 cvx_seg_loss mode 1, 3 cvx_seg_loss_opts
- * (class_weight, label_smoothing, ohem_theta, ohem_min_kept; base_stats_out = its 4 doubles); the base's kernels run unchanged, its OHEM
- * selects pixels for the base term only.  region, over the valid pixels (cvx_seg_loss's rule) of a group -- the batch, or each image when
- * per_image != 0 -- with p = softmax of the interpolated logits and y the one-hot target:
- *   I_c = sum p_c y_c, P_c = sum p_c, Y_c = sum y_c, D_c = (1 - alpha - beta) I_c + alpha P_c + beta Y_c + smooth,
- *   T_c = (I_c + smooth) / D_c (1 when D_c == 0), L_c = (1 - T_c)^gamma, group loss = sum_c m_c v_c L_c / sum_c m_c v_c (0 when that is 0),
- *   m_c = [Y_c > 0] when skip_absent != 0, else 1; v = region_class_weight (nc floats on the device; null: ones);
- *   region = mean of the group losses.  alpha = beta = 0.5 is the Dice loss, gamma != 1 the focal Tversky loss.
- * Training (dpred_f16 not null): dpred = loss_scale * d loss / d rows as for cvx_seg_loss; base_value is not read.  Value only (dpred_f16
- * null): no base chain, no gradient plane, no adjoint; base_value (1 device float, e.g. what cvx_seg_eval wrote; may be loss_out itself;
- * null: no base term) is the base's value and the base arguments are not read.  region_stats_out: (G, nc, 4) doubles on the device,
- * G = per_image ? batch : 1: I, P, Y, T.  Every floating-point sum runs in a fixed order (per-workgroup trees, then the partials in index
- * order; no floating-point atomics): two calls give the same bits.  nc <= 1024.  workspace: cvx_seg_loss_region_workspace_bytes() bytes
- * with the same base, ohem (base 3 with OHEM), per_image and value_only.  Asynchronous on hip_stream, no host read.
- * Replaces: F.interpolate + softmax + a one-hot Dice / Tversky loss (e.g. segmentation_models_pytorch's DiceLoss / TverskyLoss) added to
- * the criterion + loss.backward() down to the classifier's output; not in the reference, whose build_loss has no region loss. */
-int64_t cvx_seg_loss_region_workspace_bytes(int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t base, int32_t ohem, int32_t per_image,
-                                            int32_t value_only);
-int cvx_seg_loss_region(const float* rows_f32, int32_t ld, int32_t batch, int32_t nc, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                        const int64_t* target, int32_t base, float focal_alpha, float focal_gamma, const float* class_weight, float label_smoothing,
-                        int64_t ignore_index, float ohem_theta, int64_t ohem_min_kept, double base_weight, double weight, double alpha, double beta,
-                        double gamma, double smooth, int32_t per_image, int32_t skip_absent, const float* region_class_weight, float loss_scale,
-                        const float* base_value, float* loss_out, void* dpred_f16, int32_t* bad_target, double* base_stats_out,
-                        double* region_stats_out, void* workspace, void* hip_stream);
+#define CVX_SEG_DIMS_BYTES 28
+#define CVX_SEG_CRITERION_BYTES 128
+typedef struct cvx_seg_dims {
+  int32_t ld, batch, nc, ih, iw, oh, ow;
+} cvx_seg_dims;
+typedef struct cvx_seg_criterion {
+  int32_t base; /* 0 none, 1 focal, 2 cross-entropy */
+  float focal_alpha, focal_gamma;
+  const float* class_weight;
+  float label_smoothing;
+  int64_t ignore_index;
+  float ohem_theta;
+  int64_t ohem_min_kept;
+  int32_t region; /* 0 or 1 */
+  double base_weight, weight, alpha, beta, gamma, smooth;
+  int32_t per_image, skip_absent;
+  const float* region_class_weight;
+} cvx_seg_criterion;
+int64_t cvx_seg_criterion_workspace_bytes(const cvx_seg_dims* dims, const cvx_seg_criterion* crit, int32_t for_eval);
+int cvx_seg_criterion_loss(const float* rows_f32, const cvx_seg_dims* dims, const int64_t* target, const cvx_seg_criterion* crit, float loss_scale,
+                           float* loss_out, void* dpred_f16, int32_t* bad_target, double* stats_out, double* region_stats_out, void* workspace,
+                           void* hip_stream);
+int cvx_seg_criterion_eval(const float* rows_f32, const cvx_seg_dims* dims, const int64_t* target, const cvx_seg_criterion* crit, int64_t* confusion,
+                           float* loss_out, double* region_stats_out, void* workspace, void* hip_stream);
 /* VOC mAP evaluation of a detector (get_map at IoU min_overlap), accumulated on the device batch by batch.
  * cvx_det_match, once per batch: rows (batch, max_det, 6) [x1,y1,x2,y2,score,cls] fp32 and counts (batch) int32 exactly as cvx_nms /
  * cvx_nms_variant write them; a count of -1 (or one past max_det) adds 1 to the overflow counter and the image contributes nothing.
@@ -951,7 +943,7 @@ int cvx_draw_detections(const cvx_frame_job* jobs, int32_t batch, int32_t max_h,
 /* Colours a segmentation result and blends it 50/50 into RGB frame b, in place, with no full-resolution logits or colour image in memory.
  * logits_rows (batch, lh * lw, ld) fp32 as the DeepLab engine's forward leaves them, for a (net_h, net_w) network input.  Per frame pixel:
  * the nearest pixel at network size (cv2.resize(..., INTER_NEAREST)'s index rule), the nc logits there by the taps of
- * cvx_resize_bilinear_rows_to_nchw / cvx_seg_eval (bit-identical), arg max (the lowest class wins a tie), lut (nc x 3 bytes, RGB), and
+ * cvx_resize_bilinear_rows_to_nchw / cvx_seg_criterion_eval (bit-identical), arg max (the lowest class wins a tie), lut (nc x 3 bytes, RGB), and
  * (a + b) / 2 rounded half to even per channel; bgr_out != 0 writes the pixel as B, G, R.
  * Replaces: postprocess_seg2d, cv2.resize(INTER_NEAREST), cv2.addWeighted(.5, .5) and [..., ::-1] in DeeplabV3PlusA.predict
  * (reference core/algorithms/segmentation_2d.py:20-30, 80-113). */
@@ -1100,12 +1092,12 @@ typedef struct cvx_seg_view {
  *   xs      flip_k ? ow - 1 - x : x;
  *   z_k[c]  the logit by the taps bilinear_src(y, (float)lh_k / (float)oh, lh_k) and bilinear_src(xs, (float)lw_k / (float)ow, lw_k), mixed
  *           with bilinear_mix: bit-identical to cvx_resize_bilinear_rows_to_nchw's output for that view at (oh, ow), read at (y, xs) -- one
- *           interpolation from the logit level to the output size, as in cvx_seg_eval;
+ *           interpolation from the logit level to the output size, as in cvx_seg_criterion_eval;
  *   mode 0  ("logits") acc[c] = acc[c] + z_k[c] from 0.0f, one rounded add per view;
  *   mode 1  ("prob")   m_k = max_c z_k[c], e = expf(z_k[c] - m_k), acc[c] += e / sum_c e.
  * Outputs, each optional (at least one): labels (batch, oh, ow) uint8, the arg max of acc with strict > (the lowest class wins a tie;
  * nc <= 256); with target (batch, oh, ow) int64 and confusion (nc, nc) int64 (added to, never cleared) confusion[target * nc + label] += 1
- * for targets in [0, nc), others skipped -- an LDS histogram per workgroup for nc <= 90 and direct 64-bit atomics above, as cvx_seg_eval;
+ * for targets in [0, nc), others skipped -- an LDS histogram per workgroup for nc <= 90 and direct 64-bit atomics above, as cvx_seg_criterion_eval;
  * probs_nchw (batch, nc, oh, ow) fp32 = acc[c] / n_views, mode 1 only (refused in mode 0).  The padding columns nc .. ld - 1 are never
  * read as classes.  batch, oh <= 65535. */
 int cvx_seg_fuse(const cvx_seg_view* views_host, int32_t n_views, int32_t ld, int32_t batch, int32_t nc, int32_t oh, int32_t ow, int32_t mode,

@@ -1,4 +1,4 @@
-"""The rules of the weighted / smoothed / hard-pixel-mined cross-entropy (csrc/loss_seg_opts.hip) restated in torch
+"""The rules of the weighted / smoothed / hard-pixel-mined cross-entropy (csrc/loss_seg.hip) restated in torch
 float64, formula by formula and without F.cross_entropy, so that tests can hold both torch's call and the kernels against it.
 
     l_i   = (1 - eps) w_t (lse - z_t) + (eps / C) sum_c w_c (lse - z_c)

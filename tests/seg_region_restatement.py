@@ -1,4 +1,4 @@
-"""The rules of the Dice / Tversky / focal-Tversky region losses (csrc/loss_seg_region.hip) restated in torch float64,
+"""The rules of the Dice / Tversky / focal-Tversky region losses (csrc/loss_seg.hip) restated in torch float64,
 formula by formula and without autograd, so that tests can hold both an independent autograd formulation and the kernels against it.
 
     valid pixels: t != ignore_index and 0 <= t < C; a group is the batch, or one image under per_image; sums over a group's valid pixels

@@ -2148,7 +2148,7 @@ def test_ssd_forward_and_decode_match_the_reference_fixture(dev, gold):
 @pytest.mark.parametrize("B,ih,iw,H,W,nc,mode", [(2, 25, 33, 97, 129, 21, 0), (1, 9, 9, 33, 33, 21, 1), (3, 17, 12, 65, 45, 5, 0), (2, 33, 33, 33, 33, 19, 1),
                                                  (1, 5, 6, 40, 48, 21, 0)])
 def test_seg_loss_kernel_against_torch(dev, B, ih, iw, H, W, nc, mode):
-    """cvx_seg_loss (loss_seg.hip) against torch autograd in fp32: F.interpolate(bilinear, align_corners=False) of the logits rows
+    """cvx_seg_criterion_loss (loss_seg.hip) against torch autograd in fp32: F.interpolate(bilinear, align_corners=False) of the logits rows
     (deeplabv3plus.py:147), then FocalLoss (focal_loss.py:14-22) or nn.CrossEntropyLoss(mean) (segmentation_2d.py:61), with ignored
     pixels; the gradient w.r.t. the low-resolution rows comes back loss-scaled in fp16.  Also the bad-label flag and the adjoint
     resize entry point on its own."""

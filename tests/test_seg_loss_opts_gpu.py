@@ -1,13 +1,14 @@
-"""MI355X: ``cvx_seg_loss_opts`` / ``cvx_seg_eval_opts`` (csrc/loss_seg_opts.hip) -- cross-entropy with class weights, label smoothing
-and online hard example mining in the fused criterion chain -- against torch float64 and tests/seg_loss_restatement.py, and
+"""MI355X: the options of ``cvx_seg_criterion_loss`` / ``cvx_seg_criterion_eval`` (csrc/loss_seg.hip) -- cross-entropy with class weights, label
+smoothing and online hard example mining in the fused criterion chain -- against torch float64 and tests/seg_loss_restatement.py, and
 ``SegLoss(class_weights=, label_smoothing=, ohem=)`` end to end in ``SegTrainStep``.
 
-Bounds.  Loss: 2e-5 relative, the bound ``cvx_seg_loss`` is held to.  Gradient: 1e-3 relative in the max norm, one fp16 rounding of the
+Bounds.  Loss: 2e-5 relative, the bound the option-free criterion is held to.  Gradient: 1e-3 relative in the max norm, one fp16 rounding of the
 scaled gradient.  OHEM keys: four times the distance E between torch's own fp32 and fp64 keys on the same inputs (E is measured in the
 test from the two references, at most 1.3e-5 absolute on these cases; every test prints what it measured).  The selection itself is exact
 on the device's own keys: no tolerance.  Against the float64 selection the device's mask may differ only at pixels whose float64 key lies
 within 1e-4 of a threshold, and the restatement alone shows that at most 2 valid pixels do (tests/test_seg_loss_opts_cpu.py pins 1, 1,
 0, 1, 2, 1 for the six cases)."""
+import ctypes
 import math
 
 import numpy as np
@@ -106,29 +107,35 @@ def test_weights_and_smoothing_against_torch_fp64(dev, shape, config):
 
 
 def call_opts_entry(dev, rows, t, shape, weights=None, eps=0.0, theta=-1.0, k=0):
+    """cvx_seg_criterion_loss with a cross-entropy base and exactly these options, no SegLoss in between"""
     B, ih, iw, H, W, nc = shape
     lib = L.load()
     ld = rows.shape[2]
-    ws = torch.empty(int(lib.cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, int(theta >= 0))), dtype=torch.uint8, device=dev)
+    dims = L.SegDims(ld, B, nc, ih, iw, H, W)
+    crit = L.SegCriterion(base=2, class_weight=weights.data_ptr() if weights is not None else None, label_smoothing=eps, ignore_index=-100,
+                          ohem_theta=theta, ohem_min_kept=k)
+    ws = torch.empty(int(lib.cvx_seg_criterion_workspace_bytes(ctypes.byref(dims), ctypes.byref(crit), 0)), dtype=torch.uint8, device=dev)
     loss, bad = torch.empty(1, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
     dpred = torch.full((B, ih * iw, ld), float("nan"), dtype=torch.float16, device=dev)
     stats = torch.zeros(4, dtype=torch.float64, device=dev)
-    L.check(lib.cvx_seg_loss_opts(L.ptr(rows), ld, B, nc, ih, iw, H, W, L.ptr(t), L.ptr(weights) if weights is not None else None, eps, -100,
-                                  theta, k, SCALE, L.ptr(loss), L.ptr(dpred), L.ptr(bad), L.ptr(stats), L.ptr(ws), L.stream_ptr(dev)),
-            "cvx_seg_loss_opts")
+    L.check(lib.cvx_seg_criterion_loss(L.ptr(rows), ctypes.byref(dims), L.ptr(t), ctypes.byref(crit), SCALE, L.ptr(loss), L.ptr(dpred), L.ptr(bad),
+                                       L.ptr(stats), None, L.ptr(ws), L.stream_ptr(dev)), "cvx_seg_criterion_loss")
     return loss, dpred, stats
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_no_option_reproduces_the_plain_entry_bit_for_bit(dev, shape):
+    """unit class weights and zero smoothing go through the options kernel (Ce<true>) and reproduce SegLoss("ce"), the option-free kernel
+    (Ce<false>), bit for bit"""
     B, ih, iw, H, W, nc = shape
     rows, t, _ = R.make_case(shape, B * 1000 + H + nc)
+    ones = torch.ones(nc, device=dev)
     for r in (rows, torch.cat([rows[..., :nc], torch.zeros(B, ih * iw, 1)], 2).contiguous()):        # vector and scalar path
         d_rows, d_t = r.to(dev), t.to(dev)
         plain = SegLoss("ce")
         plain.nc = nc
         loss0, dpred0 = plain.op(d_rows, d_t, (ih, iw), SCALE)
-        loss1, dpred1, stats = call_opts_entry(dev, d_rows, d_t, shape)
+        loss1, dpred1, stats = call_opts_entry(dev, d_rows, d_t, shape, weights=ones)
         assert torch.equal(loss0.view(torch.int32), loss1.view(torch.int32))
         assert torch.equal(dpred0.view(torch.int16), dpred1.view(torch.int16))
         assert stats[0] == stats[1] == stats[3] == int((t != -100).sum())
@@ -231,11 +238,17 @@ def test_all_targets_ignored(dev):
         assert crit.last_stats.cpu()[[0, 1, 3]].tolist() == [0.0, 0.0, 0.0]
 
 
-@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[3]], ids=lambda s: "x".join(map(str, s)))
-def test_eval_opts(dev, shape):
+# the last shape: nc = 91 is the first class count whose nc * nc cells miss the LDS histogram, so the evaluation kernel counts in the global matrix
+EVAL_SHAPES = [(SHAPES[0], 0), (SHAPES[3], 0), ((1, 3, 3, 9, 11, 91), 96), ((1, 3, 3, 9, 11, 91), 92)]
+
+
+@pytest.mark.parametrize("shape,ld", EVAL_SHAPES, ids=["x".join(map(str, s)) + (f"-ld{ld}" if ld else "") for s, ld in EVAL_SHAPES])
+def test_eval_opts(dev, shape, ld):
     from core.trainer.segmentation_trainer import SegmentationMetrics
     B, ih, iw, H, W, nc = shape
     rows, t, w = R.make_case(shape, B * 1000 + H + nc)
+    if ld:
+        rows = torch.cat([rows[..., :nc], torch.zeros(B, ih * iw, ld - nc)], 2).contiguous()
     want_loss, _ = reference(shape, rows, t, w, 0.1)
     d_rows, d_t = rows.to(dev), t.to(dev)
     slots = torch.zeros(2, device=dev)

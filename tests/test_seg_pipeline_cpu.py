@@ -101,9 +101,12 @@ def test_new_symbols_in_header_library_and_prototypes():
     header = open(os.path.join(ROOT, "include", "cvx_engine.h")).read()
     declared = set(re.findall(r"\b(cvx_[a-z0-9_]+)\s*\(", header))
     lib = ctypes.CDLL(LIB_PATH)
-    for name in ("cvx_seg_pipeline", "cvx_seg_eval", "cvx_seg_eval_workspace_bytes"):
+    for name in ("cvx_seg_pipeline", "cvx_seg_criterion_eval", "cvx_seg_criterion_workspace_bytes"):
         assert name in declared and name in L.PROTOTYPES and hasattr(lib, name)
-    assert len(L.PROTOTYPES["cvx_seg_pipeline"][1]) == 12 and len(L.PROTOTYPES["cvx_seg_eval"][1]) == 17
+    assert len(L.PROTOTYPES["cvx_seg_pipeline"][1]) == 12 and len(L.PROTOTYPES["cvx_seg_criterion_eval"][1]) == 9
+    assert len(L.PROTOTYPES["cvx_seg_criterion_workspace_bytes"][1]) == 3
+    sizes = {k: int(v) for k, v in re.findall(r"#define CVX_SEG_(DIMS|CRITERION)_BYTES (\d+)", header)}      # the library's static_assert holds these
+    assert ctypes.sizeof(L.SegDims) == sizes["DIMS"] == 28 and ctypes.sizeof(L.SegCriterion) == sizes["CRITERION"] == 128
     assert "cvx_seg_job" in header and seg_pipeline.SEG_JOB_DTYPE.itemsize == 64
     assert seg_pipeline.SEG_JOB_DTYPE.fields["ih"][1] == 16 and seg_pipeline.SEG_JOB_DTYPE.fields["reserved"][1] == 48
 

@@ -1,5 +1,5 @@
 """GPU: ``cvx_seg_pipeline`` through ``DeviceSegAugmenter`` / ``DeviceSegLoader`` against torch on the CPU (tests/seg_pipeline_restatement.py),
-``cvx_seg_eval`` through ``SegmentationMetrics.add_rows`` against the unfused device path (exact) and against torch on the CPU, and the
+``cvx_seg_criterion_eval`` through ``SegmentationMetrics.add_rows`` against the unfused device path (exact) and against torch on the CPU, and the
 DeepLabv3+ trainer with device loaders on both sides."""
 import os
 
@@ -145,7 +145,7 @@ def test_loader(dev, cases):
     assert float((v[0][0][1].cpu() - S.image_torch(cases[1]["picture"], job, 33, 33)).abs().max()) < 1e-5
 
 
-# ---- cvx_seg_eval -------------------------------------------------------------------------------------------------------------------------------
+# ---- cvx_seg_criterion_eval -------------------------------------------------------------------------------------------------------------------------------
 EVAL_SHAPES = [(2, 25, 33, 97, 129, 21, 0), (1, 9, 9, 33, 33, 21, 1), (3, 17, 12, 65, 45, 5, 0), (1, 5, 6, 40, 48, 21, 0)]
 
 
@@ -215,7 +215,7 @@ def test_seg_eval_counts_in_global_memory_for_many_classes(dev):
 
 @pytest.mark.parametrize("B,ih,iw,H,W,nc,mode", EVAL_SHAPES)
 def test_seg_eval_against_torch_on_the_cpu(dev, B, ih, iw, H, W, nc, mode):
-    """the loss within 2e-5 relative of torch's fp32 value (the bound cvx_seg_loss is held to); the matrix within 2 x (the number of
+    """the loss within 2e-5 relative of torch's fp32 value (the bound cvx_seg_criterion_loss is held to); the matrix within 2 x (the number of
     pixels whose fp64 top-two logit gap is below 1e-4) of the CPU matrix in L1 -- such a pixel may move from one cell to another -- and
     those pixels are at most 0.5 % of all (the seed is that of test_seg_loss_kernel_against_torch; the reference alone shows the share)"""
     rows, t, ld = eval_inputs(B, ih, iw, H, W, nc)

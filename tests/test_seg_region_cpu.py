@@ -1,5 +1,5 @@
 """The region-loss rules (tests/seg_region_restatement.py) against an independent one-hot + torch.autograd float64 formulation, their
-edge rules, and the host side of ``SegLoss(region=)``: the refusals, ``build_loss`` and the C ABI's new entries.  No GPU."""
+edge rules, and the host side of ``SegLoss(region=)``: the refusals, ``build_loss`` and the C ABI's entries.  No GPU."""
 import ctypes
 import math
 import os
@@ -177,12 +177,26 @@ def test_the_new_entries_are_declared_bound_and_exported():
     header = open(os.path.join(ROOT, "include", "cvx_engine.h")).read()
     declared = set(re.findall(r"\b(cvx_[a-z0-9_]+)\s*\(", header))
     lib = ctypes.CDLL(os.environ.get("CVX_LIB", os.path.join(ROOT, "computervision.pytorch_amd", "lib", "libcvx_engine.so")))
-    for name in ("cvx_seg_loss_region", "cvx_seg_loss_region_workspace_bytes"):
+    for name in ("cvx_seg_criterion_loss", "cvx_seg_criterion_eval", "cvx_seg_criterion_workspace_bytes"):
         assert name in declared and name in L.PROTOTYPES and hasattr(lib, name)
-    # value only: the partials and sums, no gradient plane; training without a base: plus exactly one plane
-    ws = L.load().cvx_seg_loss_region_workspace_bytes
+    assert [len(L.PROTOTYPES[n][1]) for n in ("cvx_seg_criterion_loss", "cvx_seg_criterion_eval", "cvx_seg_criterion_workspace_bytes")] == [12, 9, 3]
+    sizes = {k: int(v) for k, v in re.findall(r"#define CVX_SEG_(DIMS|CRITERION)_BYTES (\d+)", header)}      # the library's static_assert holds these
+    assert ctypes.sizeof(L.SegDims) == sizes["DIMS"] and ctypes.sizeof(L.SegCriterion) == sizes["CRITERION"]
+    assert int(re.search(r"#define CVX_SEG_OPTS_KEY_OFFSET (\d+)", header).group(1)) == L.SEG_OPTS_KEY_OFFSET == 4096
+    # the layout: the region's own part is the same small block in every configuration, in front of whatever the base chain needs
     B, nc, H, W = 16, 21, 513, 513
-    small = int(ws(B, nc, H, W, 0, 0, 0, 1))
-    assert 0 < small < 8 * 2 ** 20
-    assert int(ws(B, nc, H, W, 0, 0, 0, 0)) == small + B * nc * H * W * 4
-    assert int(ws(B, nc, H, W, 3, 1, 0, 0)) == small + int(L.load().cvx_seg_loss_opts_workspace_bytes(B, nc, H, W, 1))
+    dims = L.SegDims(24, B, nc, 129, 129, H, W)
+    dice = dict(region=1, weight=1.0, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0)
+
+    def ws(for_eval, **kw):
+        crit = L.SegCriterion(**dict(dict(ignore_index=-100, ohem_theta=-1.0), **kw))
+        return int(L.load().cvx_seg_criterion_workspace_bytes(ctypes.byref(dims), ctypes.byref(crit), for_eval))
+
+    # value only: the partials and sums, no gradient plane; training without a base: plus exactly one plane
+    small = ws(1, base=2, base_weight=1.0, **dice) - ws(1, base=2)
+    assert 0 < small < 8 * 2 ** 20 and ws(1, base=2, base_weight=1.0, **dice) < 8 * 2 ** 20
+    assert ws(0, base=0, **dice) == L.SEG_OPTS_KEY_OFFSET + small + B * nc * H * W * 4
+    mined = dict(base=2, label_smoothing=0.1, ohem_theta=0.35, ohem_min_kept=1000)
+    assert ws(0, base_weight=1.0, **mined, **dice) == small + ws(0, **mined)
+    assert ws(0, base=2) > L.SEG_OPTS_KEY_OFFSET + B * nc * H * W * 4 and ws(0, **mined) >= ws(0, base=2) + 2 * B * H * W * 4
+    assert ws(0, base=0) == 0 and ws(0, base=1, label_smoothing=0.1) == 0                    # refused: nothing to compute; options without cross-entropy

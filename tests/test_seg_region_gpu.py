@@ -1,4 +1,4 @@
-"""MI355X: ``cvx_seg_loss_region`` (csrc/loss_seg_region.hip) -- Dice / Tversky / focal-Tversky region losses in the fused criterion
+"""MI355X: the region term of ``cvx_seg_criterion_loss`` (csrc/loss_seg.hip) -- Dice / Tversky / focal-Tversky region losses in the fused criterion
 chain -- through ``SegLoss(region=)``: against torch float64 (tests/seg_region_restatement.py, which tests/test_seg_region_cpu.py holds
 against autograd to 1e-12 on these inputs; the adjoint of the upsampling is torch's), against the existing entries by composition,
 bit repeatability, the bad-label flag, the fused validation pass and ``SegTrainStep`` end to end.

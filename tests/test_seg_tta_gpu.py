@@ -1,6 +1,6 @@
 """MI355X: multi-scale / flip test-time augmentation.  ``cvx_seg_tta_inputs`` and mode 0 of ``cvx_seg_fuse`` (csrc/seg_tta.hip) against the
 numpy restatement (tests/seg_tta_restatement.py) bit for bit; mode 1 within a derived bound; the identities that tie the fusion to
-``cvx_seg_eval``; and ``DeeplabV3PlusA.predict_labels`` / ``evaluate_on_voc`` end to end against the restatement's fusion of the rows the
+``cvx_seg_criterion_eval``; and ``DeeplabV3PlusA.predict_labels`` / ``evaluate_on_voc`` end to end against the restatement's fusion of the rows the
 network returned.
 
 The bound on mode 1's probabilities, 1e-5 absolute, is derived and not measured: the z_k are bit-identical to the restatement's, and what
@@ -78,7 +78,7 @@ def test_fuse_logits_equals_the_restatement(dev, nc, ld, out_hw, n_views, batch)
 
 
 def test_fuse_counts_128_classes_with_direct_atomics(dev):
-    """nc * nc = 16384 cells do not fit the 32 KB LDS histogram: every pixel goes to the matrix directly, as in cvx_seg_eval"""
+    """nc * nc = 16384 cells do not fit the 32 KB LDS histogram: every pixel goes to the matrix directly, as in cvx_seg_criterion_eval"""
     nc = ld = 128
     rng = np.random.RandomState(9)
     views = [((3.0 * rng.standard_normal((2, lh * lw, ld))).astype(np.float32), lh, lw, flip) for lh, lw, flip in ((9, 13, False), (17, 25, True))]
@@ -202,7 +202,7 @@ def report(path):
 
 def test_evaluate_on_voc_with_one_plain_view_writes_the_plain_numbers(dev, deeplab, tmp_path):
     """scale 1 without flip in "logits" mode is the plain evaluation: the input launch copies the batch bit for bit and 0 + z = z.  Where
-    a logit of the random-weight network is not finite the two arg max rules differ by design (cvx_seg_eval starts from -inf, the fusion
+    a logit of the random-weight network is not finite the two arg max rules differ by design (cvx_seg_criterion_eval starts from -inf, the fusion
     from class 0 as the stitch does), so those pixels' targets are set to ignored -- in both runs."""
     algo, model = deeplab
     loader = two_batches(dev, 51)

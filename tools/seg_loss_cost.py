@@ -2,12 +2,12 @@
 reduction, adjoint gather), timed with device events at the benchmark's DeepLab shape -- batch 16, 513 x 513 labels, 21 classes, logits
 rows 129 x 129 with 24 columns.
 
-    arms     plain      cross-entropy through the old entry, cvx_seg_loss (3 launches)
-             weights    class weights + label smoothing 0.1, cvx_seg_loss_opts (3 launches)
+    arms     plain      cross-entropy without options, the Ce<false> kernels (3 launches)
+             weights    class weights + label smoothing 0.1, the Ce<true> kernels (3 launches)
              ohem       OHEM thresh 0.7, min_kept 100000 per image (13 launches)
              all        weights + smoothing + OHEM
              ohem_few   OHEM thresh 1e-4: the rank decides, 100000 pixels per image are kept and the gradients of the rest are zeroed
-             dice       the Dice region loss alone, cvx_seg_loss_region without a base (5 launches)
+             dice       the Dice region loss alone, base 0 (5 launches)
              ce_dice    cross-entropy + Dice (7 launches: the plain chain's two, the region's four, the adjoint)
              all_tversky   weights + smoothing + OHEM + focal Tversky (0.3 / 0.7, gamma 0.75) per image
 

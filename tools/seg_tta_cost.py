@@ -1,6 +1,6 @@
 """What multi-scale / flip test-time augmentation costs beside the plain evaluation: event times of the ``cvx_seg_tta_inputs`` launches and of
 the ``cvx_seg_fuse`` launch alone (csrc/seg_tta.hip) -- both modes, with and without the confusion counts and the probabilities --, and of
-the whole augmented evaluation of one batch (``SegTTA.run`` + ``cvx_seg_fuse``) next to the plain ``forward_rows`` + ``cvx_seg_eval`` of the
+the whole augmented evaluation of one batch (``SegTTA.run`` + ``cvx_seg_fuse``) next to the plain ``forward_rows`` + ``cvx_seg_criterion_eval`` of the
 same batch, in the same process on the same device.
 
     python tools/seg_tta_cost.py [--batch 8] [--size 513] [--scales 0.5 0.75 1.0 1.25 1.5 1.75] [--no-flip] [--reps 20] [--out profiles/seg_tta_cost.txt]
@@ -96,7 +96,7 @@ def main():
         ("cvx_seg_fuse, prob, labels", fuse("prob")),
         ("cvx_seg_fuse, prob, labels + counts", fuse("prob", **with_counts)),
         ("cvx_seg_fuse, prob, labels + counts + probabilities", fuse("prob", probs=True, **with_counts)),
-        ("plain: forward_rows + cvx_seg_eval", plain),
+        ("plain: forward_rows + cvx_seg_criterion_eval", plain),
         ("SegTTA.run alone (inputs + forwards)", forwards_only),
         ("augmented evaluation of the batch, logits", augmented("logits")),
         ("augmented evaluation of the batch, prob", augmented("prob")),
