@@ -11,7 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB") or os.path.join(_HERE, "lib", "libcvx_engine.so")   # CVX_LIB: A/B runs of two builds on one box
-ABI_VERSION = 5
+ABI_VERSION = 6
 SEG_OPTS_KEY_OFFSET = 4096      # CVX_SEG_OPTS_KEY_OFFSET: where cvx_seg_criterion_loss keeps the OHEM key plane in its workspace
 
 
@@ -46,7 +46,7 @@ class SegDims(C.Structure):
 
 
 class SegCriterion(C.Structure):
-    """cvx_seg_criterion; base: 0 none, 1 focal, 2 cross-entropy"""
+    """cvx_seg_criterion; base: 0 none, 1 focal, 2 cross-entropy; region: 0 none, 1 Dice / Tversky, 2 Lovasz-Softmax"""
     _fields_ = [("base", C.c_int32), ("focal_alpha", C.c_float), ("focal_gamma", C.c_float), ("class_weight", C.c_void_p),
                 ("label_smoothing", C.c_float), ("ignore_index", C.c_int64), ("ohem_theta", C.c_float), ("ohem_min_kept", C.c_int64),
                 ("region", C.c_int32), ("base_weight", C.c_double), ("weight", C.c_double), ("alpha", C.c_double), ("beta", C.c_double),
@@ -176,6 +176,7 @@ PROTOTYPES = {
     "cvx_seg_criterion_workspace_bytes": (_I64, [C.POINTER(SegDims), C.POINTER(SegCriterion), _I32]),
     "cvx_seg_criterion_loss": (_I32, [_P, C.POINTER(SegDims), _P, C.POINTER(SegCriterion), _F, _P, _P, _P, _P, _P, _P, _P]),
     "cvx_seg_criterion_eval": (_I32, [_P, C.POINTER(SegDims), _P, C.POINTER(SegCriterion), _P, _P, _P, _P, _P]),
+    "cvx_seg_criterion_lovasz_view": (_I32, [C.POINTER(SegDims), C.POINTER(SegCriterion), C.POINTER(_I64)]),
     "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
     "cvx_coco_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),

@@ -1,8 +1,8 @@
 // The fused segmentation criterion of the DeepLabv3+ trainer on gfx950 (cvx_seg_criterion_loss / cvx_seg_criterion_eval): bilinear
 // upsampling of the decoder's logits to the label resolution, the loss per pixel, and the gradient w.r.t. the LOW-RESOLUTION logits rows
 // the engine's backward pass starts from -- value and gradient in one launch chain, no autograd tape, no (B, nc, H, W) logits tensor in
-// HBM, no sort, no host read.  One criterion = a base term (none / focal / cross-entropy, the latter with options) plus an optional
-// region term:   loss = base_weight * base + weight * region   (base alone: loss = base).
+// HBM, no host read.  One criterion = a base term (none / focal / cross-entropy, the latter with options) plus an optional
+// region term (Dice / Tversky, or Lovasz-Softmax -- the one term that sorts):   loss = base_weight * base + weight * region   (base alone: loss = base).
 //
 // Reference semantics (file:line under the reference tree):
 //   DeeplabV3Plus.forward        core/models/deeplabv3plus.py:143-148   x = F.interpolate(classifier(features), size=input, bilinear,
@@ -56,6 +56,20 @@
 //   K6 the adjoint, with scale 1
 //   launches: 5 (region alone), 7 (plain base + region)
 //
+// Lovasz-Softmax (region 2; the rules are the header's).  Per group and class the errors e = [t == c] ? 1 - p_c : p_c of the valid pixels,
+// sorted descending with ties by ascending pixel index, weighted by the increments of the Jaccard loss along that order:
+//   the base's K1 .. K5 as above
+//   L1 count, L2 offsets  the valid pixels per block of 1024 and their exclusive offsets per group: invalid pixels never enter a segment
+//   L3 keys               online softmax, then eight classes at a time: the fp32 bits of e and (pixel index | flag << 31) into segment
+//                         (group, class) at the pixel's compacted place; G_c by integer atomics
+//   L4 plan               coef = weight (1/G) m_c v_c / sum m v, the segment table of the sorted view
+//   L5 sort               lovasz_sort.h: four stable 8-bit passes of histogram / scan / scatter, ranks from ballots and counts
+//   L6 flagsum, L7 flagscan, L8 value   integer prefix counts of the flags, Delta from the closed form in double, sum e Delta in
+//                         fixed-order partials; in training coef * s * Delta scattered to a plane laid out like the gradient plane
+//   L9 reduce, solve      L_c, the stats, the combined loss, the base's scale
+//   L10 seg_lovasz_grad   R4 with h_c read from the plane;   K6 the adjoint, with scale 1
+//   launches: 22 and a memset for the term; evaluation stops after L9 with a one-byte payload (21)
+//
 // Evaluation: seg_eval_kernel walks the label pixels the same way -- the same taps, the same online softmax, the same policies -- and
 // keeps the arg max instead of a gradient: confusion[target][argmax] += 1 and the batch's base value (K5 finishes its sum); then R1 .. R3
 // for a region term.  OHEM is a training device and is never applied here.  The LDS histogram is seg_tail.h's.
@@ -68,6 +82,7 @@
 #include <type_traits>
 
 #include "cvx_common.h"
+#include "lovasz_sort.h"
 #include "seg_tail.h"
 #include "../../include/cvx_engine.h"
 
@@ -100,6 +115,29 @@ struct PixelTaps {
     r01 = base + ((long long)y0 * d.iw + x1) * d.ld;
     r10 = base + ((long long)y1 * d.iw + x0) * d.ld;
     r11 = base + ((long long)y1 * d.iw + x1) * d.ld;
+  }
+  // The same taps with the two weights taken from a source coordinate formed in double (sy = ih / oh, sx = iw / ow as doubles): the
+  // fp32 coordinate of bilinear_src is a number of magnitude up to ih, so its weight carries half an ulp of THAT -- 5e-7 at 8 .. 16 --
+  // which a difference of 6 between neighbouring logits turns into 3e-6 on the logit.  Only the Lovasz keys, which are held to 1e-6 of
+  // float64, take their logits this way; everything else keeps the values cvx_resize_bilinear_rows_to_nchw writes.
+  __device__ __forceinline__ PixelTaps(const float* rows, const cvx_seg_dims& d, int b, int oy, int ox, double sy, double sx) {
+    int y0, y1, x0, x1;
+    src_f64(oy, sy, d.ih, &y0, &y1, &ly);
+    src_f64(ox, sx, d.iw, &x0, &x1, &lx);
+    const float* base = rows + (long long)b * d.ih * d.iw * d.ld;
+    r00 = base + ((long long)y0 * d.iw + x0) * d.ld;
+    r01 = base + ((long long)y0 * d.iw + x1) * d.ld;
+    r10 = base + ((long long)y1 * d.iw + x0) * d.ld;
+    r11 = base + ((long long)y1 * d.iw + x1) * d.ld;
+  }
+  static __device__ __forceinline__ void src_f64(int o, double scale, int in_size, int* i0, int* i1, float* lam) {
+    double s = ((double)o + 0.5) * scale - 0.5;
+    if (s < 0.0) s = 0.0;
+    int a = (int)s;
+    if (a > in_size - 1) a = in_size - 1;
+    *i0 = a;
+    *i1 = a + (a < in_size - 1 ? 1 : 0);
+    *lam = (float)(s - (double)a);
   }
   __device__ __forceinline__ float logit(int c) const { return bilinear_mix(r00[c], r01[c], r10[c], r11[c], lx, ly); }
   // eight classes at a time with 16-byte loads issued together (rows with ld % 8 == 0 on a 16-byte boundary)
@@ -794,6 +832,338 @@ __global__ __launch_bounds__(256) void seg_region_grad_kernel(const float* rows,
   }
 }
 
+// ---- the Lovasz-Softmax term: L1 .. L9 ----------------------------------------------------------------------------------------------------------
+// (the rules: include/cvx_engine.h; the sort: lovasz_sort.h).  A group's valid pixels are compacted in index order, so segment
+// (group, class) holds nvalid[group] keys and every bit pattern is free to be a key.
+
+// The payload that travels with a key: training keeps the pixel's index inside its group (bits 0..30) and the foreground flag (bit 31);
+// the value-only chain of validation needs the flag alone, one byte.
+template <class PL>
+struct LvPay;
+template <>
+struct LvPay<unsigned> {
+  static __device__ __forceinline__ unsigned make(unsigned idx, bool fg) { return idx | (fg ? 0x80000000u : 0u); }
+  static __device__ __forceinline__ bool fg(unsigned v) { return (v >> 31) != 0u; }
+  static __device__ __forceinline__ unsigned idx(unsigned v) { return v & 0x7FFFFFFFu; }
+};
+template <>
+struct LvPay<unsigned char> {
+  static __device__ __forceinline__ unsigned char make(unsigned, bool fg) { return fg ? 1 : 0; }
+  static __device__ __forceinline__ bool fg(unsigned char v) { return v != 0; }
+  static __device__ __forceinline__ unsigned idx(unsigned char) { return 0u; }
+};
+
+// L1: the valid pixels of each block of LV_TILE consecutive pixels of an image (block blk of image b = workgroup b * bpk + blk).
+__global__ __launch_bounds__(256) void seg_lovasz_count_kernel(const long long* target, cvx_seg_dims d, long long ignore_index, int bpk, int* blkcnt) {
+  __shared__ unsigned sh[16];
+  const int b = blockIdx.x / bpk, blk = blockIdx.x % bpk;
+  const long long plane = (long long)d.oh * d.ow;
+  bool f[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const long long i = ((long long)blk * 4 + it) * 256 + threadIdx.x;
+    f[it] = i < plane && SegPixel(b, i, d, target, ignore_index, nullptr).valid;
+  }
+  unsigned rank[4], total;
+  lv_rank4(f, sh, rank, &total);
+  if (threadIdx.x == 0) blkcnt[blockIdx.x] = (int)total;
+}
+
+// L2: one workgroup per group: the exclusive running count over the group's ppg blocks in order -> blkoff; the total -> nvalid[group].
+__global__ __launch_bounds__(256) void seg_lovasz_offsets_kernel(const int* blkcnt, int ppg, int* blkoff, int* nvalid) {
+  __shared__ unsigned sh[256];
+  const int g = blockIdx.x, per = (ppg + 255) / 256;
+  const long long lo = (long long)threadIdx.x * per, hi = lo + per < ppg ? lo + per : ppg;
+  const int* cnt = blkcnt + (long long)g * ppg;
+  unsigned mine = 0u;
+  for (long long i = lo; i < hi; ++i) mine += (unsigned)cnt[i];
+  unsigned total;
+  unsigned run = lv_excl_scan_256(mine, sh, &total);
+  for (long long i = lo; i < hi; ++i) {
+    blkoff[(long long)g * ppg + i] = (int)run;
+    run += (unsigned)cnt[i];
+  }
+  if (threadIdx.x == 0) nvalid[g] = (int)total;
+}
+
+// L3: the keys.  The workgroup's pixels as in L1; per valid pixel the log-sum-exp, then the classes eight at a time as in R1 (with the
+// interpolation weights from a double coordinate, see PixelTaps): the error e = [t == c] ? 1 - p_c : p_c in fp32, its bit pattern and the payload to place blkoff + (rank among the block's valid pixels) of
+// segment (group, class).  G_c: counted in LDS, then integer atomics (exact in any order).
+template <class PL>
+__global__ __launch_bounds__(256) void seg_lovasz_keys_kernel(const float* rows, cvx_seg_dims d, const long long* target, long long ignore_index, int bpk,
+                                                              int per_image, const int* blkoff, unsigned* keys, PL* pay, int* gc, int* bad) {
+  __shared__ unsigned sh[16];
+  __shared__ int hist[REGION_MAX_NC];
+  const int b = blockIdx.x / bpk, blk = blockIdx.x % bpk, nc = d.nc;
+  const long long plane = (long long)d.oh * d.ow;
+  const int g = per_image ? b : 0;
+  const long long ng = per_image ? plane : (long long)d.batch * plane;
+  const bool vec = rows_vec(rows, d.ld);
+  const double sy = (double)d.ih / (double)d.oh, sx = (double)d.iw / (double)d.ow;  // the keys' own interpolation weights: PixelTaps
+  for (int c = threadIdx.x; c < nc; c += 256) hist[c] = 0;
+  float lse[4];
+  int tgt[4];  // -1: not a valid pixel (or past the image's end)
+  bool f[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const long long i = ((long long)blk * 4 + it) * 256 + threadIdx.x;
+    tgt[it] = -1;
+    lse[it] = 0.f;
+    if (i < plane) {
+      const SegPixel px(b, i, d, target, ignore_index, bad);
+      if (px.valid) {
+        lse[it] = online_softmax(PixelTaps(rows, d, b, px.oy, px.ox, sy, sx), nc, vec, -1, [](int, float) { return 0.f; }).lse;
+        tgt[it] = (int)px.tg;
+      }
+    }
+    f[it] = tgt[it] >= 0;
+  }
+  unsigned rank[4], total;
+  lv_rank4(f, sh, rank, &total);  // its barrier also covers the zeroing of hist
+  const long long first = blkoff[blockIdx.x];
+#pragma unroll
+  for (int it = 0; it < 4; ++it)
+    if (f[it]) atomicAdd(&hist[tgt[it]], 1);
+  for (int c0 = 0; c0 < nc; c0 += 8) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      if (!f[it]) continue;
+      const long long i = ((long long)blk * 4 + it) * 256 + threadIdx.x;
+      const PixelTaps tp(rows, d, b, (int)(i / d.ow), (int)(i % d.ow), sy, sx);
+      float z[8];
+      if (vec) {
+        tp.logits8(c0, z);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) z[k] = c0 + k < nc ? tp.logit(c0 + k) : 0.f;
+      }
+      const long long at = first + rank[it];
+      const unsigned idx = (unsigned)(per_image ? i : (long long)b * plane + i);
+      if (at >= ng) continue;  // never: the offsets count the same pixels
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (c0 + k < nc) {
+          const float p = expf(z[k] - lse[it]);
+          const bool fg = tgt[it] == c0 + k;
+          const float e = fg ? fmaxf(1.f - p, 0.f) : p;
+          const long long o = ((long long)g * nc + c0 + k) * ng + at;
+          keys[o] = __float_as_uint(e);
+          pay[o] = LvPay<PL>::make(idx, fg);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < nc; c += 256)
+    if (hist[c]) atomicAdd(&gc[(long long)g * nc + c], hist[c]);
+}
+
+struct LovaszCfg {
+  double weight, base_weight;
+  int skip_absent;
+};
+__device__ __forceinline__ double lovasz_mv(const LovaszCfg& cfg, const int* gc, const float* v, int c) {
+  return (cfg.skip_absent && gc[c] == 0) ? 0.0 : (v ? (double)v[c] : 1.0);
+}
+
+// L4: one workgroup, once the counts are known: coef[g][c] = weight (1/G) m_c v_c / sum m v -- what a pixel's s * Delta is scaled by --
+// and the segment table (element offset, length) of the sorted view; a segment the sort skips has length 0.
+__global__ __launch_bounds__(256) void seg_lovasz_plan_kernel(const int* gc, const int* nvalid, int G, int nc, long long ng, LovaszCfg cfg, const float* v,
+                                                              double* coef, long long* segtab) {
+  __shared__ double sh[1][256];
+  for (int g = 0; g < G; ++g) {
+    const int* gg = gc + (long long)g * nc;
+    double m[1] = {0.0};
+    for (int c = threadIdx.x; c < nc; c += 256) m[0] += lovasz_mv(cfg, gg, v, c);
+    block_tree_256<1>(m, sh);
+    for (int c = threadIdx.x; c < nc; c += 256) {
+      const long long s = (long long)g * nc + c;
+      coef[s] = m[0] > 0.0 ? cfg.weight * (1.0 / (double)G) * lovasz_mv(cfg, gg, v, c) / m[0] : 0.0;
+      segtab[2 * s] = s * ng;
+      segtab[2 * s + 1] = (cfg.skip_absent && gg[c] == 0) ? 0 : nvalid[g];
+    }
+  }
+}
+
+// L6: the foreground flags of a tile of the sorted segment.
+template <class PL>
+__global__ __launch_bounds__(256) void seg_lovasz_flagsum_kernel(const PL* pay, LvGeom q, const int* nvalid, const int* gc, unsigned* tilefg) {
+  __shared__ unsigned sh[16];
+  const LvTile t = lv_tile(q, nvalid, gc);
+  if (!t.live) return;
+  bool f[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long long i = (long long)t.tile * LV_TILE + j * 256 + threadIdx.x;
+    f[j] = i < t.n && LvPay<PL>::fg(pay[t.base + i]);
+  }
+  unsigned rank[4], total;
+  lv_rank4(f, sh, rank, &total);
+  if (threadIdx.x == 0) tilefg[blockIdx.x] = total;
+}
+
+// L7: one workgroup per segment: the exclusive running count of the tiles' flags, in place.
+__global__ __launch_bounds__(256) void seg_lovasz_flagscan_kernel(LvGeom q, const int* nvalid, const int* gc, unsigned* tilefg) {
+  __shared__ unsigned sh[256];
+  const int seg = blockIdx.x;
+  int nt;
+  if (!lv_segment_live(q, nvalid, gc, seg, &nt)) return;
+  unsigned* tf = tilefg + (long long)seg * q.tps;
+  const int per = (nt + 255) / 256;
+  const int lo = min(threadIdx.x * per, (unsigned)nt), hi = min(lo + per, nt);
+  unsigned mine = 0u;
+  for (int i = lo; i < hi; ++i) mine += tf[i];
+  unsigned total;
+  unsigned run = lv_excl_scan_256(mine, sh, &total);
+  for (int i = lo; i < hi; ++i) {
+    const unsigned v = tf[i];
+    tf[i] = run;
+    run += v;
+  }
+}
+
+// L8: the element of rank k of a segment has fb foreground and k - fb background elements in front of it (integers: the tile's offset
+// plus a ballot count), so I = G_c - fb, U = G_c + k - fb and Delta = 1 / U at a foreground element, I / (U (U + 1)) at a background
+// one (1 for the first element of a class without a target pixel): one division in double.  sum e Delta -> one partial per tile;
+// TRAIN: coef * s * Delta -> the plane, at the pixel's place in the gradient plane's layout (b, c, y, x).
+template <class PL, bool TRAIN>
+__global__ __launch_bounds__(256) void seg_lovasz_value_kernel(const unsigned* keys, const PL* pay, LvGeom q, const int* nvalid, const int* gc,
+                                                               const unsigned* tilefg, const double* coef, int per_image, long long plane, float* hplane,
+                                                               double* part) {
+  __shared__ unsigned sh[16];
+  __shared__ double sm[1][4];
+  const LvTile t = lv_tile(q, nvalid, gc);
+  if (!t.live) return;
+  bool f[4], ok[4];
+  unsigned key[4];
+  PL pl[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long long i = (long long)t.tile * LV_TILE + j * 256 + threadIdx.x;
+    ok[j] = i < t.n;
+    key[j] = ok[j] ? keys[t.base + i] : 0u;
+    pl[j] = ok[j] ? pay[t.base + i] : PL(0);
+    f[j] = ok[j] && LvPay<PL>::fg(pl[j]);
+  }
+  unsigned rank[4], total;
+  lv_rank4(f, sh, rank, &total);
+  const long long Gc = gc[t.seg], F0 = tilefg[blockIdx.x];
+  const double cf = TRAIN ? coef[t.seg] : 0.0;
+  const int g = t.seg / q.nc, c = t.seg % q.nc;
+  double my[1] = {0.0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (!ok[j]) continue;
+    const long long k = (long long)t.tile * LV_TILE + j * 256 + threadIdx.x;
+    const long long fb = F0 + rank[j], I = Gc - fb, U = Gc + (k - fb);
+    const double dl = U <= 0 ? 1.0 : f[j] ? 1.0 / (double)U : (double)I / ((double)U * (double)(U + 1));
+    my[0] += (double)__uint_as_float(key[j]) * dl;
+    if (TRAIN) {
+      const long long idx = (long long)LvPay<PL>::idx(pl[j]);
+      const long long b = per_image ? g : idx / plane, in = per_image ? idx : idx % plane;
+      if (idx < q.ng) hplane[(b * q.nc + c) * plane + in] = (float)(cf * (f[j] ? -dl : dl));  // idx < ng always: the keys kernel wrote it
+    }
+  }
+  block_to_part<1>(my, sm, part);
+}
+
+// L9a: one workgroup per segment: L_c = the tiles' partials in order (0 for a segment the sort skipped).
+__global__ __launch_bounds__(256) void seg_lovasz_reduce_kernel(const double* part, LvGeom q, const int* nvalid, const int* gc, double* L) {
+  __shared__ double sh[1][256];
+  const int seg = blockIdx.x;
+  int nt;
+  if (!lv_segment_live(q, nvalid, gc, seg, &nt)) nt = 0;
+  double v[1];
+  partials_sum_256<1>(part + (long long)seg * q.tps, nt, 1, v, sh);
+  if (threadIdx.x == 0) L[seg] = v[0];
+}
+
+// L9b: one workgroup: the group losses, the stats (0, 0, Y_c, L_c), the combined loss and, in training (hdr not null), the base's scale --
+// seg_region_solve_kernel's tail.
+__global__ __launch_bounds__(256) void seg_lovasz_solve_kernel(const double* L, const int* gc, int G, int nc, LovaszCfg cfg, const float* v,
+                                                               const float* base_loss, const double* base_acc, int norm_mode, double norm_const, float* hdr,
+                                                               double* stats, float* loss_out) {
+  __shared__ double sh[2][256];
+  double total = 0.0;
+  for (int g = 0; g < G; ++g) {
+    const int* gg = gc + (long long)g * nc;
+    double m[2] = {0.0, 0.0};
+    for (int c = threadIdx.x; c < nc; c += 256) {
+      const double w = lovasz_mv(cfg, gg, v, c);
+      m[0] += w;
+      m[1] += w * L[(long long)g * nc + c];
+    }
+    block_tree_256<2>(m, sh);
+    total += m[0] > 0.0 ? m[1] / m[0] : 0.0;
+    for (int c = threadIdx.x; c < nc; c += 256) {
+      const long long o = (long long)g * nc + c;
+      stats[4 * o] = 0.0;
+      stats[4 * o + 1] = 0.0;
+      stats[4 * o + 2] = (double)gg[c];
+      stats[4 * o + 3] = L[o];
+    }
+  }
+  if (threadIdx.x == 0) {
+    const double lov = total / (double)G;
+    loss_out[0] = base_loss ? (float)(cfg.base_weight * (double)base_loss[0] + cfg.weight * lov) : (float)(cfg.weight * lov);
+    if (hdr) {
+      const double denom = norm_mode == 0 ? norm_const : (base_acc && base_acc[1] > 0.0 ? base_acc[1] : 1.0);
+      hdr[0] = (float)(cfg.base_weight / denom);
+    }
+  }
+}
+
+// L10: seg_region_grad_kernel with h_c read from the plane L8 wrote (0 where coef is 0: the sort skipped the class and wrote nothing):
+// base_weight * g_base / normaliser + p_k (h_k - sum_c p_c h_c) -> the gradient plane, in place with a base.
+__global__ __launch_bounds__(256) void seg_lovasz_grad_kernel(const float* rows, cvx_seg_dims d, const long long* target, long long ignore_index,
+                                                              const float* hplane, const double* coef, int per_image, const float* hdr, int has_base,
+                                                              float* dlogits) {
+  const int nc = d.nc;
+  const long long plane = (long long)d.oh * d.ow;
+  const long long n = (long long)d.batch * plane;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const SegPixel px(i, d, target, ignore_index, nullptr);
+  const long long at = (long long)px.b * nc * plane + (long long)px.oy * d.ow + px.ox;
+  float* dl = dlogits + at;
+  if (!px.valid) {  // with a base the plane holds the base's zero here already
+    if (!has_base)
+      for (int c = 0; c < nc; ++c) dl[(long long)c * plane] = 0.f;
+    return;
+  }
+  const int tg = (int)px.tg;
+  const float* hp = hplane + at;
+  const double* cf = coef + (long long)(per_image ? px.b : 0) * nc;
+  const PixelTaps tp(rows, d, px.b, px.oy, px.ox);
+  const bool vec = rows_vec(rows, d.ld);
+  auto h = [&](int c) {
+    const float x = hp[(long long)c * plane];
+    return cf[c] != 0.0 ? x : 0.f;
+  };
+  const Softmax q = online_softmax(tp, nc, vec, tg, [&](int c, float) { return h(c); });
+  const float lse = q.lse, S = q.sg / q.se;
+  const float sb = has_base ? hdr[0] : 0.f;
+  if (vec) {  // eight classes at a time: the base's eight gradients and the eight coefficients are loaded together, ahead of the eight stores
+    for (int c0 = 0; c0 < nc; c0 += 8) {
+      float z[8], old[8], hc[8];
+      tp.logits8(c0, z);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        old[k] = has_base && c0 + k < nc ? dl[(long long)(c0 + k) * plane] : 0.f;
+        hc[k] = c0 + k < nc ? h(c0 + k) : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c0 + k < nc) dl[(long long)(c0 + k) * plane] = fmaf(sb, old[k], expf(z[k] - lse) * (hc[k] - S));
+    }
+  } else {
+    for (int c = 0; c < nc; ++c) {
+      float* o = dl + (long long)c * plane;
+      *o = fmaf(sb, has_base ? *o : 0.f, expf(tp.logit(c) - lse) * (h(c) - S));
+    }
+  }
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------
 
 inline bool seg_ohem(const cvx_seg_criterion& c) { return !(c.ohem_theta < 0.f); }  // -ln thresh >= 0; negative: off
@@ -804,17 +1174,22 @@ inline long long seg_eval_blocks(long long npix) { return cvx_cdiv(npix, 256 * E
 inline long long seg_kept_sum_blocks(long long npix) { return cvx_cdiv(npix, 256 * KS_PIX); }
 inline int seg_region_bpi(const cvx_seg_dims& d) { return cvx_cdiv((long long)d.oh * d.ow, 256 * RS_PIX); }
 inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline int seg_lovasz_bpk(const cvx_seg_dims& d) { return cvx_cdiv((long long)d.oh * d.ow, LV_TILE); }
+inline long long seg_lovasz_ng(const cvx_seg_dims& d, const cvx_seg_criterion& c) { return (c.per_image ? 1LL : (long long)d.batch) * d.oh * d.ow; }
 
 // Every offset into the workspace.  The first CVX_SEG_OPTS_KEY_OFFSET bytes hold the small state -- the totals acc[2] at 0, the OHEM
 // selection at 64, the region header at SEG_HDR (hdr[0] the base's scale, hdr[1] the base's value, then evaluation's bad-label flag) --
 // so the key plane starts at that constant in every configuration.  Then, each a multiple of 256 bytes and present only when used:
 // [key plane, loss plane] (OHEM); the base's partials [and the kept sum's]; the region's sums, coefficients and partials (its size does
-// not depend on the base or on for_eval); last the gradient plane (training).
+// not depend on the base or on for_eval); the Lovasz term's state (region 2: the block counts and offsets, the counts per group and
+// class, the coefficients, L_c, the segment table, the sort's tables, the tiles' flag counts and partials, then the two ping-pong
+// buffers of keys and payload -- the payload is one byte in evaluation, four in training); last the gradient plane (training).
 constexpr size_t SEG_SELECT = 64, SEG_HDR = 2048;
 static_assert(SEG_SELECT + sizeof(SegSelect) <= SEG_HDR && SEG_HDR + 256 <= CVX_SEG_OPTS_KEY_OFFSET,
               "the totals, the selection state and the region header sit in front of the key plane");
 struct SegLayout {
   size_t key, lplane, part, part_kept, sums, coef, rpart, dlogits, total;
+  size_t lv_blkcnt, lv_blkoff, lv_nvalid, lv_gc, lv_coef, lv_L, lv_segtab, lv_binbase, lv_tilehist, lv_tilefg, lv_part, lv_key[2], lv_pay[2];
   SegLayout(const cvx_seg_dims& d, const cvx_seg_criterion& c, bool for_eval) {
     const size_t npix = (size_t)seg_npix(d);
     size_t o = CVX_SEG_OPTS_KEY_OFFSET;
@@ -829,9 +1204,27 @@ struct SegLayout {
     part = take(for_eval ? (size_t)seg_eval_blocks(npix) * 16 : c.base == 0 ? 0 : (size_t)seg_pixel_blocks(npix) * 24);
     part_kept = take(ohem ? (size_t)seg_kept_sum_blocks(npix) * 24 : 0);
     const size_t G = c.per_image ? (size_t)d.batch : 1, nc = (size_t)d.nc;
-    sums = take(c.region ? G * 3 * nc * 8 : 0);
-    coef = take(c.region ? G * 2 * nc * 4 : 0);
-    rpart = take(c.region ? (size_t)d.batch * seg_region_bpi(d) * 3 * nc * 8 : 0);
+    sums = take(c.region == 1 ? G * 3 * nc * 8 : 0);
+    coef = take(c.region == 1 ? G * 2 * nc * 4 : 0);
+    rpart = take(c.region == 1 ? (size_t)d.batch * seg_region_bpi(d) * 3 * nc * 8 : 0);
+    const bool lv = c.region == 2;
+    const size_t nblk = lv ? (size_t)d.batch * seg_lovasz_bpk(d) : 0, nseg = lv ? G * nc : 0, ng = lv ? (size_t)seg_lovasz_ng(d, c) : 0;
+    const size_t tiles = nseg * (size_t)cvx_cdiv((long long)ng, LV_TILE), pay = for_eval ? 1 : 4;
+    lv_blkcnt = take(nblk * 4);
+    lv_blkoff = take(nblk * 4);
+    lv_nvalid = take(lv ? G * 4 : 0);
+    lv_gc = take(nseg * 4);
+    lv_coef = take(nseg * 8);
+    lv_L = take(nseg * 8);
+    lv_segtab = take(nseg * 16);
+    lv_binbase = take(nseg * 256 * 4);
+    lv_tilehist = take(tiles * 256 * 4);
+    lv_tilefg = take(tiles * 4);
+    lv_part = take(tiles * 8);
+    for (int q = 0; q < 2; ++q) {
+      lv_key[q] = take(nseg * ng * 4);
+      lv_pay[q] = take(nseg * ng * pay);
+    }
     dlogits = o;
     total = o + (for_eval ? 0 : npix * nc * 4);
   }
@@ -925,6 +1318,45 @@ void seg_region_chain(const float* rows, const cvx_seg_dims& d, const long long*
                        ch->acc != nullptr, ch->dlogits);
 }
 
+// L1 .. L9 and, in training (ch not null), L10 on the gradient plane the base chain left (ch->acc null: no base).  PL: the payload.
+// The plane of L8 lies in the second key buffer, which the sort has left by then; the sorted keys and payload stay in the first.
+template <class PL>
+void seg_lovasz_chain(const float* rows, const cvx_seg_dims& d, const long long* tg, const cvx_seg_criterion& c, const SegLayout& lay, char* w,
+                      const float* base_loss, const SegChain* ch, int32_t* bad, double* region_stats_out, float* loss_out, hipStream_t st) {
+  const int bpk = seg_lovasz_bpk(d), G = c.per_image ? d.batch : 1, nseg = G * d.nc, nblk = d.batch * bpk, ppg = c.per_image ? bpk : nblk;
+  const long long ig = (long long)c.ignore_index, plane = (long long)d.oh * d.ow;
+  const LvGeom q{seg_lovasz_ng(d, c), cvx_cdiv(seg_lovasz_ng(d, c), LV_TILE), d.nc, c.skip_absent != 0};
+  const unsigned tiles = (unsigned)nseg * (unsigned)q.tps;
+  int *blkcnt = (int*)(w + lay.lv_blkcnt), *blkoff = (int*)(w + lay.lv_blkoff), *nvalid = (int*)(w + lay.lv_nvalid), *gc = (int*)(w + lay.lv_gc);
+  double *coef = (double*)(w + lay.lv_coef), *L = (double*)(w + lay.lv_L), *part = (double*)(w + lay.lv_part);
+  unsigned *binbase = (unsigned*)(w + lay.lv_binbase), *tilehist = (unsigned*)(w + lay.lv_tilehist), *tilefg = (unsigned*)(w + lay.lv_tilefg);
+  unsigned *ka = (unsigned*)(w + lay.lv_key[0]), *kb = (unsigned*)(w + lay.lv_key[1]);
+  PL *pa = (PL*)(w + lay.lv_pay[0]), *pb = (PL*)(w + lay.lv_pay[1]);
+  float *hdr = (float*)(w + SEG_HDR), *hplane = (float*)kb;
+  const LovaszCfg cfg{c.weight, c.base_weight, c.skip_absent != 0};
+  hipMemsetAsync(gc, 0, (size_t)nseg * 4, st);
+  hipLaunchKernelGGL(seg_lovasz_count_kernel, dim3((unsigned)nblk), dim3(256), 0, st, tg, d, ig, bpk, blkcnt);
+  hipLaunchKernelGGL(seg_lovasz_offsets_kernel, dim3((unsigned)G), dim3(256), 0, st, (const int*)blkcnt, ppg, blkoff, nvalid);
+  hipLaunchKernelGGL(seg_lovasz_keys_kernel<PL>, dim3((unsigned)nblk), dim3(256), 0, st, rows, d, tg, ig, bpk, c.per_image, (const int*)blkoff, ka, pa, gc, bad);
+  hipLaunchKernelGGL(seg_lovasz_plan_kernel, dim3(1), dim3(256), 0, st, (const int*)gc, (const int*)nvalid, G, d.nc, q.ng, cfg, c.region_class_weight, coef,
+                     (long long*)(w + lay.lv_segtab));
+  lv_sort<PL>(ka, pa, kb, pb, q, nseg, nvalid, gc, tilehist, binbase, st);
+  hipLaunchKernelGGL(seg_lovasz_flagsum_kernel<PL>, dim3(tiles), dim3(256), 0, st, (const PL*)pa, q, (const int*)nvalid, (const int*)gc, tilefg);
+  hipLaunchKernelGGL(seg_lovasz_flagscan_kernel, dim3((unsigned)nseg), dim3(256), 0, st, q, (const int*)nvalid, (const int*)gc, tilefg);
+  if (ch)
+    hipLaunchKernelGGL((seg_lovasz_value_kernel<PL, true>), dim3(tiles), dim3(256), 0, st, (const unsigned*)ka, (const PL*)pa, q, (const int*)nvalid,
+                       (const int*)gc, (const unsigned*)tilefg, (const double*)coef, c.per_image, plane, hplane, part);
+  else
+    hipLaunchKernelGGL((seg_lovasz_value_kernel<PL, false>), dim3(tiles), dim3(256), 0, st, (const unsigned*)ka, (const PL*)pa, q, (const int*)nvalid,
+                       (const int*)gc, (const unsigned*)tilefg, (const double*)coef, c.per_image, plane, (float*)nullptr, part);
+  hipLaunchKernelGGL(seg_lovasz_reduce_kernel, dim3((unsigned)nseg), dim3(256), 0, st, (const double*)part, q, (const int*)nvalid, (const int*)gc, L);
+  hipLaunchKernelGGL(seg_lovasz_solve_kernel, dim3(1), dim3(256), 0, st, (const double*)L, (const int*)gc, G, d.nc, cfg, c.region_class_weight, base_loss,
+                     ch ? ch->acc : nullptr, ch ? ch->norm_mode : 0, ch ? ch->norm_const : 1.0, ch ? hdr : nullptr, region_stats_out, loss_out);
+  if (ch)
+    hipLaunchKernelGGL(seg_lovasz_grad_kernel, dim3((unsigned)seg_pixel_blocks(seg_npix(d))), dim3(256), 0, st, rows, d, tg, ig, (const float*)hplane,
+                       (const double*)coef, c.per_image, (const float*)hdr, ch->acc != nullptr, ch->dlogits);
+}
+
 // The checks every entry makes; null when the arguments are good.
 const char* seg_check(const cvx_seg_dims* dp, const cvx_seg_criterion* cp, bool for_eval) {
   if (!dp || !cp) return "null arguments";
@@ -941,7 +1373,15 @@ const char* seg_check(const cvx_seg_dims* dp, const cvx_seg_criterion* cp, bool 
   }
   if (!c.region) return c.base != 0 ? nullptr : "base 0 takes a region term";
   if (!(d.nc <= REGION_MAX_NC)) return "the region losses take at most 1024 classes";
+  if (!(c.region == 1 || c.region == 2)) return "region: 0 none, 1 Dice / Tversky, 2 Lovasz-Softmax";
   if (!(isfinite(c.weight) && c.weight > 0.0 && isfinite(c.base_weight) && c.base_weight >= 0.0)) return "weight > 0, base_weight >= 0";
+  if (c.region == 2) {
+    if ((c.base != 0) != (c.base_weight > 0.0)) return "a base term needs base_weight > 0, and base_weight = 0 takes base = 0";
+    const long long ng = seg_lovasz_ng(d, c);
+    if (!(ng < (1LL << 31))) return "the Lovasz term takes groups of fewer than 2^31 pixels";
+    if (!((long long)(c.per_image ? d.batch : 1) * d.nc * cvx_cdiv(ng, LV_TILE) < (1LL << 31))) return "too many sort tiles";
+    return nullptr;
+  }
   if (!(isfinite(c.alpha) && c.alpha >= 0.0 && isfinite(c.beta) && c.beta >= 0.0 && isfinite(c.gamma) && c.gamma > 0.0 && isfinite(c.smooth) && c.smooth >= 0.0))
     return "alpha, beta, smooth >= 0 and gamma > 0";
   if ((c.base != 0) != (c.base_weight > 0.0)) return "a base term needs base_weight > 0, and base_weight = 0 takes base = 0";
@@ -954,6 +1394,18 @@ const char* seg_check(const cvx_seg_dims* dp, const cvx_seg_criterion* cp, bool 
 extern "C" int64_t cvx_seg_criterion_workspace_bytes(const cvx_seg_dims* dims, const cvx_seg_criterion* crit, int32_t for_eval) {
   if (seg_check(dims, crit, for_eval != 0)) return 0;
   return (int64_t)SegLayout(*dims, *crit, for_eval != 0).total;
+}
+
+extern "C" int cvx_seg_criterion_lovasz_view(const cvx_seg_dims* dims, const cvx_seg_criterion* crit, int64_t offsets_out[3]) {
+  CVX_CHECK(offsets_out != nullptr, "null arguments");
+  const char* why = seg_check(dims, crit, false);
+  CVX_CHECK(why == nullptr, why);
+  CVX_CHECK(crit->region == 2, "the criterion has no Lovasz term");
+  const SegLayout lay(*dims, *crit, false);
+  offsets_out[0] = (int64_t)lay.lv_key[0];
+  offsets_out[1] = (int64_t)lay.lv_pay[0];
+  offsets_out[2] = (int64_t)lay.lv_segtab;
+  return 0;
 }
 
 extern "C" int cvx_seg_criterion_loss(const float* rows_f32, const cvx_seg_dims* dims, const int64_t* target, const cvx_seg_criterion* crit,
@@ -976,8 +1428,9 @@ extern "C" int cvx_seg_criterion_loss(const float* rows_f32, const cvx_seg_dims*
   SegChain ch{(float*)(w + lay.dlogits), nullptr, 0, 1.0};
   if (c.base != 0) ch = seg_base_chain(rows_f32, d, tg, c, lay, w, nullptr, c.region ? hdr + 1 : loss_out, bad_target, stats_out, st);
   if (c.region) {
-    seg_region_chain(rows_f32, d, tg, c, lay, w, c.base != 0 ? hdr + 1 : nullptr, &ch, bad_target, region_stats_out, loss_out, st);
-    ch = SegChain{ch.dlogits, nullptr, 0, 1.0};  // R4 left the plane normalised
+    if (c.region == 2) seg_lovasz_chain<unsigned>(rows_f32, d, tg, c, lay, w, c.base != 0 ? hdr + 1 : nullptr, &ch, bad_target, region_stats_out, loss_out, st);
+    else seg_region_chain(rows_f32, d, tg, c, lay, w, c.base != 0 ? hdr + 1 : nullptr, &ch, bad_target, region_stats_out, loss_out, st);
+    ch = SegChain{ch.dlogits, nullptr, 0, 1.0};  // R4 / L10 left the plane normalised
   }
   launch_adjoint(ch, d, loss_scale, dpred_f16, st);
   CVX_HIP(hipGetLastError());
@@ -1000,7 +1453,8 @@ extern "C" int cvx_seg_criterion_eval(const float* rows_f32, const cvx_seg_dims*
   if (c.region) {
     int32_t* bad = (int32_t*)(w + SEG_HDR + 8);  // R1 raises it; evaluation does not report it
     CVX_HIP(hipMemsetAsync(bad, 0, 4, st));
-    seg_region_chain(rows_f32, d, tg, c, lay, w, c.base != 0 ? loss_out : nullptr, nullptr, bad, region_stats_out, loss_out, st);
+    if (c.region == 2) seg_lovasz_chain<unsigned char>(rows_f32, d, tg, c, lay, w, c.base != 0 ? loss_out : nullptr, nullptr, bad, region_stats_out, loss_out, st);
+    else seg_region_chain(rows_f32, d, tg, c, lay, w, c.base != 0 ? loss_out : nullptr, nullptr, bad, region_stats_out, loss_out, st);
   }
   CVX_HIP(hipGetLastError());
   return 0;

@@ -376,10 +376,20 @@ class SegLoss:
     ``(1 - T_c)^gamma`` over the classes, those without a target pixel left out under ``skip_absent``.  Dice is ``alpha = beta = 0.5``.
     ``base_weight = 0`` trains on the region loss alone (the base chain is skipped).  OHEM selects pixels for the base term only.
     ``region_stats`` is the float64 device tensor ``(G, nc, 4)`` = I, P = sum p, Y = sum y, T of the last call (G = batch under
-    ``per_image``, else 1).  Data parallel: every rank takes the sums over its own shard, like OHEM and the weighted denominators."""
+    ``per_image``, else 1).  Data parallel: every rank takes the sums over its own shard, like OHEM and the weighted denominators.
+
+    ``lovasz=dict(weight=1.0, base_weight=1.0, per_image=False, skip_absent=True, class_weights=None)`` (see ``seg_lovasz_defaults``;
+    not together with ``region=``) adds the Lovasz-Softmax loss (Berman et al., CVPR 2018), the surrogate of the mean IoU, in the same
+    way: the value is ``base_weight * base + weight * lovasz``, the keys mean what they mean under ``region=``, ``skip_absent=True`` is
+    the paper's ``classes="present"`` and ``False`` its ``"all"``.  Per group and class the errors ``e = [t == c] ? 1 - p_c : p_c`` of
+    the valid pixels are sorted on the device (descending, ties by ascending pixel index) and weighted by the Lovasz extension's
+    increments of the Jaccard loss along that order; the rules are in ``include/cvx_engine.h``.  ``region_stats`` is then
+    ``(G, nc, 4)`` = 0, 0, Y_c, L_c, and ``lovasz_sorted()`` shows the order.  The sort's two ping-pong buffers of key + payload take
+    ``2 * 8`` bytes per pixel and class -- 1.4 GB of workspace at batch 16, 513 x 513 labels and 21 classes, next to the gradient
+    plane's 0.35 GB.  Data parallel: every rank sorts its own shard."""
 
     def __init__(self, loss_type: str = "focal", alpha: float = 0.25, gamma: float = 2.0, ignore_index: int = -100, check_targets: bool = True,
-                 class_weights=None, label_smoothing: float = 0.0, ohem=None, region=None):
+                 class_weights=None, label_smoothing: float = 0.0, ohem=None, region=None, lovasz=None):
         if loss_type not in ("focal", "ce"):
             raise ValueError("loss_type must be 'focal' or 'ce' (segmentation_2d.py:59-64)")
         self.mode = 0 if loss_type == "focal" else 1
@@ -392,8 +402,13 @@ class SegLoss:
         self.label_smoothing = float(label_smoothing)
         self.last_stats = None
         self._weights_dev = self._keys_shape = None
+        if region is not None and lovasz is not None:
+            raise ValueError("region= and lovasz= exclude each other: a criterion has one region term")
         self.region = seg_region_defaults(**region) if region is not None else None
         self.has_region = self.region is not None
+        self.lovasz = seg_lovasz_defaults(**lovasz) if lovasz is not None else None
+        self.has_lovasz = self.lovasz is not None
+        self._lovasz_view = None
         self.region_stats = None
         self._region_weights_dev = None
         self.has_options = class_weights is not None or self.label_smoothing != 0.0 or ohem is not None
@@ -440,13 +455,27 @@ class SegLoss:
         o = L.SEG_OPTS_KEY_OFFSET                          # the same offset whatever else the criterion holds
         return self._ws[o:o + B * H * W * 4].view(torch.float32).view(B, H, W)
 
+    def lovasz_sorted(self):
+        """``(keys, payload, segments)`` of the last training call, views of the workspace that the next call overwrites: ``keys``
+        uint32 (the fp32 bit patterns of the errors, sorted descending inside each segment), ``payload`` uint32 (the pixel's linear
+        index inside its group in bits 0..30, the foreground flag ``t == c`` in bit 31) and ``segments`` ``(G, nc, 2)`` int64 = element
+        offset into both arrays and length (the group's valid pixels; 0 for a class the sort skipped: one without a target pixel under
+        ``skip_absent``).  A debugging and test surface, like ``ohem_keys()``.  Does not synchronise."""
+        if not self.has_lovasz or self._lovasz_view is None:
+            raise L.CvxError("lovasz_sorted: the criterion has no lovasz term, or has not been called yet")
+        (groups, nc, ng), (okey, opay, oseg) = self._lovasz_view
+        n = groups * nc * ng
+        keys = self._ws[okey:okey + n * 4].view(torch.uint32)
+        payload = self._ws[opay:opay + n * 4].view(torch.uint32)
+        return keys, payload, self._ws[oseg:oseg + groups * nc * 16].view(torch.int64).view(groups, nc, 2)
+
     def _criterion_struct(self, dev, nc: int, batch: int) -> L.SegCriterion:
         """``cvx_seg_criterion`` of this criterion for ``nc`` classes and ``batch`` images, its weights on ``dev`` (copied once; their
         lengths are checked here, where ``nc`` is known).  ``base_weight = 0`` drops the base term and its options with it."""
-        r = self.region
+        r = self.region if self.region is not None else self.lovasz
         with_base = r is None or r["base_weight"] > 0.0
         c = L.SegCriterion(base=(1 if self.mode == 0 else 2) if with_base else 0, focal_alpha=self.alpha, focal_gamma=self.gamma,
-                           ignore_index=self.ignore_index, ohem_theta=-1.0, region=int(r is not None))
+                           ignore_index=self.ignore_index, ohem_theta=-1.0, region=2 if self.has_lovasz else int(r is not None))
         if with_base and self.has_options:
             weights = self.weights_on(dev, nc)
             c.class_weight = weights.data_ptr() if weights is not None else None
@@ -457,17 +486,19 @@ class SegLoss:
             rw = r["class_weights"]
             if rw is not None:
                 if rw.numel() != nc:
-                    raise ValueError(f"region class_weights has {rw.numel()} entries for {nc} classes")
+                    raise ValueError(f"{'lovasz' if self.has_lovasz else 'region'} class_weights has {rw.numel()} entries for {nc} classes")
                 if self._region_weights_dev is None or self._region_weights_dev.device != dev:
                     self._region_weights_dev = rw.to(dev)
                 c.region_class_weight = self._region_weights_dev.data_ptr()
-            c.base_weight, c.weight, c.alpha, c.beta, c.gamma, c.smooth = (r[k] for k in ("base_weight", "weight", "alpha", "beta", "gamma", "smooth"))
+            c.base_weight, c.weight = r["base_weight"], r["weight"]
+            if not self.has_lovasz:
+                c.alpha, c.beta, c.gamma, c.smooth = (r[k] for k in ("alpha", "beta", "gamma", "smooth"))
             c.per_image, c.skip_absent = int(r["per_image"]), int(r["skip_absent"])
         return c
 
     def _ensure_buffers(self, lib, dev, dims: L.SegDims, crit: L.SegCriterion, for_eval: bool = False) -> torch.Tensor:
         """The workspace of this call (training and validation each keep their own), with the bad-label flag, ``last_stats`` (a
-        criterion with options or a region term) and ``region_stats`` (one with a region term) next to it: allocated by the first call of a shape and kept."""
+        criterion with options or a region / Lovasz term) and ``region_stats`` (one with such a term) next to it: allocated by the first call of a shape and kept."""
         need = int(lib.cvx_seg_criterion_workspace_bytes(C.byref(dims), C.byref(crit), int(for_eval)))
         if need <= 0:
             raise L.CvxError("cvx_seg_criterion_workspace_bytes: bad sizes, or a criterion the library refuses")
@@ -478,10 +509,11 @@ class SegLoss:
             setattr(self, name, ws)
         if self._bad is None or self._bad.device != dev:
             self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        if (self.has_options or self.has_region) and (self.last_stats is None or self.last_stats.device != dev):   # zeros without an option
+        has_term = self.has_region or self.has_lovasz
+        if (self.has_options or has_term) and (self.last_stats is None or self.last_stats.device != dev):   # zeros without an option
             self.last_stats = torch.zeros(4, dtype=torch.float64, device=dev)
         shape = (dims.batch if crit.per_image else 1, dims.nc, 4)
-        if self.has_region and (self.region_stats is None or self.region_stats.device != dev or tuple(self.region_stats.shape) != shape):
+        if has_term and (self.region_stats is None or self.region_stats.device != dev or tuple(self.region_stats.shape) != shape):
             self.region_stats = torch.zeros(shape, dtype=torch.float64, device=dev)
         return ws
 
@@ -508,6 +540,13 @@ class SegLoss:
                     "cvx_seg_criterion_loss")
         if crit.ohem_theta >= 0.0:
             self._keys_shape = (B, dims.oh, dims.ow)
+        if self.has_lovasz:
+            groups = B if crit.per_image else 1
+            key = (groups, nc, (B // groups) * dims.oh * dims.ow)
+            if self._lovasz_view is None or self._lovasz_view[0] != key:
+                offs = (C.c_int64 * 3)()
+                L.check(lib.cvx_seg_criterion_lovasz_view(C.byref(dims), C.byref(crit), offs), "cvx_seg_criterion_lovasz_view")
+                self._lovasz_view = (key, tuple(int(o) for o in offs))
         if (self.check_targets if check is None else check) and self.bad_targets():
             raise L.CvxError("SegLoss: a target label is neither ignore_index nor in [0, num_classes)")
         return loss, dpred
@@ -557,6 +596,31 @@ def seg_region_defaults(kind: str = "dice", **kw) -> dict:
         w = torch.as_tensor(kw["class_weights"], dtype=torch.float32).detach().cpu().reshape(-1).clone()
         if w.numel() == 0 or not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not bool((w > 0).any()):
             raise ValueError("region: class_weights must be finite, non-negative and not all zero")
+        r["class_weights"] = w
+    return r
+
+
+_LOVASZ_KEYS = ("weight", "base_weight", "per_image", "skip_absent", "class_weights")
+
+
+def seg_lovasz_defaults(**kw) -> dict:
+    """The filled-in ``lovasz=`` dict of ``SegLoss``: ``weight`` 1, ``base_weight`` 1 (0: the Lovasz term alone), ``per_image`` False,
+    ``skip_absent`` True (the paper's ``classes="present"``), ``class_weights`` None.  Raises ``ValueError`` for an unknown key and for
+    a value outside its range."""
+    unknown = sorted(set(kw) - set(_LOVASZ_KEYS))
+    if unknown:
+        raise ValueError(f"lovasz: unknown keys {unknown}")
+    r = {"weight": 1.0 if kw.get("weight") is None else float(kw["weight"]),
+         "base_weight": 1.0 if kw.get("base_weight") is None else float(kw["base_weight"]), "per_image": bool(kw.get("per_image", False)),
+         "skip_absent": True if kw.get("skip_absent") is None else bool(kw["skip_absent"]), "class_weights": None}
+    if not (math.isfinite(r["weight"]) and math.isfinite(r["base_weight"])):
+        raise ValueError("lovasz: every value must be finite")
+    if r["weight"] <= 0 or r["base_weight"] < 0:
+        raise ValueError("lovasz: weight > 0 and base_weight >= 0")
+    if kw.get("class_weights") is not None:
+        w = torch.as_tensor(kw["class_weights"], dtype=torch.float32).detach().cpu().reshape(-1).clone()
+        if w.numel() == 0 or not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not bool((w > 0).any()):
+            raise ValueError("lovasz: class_weights must be finite, non-negative and not all zero")
         r["class_weights"] = w
     return r
 

@@ -63,13 +63,13 @@ class DeeplabV3PlusA(FramePredictor):
         ignore_index -100, mean over all pixels; core/loss/focal_loss.py:6-22).  Beyond the reference, ``cfg.loss.class_weights``,
         ``cfg.loss.label_smoothing`` and ``cfg.loss.ohem`` (absent by default: the config file stays the reference's) select the
         options of the fused cross-entropy, and ``cfg.loss.region = dict(kind="dice" | "tversky", ...)`` adds a region loss to either
-        loss type, see ``SegLoss``."""
+        loss type and ``cfg.loss.lovasz = dict(...)`` the Lovasz-Softmax loss, see ``SegLoss``."""
         if self.loss_type not in ("ce", "focal"):
             raise L.CvxError(f"loss_type {self.loss_type!r}: the reference knows 'ce' and 'focal'")
         loss_cfg = self.cfg.loss
         return SegLoss(self.loss_type, class_weights=getattr(loss_cfg, "class_weights", None),
                        label_smoothing=getattr(loss_cfg, "label_smoothing", 0.0), ohem=getattr(loss_cfg, "ohem", None),
-                       region=getattr(loss_cfg, "region", None))
+                       region=getattr(loss_cfg, "region", None), lovasz=getattr(loss_cfg, "lovasz", None))
 
     def predict_tensor(self, model, images: torch.Tensor, scales=None, flip=False, fuse="prob"):
         """(B,3,H,W) normalised images on the device -> (B,H,W,3) class colours (the tensor part of ``predict``).  ``scales`` / ``flip``

@@ -80,7 +80,7 @@ class SegmentationMetrics:
         ``confusion[target][argmax of the upsampled logits] += 1`` and ``criterion``'s (a ``SegLoss``) value of the batch into
         ``loss_slot``, a one-element float32 view on the rows' device, in one ``cvx_seg_criterion_eval`` call.  A criterion with options
         (class weights, label smoothing) gives the weighted, smoothed value over all valid pixels and the same matrix; its OHEM setting
-        is not applied in evaluation.  With a region term (``SegLoss(region=)``) the value-only region chain follows (no gradient plane,
+        is not applied in evaluation.  With a region term (``SegLoss(region=)`` or ``SegLoss(lovasz=)``) the value-only chain of that term follows (no gradient plane,
         no adjoint), so that the slot holds ``base_weight * base + weight * region`` of the batch; the matrix is the
         eval launch's.  Asynchronous: nothing is read back."""
         if not (torch.is_tensor(rows) and rows.is_cuda):

@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define CVX_ABI_VERSION 5
+#define CVX_ABI_VERSION 6
 
 const char* cvx_last_error(void);
 int cvx_abi_version(void);
@@ -508,6 +508,36 @@ int cvx_resize_bilinear_rows_to_nchw(const float* rows_f32, int32_t ld, int32_t 
  *     m_c = [Y_c > 0] when skip_absent != 0, else 1; v = region_class_weight (nc floats on the device; null: ones);
  *     region = mean of the group losses.  alpha = beta = 0.5 is the Dice loss, gamma != 1 the focal Tversky loss.  nc <= 1024.
  *   OHEM selects pixels for the base term only.
+ * region == 2, the Lovasz-Softmax loss (Berman et al., CVPR 2018), the surrogate of the mean IoU.  weight, base_weight, per_image,
+ *   skip_absent and region_class_weight are read as above; alpha, beta, gamma and smooth are ignored.  Groups and valid pixels as above;
+ *   the pixel index inside a group is its linear (b, y, x) index.  Per group and class c, over the group's valid pixels:
+ *     f = [t == c], e = f ? 1 - p_c : p_c, in fp32 from exp(z_c - lse) (1 - p_c clamped at 0); G_c = sum f (the Y_c of the stats).
+ *     For e alone the two interpolation weights of a pixel come from a source coordinate formed in double -- the fp32 coordinate the
+ *     rest of the criterion shares with cvx_resize_bilinear_rows_to_nchw puts up to 3e-6 on a logit, and the keys are held to 1e-6 of
+ *     float64 --; the gradient's p_k are the shared values.
+ *     The pixels are ordered by e descending, ties by ascending pixel index; the order is that of the fp32 bit patterns of e, which are
+ *     non-negative and so order as uint32.  Along that order I_k = G_c - #foreground among the first k + 1, U_k = G_c + #background
+ *     among the first k + 1, J_k = 1 - I_k / U_k, Delta_k = J_k - J_{k-1} with J_{-1} = 0, and L_c = sum_k e_(k) Delta_k.  With the
+ *     state before element k: Delta = 1 / U_prev at a foreground element, I_prev / (U_prev (U_prev + 1)) at a background one; the
+ *     first element of a class with G_c = 0 has Delta = 1.  I and U are integers: Delta is exact to one division in double and no
+ *     prefix sum is a floating-point sum.
+ *     group loss = sum_c m_c v_c L_c / sum_c m_c v_c (0 when that is 0), m_c = [G_c > 0] when skip_absent != 0 (the paper's
+ *     classes="present"), else 1 ("all"); lovasz = the mean of the group losses over the G groups; a group without a valid pixel
+ *     contributes 0 and still counts.  loss = base_weight * base + weight * lovasz.
+ *     Gradient: h_c(pixel) = (1/G) m_c v_c / sum m v * s * Delta_{rank_c(pixel)}, s = -1 where t == c and +1 elsewhere;
+ *     d lovasz / d z_k = p_k (h_k - sum_c p_c h_c) at a valid pixel, 0 elsewhere.
+ *   The order comes from a segmented, stable radix sort on the device (four 8-bit passes; ranks are ballot counts, never the arrival
+ *   order of atomics; kernel boundaries are the only synchronisation between workgroups).  Any bit pattern is a legal key: logits that
+ *   are not finite give some order and no store outside the segment.  Classes without a target pixel under skip_absent, and groups
+ *   without a valid pixel, are not sorted.  nc <= 1024, a group has fewer than 2^31 pixels, and base_weight fits base as for region 1;
+ *   otherwise the entry refuses.  region_stats_out: (G, nc, 4) = 0, 0, Y_c, L_c (L_c = 0 for a class that was not sorted).
+ *   cvx_seg_criterion_lovasz_view (host only) writes three byte offsets into the TRAINING workspace: the sorted keys (uint32, the bit
+ *   patterns of e), the payload (uint32: the pixel index inside its group in bits 0..30, the foreground flag in bit 31) and the segment
+ *   table (G, nc, 2) int64 = element offset into the two arrays and length (the group's valid pixels; 0 for a class that was not
+ *   sorted).  They hold the last training call's order until the next call.  The workspace holds two ping-pong buffers of key + payload,
+ *   2 * 8 bytes per (pixel, class) in training -- 1.4 GB at batch 16, 513 x 513, 21 classes -- next to the gradient plane's 4;
+ *   evaluation (value only: the chain stops at L_c) carries a one-byte payload and no gradient plane: 10 bytes against 20.
+ *   Launches: 22 and one memset for the term in training (21 in evaluation), plus the base's and the adjoint.
  * Every floating-point sum runs in a fixed order (per-workgroup trees, then the partials in index order; no floating-point atomics): two
  * calls give the same bits.
  * cvx_seg_criterion_loss: loss_out: 1 float (device).  dpred: (batch, ih*iw, ld) fp16 = loss_scale * dLoss/drows (columns nc..ld-1 zero) --
@@ -544,7 +574,7 @@ typedef struct cvx_seg_criterion {
   int64_t ignore_index;
   float ohem_theta;
   int64_t ohem_min_kept;
-  int32_t region; /* 0 or 1 */
+  int32_t region; /* 0 none, 1 Dice / Tversky, 2 Lovasz-Softmax */
   double base_weight, weight, alpha, beta, gamma, smooth;
   int32_t per_image, skip_absent;
   const float* region_class_weight;
@@ -555,6 +585,7 @@ int cvx_seg_criterion_loss(const float* rows_f32, const cvx_seg_dims* dims, cons
                            void* hip_stream);
 int cvx_seg_criterion_eval(const float* rows_f32, const cvx_seg_dims* dims, const int64_t* target, const cvx_seg_criterion* crit, int64_t* confusion,
                            float* loss_out, double* region_stats_out, void* workspace, void* hip_stream);
+int cvx_seg_criterion_lovasz_view(const cvx_seg_dims* dims, const cvx_seg_criterion* crit, int64_t offsets_out[3]);
 /* VOC mAP evaluation of a detector (get_map at IoU min_overlap), accumulated on the device batch by batch.
  * cvx_det_match, once per batch: rows (batch, max_det, 6) [x1,y1,x2,y2,score,cls] fp32 and counts (batch) int32 exactly as cvx_nms /
  * cvx_nms_variant write them; a count of -1 (or one past max_det) adds 1 to the overflow counter and the image contributes nothing.

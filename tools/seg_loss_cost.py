@@ -10,6 +10,8 @@ rows 129 x 129 with 24 columns.
              dice       the Dice region loss alone, base 0 (5 launches)
              ce_dice    cross-entropy + Dice (7 launches: the plain chain's two, the region's four, the adjoint)
              all_tversky   weights + smoothing + OHEM + focal Tversky (0.3 / 0.7, gamma 0.75) per image
+             lovasz     the Lovasz-Softmax loss alone, base 0 (23 launches and a memset: keys, four sort passes, scan, value, gradient, adjoint)
+             ce_lovasz  cross-entropy + Lovasz-Softmax (the plain chain's two launches in front)
 
 Every arm has its own criterion (workspace) and gradient buffer and the same rows and targets.  The arms are interleaved in blocks; each
 block times `--reps` back-to-back calls of every arm between two device events after a warm-up of every arm, and an arm's figure is the
@@ -20,6 +22,11 @@ histogram passes and the masked sum (with the loss plane and the targets), which
 kept (counted from the arm's own kept / valid figures).  A region term reads the rows and the targets once more for its sums and, in
 its gradient pass, a third time; with a base that pass reads and rewrites the gradient plane, without one it writes the plane (then
 the rows and targets are read twice in all, by the two region passes).  The partial sums (3 nc doubles per 2048 pixels) are not counted.
+The Lovasz term moves, per pixel and class: key + payload written once (8 bytes), read by each of the four histogram passes (4) and
+scatter passes (8) and written by each scatter (8), the payload read by the flag count (4), both read by the value pass (8), which
+writes the coefficient plane (4) that the gradient pass reads (4); it reads the rows and the targets three times (count and keys, then
+the gradient pass; the count reads the targets alone).  The sort's per-tile histograms (1 KB per 1024 keys and pass, written, scanned
+in place and read) are not counted.
 
     python tools/seg_loss_cost.py --blocks 9 --reps 20 --out profiles/seg_loss_cost.json
 """
@@ -69,6 +76,9 @@ def main():
                  "ce_dice": (SegLoss("ce", region=dict(kind="dice")), base + 2 * again + 2 * npix * nc * 4),
                  "all_tversky": (SegLoss("ce", class_weights=weights, label_smoothing=0.1, ohem=ohem,
                                          region=dict(kind="tversky", gamma=0.75, per_image=True)), mined + 2 * again + 2 * npix * nc * 4)})
+    lov = npix * nc * (8 + 4 * (4 + 8 + 8) + 4 + 8 + 4 + 4)
+    arms.update({"lovasz": (SegLoss("ce", lovasz=dict(base_weight=0.0)), base + again + npix * 8 + lov),
+                 "ce_lovasz": (SegLoss("ce", lovasz={}), base + 2 * again + npix * 8 + 2 * npix * nc * 4 + lov)})
     runs, values = {}, {}
     for name, (crit, _) in arms.items():
         crit.nc = nc
