@@ -153,6 +153,8 @@ PROTOTYPES = {
     "cvx_seg_fuse": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_det_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _F, _P, _P]),
     "cvx_det_fuse_views": (_I32, [_P, _P, _I32, _P, _P, _I32, _I32, _F, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "cvx_det_wbf_workspace_bytes": (_I64, [_I32]),
+    "cvx_det_fuse_wbf": (_I32, [_P, _P, _I32, _P, _P, _I32, _I32, _P, _F, _F, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "cvx_aug_images": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _P]),
     "cvx_aug_boxes": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_aug_images_plain": (_I32, [_P, _P, _I32, _P, _I32, _I32, _P]),

@@ -22,6 +22,7 @@
 #include "box_overlap.h"
 #include "lds_sort.h"
 #include "mask_nms.h"
+#include "view_box.h"
 #include "../../include/cvx_engine.h"
 
 #pragma clang fp contract(off)
@@ -131,13 +132,6 @@ struct FuseWs {
   unsigned long long* mat;  // [frames][FUSE_CAP][FUSE_CAP / 64]
 };
 
-// what a view reports -> the picture: a rounded product, a rounded add
-__device__ __forceinline__ float through(float v, float a, float c) {
-  const float m = v * a;
-  return m + c;
-}
-__device__ __forceinline__ float clamp_to(float v, int size) { return fminf(fmaxf(v, 0.f), (float)size); }
-
 __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int max_det_in,
                                                             const float* __restrict__ view_map, const int* __restrict__ frame_hw, int frames, int views,
                                                             float threshold, int class_agnostic, int mode, int score_mode, int max_det, FuseWs ws,
@@ -190,10 +184,8 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(const float* __restr
   for (int i = tid; i < n; i += FUSE_THREADS) {
     const int e = (int)(keys[i] & 0xFFFFFFFFu);
     const int s = e / max_det_in;
-    const float ax = view_map[4 * s], cx = view_map[4 * s + 1], ay = view_map[4 * s + 2], cy = view_map[4 * s + 3];
     const float* row = rows + (long long)e * 6;
-    const float tx1 = through(row[0], ax, cx), ty1 = through(row[1], ay, cy), tx2 = through(row[2], ax, cx), ty2 = through(row[3], ay, cy);
-    box[i] = make_float4(clamp_to(fminf(tx1, tx2), fw), clamp_to(fminf(ty1, ty2), fh), clamp_to(fmaxf(tx1, tx2), fw), clamp_to(fmaxf(ty1, ty2), fh));
+    box[i] = mapped_box(row, view_map + 4 * s, fh, fw);   // view_box.h
     score[i] = row[4];
     cls[i] = row[5];
     ord[i] = e;

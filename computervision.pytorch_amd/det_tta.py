@@ -90,6 +90,17 @@ def box_map_terms(image_hw: torch.Tensor, input_hw, letterbox: bool):
     return zero, zero, img_w / in_w, img_h / in_h
 
 
+def pad_blocks(parts, device):
+    """[(rows (B, K_k, 6), counts (B))] of S sources -> (rows (S * B, K, 6), counts (S * B)), slot ``k * B + b``: the tails' row blocks may
+    differ in size -- one block, the rest zero"""
+    B = int(parts[0][0].shape[0])
+    K = max(int(r.shape[1]) for r, _ in parts)
+    slot_rows = torch.zeros(len(parts) * B, K, 6, dtype=torch.float32, device=device)
+    for k, (r, _) in enumerate(parts):
+        slot_rows[k * B:(k + 1) * B, :r.shape[1]] = r
+    return slot_rows, torch.cat([c for _, c in parts])
+
+
 _fuse_ws = {}
 
 
@@ -152,10 +163,12 @@ class DetTTA:
     """The views of one test-time augmentation: view k is the picture at zoom ``scales[k]``, mirrored when ``flips[k]``.  The defaults
     are YOLOv5's three (``augment=True``).  ``fuse``: ``"vote"`` or ``"nms"``; ``iou``: the fusion's IoU threshold, None for the
     detector's configured NMS threshold; ``score``: ``"max"`` or ``"views"``; ``max_det``: rows per frame after the fusion; ``pad``: the
-    value around a view's content."""
+    value around a view's content.  ``fusion``: a ``box_fusion.WBF`` -- the views are then fused by Weighted Boxes Fusion
+    (``cvx_det_fuse_wbf``) with the views as its sources, ``fusion.weights`` one per view or None for ones; ``fuse``, ``iou``, ``score`` and
+    ``class_agnostic`` are unused (the ``WBF`` has its own), ``max_det`` still bounds the rows.  With None every path is what it was."""
 
     def __init__(self, scales: Sequence[float] = (1.0, 0.83, 0.67), flips: Sequence[bool] = (False, True, False), fuse: str = "vote",
-                 iou: Optional[float] = None, score: str = "max", class_agnostic: bool = False, max_det: int = 300, pad: float = PAD):
+                 iou: Optional[float] = None, score: str = "max", class_agnostic: bool = False, max_det: int = 300, pad: float = PAD, fusion=None):
         scales, flips = tuple(float(z) for z in scales), tuple(bool(f) for f in flips)
         if not scales or len(scales) != len(flips):
             raise ValueError(f"scales and flips: one entry per view, got {len(scales)} and {len(flips)}")
@@ -179,6 +192,13 @@ class DetTTA:
         self.scales, self.flips, self.fuse_mode, self.score = scales, flips, fuse, score
         self.iou = None if iou is None else float(iou)
         self.class_agnostic, self.max_det, self.pad = bool(class_agnostic), int(max_det), float(pad)
+        if fusion is not None:
+            from .box_fusion import WBF
+            if not isinstance(fusion, WBF):
+                raise ValueError(f"fusion: a box_fusion.WBF or None, got {type(fusion).__name__}")
+            if fusion.weights is not None and len(fusion.weights) != len(scales):
+                raise ValueError(f"fusion.weights: one per view, {len(scales)}, got {len(fusion.weights)}")
+        self.fusion = fusion
 
     @property
     def n_views(self) -> int:
@@ -217,7 +237,9 @@ class DetTTA:
         return torch.cat(out).to(torch.float32).contiguous()
 
     def fuse(self, rows, counts, view_map, frame_hw, iou: Optional[float] = None, max_det: Optional[int] = None, overflow=None):
-        """``fuse_views`` with this object's parameters; ``iou`` stands in where the object has none"""
+        """``fuse_views`` with this object's parameters; ``iou`` stands in where the object has none.  With a ``fusion``: its ``fuse_wbf``"""
+        if self.fusion is not None:
+            return self.fusion.fuse(rows, counts, view_map, frame_hw, None, self.max_det if max_det is None else max_det, overflow)
         thr = self.iou if self.iou is not None else iou
         if thr is None:
             raise ValueError("iou: this DetTTA has no threshold of its own; pass iou=")
@@ -228,8 +250,8 @@ class DetTTA:
         """``rows_of`` of ``Detector._evaluation_rows`` -> a callable with the same signature that runs it on every view and returns
         ``(rows (B, max_det, 6), counts (B), None)`` with final boxes: one ``cvx_det_tta_inputs`` launch, ``rows_of`` on the B slots of
         each view (``meta`` unchanged), ``render.det_to_image`` per view, the row blocks padded to one width, one ``cvx_det_fuse_views``
-        launch.  A frame one of whose views overflowed its tail comes back with count -1, as the tail's own overflow does.  No host read
-        of its own."""
+        launch (``cvx_det_fuse_wbf`` with a ``fusion``).  A frame one of whose views overflowed its tail comes back with count -1, as the
+        tail's own overflow does.  No host read of its own."""
         from . import render
         nms = getattr(detector, "iou_threshold", None)
         nms = getattr(detector, "nms_threshold", None) if nms is None else nms
@@ -249,11 +271,7 @@ class DetTTA:
                 bad = flagged if bad is None else bad | flagged
                 rows, counts, _ = render.det_to_image(rows, counts, box_map)
                 parts.append((rows, counts))
-            K = max(int(r.shape[1]) for r, _ in parts)               # the tails' row blocks may differ in size: one block, the rest zero
-            slot_rows = torch.zeros(V * B, K, 6, dtype=torch.float32, device=x.device)
-            for k, (r, _) in enumerate(parts):
-                slot_rows[k * B:(k + 1) * B, :r.shape[1]] = r
-            slot_counts = torch.cat([c for _, c in parts])
+            slot_rows, slot_counts = pad_blocks(parts, x.device)
             rows, counts, _, _, _ = self.fuse(slot_rows, slot_counts, vmap, image_hw.to(torch.int32), iou=nms, max_det=max_det)
             counts = torch.where(bad, torch.full_like(counts, -1), counts)
             rows = torch.where(bad.view(B, 1, 1), torch.zeros_like(rows), rows)

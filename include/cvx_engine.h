@@ -1182,6 +1182,31 @@ int cvx_det_fuse_views(const float* rows, const int32_t* counts, int32_t max_det
                        int32_t max_det_out, float* out_rows, int32_t* out_counts, int32_t* out_source, int32_t* out_members, int32_t* overflow,
                        void* workspace, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- Weighted Boxes Fusion of several sources per frame (csrc/box_fusion.hip) --------------------------------------
+ * The sources are the views of a test-time augmentation or the members of a detector ensemble.  rows, counts, view_map, frame_hw and the
+ * candidates, their ordinals and their boxes are those of cvx_det_fuse_views, `sources` in the place of `views` (1 to 32).  weights
+ * (sources) fp32 on the device, positive and finite.  One workgroup per frame; per frame f:
+ *   skipped     a row whose score is below skip_score, or whose mapped and clamped box does not have x2 > x1 and y2 > y1.
+ *   order       class ascending (the fp32 value; the bits, for the non-negative classes the tails emit), then s = score * weights[k]
+ *               descending, then ordinal ascending.  class_agnostic: one segment per frame, (s, ordinal) alone.
+ *   clusters    each class segment is walked in order.  Candidate j joins the cluster c of its segment with the largest
+ *               IoU(fused_c, box_j) (cvx_nms's IoU to the bit) strictly above iou_thr, the lowest c among equals; a NaN never matches.
+ *               No match opens a cluster: fused = box_j bit for bit, sw = s_j, sx = s_j * box_j per corner, n = 1, smax = s_j, first = j.
+ *               A match updates it: sw = sw + s_j, sx = sx + s_j * box_j, n += 1, fused = sx / sw -- every operation rounded on its own.
+ *   score       m = fminf((float)n, W), W the fp32 sum of weights in index order.  conf_mode 0 ("avg"): ((sw / (float)n) * m) / W;
+ *               1 ("max"): (smax * m) / W; with rescale == 0 sw / (float)n or smax as it stands.
+ *   outputs     the clusters of the frame by (score descending, first ordinal ascending), the first max_det_out: out_rows (frames,
+ *               max_det_out, 6) [fused box, score, class of the first member], zero past the count; out_counts (frames); out_source the
+ *               ordinal of the first member, -1 past the count; out_members n, 0 past the count.
+ *   capacity    8192 rows per frame before skipping: beyond it out_counts[f] = -1, the frame's rows are zero and *overflow grows by 1.
+ *               A count below 0 or above max_det_in contributes nothing and adds 1 to *overflow.
+ * workspace: cvx_det_wbf_workspace_bytes(frames) bytes of device memory (under 1 MB per frame). */
+int64_t cvx_det_wbf_workspace_bytes(int32_t frames);
+int cvx_det_fuse_wbf(const float* rows, const int32_t* counts, int32_t max_det_in, const float* view_map, const int32_t* frame_hw,
+                     int32_t frames, int32_t sources, const float* weights, float iou_thr, float skip_score, int32_t class_agnostic,
+                     int32_t conf_mode, int32_t rescale, int32_t max_det_out, float* out_rows, int32_t* out_counts, int32_t* out_source,
+                     int32_t* out_members, int32_t* overflow, void* workspace, int64_t workspace_bytes, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 
