@@ -99,6 +99,8 @@ PROTOTYPES = {
     "cvx_debug_conv_halo_plan": (_I32, [_I32, _I32, _I32, _I32, _I32, _P]),
     "cvx_debug_conv_pw_plan": (_I32, [_I64, _I32, _I32, _P]),
     "cvx_debug_conv_grid_div": (_I32, [_I32]),
+    "cvx_debug_conv_wgrad_plan": (_I32, [_I32] * 14 + [_P]),
+    "cvx_debug_conv2d_wgrad_nhwc": (_I32, [_P, _P] + [_I32] * 13 + [_P, _P, _I64, _P]),
     "cvx_engine_profile_dump": (_I32, [_P, C.c_char_p]),
     "cvx_pred_level_to_nchw": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "cvx_nchw_grad_to_dpred": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P]),

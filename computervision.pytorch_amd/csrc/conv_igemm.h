@@ -160,6 +160,23 @@ struct WgradParams {
   int std3x3;     // 1 when taps[t] == (t/3-1, t%3-1, wtap t), t = 0..8: the register-tile kernel (conv_wgrad_halo.hip) applies
 };
 int cvx_conv_wgrad_launch(const WgradParams& p, hipStream_t stream);
+// The five kernels of the cascade.  Every `*_supported` is `*_can` (what the kernel computes correctly) && where the dispatcher prefers it;
+// the pin tests (cvx_debug_conv_wgrad_plan / cvx_debug_conv2d_wgrad_nhwc) run a kernel wherever it can.
+enum { CVX_WGK_AUTO = 0, CVX_WGK_K3 = 1, CVX_WGK_STREAM = 2, CVX_WGK_HALO = 3, CVX_WGK_GEMM = 4, CVX_WGK_GENERIC = 5 };
+constexpr int CVX_WGRAD_DESC = 12;  // words of a launch description (cvx_conv_wgrad_describe)
+int cvx_conv_wgrad_pick(const WgradParams& p);                                       // the kernel cvx_conv_wgrad_launch takes
+bool cvx_conv_wgrad_can(const WgradParams& p, int kernel);                            // CVX_WGK_K3 ... CVX_WGK_GENERIC
+int cvx_conv_wgrad_launch_kernel(const WgradParams& p, int kernel, hipStream_t stream);  // that kernel, where it can run; else an error
+// instantiation and derived geometry of the launch `kernel` makes with p.nsplit splits -> out[CVX_WGRAD_DESC] (layouts: cvx_engine.h)
+int cvx_conv_wgrad_describe(const WgradParams& p, int kernel, int* out);
+bool cvx_conv_wgrad_gemm_can(const WgradParams& p);
+bool cvx_conv_wgrad_halo_can(const WgradParams& p);
+bool cvx_conv_wgrad_stream_can(const WgradParams& p);
+bool cvx_conv_wgrad_k3_can(const WgradParams& p);
+void cvx_conv_wgrad_gemm_describe(const WgradParams& p, int* out);
+void cvx_conv_wgrad_halo_describe(const WgradParams& p, int* out);
+bool cvx_conv_wgrad_stream_describe(const WgradParams& p, int* out);
+bool cvx_conv_wgrad_k3_describe(const WgradParams& p, int* out);
 void cvx_conv_wgrad_tile(int cout, int jtot, int* co_b, int* j_b);  // (co, j) tile the generic kernel takes for a layer
 // GEMM-shaped weight gradient for the big-channel layers (conv_wgrad_gemm.hip); `supported` needs the geometry and strides filled in
 bool cvx_conv_wgrad_gemm_supported(const WgradParams& p);

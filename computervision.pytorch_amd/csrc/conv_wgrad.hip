@@ -200,15 +200,16 @@ void cvx_conv_wgrad_tile(int cout, int jtot, int* co_b, int* j_b) {
   }
 }
 
-int cvx_conv_wgrad_launch(const WgradParams& p, hipStream_t st) {
+namespace {
+int wgrad_check_operands(const WgradParams& p) {
   CVX_CHECK(p.Cin % 8 == 0 && p.x_ld % 8 == 0 && p.dy_ld % 8 == 0 && p.Cout % 8 == 0, "wgrad: channels must be multiples of 8");
   CVX_CHECK(p.cin_pad16 % 16 == 0 && p.cin_pad16 >= p.Cin, "wgrad: cin_pad16");
   CVX_CHECK(p.nsplit >= 1 && p.ntaps >= 1 && p.ntaps <= CVX_MAX_TAPS, "wgrad: nsplit/ntaps");
   CVX_CHECK(((uintptr_t)p.x % 16) == 0 && ((uintptr_t)p.dy % 16) == 0, "wgrad: operands must be 16-byte aligned");
-  if (cvx_conv_wgrad_k3_supported(p)) return cvx_conv_wgrad_k3_launch(p, st);
-  if (cvx_conv_wgrad_stream_supported(p)) return cvx_conv_wgrad_stream_launch(p, st);
-  if (cvx_conv_wgrad_halo_supported(p)) return cvx_conv_wgrad_halo_launch(p, st);
-  if (cvx_conv_wgrad_gemm_supported(p)) return cvx_conv_wgrad_gemm_launch(p, st);
+  return 0;
+}
+
+int generic_launch(const WgradParams& p, hipStream_t st) {
   int co_b, j_b;
   cvx_conv_wgrad_tile(p.Cout, p.ntaps * p.cin_pad16, &co_b, &j_b);
   if (co_b == 16)
@@ -223,4 +224,62 @@ int cvx_conv_wgrad_launch(const WgradParams& p, hipStream_t st) {
     launch_cfg<2, 2, 2, 2>(p, st);
   CVX_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_one(const WgradParams& p, int kernel, hipStream_t st) {
+  switch (kernel) {
+    case CVX_WGK_K3: return cvx_conv_wgrad_k3_launch(p, st);
+    case CVX_WGK_STREAM: return cvx_conv_wgrad_stream_launch(p, st);
+    case CVX_WGK_HALO: return cvx_conv_wgrad_halo_launch(p, st);
+    case CVX_WGK_GEMM: return cvx_conv_wgrad_gemm_launch(p, st);
+  }
+  return generic_launch(p, st);
+}
+}  // namespace
+
+int cvx_conv_wgrad_pick(const WgradParams& p) {
+  if (cvx_conv_wgrad_k3_supported(p)) return CVX_WGK_K3;
+  if (cvx_conv_wgrad_stream_supported(p)) return CVX_WGK_STREAM;
+  if (cvx_conv_wgrad_halo_supported(p)) return CVX_WGK_HALO;
+  if (cvx_conv_wgrad_gemm_supported(p)) return CVX_WGK_GEMM;
+  return CVX_WGK_GENERIC;
+}
+
+// The generic kernel gathers by the tap table with 64-bit addresses and guards every channel group and pixel: any layer the common
+// operand checks (multiples of 8, 16-byte alignment) admit.
+bool cvx_conv_wgrad_can(const WgradParams& p, int kernel) {
+  switch (kernel) {
+    case CVX_WGK_K3: return cvx_conv_wgrad_k3_can(p);
+    case CVX_WGK_STREAM: return cvx_conv_wgrad_stream_can(p);
+    case CVX_WGK_HALO: return cvx_conv_wgrad_halo_can(p);
+    case CVX_WGK_GEMM: return cvx_conv_wgrad_gemm_can(p);
+    case CVX_WGK_GENERIC: return true;
+  }
+  return false;
+}
+
+int cvx_conv_wgrad_launch_kernel(const WgradParams& p, int kernel, hipStream_t st) {
+  CVX_TRY(wgrad_check_operands(p));
+  CVX_CHECK(cvx_conv_wgrad_can(p, kernel), "wgrad: the shape lies outside the kernel asked for");
+  return launch_one(p, kernel, st);
+}
+
+int cvx_conv_wgrad_describe(const WgradParams& p, int kernel, int* out) {
+  CVX_TRY(wgrad_check_operands(p));
+  CVX_CHECK(cvx_conv_wgrad_can(p, kernel), "wgrad: the shape lies outside the kernel asked for");
+  for (int i = 0; i < CVX_WGRAD_DESC; ++i) out[i] = 0;
+  switch (kernel) {
+    case CVX_WGK_K3: CVX_CHECK(cvx_conv_wgrad_k3_describe(p, out), "wgrad k3: unsupported shape"); return 0;
+    case CVX_WGK_STREAM: CVX_CHECK(cvx_conv_wgrad_stream_describe(p, out), "wgrad stream: unsupported shape"); return 0;
+    case CVX_WGK_HALO: cvx_conv_wgrad_halo_describe(p, out); return 0;
+    case CVX_WGK_GEMM: cvx_conv_wgrad_gemm_describe(p, out); return 0;
+  }
+  cvx_conv_wgrad_tile(p.Cout, p.ntaps * p.cin_pad16, &out[0], &out[1]);
+  out[2] = cvx_cdiv(p.Cout, out[0]) * cvx_cdiv(p.ntaps * p.cin_pad16, out[1]);  // (co, j) tiles per pixel split
+  return 0;
+}
+
+int cvx_conv_wgrad_launch(const WgradParams& p, hipStream_t st) {
+  CVX_TRY(wgrad_check_operands(p));
+  return launch_one(p, cvx_conv_wgrad_pick(p), st);
 }

@@ -266,16 +266,23 @@ int launch_wg(const WgradParams& p, hipStream_t st) {
 
 }  // namespace
 
-// Layers the kernel takes: 128+ output channels and 256+ weight columns, dy dense (a BatchNorm layer's dy buffer: pixel rows advance by a
-// scalar), output maps of at least 8 x 4 (the per-chunk pixel step wraps by compares), operands addressable with 32-bit byte offsets.
+// What the kernel computes correctly: dy dense over the images (a BatchNorm layer's dy buffer: pixel rows advance by a scalar offset and
+// the end of a split is the end of the buffer descriptor), output maps of at least 8 x 4 (the per-chunk pixel step wraps by compares),
+// operands addressable with 32-bit byte offsets.  Narrower layers than the dispatcher sends are correct: every channel group past Cout
+// and every column past ntaps * cin_pad16 is an out-of-range DMA lane, and the slab stores are guarded.
+bool cvx_conv_wgrad_gemm_can(const WgradParams& p) {
+  const long long M = (long long)p.B * p.OH * p.OW;
+  const long long ohw = (long long)p.OH * p.OW;
+  return p.Cout % 8 == 0 && p.dy_ld % 8 == 0 && p.x_ld % 8 == 0 && p.Cin % 8 == 0 && p.dy_bstride == ohw * p.dy_ld && p.OW >= 8 && p.OH >= 4 &&
+         M * p.dy_ld * 2 < (1LL << 32) && (long long)p.B * p.x_bstride * 2 < (1LL << 32);
+}
+
+// Layers the dispatcher gives it: 128+ output channels and 256+ weight columns (preferences).
 bool cvx_conv_wgrad_gemm_supported(const WgradParams& p) {
   static const bool off = cvx_tune_set("CVX_NO_WGRAD_GEMM");
   if (off) return false;
-  const long long M = (long long)p.B * p.OH * p.OW;
-  const long long ohw = (long long)p.OH * p.OW;
   static const int cmin = cvx_tune_int("CVX_WGG_CMIN", 128), jmin = cvx_tune_int("CVX_WGG_JMIN", 256);
-  return p.Cout >= cmin && p.Cout % 8 == 0 && p.ntaps * p.cin_pad16 >= jmin && p.dy_ld % 8 == 0 && p.x_ld % 8 == 0 && p.Cin % 8 == 0 &&
-         p.dy_bstride == ohw * p.dy_ld && p.OW >= 8 && p.OH >= 4 && M * p.dy_ld * 2 < (1LL << 32) && (long long)p.B * p.x_bstride * 2 < (1LL << 32);
+  return p.Cout >= cmin && p.ntaps * p.cin_pad16 >= jmin && cvx_conv_wgrad_gemm_can(p);
 }
 
 // (co, j) tile: 256 x 256 where the layer has at least that much of both, 128 x 128 otherwise
@@ -283,6 +290,12 @@ void cvx_conv_wgrad_gemm_tile(int cout, int jtot, int* co_b, int* j_b) {
   static const int force = cvx_tune_int("CVX_WGG_TILE", 0);  // tuning build: 1 = 256 x 256, 2 = 128 x 128
   const bool big = force ? force == 1 : (cout >= 256 && jtot >= 512 && cout % 256 == 0);
   *co_b = *j_b = big ? 256 : 128;
+}
+
+// (co, j) tile, tiles per pixel split
+void cvx_conv_wgrad_gemm_describe(const WgradParams& p, int* out) {
+  cvx_conv_wgrad_gemm_tile(p.Cout, p.ntaps * p.cin_pad16, &out[0], &out[1]);
+  out[2] = cvx_cdiv(p.Cout, out[0]) * cvx_cdiv(p.ntaps * p.cin_pad16, out[1]);
 }
 
 int cvx_conv_wgrad_gemm_launch(const WgradParams& p, hipStream_t st) {

@@ -226,13 +226,21 @@ int pick_tiles(int c) {
 
 }  // namespace
 
+// What the kernel computes correctly: the standard 3x3 taps at stride 1 on a map whose input and output sizes agree, and at least one
+// whole 16-channel input tile (Cin >= 16: an 8-channel layer is the stem's business, and nothing runs the kernel on one).
+bool cvx_conv_wgrad_halo_can(const WgradParams& p) {
+  return p.std3x3 && p.stride == 1 && p.ntaps == 9 && p.Cin >= 16 && p.IH == p.OH && p.IW == p.OW;
+}
+
+// ... and where the dispatcher prefers it
 bool cvx_conv_wgrad_halo_supported(const WgradParams& p) {
   static const bool off = cvx_tune_set("CVX_NO_WGRAD_HALO");
   // wide layers (Cin * Cout >= 256 * 256) take the generic kernel's 128 x 128 tile: 3-4x faster there (DeepLabv3+ R101: 256 -> 256 at
   // 33 x 33: 260 -> 70 us, 304 -> 256 at 129 x 129: 3.1 -> 1.0 ms); the register-tile kernel is built for YOLO's narrow layers
   // ... and from 128 x 128 channels up the GEMM-shaped kernel (conv_wgrad_gemm.hip) is ahead: 339 vs 427 us at 150 x 150, 100 vs 119 us at 80 x 80
+  // (a preference: the channel blocks of pick_tiles cover any count)
   static const int max_c = cvx_tune_int("CVX_WH_MAX_C", 16383);
-  return !off && p.std3x3 && p.stride == 1 && p.ntaps == 9 && p.Cin >= 16 && p.IH == p.OH && p.IW == p.OW && (long long)p.Cin * p.Cout <= max_c;
+  return !off && cvx_conv_wgrad_halo_can(p) && (long long)p.Cin * p.Cout <= max_c;
 }
 
 // workgroups per pixel split: gx channel blocks x gy (input-channel blocks x tap groups)
@@ -243,9 +251,32 @@ void cvx_conv_wgrad_halo_grid(int cout, int cin, int* gx, int* gy) {
 
 int cvx_conv_wgrad_halo_tiles(int B, int OH, int OW) { return ((OW + 15) / 16) * ((OH + TH - 1) / TH) * B; }
 
-int cvx_conv_wgrad_halo_launch(const WgradParams& p, hipStream_t st) {
+namespace {
+struct WhGeom {
+  int cot, cit, gx, gy;  // 16-channel tiles per workgroup; output-channel blocks, input-channel blocks (without the tap groups)
+};
+WhGeom wh_geom(const WgradParams& p) {
   const int cot = pick_tiles(p.Cout), cit = pick_tiles(p.Cin);
-  const int gx = cvx_cdiv(p.Cout, 16 * cot), gy = cvx_cdiv(p.Cin, 16 * cit);  // gy: input-channel blocks only
+  return WhGeom{cot, cit, cvx_cdiv(p.Cout, 16 * cot), cvx_cdiv(p.Cin, 16 * cit)};
+}
+}  // namespace
+
+// CO_T, CI_T, taps per workgroup (3 or 9), pixel tiles, tiles per split, workgroups per split
+void cvx_conv_wgrad_halo_describe(const WgradParams& p, int* out) {
+  const WhGeom g = wh_geom(p);
+  int gx, gy;
+  cvx_conv_wgrad_halo_grid(p.Cout, p.Cin, &gx, &gy);
+  out[0] = g.cot;
+  out[1] = g.cit;
+  out[2] = gy == g.gy ? 9 : 3;
+  out[3] = cvx_conv_wgrad_halo_tiles(p.B, p.OH, p.OW);
+  out[4] = cvx_cdiv(out[3], p.nsplit);
+  out[5] = gx * gy;
+}
+
+int cvx_conv_wgrad_halo_launch(const WgradParams& p, hipStream_t st) {
+  const WhGeom g = wh_geom(p);
+  const int cot = g.cot, cit = g.cit, gx = g.gx, gy = g.gy;  // gy: input-channel blocks only
   switch (cot) {
     case 1: CVX_TRY((launch_wh_ci<1>(cit, p, st, gx, gy))); break;
     case 2: CVX_TRY((launch_wh_ci<2>(cit, p, st, gx, gy))); break;

@@ -565,17 +565,43 @@ int launch_k3(const WgradParams& p, const K3Plan& a, hipStream_t st) {
   return 0;
 }
 
+// the plan of the launch with p.nsplit pixel splits: the chunk ranges follow the caller's count
+bool k3_launch_plan(const WgradParams& p, K3Plan* a, K3Shape* sh) {
+  int ns;
+  if (p.nsplit < 1 || !k3_plan(p, p.nsplit, a, sh, &ns)) return false;
+  a->units_per_split = cvx_cdiv(a->total_units, p.nsplit);
+  return true;
+}
+
 }  // namespace
 
+// What the kernel computes correctly: k3_shape_ok (standard 3x3 taps at stride 1 or 2, channel multiples of 8, 32-bit operand offsets,
+// OH <= 250: the chunk's row bounds ride in 8-bit tags; a configuration of k3_pick for the channel tiles) and a chunk geometry that fits
+// the ring (k3_plan) -- which in effect asks for OW >= 6, the narrowest column block it cuts.
+bool cvx_conv_wgrad_k3_can(const WgradParams& p) {
+  K3Plan a;
+  K3Shape sh;
+  int ns;
+  return k3_plan(p, 0, &a, &sh, &ns);
+}
+
+// ... and where the dispatcher prefers it: up to Cin * Cout = 256 * 144 (a preference: the configurations tile any channel count)
 bool cvx_conv_wgrad_k3_supported(const WgradParams& p) {
   static const bool off = cvx_tune_set("CVX_NO_WGRAD_K3");
   if (off) return false;
   static const int max_cc = cvx_tune_int("CVX_K3_MAX_CC", 256 * 144);  // wider layers: the GEMM-shaped kernel (conv_wgrad_gemm.hip)
   if ((long long)p.Cin * p.Cout > max_cc) return false;
+  return cvx_conv_wgrad_k3_can(p);
+}
+
+// configuration, R, Wc, column blocks, ring slots, stride-2 flag, chunks, chunks per split, workgroups per split
+bool cvx_conv_wgrad_k3_describe(const WgradParams& p, int* out) {
   K3Plan a;
   K3Shape sh;
-  int ns;
-  return k3_plan(p, 0, &a, &sh, &ns);
+  if (!k3_launch_plan(p, &a, &sh)) return false;
+  const int v[9] = {sh.cfg, a.R, a.Wc, a.ncb, a.nslot, a.s2, a.total_units, a.units_per_split, a.n_co_blk * a.n_ci_blk};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return true;
 }
 
 // the planner's pixel-split count for a layer (the engine sizes the layer's slabs with it)
@@ -590,9 +616,7 @@ int cvx_conv_wgrad_k3_nsplit(const WgradParams& p, bool wide) {
 int cvx_conv_wgrad_k3_launch(const WgradParams& p, hipStream_t st) {
   K3Plan a;
   K3Shape sh;
-  int ns;
-  CVX_CHECK(k3_plan(p, p.nsplit, &a, &sh, &ns), "wgrad k3: unsupported shape");
-  a.units_per_split = cvx_cdiv(a.total_units, p.nsplit);
+  CVX_CHECK(k3_launch_plan(p, &a, &sh), "wgrad k3: unsupported shape");
   a.clk = g_cvx_clk;
   switch (sh.cfg) {
     case 0: return launch_k3<CfgA>(p, a, st);

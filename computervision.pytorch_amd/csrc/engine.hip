@@ -460,6 +460,65 @@ void fill_wgrad(const cvx_engine* e, int i, int B, ViewDesc dy, float* slabs, in
   fill_wgrad(geom_of(e->ops[i], B), x, dy, c.taps_fwd, c.tr.std3x3, slabs, nsplit, wp);
 }
 
+// The weight-gradient kernel (CVX_WGK_*) a layer's pixel splits are sized for: the cascade of cvx_conv_wgrad_launch, except that a head's
+// output conv (bias_head: its dy is a slice of the prediction rows) is never sized for the GEMM-shaped kernel.
+int wgrad_sizing_kernel(const WgradParams& q, bool bias_head) {
+  const int k = cvx_conv_wgrad_pick(q);
+  return (k == CVX_WGK_GEMM && bias_head) ? CVX_WGK_GENERIC : k;
+}
+
+// Pixel splits the engine gives a (non-stem) layer's weight gradient when `kernel` takes it; the layer's slabs are sized with the count.
+// tail_layer: one of the last launches of the backward pass, which may fill the whole chip.
+long long wgrad_engine_splits(const WgradParams& q, int kernel, bool tail_layer) {
+  if (kernel == CVX_WGK_K3) return cvx_conv_wgrad_k3_nsplit(q, tail_layer);
+  if (kernel == CVX_WGK_STREAM) return cvx_conv_wgrad_stream_nsplit(q);
+  const long long M = (long long)q.B * q.OH * q.OW;
+  const int C = q.Cout, Jtot = q.ntaps * q.cin_pad16;
+  const long long slab_elems = (long long)C * Jtot;
+  if (kernel == CVX_WGK_HALO) {  // 3x3 stride-1 layers on the register-tile kernel: few, fat workgroups per pixel split
+    int gx, gy;
+    cvx_conv_wgrad_halo_grid(C, q.Cin, &gx, &gy);
+    const long long ptiles = cvx_conv_wgrad_halo_tiles(q.B, q.OH, q.OW);
+    // split count by the layer's work: 128 workgroups for the small layers (YOLOv8-n: 128 beats 64/256/512 -- slab volume vs.
+    // parallelism), 512 from 8 GFLOP up (SSD300's 150^2 / 300^2 layers: -9 % on the whole step; tools/sweeps/sweep_wh.sh, sweep_wh2.sh)
+    static const long long wh_small = cvx_tune_int("CVX_WH_BLOCKS", 128), wh_big = cvx_tune_int("CVX_WH_BLOCKS_BIG", 512);
+    static const long long wh_big_gf = cvx_tune_int("CVX_WH_BIG_GF", 8);
+    static const long long wh_slab_mb = cvx_tune_int("CVX_WH_SLAB_MB", 16);
+    const double gflop = 2.0 * (double)M * C * q.Cin * q.ntaps * 1e-9;
+    const long long wh_blocks = gflop >= (double)wh_big_gf ? wh_big : wh_small;
+    long long ns = std::max<long long>(1, wh_blocks / ((long long)gx * gy));
+    ns = std::min(ns, ptiles);
+    return std::min(ns, std::max<long long>(1, (wh_slab_mb << 20) / (slab_elems * 4)));
+  }
+  // the GEMM-shaped kernel (conv_wgrad_gemm.hip) takes the BatchNorm / bias layers with 128+ output channels: its tiles and its 512-thread
+  // workgroups size the pixel splits; every other layer: the generic kernel's tile
+  const bool wgg = kernel == CVX_WGK_GEMM;
+  int co_b, j_b;
+  if (wgg) cvx_conv_wgrad_gemm_tile(C, Jtot, &co_b, &j_b);
+  else cvx_conv_wgrad_tile(C, Jtot, &co_b, &j_b);
+  const long long tiles = (long long)cvx_cdiv(C, co_b) * cvx_cdiv(Jtot, j_b);
+  // the 128 x 128 tile (ResNet-sized layers) has few, fat tiles: it takes its parallelism from more pixel splits, and its slabs
+  // may grow accordingly (measured on DeepLabv3+ R101: 8 -> 64 MB of slabs per layer took the step from 48.6 to 38.5 ms)
+  static const long long blk_narrow = cvx_tune_int("CVX_WGRAD_BLOCKS", 2048), blk_wide = cvx_tune_int("CVX_WGRAD_BLOCKS_WIDE", 1024);
+  static const long long blk_wgg_big = cvx_tune_int("CVX_WGG_BLOCKS_BIG", 256), blk_wgg = cvx_tune_int("CVX_WGG_BLOCKS", 512);
+  // Round 5: these launches run beside the backward pass on the lowest-priority stream, and what they cost the step is the CUs their
+  // workgroups hold while a main-chain kernel waits to be placed -- not their own duration.  A small layer therefore gets
+  // only as many workgroups as its work needs (YOLOv8-n, same box: 512 -> 96 and 2048 -> 256 took 0.12 ms off the step); the big layers
+  // of the other models keep the counts that were tuned on them.
+  static const long long wgg_mflop = cvx_tune_int("CVX_WGG_MFLOP", 40), gen_mflop = cvx_tune_int("CVX_WGRAD_MFLOP", 20);
+  static const long long wgg_min = cvx_tune_int("CVX_WGG_BLOCKS_MIN", 96), gen_min = cvx_tune_int("CVX_WGRAD_BLOCKS_MIN", 256);
+  const double wflops = 2.0 * (double)M * C * q.Cin * q.ntaps;
+  const long long wgg_by_work = std::max(wgg_min, std::min(blk_wgg, (long long)(wflops / (wgg_mflop * 1e6))));
+  const long long gen_by_work = std::max(gen_min, std::min(blk_narrow, (long long)(wflops / (gen_mflop * 1e6))));
+  const long long blk_target = wgg ? (co_b == 256 ? blk_wgg_big : tail_layer ? blk_wgg : wgg_by_work) : co_b == 128 ? blk_wide : tail_layer ? blk_narrow : gen_by_work;
+  long long ns = std::min<long long>(std::max<long long>(1, M / 256), std::max<long long>(1, blk_target / tiles));
+  static const long long cap_narrow = cvx_tune_int("CVX_SLAB_MB", 8), cap_wide = cvx_tune_int("CVX_SLAB_MB_WIDE", 64);
+  const long long slab_cap_mb = (wgg || co_b == 128) ? cap_wide : cap_narrow;
+  static const long long ns_cap = cvx_tune_int("CVX_NSPLIT_CAP", 512);
+  ns = std::min(ns, std::max<long long>(1, (slab_cap_mb << 20) / (slab_elems * 4)));
+  return std::min<long long>(ns, ns_cap);
+}
+
 int build_static(cvx_engine* e) {
   const int nops = (int)e->ops.size();
   e->conv.assign(nops, ConvRt());
@@ -882,71 +941,19 @@ int plan_batch(cvx_engine* e, int B, bool training) {
     c.stat_fwd = (long long*)nullptr + stat_floats;  // offset for now, rebased below
     stat_floats += (long long)cvx_stat_replicas(C) * C * CVX_STAT_WORDS + CVX_STAT_GATE_WORDS;  // + the gate counter of the one-launch BN backward
     if (training) {
-      int co_b, j_b;
-      const int Jtot = c.ntaps * c.cin_pad16;
-      cvx_conv_wgrad_tile(C, Jtot, &co_b, &j_b);
-      // the GEMM-shaped weight-gradient kernel (conv_wgrad_gemm.hip) takes the BatchNorm / bias layers with 128+ output channels: its tiles
-      // and its 512-thread workgroups size the pixel splits
       // the first conv ops are the LAST of the backward pass: their weight gradients are the tail of the step (nothing of the main chain is
       // left to disturb) and may keep the whole-chip workgroup counts -- measured: no difference (6.16-6.23 ms for 0 ... 7 such layers), so off
       static const int tail_convs = cvx_tune_int("CVX_WGRAD_TAIL_OPS", -1);
       const bool tail_layer = (int)i <= tail_convs;
-      bool wgg = false;
-      int ws_splits = 0;  // > 0: the streaming kernel (conv_wgrad_stream.hip) takes the layer, with its planner's pixel splits
-      WgradParams q;
-      fill_wgrad(e, (int)i, B, dy_view(e, (int)i, nullptr), nullptr, 0, &q);
-      if (!c.stem) {
-        if (cvx_conv_wgrad_k3_supported(q)) {
-          ws_splits = cvx_conv_wgrad_k3_nsplit(q, tail_layer);
-        } else if (cvx_conv_wgrad_stream_supported(q)) {
-          ws_splits = cvx_conv_wgrad_stream_nsplit(q);
-        } else if (o.act != CVX_ACT_BIAS && !cvx_conv_wgrad_halo_supported(q) && cvx_conv_wgrad_gemm_supported(q)) {
-          wgg = true;
-          cvx_conv_wgrad_gemm_tile(C, Jtot, &co_b, &j_b);
-        }
-      }
-      const long long tiles = (long long)cvx_cdiv(C, co_b) * cvx_cdiv(Jtot, j_b);
-      // the 128 x 128 tile (ResNet-sized layers) has few, fat tiles: it takes its parallelism from more pixel splits, and its slabs
-      // may grow accordingly (measured on DeepLabv3+ R101: 8 -> 64 MB of slabs per layer took the step from 48.6 to 38.5 ms)
-      static const long long blk_narrow = cvx_tune_int("CVX_WGRAD_BLOCKS", 2048), blk_wide = cvx_tune_int("CVX_WGRAD_BLOCKS_WIDE", 1024);
-      static const long long blk_wgg_big = cvx_tune_int("CVX_WGG_BLOCKS_BIG", 256), blk_wgg = cvx_tune_int("CVX_WGG_BLOCKS", 512);
-      // Round 5: these launches run beside the backward pass on the lowest-priority stream, and what they cost the step is the CUs their
-      // workgroups hold while a main-chain kernel waits to be placed -- not their own duration.  A small layer therefore gets
-      // only as many workgroups as its work needs (YOLOv8-n, same box: 512 -> 96 and 2048 -> 256 took 0.12 ms off the step); the big layers
-      // of the other models keep the counts that were tuned on them.
-      static const long long wgg_mflop = cvx_tune_int("CVX_WGG_MFLOP", 40), gen_mflop = cvx_tune_int("CVX_WGRAD_MFLOP", 20);
-      static const long long wgg_min = cvx_tune_int("CVX_WGG_BLOCKS_MIN", 96), gen_min = cvx_tune_int("CVX_WGRAD_BLOCKS_MIN", 256);
-      const double wflops = 2.0 * (double)M * C * c.cin_g * c.ntaps;
-      const long long wgg_by_work = std::max(wgg_min, std::min(blk_wgg, (long long)(wflops / (wgg_mflop * 1e6))));
-      const long long gen_by_work = std::max(gen_min, std::min(blk_narrow, (long long)(wflops / (gen_mflop * 1e6))));
-      const long long blk_target = wgg ? (co_b == 256 ? blk_wgg_big : tail_layer ? blk_wgg : wgg_by_work) : co_b == 128 ? blk_wide : tail_layer ? blk_narrow : gen_by_work;
-      long long ns = std::min<long long>(std::max<long long>(1, M / 256), std::max<long long>(1, blk_target / tiles));
+      const int Jtot = c.ntaps * c.cin_pad16;
       const long long slab_elems = (long long)C * Jtot;
-      static const long long cap_narrow = cvx_tune_int("CVX_SLAB_MB", 8), cap_wide = cvx_tune_int("CVX_SLAB_MB_WIDE", 64);
-      const long long slab_cap_mb = (wgg || co_b == 128) ? cap_wide : cap_narrow;
-      static const long long ns_cap = cvx_tune_int("CVX_NSPLIT_CAP", 512);
-      ns = std::min(ns, std::max<long long>(1, (slab_cap_mb << 20) / (slab_elems * 4)));
-      ns = std::min<long long>(ns, ns_cap);
-      {  // 3x3 stride-1 layers take the register-tile kernel: few, fat workgroups per pixel split
-        if (c.stem) {
-          ns = cvx_stem_wgrad_splits(M);
-        } else if (ws_splits > 0) {
-          ns = ws_splits;
-        } else if (cvx_conv_wgrad_halo_supported(q)) {
-          int gx, gy;
-          cvx_conv_wgrad_halo_grid(C, c.cin_g, &gx, &gy);
-          const long long ptiles = cvx_conv_wgrad_halo_tiles(B, o.oh, o.ow);
-          // split count by the layer's work: 128 workgroups for the small layers (YOLOv8-n: 128 beats 64/256/512 -- slab volume vs.
-          // parallelism), 512 from 8 GFLOP up (SSD300's 150^2 / 300^2 layers: -9 % on the whole step; tools/sweeps/sweep_wh.sh, sweep_wh2.sh)
-          static const long long wh_small = cvx_tune_int("CVX_WH_BLOCKS", 128), wh_big = cvx_tune_int("CVX_WH_BLOCKS_BIG", 512);
-          static const long long wh_big_gf = cvx_tune_int("CVX_WH_BIG_GF", 8);
-          static const long long wh_slab_mb = cvx_tune_int("CVX_WH_SLAB_MB", 16);
-          const double gflop = 2.0 * (double)M * C * c.cin_g * c.ntaps * 1e-9;
-          const long long wh_blocks = gflop >= (double)wh_big_gf ? wh_big : wh_small;
-          ns = std::max<long long>(1, wh_blocks / ((long long)gx * gy));
-          ns = std::min(ns, ptiles);
-          ns = std::min(ns, std::max<long long>(1, (wh_slab_mb << 20) / (slab_elems * 4)));
-        }
+      long long ns;
+      if (c.stem) {
+        ns = cvx_stem_wgrad_splits(M);
+      } else {
+        WgradParams q;
+        fill_wgrad(e, (int)i, B, dy_view(e, (int)i, nullptr), nullptr, 0, &q);
+        ns = wgrad_engine_splits(q, wgrad_sizing_kernel(q, o.act == CVX_ACT_BIAS), tail_layer);
       }
       c.nsplit = (int)ns;
       c.slab_off = slab_total;
@@ -2450,6 +2457,24 @@ struct DevTemps {
 ViewDesc dense_view(const void* p, long long pixels, int c) { return ViewDesc{(half_t*)p, pixels * c, c}; }
 // pixel splits of the single-op weight gradient; its workspace is sized with the same count
 long long unit_wgrad_splits(long long M) { return std::min<long long>(std::max<long long>(1, M / 256), 64); }
+// reduce the slabs of a single-op weight gradient into dw (overwrite): zero, then the table-driven reducer with one descriptor
+int unit_wgrad_reduce(DevTemps& tmp, const WgradParams& wp, int k, float* dw, hipStream_t st) {
+  const int cout = wp.Cout, cin = wp.Cin;
+  int rc = hipMemsetAsync(dw, 0, (size_t)cout * k * k * cin * 4, st) == hipSuccess ? 0 : -1;
+  SlabDesc sd{0, 0, wp.nsplit, cout * k * k, cin, wp.cin_pad16, cvx_slab_lanes(wp.nsplit)};
+  std::vector<BlockRef> blocks;
+  const long long total = (long long)sd.rows * sd.Cin;
+  for (long long s0 = 0; s0 < total; s0 += 256 / sd.lanes) blocks.push_back(BlockRef{0, (int)s0});
+  SlabDesc* dsd = nullptr;
+  BlockRef* dbl = nullptr;
+  if (tmp.alloc(&dsd, sizeof(sd)) != 0 || tmp.alloc(&dbl, blocks.size() * sizeof(BlockRef)) != 0) rc = -1;
+  if (rc == 0) {
+    (void)hipMemcpy(dsd, &sd, sizeof(sd), hipMemcpyHostToDevice);
+    (void)hipMemcpy(dbl, blocks.data(), blocks.size() * sizeof(BlockRef), hipMemcpyHostToDevice);
+    rc = cvx_reduce_slabs(wp.slabs, dw, 1.0f, dsd, dbl, (int)blocks.size(), st);
+  }
+  return rc;
+}
 }  // namespace
 
 extern "C" int cvx_conv2d_nhwc(const void* x_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, const void* w_f16, int32_t cout,
@@ -2615,22 +2640,73 @@ extern "C" int cvx_conv2d_wgrad_nhwc(const void* x_f16, const void* dy_f16, int3
              dense_view(dy_f16, (long long)oh * ow, cout), dt, cvx_tap_traits(taps).std3x3, (float*)workspace,
              (int)unit_wgrad_splits((long long)batch * oh * ow), &wp);
   int rc = cvx_conv_wgrad_launch(wp, st);
-  if (rc == 0) {
-    // reduce the slabs into dw (overwrite): zero, then the table-driven reducer with one descriptor
-    rc = hipMemsetAsync(dw, 0, (size_t)cout * k * k * cin * 4, st) == hipSuccess ? 0 : -1;
-    SlabDesc sd{0, 0, wp.nsplit, cout * k * k, cin, wp.cin_pad16, cvx_slab_lanes(wp.nsplit)};
-    std::vector<BlockRef> blocks;
-    const long long total = (long long)sd.rows * sd.Cin;
-    for (long long s0 = 0; s0 < total; s0 += 256 / sd.lanes) blocks.push_back(BlockRef{0, (int)s0});
-    SlabDesc* dsd = nullptr;
-    BlockRef* dbl = nullptr;
-    if (tmp.alloc(&dsd, sizeof(sd)) != 0 || tmp.alloc(&dbl, blocks.size() * sizeof(BlockRef)) != 0) rc = -1;
-    if (rc == 0) {
-      (void)hipMemcpy(dsd, &sd, sizeof(sd), hipMemcpyHostToDevice);
-      (void)hipMemcpy(dbl, blocks.data(), blocks.size() * sizeof(BlockRef), hipMemcpyHostToDevice);
-      rc = cvx_reduce_slabs((float*)workspace, dw, 1.0f, dsd, dbl, (int)blocks.size(), st);
-    }
-  }
+  if (rc == 0) rc = unit_wgrad_reduce(tmp, wp, k, dw, st);
+  (void)hipStreamSynchronize(st);
+  return rc;
+}
+
+namespace {
+// The layer of the two weight-gradient pin entries: operands with pixel pitches x_ld / dy_ld (images follow each other without a gap), the
+// kernel (`kernel` 0: the cascade's) and the split count (`nsplit` 0: the engine's for that kernel) -> *wp, *kernel_out.
+int debug_wgrad_layer(const void* x, const void* dy, const ConvTap* dev_taps, int batch, int ih, int iw, int cin, int cout, int k, int stride, int pad,
+                      int dil, int x_ld, int dy_ld, int kernel, int nsplit, int wide, float* slabs, WgradParams* wp, int* kernel_out) {
+  CVX_CHECK(batch > 0 && ih > 0 && iw > 0 && cin > 0 && cout > 0 && k >= 1 && k * k <= CVX_MAX_TAPS && stride >= 1 && pad >= 0 && dil >= 1, "bad arguments");
+  CVX_CHECK(kernel >= CVX_WGK_AUTO && kernel <= CVX_WGK_GENERIC && nsplit >= 0, "kernel 0 .. 5, nsplit >= 0");
+  CVX_CHECK(ih + 2 * pad >= dil * (k - 1) + 1 && iw + 2 * pad >= dil * (k - 1) + 1, "the kernel does not fit the padded map");
+  CVX_CHECK(cin % 8 == 0 && cout % 8 == 0 && x_ld % 8 == 0 && dy_ld % 8 == 0 && x_ld >= cin && dy_ld >= cout, "channels and pitches: multiples of 8, pitch >= channels");
+  const int oh = cvx_conv_out_size(ih, k, stride, pad, dil), ow = cvx_conv_out_size(iw, k, stride, pad, dil);
+  const std::vector<ConvTap> taps = cvx_conv_fwd_taps(k, pad, dil);
+  fill_wgrad(ConvGeom{batch, ih, iw, cin, oh, ow, cout, stride, k * k}, ViewDesc{(half_t*)x, (long long)ih * iw * x_ld, x_ld},
+             ViewDesc{(half_t*)dy, (long long)oh * ow * dy_ld, dy_ld}, dev_taps, cvx_tap_traits(taps).std3x3, slabs, 1, wp);
+  const int kern = kernel != CVX_WGK_AUTO ? kernel : cvx_conv_wgrad_pick(*wp);
+  CVX_CHECK(cvx_conv_wgrad_can(*wp, kern), "the shape lies outside the kernel asked for");
+  // stricter than the kernel's own condition (images at oh * ow * dy_ld): the engine gives it the dense dy buffers of BatchNorm layers only
+  CVX_CHECK(kernel != CVX_WGK_GEMM || dy_ld == cout, "the GEMM-shaped kernel is run on dense dy only");
+  const long long ns = nsplit > 0 ? nsplit : wgrad_engine_splits(*wp, kern, wide != 0);
+  CVX_CHECK(ns >= 1 && ns <= (1 << 20), "split count");
+  wp->nsplit = (int)ns;
+  *kernel_out = kern;
+  return 0;
+}
+long long wgrad_slab_bytes(const WgradParams& wp) { return (long long)wp.nsplit * wp.Cout * wp.ntaps * wp.cin_pad16 * 4; }
+}  // namespace
+
+extern "C" int cvx_debug_conv_wgrad_plan(int32_t batch, int32_t ih, int32_t iw, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad,
+                                         int32_t dil, int32_t x_ld, int32_t dy_ld, int32_t kernel, int32_t nsplit, int32_t wide, int32_t* out16) {
+  CVX_CHECK(out16, "bad arguments");
+  WgradParams wp;
+  int kern = 0;
+  CVX_TRY(debug_wgrad_layer(nullptr, nullptr, nullptr, batch, ih, iw, cin, cout, k, stride, pad, dil, x_ld, dy_ld, kernel, nsplit, wide, nullptr, &wp, &kern));
+  int desc[CVX_WGRAD_DESC];
+  CVX_TRY(cvx_conv_wgrad_describe(wp, kern, desc));
+  const long long bytes = wgrad_slab_bytes(wp);
+  out16[0] = kern;
+  out16[1] = wp.nsplit;
+  out16[2] = (int32_t)(bytes & 0x7fffffff);
+  out16[3] = (int32_t)(bytes >> 31);
+  for (int i = 0; i < CVX_WGRAD_DESC; ++i) out16[4 + i] = desc[i];
+  return 0;
+}
+
+extern "C" int cvx_debug_conv2d_wgrad_nhwc(const void* x_f16, const void* dy_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, int32_t cout,
+                                           int32_t k, int32_t stride, int32_t pad, int32_t dil, int32_t x_ld, int32_t dy_ld, int32_t kernel,
+                                           int32_t nsplit, float* dw, void* workspace, int64_t workspace_bytes, void* hip_stream) {
+  CVX_CHECK(x_f16 && dy_f16 && dw && workspace, "bad arguments");
+  hipStream_t st = (hipStream_t)hip_stream;
+  WgradParams wp;
+  int kern = 0;
+  // every refusal comes before the first device call: a refused call launches nothing and writes nothing
+  CVX_TRY(debug_wgrad_layer(x_f16, dy_f16, nullptr, batch, ih, iw, cin, cout, k, stride, pad, dil, x_ld, dy_ld, kernel, nsplit, 0, (float*)workspace, &wp,
+                            &kern));
+  int desc[CVX_WGRAD_DESC];
+  CVX_TRY(cvx_conv_wgrad_describe(wp, kern, desc));  // (the operand checks of the launch, and a plan for the split count)
+  CVX_CHECK(workspace_bytes >= wgrad_slab_bytes(wp), "workspace too small");
+  DevTemps tmp;
+  const ConvTap* dt = nullptr;
+  CVX_TRY(tmp.taps(cvx_conv_fwd_taps(k, pad, dil), &dt));
+  wp.taps = dt;
+  int rc = cvx_conv_wgrad_launch_kernel(wp, kern, st);
+  if (rc == 0) rc = unit_wgrad_reduce(tmp, wp, k, dw, st);
   (void)hipStreamSynchronize(st);
   return rc;
 }

@@ -212,6 +212,25 @@ int cvx_debug_conv_pw_plan(int64_t pixels, int32_t cin, int32_t cout, int32_t* o
 /* Test hook: the persistent convolution kernels size their grids for 1 / div of the chip (1: all of it), so that every workgroup walks
  * many tiles of a small map.  Returns the previous divisor, or -1 for div < 1 (nothing changes).  Process-wide: restore it. */
 int cvx_debug_conv_grid_div(int32_t div);
+/* Test hooks of the weight gradient's five kernels (csrc/conv_wgrad*.hip).  Both take the layer of cvx_conv2d_wgrad_nhwc with operand pixel
+ * pitches x_ld >= cin / dy_ld >= cout (images follow each other without a gap), a kernel -- 0: whatever cvx_conv_wgrad_launch's cascade takes,
+ * 1 k3, 2 stream, 3 halo, 4 gemm, 5 generic -- and a pixel-split count -- 0: the count the engine gives that kernel (wide != 0: as one of
+ * the last launches of the backward pass), > 0: the caller's.  A forced kernel keeps every condition that makes it correct (the `*_can`
+ * functions beside the kernels say which) and drops the dispatcher's preferences; the gemm kernel is forced on dense dy only.  A shape the
+ * kernel cannot run is an error (-1), before anything is launched or written.
+ * cvx_debug_conv_wgrad_plan needs no GPU.  out[0] = kernel (1 .. 5), out[1] = pixel splits, out[2] + (out[3] << 31) = bytes of the slabs
+ * (splits * cout * k * k * round_up(cin, 16) * 4), out[4 ..] = what the launcher derives, by the planners it calls itself:
+ *   k3:      configuration (0 .. 7 = CfgA .. CfgH), R, Wc, column blocks, ring slots, stride-2 flag, chunks, chunks per split, workgroups per split
+ *   stream:  CO_T, JW, WN, WK, tap blocks, R (3x3) or Qd (1x1), ring slots, chunks, chunks per split, workgroups per split, CI_T
+ *   halo:    CO_T, CI_T, taps per workgroup (3 or 9), pixel tiles, tiles per split, workgroups per split
+ *   gemm, generic: output-channel rows and weight columns of the tile, tiles per split
+ * cvx_debug_conv2d_wgrad_nhwc launches that kernel and reduces its slabs into dw [cout][k][k][cin] as cvx_conv2d_wgrad_nhwc does; the
+ * workspace holds at least the slab bytes the plan reports.  (No reference counterpart, as above.) */
+int cvx_debug_conv_wgrad_plan(int32_t batch, int32_t ih, int32_t iw, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t dil,
+                              int32_t x_ld, int32_t dy_ld, int32_t kernel, int32_t nsplit, int32_t wide, int32_t* out16);
+int cvx_debug_conv2d_wgrad_nhwc(const void* x_f16, const void* dy_f16, int32_t batch, int32_t ih, int32_t iw, int32_t cin, int32_t cout, int32_t k,
+                                int32_t stride, int32_t pad, int32_t dil, int32_t x_ld, int32_t dy_ld, int32_t kernel, int32_t nsplit, float* dw,
+                                void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* Bytes of device memory the engine currently owns (workspaces). */
 int64_t cvx_engine_workspace_bytes(const cvx_engine* e);
