@@ -201,6 +201,9 @@ PROTOTYPES = {
     "cvx_dropout_nhwc": (_I32, [_P, _I32, _I32, _I32, _F, _U64, _P, _I32, _P]),
     "cvx_bn_act_train_nhwc": (_I32, [_P, _I32, _I32, _I32, _P, _P, _F, _F, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_bn_act_bwd_nhwc": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _I32, _P]),
+    "cvx_debug_bn_bwd_plan": (_I32, [_I64, _I32, _P]),
+    "cvx_debug_bn_bwd_views": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F, _P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _I32,
+                                      _P, _P, _P, _P]),
     "cvx_maxpool5_nhwc": (_I32, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "cvx_maxpool5_bwd_nhwc": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P]),
     "cvx_resize_bilinear_rows_to_nchw": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),

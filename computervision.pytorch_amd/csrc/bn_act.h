@@ -3,8 +3,10 @@
 #include "cvx_common.h"
 #define CVX_BN_MAX_C 2048    // widest BatchNorm the streaming passes hold coefficients for (one channel group of 8 per thread: ResNet-101 layer4)
 // Replica slabs the reduction kernels scatter their atomics over, by channel count.  Every consumer block folds all R
-// replicas of all C channels first, so R * C is held at ~512: 16 replicas up to 32 channels, 2 from 256 channels on (the
-// fold used to be 131 KB per block at 256 channels -- more than the block's share of the tensor on the 20x20 layers).
+// replicas of all C channels first (fold_replicas, bn_common.h: R 16-byte loads per (channel, value) pair, all in flight at
+// once, summed in registers), so R * C is held at ~512 -- four loads per thread: 16 replicas up to 32 channels, 2 from 256
+// channels on (the fold used to be 131 KB per block at 256 channels -- more than the block's share of the tensor on the
+// 20x20 layers).
 __host__ __device__ constexpr int cvx_stat_replicas(int C) { return C <= 32 ? 16 : C <= 64 ? 8 : C <= 128 ? 4 : C <= 256 ? 2 : 1; }
 #define CVX_STAT_REPLICAS_MAX 16
 #define CVX_STAT_WORDS (2 * CVX_FIX_WORDS)  // 64-bit words per channel and replica: (value 0, value 1) x (coarse, fine)
@@ -78,6 +80,8 @@ int cvx_bn_bwd_reduce(const half_t* xhat, long long M, int C, int hw, const BnCo
 // gres receives the incoming gradient (res_pre: the pre-activation gradient dz), accumulated when res_accumulate
 int cvx_bn_bwd_apply(const half_t* xhat, long long M, int C, int hw, const BnCoef& k, const long long* part, float inv_scale, float* dgamma,
                      float* dbeta, const ViewDesc& gout, const BnActKind& ak, half_t* dy, const ViewDesc& gres, int res_accumulate, hipStream_t st);
+// test hook: how the two backward passes walk M rows -- out4 = rows per block, rows per step of a block, rows of one trip (UNR steps), blocks
+int cvx_bn_bwd_plan(long long M, int C, int* out4);
 // reduce + apply in ONE launch behind a grid-wide gate (bn_act.hip); 1 = the layer does not qualify, take the two passes.  gate: one 64-bit
 // counter, zero on entry (the engine keeps it behind the layer's replica slabs).  Main stream only: see the kernel's comment.
 #define CVX_STAT_GATE_WORDS 2  // 64-bit words behind a layer's slabs: (gate counter, spare) -- keeps the next slab 16-byte aligned

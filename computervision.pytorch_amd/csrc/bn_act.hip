@@ -100,8 +100,8 @@ __global__ __launch_bounds__(256) void bn_act_apply_kernel(const typename std::c
   // 5.911 / 5.933 / 5.938 ms per step, same box (round 5)
   constexpr int RIF = RAW16 ? CVX_BN_RAW_MULT * UNR : UNR;
   using YV = typename std::conditional<RAW16, h8, f8>::type;  // a row as loaded: converted where it is used
-  // The first trip's rows and the coefficients are requested BEFORE the statistics are folded: the fold (slab reads, LDS atomics, three
-  // barriers, fp64 conversion) is 2-3 us of every block's life that the rows' memory latency now runs under.
+  // The first trip's rows and the coefficients are requested BEFORE the statistics are folded: the fold (one round of slab reads, integer
+  // adds in registers, fp64 conversion, one barrier: bn_common.h) is a memory latency of every block's life that the rows' latency runs under.
   const bool first = active && m + (long long)(RIF - 1) * RP < m1;
   YV v0[RIF];
   h8 rr0[RIF] = {};
@@ -276,7 +276,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const half_t* xhat, 
 }
 
 // RES_PRE: the residual branch receives dz (the gradient of the shared pre-activation), else the incoming gradient g
-// (requesting the first trip's rows before the fold, as the forward pass does, measured SLOWER here: 64 more live registers across the fold)
+// (requesting the first trip's rows before the fold, as the forward pass does, measured SLOWER here, twice: into registers -- 64 more of them
+// live across the fold -- and, with the fold on raw barriers, by LDS-DMA into 32-64 KB of staging behind the fold workspace: +0.06 ms per
+// step, profiles/bn_handoff_ab.txt.  What the step pays for is the CU share these blocks leave the weight-gradient stream)
 template <int ACT, bool RES_PRE, bool RAW = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const half_t* xhat, long long M, int C, int hw, BnCoef k, const long long* part,
                                                            float inv_scale, float* dgamma, float* dbeta, ViewDesc gout, ViewDesc fout, half_t* dy,
@@ -777,6 +779,16 @@ int cvx_bn_bwd_reduce(const half_t* xhat, long long M, int C, int hw, const BnCo
   else
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<2>, grid, block, 0, st, xhat, M, C, hw, k, gout, ak.fout, part, rows);
   CVX_HIP(hipGetLastError());
+  return 0;
+}
+int cvx_bn_bwd_plan(long long M, int C, int* out4) {
+  CVX_TRY(check_c(C, M));
+  CVX_CHECK(M > 0 && out4, "bn_bwd plan: bad arguments");
+  const int rows = cvx_stream_rows_per_block(M, C, 32);
+  out4[0] = rows;
+  out4[1] = 256 / (C / 8);
+  out4[2] = UNR * out4[1];
+  out4[3] = blocks_for(M, rows);
   return 0;
 }
 int cvx_bn_bwd_apply(const half_t* xhat, long long M, int C, int hw, const BnCoef& k, const long long* part, float inv_scale, float* dgamma,

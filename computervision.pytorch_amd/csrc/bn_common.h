@@ -12,39 +12,60 @@ __device__ __forceinline__ long long view_off(const ViewDesc& v, long long m, in
   return (long long)b * v.bstride + (long long)pix * v.ld;
 }
 
-// LDS bytes fold_replicas needs for C channels: [C][2 values][CVX_FIX_WORDS] 64-bit accumulators, reused for the result
+// LDS bytes the callers of fold_replicas set aside for C channels (their own arrays follow at this offset): the result, [2 values][C]
+// doubles, takes the first half
 __host__ __device__ constexpr int fold_ws_bytes(int C) { return C * 2 * CVX_FIX_WORDS * 8; }
 
 // Sums the cvx_stat_replicas(C) fixed-point slabs [R][C][2][CVX_FIX_WORDS] and leaves the two per-channel totals as doubles
-// in ws: value q of channel c at ((double*)ws)[q * C + c].  All 256 threads load slab entries in parallel (one round of
-// independent, coalesced 16-byte loads) and add them with INTEGER LDS atomics: exact and order-independent, and the
-// block pays one memory latency instead of R dependent ones.  Every thread of the 256-thread block must call it; it ends
-// with a barrier.
+// in ws: value q of channel c at ((double*)ws)[q * C + c].  A thread owns (channel, value) pairs cv = thread, thread + 256, ...
+// and adds their R replica entries in REGISTERS: integer adds, exact and order-independent, so every block of every launch
+// gets the same bits whatever the order.  All loads of a round are requested before the first is used (one memory latency;
+// consecutive threads read consecutive 16-byte entries of a slab), and the only LDS traffic is the result and ONE barrier.
+// (Until this form the entries went through 64-bit LDS atomics -- zeroed accumulators, four barriers -- from a loop of one
+// load and its adds per trip, which compiled to a wait per trip: R * C / 128 = 4 dependent latencies on every layer up to
+// 256 channels.)  Every thread of the 256-thread block must call it; it ends with a barrier.
+template <int R>
+__device__ __forceinline__ void fold_replicas_of(const long long* part, int C, double* out) {
+  constexpr int RB = R < 8 ? R : 8;   // replica entries of one pair in flight
+  constexpr int KU = 8 / RB;          // pairs per thread and round: 8 loads of 16 bytes in flight
+  const int ncv = C * 2;
+  for (int cv0 = threadIdx.x; cv0 < ncv; cv0 += 256 * KU) {
+    unsigned long long hi[KU], lo[KU];
+#pragma unroll
+    for (int k = 0; k < KU; ++k) hi[k] = lo[k] = 0;
+#pragma unroll
+    for (int r0 = 0; r0 < R; r0 += RB) {
+      longlong2 q[KU][RB];
+      // pairs past the end re-read the last one and are dropped below: a branch-free load (a select between a load and a
+      // constant makes the compiler branch, and wait, per element)
+#pragma unroll
+      for (int k = 0; k < KU; ++k)
+#pragma unroll
+        for (int r = 0; r < RB; ++r)
+          q[k][r] = *reinterpret_cast<const longlong2*>(part + ((long long)(r0 + r) * ncv + min(cv0 + 256 * k, ncv - 1)) * CVX_FIX_WORDS);
+#pragma unroll
+      for (int k = 0; k < KU; ++k)
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+          hi[k] += (unsigned long long)q[k][r].x;
+          lo[k] += (unsigned long long)q[k][r].y;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KU; ++k) {
+      const int cv = cv0 + 256 * k;  // channel * 2 + value
+      if (cv < ncv) out[(cv & 1) * C + (cv >> 1)] = cvx_fix_to_double((long long)hi[k], (long long)lo[k]);
+    }
+  }
+}
 __device__ __forceinline__ void fold_replicas(const long long* part, int C, long long* ws) {
-  const int nacc = C * 2 * CVX_FIX_WORDS;
-  for (int i = threadIdx.x; i < nacc; i += 256) ws[i] = 0;
-  __syncthreads();
-  const int total = cvx_stat_replicas(C) * C * 2;  // (replica, channel, value) entries of two 64-bit words (coarse, fine)
-  for (int e = threadIdx.x; e < total; e += 256) {
-    const longlong2 q = *reinterpret_cast<const longlong2*>(part + (long long)e * CVX_FIX_WORDS);
-    const int cv = e % (C * 2);  // channel * 2 + value
-    atomicAdd(reinterpret_cast<unsigned long long*>(&ws[cv * 2]), (unsigned long long)q.x);
-    atomicAdd(reinterpret_cast<unsigned long long*>(&ws[cv * 2 + 1]), (unsigned long long)q.y);
-  }
-  __syncthreads();
-  // convert in place: hold this thread's results in registers across the barrier (C <= 2048: at most 16 per thread)
-  double r[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int cv = threadIdx.x + 256 * k;
-    r[k] = cv < C * 2 ? cvx_fix_to_double(ws[cv * 2], ws[cv * 2 + 1]) : 0.0;
-  }
-  __syncthreads();
   double* out = reinterpret_cast<double*>(ws);
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int cv = threadIdx.x + 256 * k;
-    if (cv < C * 2) out[(cv & 1) * C + (cv >> 1)] = r[k];
+  switch (cvx_stat_replicas(C)) {  // block-uniform
+    case 16: fold_replicas_of<16>(part, C, out); break;
+    case 8: fold_replicas_of<8>(part, C, out); break;
+    case 4: fold_replicas_of<4>(part, C, out); break;
+    case 2: fold_replicas_of<2>(part, C, out); break;
+    default: fold_replicas_of<1>(part, C, out); break;
   }
   __syncthreads();
 }

@@ -80,6 +80,41 @@ extern "C" int cvx_bn_act_bwd_nhwc(const void* xhat_f16, const void* gout_f16, c
   return 0;
 }
 
+extern "C" int cvx_debug_bn_bwd_plan(int64_t rows, int32_t c, int32_t* out4) {
+  int o[4] = {0, 0, 0, 0};
+  CVX_CHECK(out4, "bad arguments");
+  CVX_TRY(cvx_bn_bwd_plan(rows, c, o));
+  for (int i = 0; i < 4; ++i) out4[i] = o[i];
+  return 0;
+}
+extern "C" int cvx_debug_bn_bwd_views(const void* kept_f16, int32_t batch, int32_t hw, int32_t c, const float* gamma, const float* beta,
+                                      const float* invstd, const float* mean, int32_t act, int32_t res_pre, float inv_scale, const void* gout_f16,
+                                      int64_t gout_bstride, int32_t gout_ld, const void* fwd_f16, int64_t fwd_bstride, int32_t fwd_ld,
+                                      void* gres_f16, int64_t gres_bstride, int32_t gres_ld, int32_t res_accumulate, float* dgamma, float* dbeta,
+                                      void* dy_f16, void* hip_stream) {
+  CVX_CHECK(kept_f16 && gout_f16 && gamma && beta && invstd && dgamma && dbeta && dy_f16 && batch > 0 && hw > 0, "bad arguments");
+  CVX_CHECK(gout_ld >= c && gout_bstride >= (int64_t)hw * gout_ld && (!fwd_f16 || (fwd_ld >= c && fwd_bstride >= (int64_t)hw * fwd_ld)) &&
+                (!gres_f16 || (gres_ld >= c && gres_bstride >= (int64_t)hw * gres_ld)),
+            "a view's pixel pitch is below its channels, or its image pitch below its pixels");
+  CVX_CHECK(gout_ld % 8 == 0 && gout_bstride % 8 == 0 && (!fwd_f16 || (fwd_ld % 8 == 0 && fwd_bstride % 8 == 0)) &&
+                (!gres_f16 || (gres_ld % 8 == 0 && gres_bstride % 8 == 0)),
+            "view pitches in multiples of 8 elements (16-byte rows)");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const long long M = (long long)batch * hw;
+  const ViewDesc none{nullptr, 0, 0};
+  const BnActKind ak{act, res_pre, fwd_f16 ? ViewDesc{(half_t*)fwd_f16, fwd_bstride, fwd_ld} : none};
+  const ViewDesc g{(half_t*)gout_f16, gout_bstride, gout_ld};
+  const ViewDesc gres = gres_f16 ? ViewDesc{(half_t*)gres_f16, gres_bstride, gres_ld} : none;
+  Scratch slab;
+  CVX_TRY(slab.alloc(slab_bytes(c)));
+  BnCoef k{invstd, gamma, beta, mean};
+  CVX_TRY(cvx_bn_bwd_reduce((const half_t*)kept_f16, M, c, hw, k, g, ak, (long long*)slab.p, st));
+  CVX_TRY(cvx_bn_bwd_apply((const half_t*)kept_f16, M, c, hw, k, (const long long*)slab.p, inv_scale, dgamma, dbeta, g, ak, (half_t*)dy_f16, gres,
+                           res_accumulate, st));
+  CVX_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
 extern "C" int cvx_maxpool5_nhwc(const void* x_f16, int32_t batch, int32_t h, int32_t w, int32_t c, void* out_f16, uint8_t* argmax,
                                  void* hip_stream) {
   CVX_CHECK(x_f16 && out_f16 && batch > 0 && c % 8 == 0, "bad arguments (channels in multiples of 8)");

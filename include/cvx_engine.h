@@ -477,6 +477,19 @@ int cvx_bn_act_train_nhwc(const float* y_f32, int32_t batch, int32_t hw, int32_t
 int cvx_bn_act_bwd_nhwc(const void* xhat_f16, const void* gout_f16, const void* out_f16, int32_t batch, int32_t hw, int32_t c,
                         const float* gamma, const float* beta, const float* invstd, int32_t act, int32_t res_pre, float inv_scale,
                         float* dgamma, float* dbeta, void* dy_f16, void* gres_f16, int32_t res_accumulate, void* hip_stream);
+/* Test hooks of the two backward passes (csrc/bn_act.hip), as the engine calls them.  cvx_debug_bn_bwd_plan (host only): how they walk
+ * `rows` = batch * hw rows of c channels -- out4 = rows per workgroup, rows per step of a workgroup, rows of one trip (the steps a thread
+ * keeps in flight; shorter remainders go row by row), workgroups.
+ * cvx_debug_bn_bwd_views is cvx_bn_act_bwd_nhwc on strided operands: gout / fwd / gres are channel-slice views, element (b, pix, ch) at
+ * p[b * bstride + pix * ld + ch] (pitches in multiples of 8 elements); kept_f16 and dy_f16 stay dense.  mean != NULL: kept_f16 is the raw
+ * conv output rounded to fp16 and xhat = (kept - mean) * invstd is formed on the fly (SiLU without a pre-activation residual only).
+ * (No reference counterpart.) */
+int cvx_debug_bn_bwd_plan(int64_t rows, int32_t c, int32_t* out4);
+int cvx_debug_bn_bwd_views(const void* kept_f16, int32_t batch, int32_t hw, int32_t c, const float* gamma, const float* beta,
+                           const float* invstd, const float* mean, int32_t act, int32_t res_pre, float inv_scale, const void* gout_f16,
+                           int64_t gout_bstride, int32_t gout_ld, const void* fwd_f16, int64_t fwd_bstride, int32_t fwd_ld, void* gres_f16,
+                           int64_t gres_bstride, int32_t gres_ld, int32_t res_accumulate, float* dgamma, float* dbeta, void* dy_f16,
+                           void* hip_stream);
 /* 5x5 / stride 1 / pad 2 max pool (SPPF, core/models/yolov8/modules.py:312-318) and its backward; argmax (optional in
  * the forward): one byte per element, the window tap 0..24 of the first maximum in row-major scan order. */
 int cvx_maxpool5_nhwc(const void* x_f16, int32_t batch, int32_t h, int32_t w, int32_t c, void* out_f16, uint8_t* argmax, void* hip_stream);
