@@ -130,6 +130,8 @@ PROTOTYPES = {
     "cvx_nms_workspace_bytes": (_I64, [_I32, _I32]),
     "cvx_nms": (_I32, [_P, _I32, _I32, _I32, _F, _F, _I32, _P, _P, _P, _P, _I64, _P]),
     "cvx_nms_variant": (_I32, [_P, _I32, _I32, _I32, _F, _F, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "cvx_soft_nms_workspace_bytes": (_I64, [_I32, _I32]),
+    "cvx_soft_nms": (_I32, [_P, _I32, _I32, _I32, _F, _F, _I32, _I32, _F, _F, _I32, _P, _P, _P, _P, _I64, _P]),
     "cvx_centernet_decode_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "cvx_centernet_decode": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "cvx_conv2d_nhwc": (_I32, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -372,10 +372,15 @@ _nms_ws = {}
 NMS_VARIANTS = {"tv0141_cuda": 0, "tv0141_cpu": 1, "offset": 2, "vanilla": 3}
 
 
-def nms(y: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, variant: str = "tv0141_cuda", boxes_xyxy: bool = False):
+def nms(y: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, variant: str = "tv0141_cuda", boxes_xyxy: bool = False,
+        soft=None):
     """y (B, 4+nc, A) fp32 -> (rows (B,max_det,6), anchor_index (B,max_det) int32, counts (B,) int32), all on device.
     ``variant``: torchvision 0.14.1 ``batched_nms`` strategy (include/cvx_engine.h); the default is the library's own
-    switch for CUDA tensors, i.e. what the reference's GPU predict path runs."""
+    switch for CUDA tensors, i.e. what the reference's GPU predict path runs.  ``soft``: a ``soft_nms.SoftNMS`` -- the call is then
+    ``soft_nms.soft_nms`` (``cvx_soft_nms``: per class, or over the whole block when ``soft.class_agnostic``; ``variant`` plays no part)."""
+    if soft is not None:
+        from .soft_nms import soft_nms
+        return soft_nms(y, conf_thres, soft, iou_thres, max_det, boxes_xyxy)
     lib = L.load()
     _need_gpu(y, "y")
     if not (0 <= conf_thres <= 1 and 0 <= iou_thres <= 1):

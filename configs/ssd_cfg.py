@@ -24,4 +24,5 @@ class SsdConfig:
         self.loss = _Group(alpha=0.25, gamma=2.0, overlap_threshold=0.5, neg_pos=3, variance=[0.1, 0.2])
         self.optimizer = _Group(name="Adam")
         self.log = _Group(root="log", print_interval=50)
-        self.decode = _Group(test_results="result", letterbox_image=True, nms_threshold=0.5, confidence_threshold=0.7)
+        self.decode = _Group(test_results="result", letterbox_image=True, nms_threshold=0.5, confidence_threshold=0.7,
+                             soft_nms=None)      # (new) None: hard NMS; a dict of soft_nms.SoftNMS keywords or a SoftNMS: Soft-NMS

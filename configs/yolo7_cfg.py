@@ -22,4 +22,5 @@ class Yolo7Config:
         self.loss = _Group(ignore_threshold=0.5, label_smoothing=0)
         self.optimizer = _Group(name="Adam", scheduler_name="multi_step")
         self.log = _Group(root="log", print_interval=50)
-        self.decode = _Group(test_results="result", letterbox_image=True, conf_threshold=0.5, nms_threshold=0.3)  # (:88-96)
+        self.decode = _Group(test_results="result", letterbox_image=True, conf_threshold=0.5, nms_threshold=0.3,  # (:88-96)
+                             soft_nms=None)      # (new) None: hard NMS; a dict of soft_nms.SoftNMS keywords or a SoftNMS: Soft-NMS

@@ -52,6 +52,7 @@ class Yolo8DetConfig:
             conf_threshold=0.25,
             nms_threshold=0.7,
             max_det=300,
+            soft_nms=None,      # (new; not in the reference) None: hard NMS; a dict of soft_nms.SoftNMS keywords or a SoftNMS: Soft-NMS
         )
         # --- MI355X engine knobs (new; not in the reference) ---------------------------------
         self.engine = _Group(

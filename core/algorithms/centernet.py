@@ -29,6 +29,9 @@ class CenterNetA(Detector):
         self.nms_threshold = cfg.decode.nms_threshold
         self.use_nms = cfg.decode.use_nms
         self.letterbox_image = cfg.decode.letterbox_image
+        if getattr(cfg.decode, "soft_nms", None) is not None:
+            raise L.CvxError("cfg.decode.soft_nms is not built for CenterNet: its DIoU-NMS is part of cvx_centernet_decode "
+                             "(the YOLOv8, YOLOv7 and SSD tails have it)")
 
     def build_model(self):
         return CenterNetDLA34(self.num_classes), "CenterNet"

@@ -9,6 +9,7 @@ import torch
 
 from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd import engine as _engine
+from computervision.pytorch_amd import soft_nms as _soft_nms
 from computervision.pytorch_amd.ssd import MultiBoxLoss, SSD300VGG
 from configs import SsdConfig
 from core.algorithms.base import NmsDetector, nms_with_room
@@ -30,6 +31,10 @@ class Ssd(NmsDetector):
         self.conf_threshold = cfg.decode.confidence_threshold
         self.nms_threshold = cfg.decode.nms_threshold
         self.letterbox_image = cfg.decode.letterbox_image
+        self.soft_nms = _soft_nms.configured(cfg)      # None: cvx_nms_variant; a SoftNMS: cvx_soft_nms in its place
+        if self.soft_nms is not None and self.soft_nms.class_agnostic:
+            raise L.CvxError("cfg.decode.soft_nms: class_agnostic=True is not built for SSD -- its decode scores every prior in every class "
+                             "and suppresses one (class, image) block at a time, so a block holds one class and there is nothing to cross")
         self._priors_dev = None
 
     def _get_ssd_anchors(self):
@@ -122,7 +127,8 @@ class Ssd(NmsDetector):
         stacked = torch.cat((bt.unsqueeze(0).expand(nc_act, -1, -1, -1), prob.index_select(2, cidx).permute(2, 0, 1).unsqueeze(2)), 2).reshape(nc_act * B, 5, A)
         # 8732 priors never exceed the 16384 candidates the in-LDS sort holds: the overflow error is kept for other prior sets
         overflow = "cvx_nms: more than 16384 candidates of one class above the confidence threshold in one image"
-        r_, i_, counts, counts_h = nms_with_room(stacked, float(conf_thr), self.nms_threshold, lambda block: overflow, boxes_xyxy=True)
+        more = {} if self.soft_nms is None else {"soft": self.soft_nms}     # the blocks are one class each: per-class Soft-NMS, column 5 the decayed score
+        r_, i_, counts, counts_h = nms_with_room(stacked, float(conf_thr), self.nms_threshold, lambda block: overflow, boxes_xyxy=True, **more)
         rows = r_.view(nc_act, B, *r_.shape[1:])                                 # (C', B, max_det, 6)
         index = i_.long().view(nc_act, B, -1)                                    # (C', B, max_det)
         counts, counts_h = counts.view(nc_act, B), counts_h.view(nc_act, B)      # (C', B), on the device and on the host

@@ -9,6 +9,7 @@ import torch
 
 from computervision.pytorch_amd import _lib as L
 from computervision.pytorch_amd import engine as _engine
+from computervision.pytorch_amd import soft_nms as _soft_nms
 from computervision.pytorch_amd.yolov7 import Yolo7L, Yolo7Loss
 from configs import Yolo7Config
 from core.algorithms.base import MAX_CANDIDATES, NmsDetector, nms_with_room
@@ -27,6 +28,7 @@ class YOLOv7(NmsDetector):
         self.letterbox_image = cfg.decode.letterbox_image
         self.conf_threshold = cfg.decode.conf_threshold
         self.nms_threshold = cfg.decode.nms_threshold
+        self.soft_nms = _soft_nms.configured(cfg)      # None: cvx_nms_variant; a SoftNMS: cvx_soft_nms in its place
 
     def get_anchors(self) -> np.ndarray:
         return np.array(self.cfg.arch.anchors, dtype=np.float32).reshape(-1, 2)
@@ -59,13 +61,16 @@ class YOLOv7(NmsDetector):
     def nms_device(self, y: torch.Tensor, dec: torch.Tensor, conf_threshold=None):
         """Per-class greedy NMS with score = objectness * best class probability (``_nms``, yolo_v7.py:348-415) on the device:
         per image an (n, 7) tensor [x1, y1, x2, y2, obj_conf, class_conf, class_pred] in normalised corner coordinates -- classes
-        ascending, scores descending inside a class, like the reference's concatenation -- and the kept rows of ``dec``."""
+        ascending, scores descending inside a class, like the reference's concatenation -- and the kept rows of ``dec``.  With
+        ``cfg.decode.soft_nms`` set the rows come from ``cvx_soft_nms``: column 4 carries the decayed score and column 5 is 1.0, so that
+        every consumer's product ``obj_conf * class_conf`` is the decayed score exactly."""
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
         # cvx_nms keeps scores > threshold (ultralytics_ops.py:190), the reference here keeps >= : the next float below
         thr = float(np.nextafter(np.float32(conf), np.float32(-1.0)))
         # the in-LDS sort holds 16384 candidates per image: only beyond that is the reference's unlimited _nms out of reach
         overflow = f"cvx_nms: more than {MAX_CANDIDATES} candidates above the confidence threshold in image "
-        rows, index, counts, counts_h = nms_with_room(y, thr, self.nms_threshold, lambda b: overflow + str(b))
+        more = {} if self.soft_nms is None else {"soft": self.soft_nms}
+        rows, index, counts, counts_h = nms_with_room(y, thr, self.nms_threshold, lambda b: overflow + str(b), **more)
         counts_h = counts_h.tolist()
         # re-order every image's kept rows at once (no per-image kernels): class ascending, cvx_nms's descending score inside a class;
         # rows past an image's count sort to the end
@@ -76,7 +81,10 @@ class YOLOv7(NmsDetector):
         idx = index.long().gather(1, order).clamp_(min=0)
         d = dec.gather(1, idx.unsqueeze(2).expand(-1, -1, dec.shape[2]))
         cconf = d[:, :, 5:5 + self.num_classes].gather(2, r[:, :, 5:6].long().clamp_(0, self.num_classes - 1))
-        det = torch.cat((r[:, :, :4], d[:, :, 4:5], cconf, r[:, :, 5:6]), 2)
+        if self.soft_nms is None:
+            det = torch.cat((r[:, :, :4], d[:, :, 4:5], cconf, r[:, :, 5:6]), 2)
+        else:       # the decayed score is no product of the two columns of ``dec`` any more: it goes out whole, beside 1.0
+            det = torch.cat((r[:, :, :4], r[:, :, 4:5], torch.ones_like(cconf), r[:, :, 5:6]), 2)
         return [(det[b, :n], idx[b, :n]) if n > 0 else (None, None) for b, n in enumerate(counts_h)]
 
     def decode_box(self, preds, image_h, image_w, conf_threshold=None, model=None):

@@ -10,6 +10,7 @@ from computervision.pytorch_amd._lib import CvxError
 
 from computervision.pytorch_amd import det_eval
 from computervision.pytorch_amd import engine as _engine
+from computervision.pytorch_amd import soft_nms as _soft_nms
 from computervision.pytorch_amd.model import Yolo8
 from computervision.pytorch_amd.train import V8DetectionLoss
 from configs import Yolo8DetConfig
@@ -34,6 +35,7 @@ class YOLOv8(Detector):
         self.iou_threshold = cfg.decode.nms_threshold
         self.max_det = cfg.decode.max_det
         self.letterbox_image = cfg.decode.letterbox_image
+        self.soft_nms = _soft_nms.configured(cfg)      # None: cvx_nms_variant; a SoftNMS: cvx_soft_nms in its place
 
     def build_model(self):
         if self.model_type not in _NAMES:
@@ -50,7 +52,7 @@ class YOLOv8(Detector):
         (ultralytics_ops.non_max_suppression's return format, class-aware, max_det rows)."""
         y = preds[0] if isinstance(preds, (list, tuple)) else preds
         conf = self.conf_threshold if conf_threshold is None else conf_threshold
-        rows, _, counts = _engine.nms(y, conf, self.iou_threshold, self.max_det)
+        rows, _, counts = _engine.nms(y, conf, self.iou_threshold, self.max_det, soft=self.soft_nms)
         counts = counts.cpu().tolist()
         if min(counts, default=0) < 0:   # cvx_nms_variant signals "more candidates than the in-LDS sort holds" with -1: never slice rows[:-1]
             raise CvxError(f"non_max_suppression: image {counts.index(min(counts))} has more than 16384 candidates above conf {conf} "
@@ -68,13 +70,13 @@ class YOLOv8(Detector):
 
     def _evaluation_rows(self, model):
         """(images, meta, conf_threshold=0.001) -> (rows, counts, box map) of one batch, for ``evaluate_on_voc`` / ``evaluate_on_coco``:
-        one engine forward and ``cvx_nms`` with the counts kept on the device; the evaluators' match launch undoes the letterbox (box-map
+        one engine forward and ``cvx_nms`` (``cvx_soft_nms`` with ``cfg.decode.soft_nms`` set) with the counts kept on the device; the evaluators' match launch undoes the letterbox (box-map
         mode 1), so the host reads once, at the end."""
         def rows_of(images, meta, conf_threshold=0.001):
             with torch.no_grad():
                 preds = model(images.to(self.device))
             y = preds[0] if isinstance(preds, (list, tuple)) else preds
-            rows, _, counts = _engine.nms(y, conf_threshold, self.iou_threshold, self.max_det)
+            rows, _, counts = _engine.nms(y, conf_threshold, self.iou_threshold, self.max_det, soft=self.soft_nms)
             return rows, counts, det_eval.letterbox_box_map(meta["image_hw"], self.input_image_size, self.letterbox_image)
 
         return rows_of

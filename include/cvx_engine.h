@@ -414,6 +414,42 @@ int cvx_nms_variant(const float* y, int32_t batch, int32_t anchors, int32_t nc, 
                     int32_t variant, float* out_rows, int32_t* out_index, int32_t* counts, void* workspace, int64_t workspace_bytes,
                     void* hip_stream);
 
+/* ---- Soft-NMS (Bodla et al., ICCV 2017; csrc/soft_nms.hip) -----------------------------------------------------
+ * A sibling of cvx_nms_variant: the same y (batch, 4+nc, anchors), the same outputs -- out_rows (batch, max_det, 6) [x1, y1, x2, y2, final
+ * score, cls], out_index (batch, max_det) the anchor of each row, counts (batch) -- and one workgroup per block of the batch (an image;
+ * a (class, image) pair for SSD).  The score of a box that overlaps a better one decays instead of the box disappearing.  Every fp32
+ * operation below is rounded on its own (no contraction).  tests/soft_nms_restatement.py restates the rules in numpy float32.
+ *   candidates  an anchor whose best class score is > conf_thres; its class is the first arg max.  Boxes: hw = w * 0.5f, x1 = cx - hw,
+ *               x2 = cx + hw, likewise y (cvx_nms's box_corners); with CVX_NMS_BOXES_XYXY in `flags` rows 0..3 are taken as they are.
+ *   order       score descending, then anchor ascending (the 64-bit key of cvx_nms).  "Position" is the position in this order.
+ *   segments    the candidates of one class; the whole block with CVX_SOFT_NMS_CLASS_AGNOSTIC in `flags`.  Candidates of different
+ *               segments never touch each other.
+ *   walk        of a segment: every candidate starts live with s = score.  Repeat: M = the live candidate with the largest s, the
+ *               lowest position among equals (a candidate whose s is not >= 0 -- only a degenerate overlap above 1 gets one there -- is
+ *               never taken).  The segment stops when method != HARD and s_M is not > min_score.  M is emitted with final score s_M and
+ *               dies.  For every other live i of the segment o = IoU(M, i), cvx_nms's IoU to the bit (box_overlap.h:iou_value), and
+ *                 CVX_SOFT_NMS_HARD      o > iou_thres removes i; its score is not touched.
+ *                 CVX_SOFT_NMS_LINEAR    o > iou_thres gives s_i = s_i * (1.0f - o).
+ *                 CVX_SOFT_NMS_GAUSSIAN  o > 0 gives s_i = s_i * E((o * o) / sigma).
+ *               A NaN overlap satisfies neither comparison: it never decays or removes anything.
+ *   E(x)        the library's own exp(-x): x >= 80 gives 0.0f; else t = -x, k = rintf(t * 1.44269504f), r = (t - k * 0.693359375f)
+ *               - k * -2.12194440e-4f, p = 1/720 then p = p * r + c for c = 1/120, 1/24, 1/6, 1/2, 1, 1 (the fp32 quotients; a rounded
+ *               product, then a rounded add), and ldexpf(p, k), which is exact.  Within 1e-6 relative of exp(-x) on [0, 20].
+ *   merge       a segment's emissions come out in non-increasing score.  The emitted candidates of all segments are merged by (final
+ *               score descending, position ascending); the first max_det leave, rows and indices past the count are zero.
+ *   capacity    16384 candidates per block: more sets counts[b] = -1 (rows zero), never truncated.
+ * Consequence: CVX_SOFT_NMS_HARD without CVX_SOFT_NMS_CLASS_AGNOSTIC is cvx_nms_variant(CVX_NMS_VANILLA) bit for bit in rows, indices
+ * and counts.  Two calls give the same bits.
+ * Refused: thresholds outside [0, 1]; sigma outside [0.05, 10] (so that x <= 20); min_score outside [0, 1); max_det outside [1, 16384];
+ * an unknown method or flag.  sigma and min_score are checked, and ignored, in the methods that do not use them.
+ * workspace: cvx_soft_nms_workspace_bytes(batch, anchors) bytes of device memory. */
+enum { CVX_SOFT_NMS_HARD = 0, CVX_SOFT_NMS_LINEAR = 1, CVX_SOFT_NMS_GAUSSIAN = 2 };
+#define CVX_SOFT_NMS_CLASS_AGNOSTIC 0x200 /* OR-ed into `flags` beside CVX_NMS_BOXES_XYXY: one segment per block */
+int64_t cvx_soft_nms_workspace_bytes(int32_t batch, int32_t anchors);
+int cvx_soft_nms(const float* y, int32_t batch, int32_t anchors, int32_t nc, float conf_thres, float iou_thres, int32_t max_det,
+                 int32_t method, float sigma, float min_score, int32_t flags, float* out_rows, int32_t* out_index, int32_t* counts,
+                 void* workspace, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- CenterNet heat-map decode (BASELINE.json configs[3]) -----------------------------------------------------
  * pred: (B, H*W, pred_ld) fp32 head tensor, heat-map logits in columns [0, nc), the two channels the reference reads as
  * centre offsets at reg_col (its "wh" head), the two it reads as sizes at wh_col (its "reg" head).  Per image: sigmoid,
