@@ -153,6 +153,8 @@ PROTOTYPES = {
     "cvx_track_update": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "cvx_draw_tracks": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_seg_stitch": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "cvx_seg_regions_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "cvx_seg_regions": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "cvx_seg_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "cvx_seg_fuse": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_det_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _F, _P, _P]),
@@ -232,6 +234,9 @@ PROTOTYPES = {
 SEG_VIEW_DTYPE = np.dtype([("rows", "<u8"), ("lh", "<i4"), ("lw", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
 # cvx_det_view (include/cvx_engine.h): one view of cvx_det_tta_inputs's host table, 24 bytes
 DET_VIEW_DTYPE = np.dtype([("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
+# cvx_seg_plane / cvx_seg_imap (include/cvx_engine.h): an fp32 / int32 map of a frame for cvx_seg_regions, pitch in elements, 16 bytes
+SEG_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<i4"), ("reserved", "<i4")])
+SEG_IMAP_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<i4"), ("reserved", "<i4")])
 
 _lib = None
 

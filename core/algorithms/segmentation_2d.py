@@ -174,27 +174,75 @@ class DeeplabV3PlusA(FramePredictor):
             torch.cuda.synchronize(block.device)
         return labels
 
-    def segment_frames(self, model, frames, batch_size, **tiled):
+    def predict_regions(self, model, frames, regions=None, conf=False, draw=False, tracker=None, sync=False, **tiled):
+        """Things from the label maps: ``segment_tiled(model, frames, draw=draw, **tiled)`` -- frames of any size, a
+        frame no larger than the network input is one tile -- and then ``seg_regions.label_regions`` on its label maps under ``regions``
+        (a ``seg_regions.SegRegions``, default ``SegRegions()``): the connected regions of every class as rows ``[x1, y1, x2, y2, score,
+        cls]`` with counts, the detectors' format.  With ``draw`` the boxes are painted over the class overlay (``cvx_draw_detections``);
+        ``tracker``: a ``track.Tracker`` -- the frames are consecutive frames of its stream 0, the batch gains ``ids`` and ``draw`` paints
+        them with ``cvx_draw_tracks``.  Returns the ``seg_regions.RegionBatch`` (with ``labels``, the label maps) on the device; ``sync``
+        waits for the device, ``RegionBatch.read()`` is the one host read.  ``conf=True`` is refused: ``segment_tiled`` keeps no
+        probabilities (every region scores 1); ``predict_labels(..., probs=True)`` has them, see ``seg_regions.label_regions``."""
+        from computervision.pytorch_amd import render, seg_regions
+        self._need_gpu("predict_regions")
+        if conf:
+            raise L.CvxError("predict_regions(conf=True): segment_tiled stitches labels and keeps no probabilities, so there is no confidence "
+                             "to average; use predict_labels(..., probs=True) and pass conf= to seg_regions.label_regions")
+        if tracker is not None:
+            from computervision.pytorch_amd.track import Tracker
+            if not isinstance(tracker, Tracker):
+                raise ValueError(f"tracker: a track.Tracker, got {type(tracker).__name__}")
+        frames = list(frames)
+        labels = self.segment_tiled(model, frames, draw=draw, sync=False, **tiled)
+        found = seg_regions.label_regions(labels, regions)
+        found.labels = labels
+        if tracker is not None:
+            found.ids = tracker.update(found.rows, found.counts)
+        if draw:
+            if tracker is not None:
+                render.draw_tracks(frames, found.rows, found.ids, found.counts)
+            else:
+                render.draw_detections(frames, found.rows, found.counts)
+        if sync:
+            torch.cuda.synchronize(found.rows.device)
+        return found
+
+    def segment_frames(self, model, frames, batch_size, regions=None, track=None, **tiled):
         """``detect_frames`` for ``segment_tiled``: a generator over any iterable of uint8 HWC RGB device frames that yields the list of
         drawn frames of each batch of ``batch_size`` (the last one may be short).  Each batch is one ``segment_tiled(..., draw=True,
         sync=False, **tiled)``, so nothing inside the loop waits on the host.  ``batch_size`` counts frames; the slots per forward stay at
-        ``segment_tiled``'s default.  (``detect_frames(..., tiled=...)`` stays the detectors'.)"""
+        ``segment_tiled``'s default.  (``detect_frames(..., tiled=...)`` stays the detectors'.)
+        ``regions``: a ``seg_regions.SegRegions`` -- each batch is then one ``predict_regions(..., regions=regions, draw=True)``: the boxes
+        of the connected regions are painted over the overlay.  ``track``: a ``track.Tracker``, or a dict of its parameters from which one
+        is created for the generator's lifetime -- the regions keep an identity from frame to frame and are painted with their track ids
+        (``regions`` defaults to ``SegRegions()`` then).  With both None nothing changes."""
         self._need_gpu("segment_frames")
         if int(batch_size) <= 0:
             raise ValueError("batch_size is positive")
         if {"draw", "sync"} & set(tiled):
             raise ValueError("segment_frames draws and does not wait: it takes neither draw nor sync")
+        if regions is None and track is None:
+            def segment(batch):
+                self.segment_tiled(model, batch, draw=True, sync=False, **tiled)
+        else:
+            tracker = None
+            if track is not None:
+                from computervision.pytorch_amd.track import Tracker
+                tracker = track if isinstance(track, Tracker) else Tracker(self.device, **dict(track))
+
+            def segment(batch):
+                self.predict_regions(model, batch, regions=regions, draw=True, tracker=tracker, sync=False, **tiled)
 
         def batches():
             batch = []
             for frame in frames:
                 batch.append(frame)
                 if len(batch) == int(batch_size):
-                    self.segment_tiled(model, batch, draw=True, sync=False, **tiled)
+                    segment(batch)
                     yield batch
                     batch = []
             if batch:
-                self.segment_tiled(model, batch, draw=True, sync=False, **tiled)
+                segment(batch)
                 yield batch
 
         return batches()

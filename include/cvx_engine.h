@@ -1275,6 +1275,56 @@ int cvx_det_fuse_wbf(const float* rows, const int32_t* counts, int32_t max_det_i
                      int32_t conf_mode, int32_t rescale, int32_t max_det_out, float* out_rows, int32_t* out_counts, int32_t* out_source,
                      int32_t* out_members, int32_t* overflow, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- connected-component regions of label maps (csrc/seg_regions.hip) ------------------------------------------------
+ * Boxes from label maps: the connected regions of each class of a uint8 label map (cvx_seg_stitch's, cvx_seg_fuse's), in the detectors'
+ * row format, so that cvx_draw_detections, cvx_draw_tracks, cvx_track_update, cvx_det_match and cvx_coco_match take them as they are.
+ * All frames of a batch run together: a fixed number of launches (five, six with a map) whatever the maps hold, asynchronous on
+ * hip_stream, tables in device memory, nothing read back.  The reference has no counterpart: the rules are the project's own, restated in
+ * numpy in tests/seg_regions_restatement.py, and the kernels are held to the restatement bit for bit.
+ * An fp32 (h, w) plane of a frame with its row pitch in ELEMENTS; data NULL: this frame has none.  16 bytes. */
+typedef struct cvx_seg_plane {
+  const float* data;
+  int32_t pitch, reserved;
+} cvx_seg_plane;
+/* An int32 (h, w) map of a frame with its row pitch in ELEMENTS; data NULL: this frame has none.  16 bytes. */
+typedef struct cvx_seg_imap {
+  int32_t* data;
+  int32_t pitch, reserved;
+} cvx_seg_imap;
+/* label_maps (frames) with data != NULL and frame_hw (frames, 2) int32 [h, w] on the device; (max_h, max_w): the largest frame (the grid
+ * and the workspace planes).  class_mask_host: 8 uint32 in HOST memory, read before the call returns; bit (c & 31) of word c >> 5 selects
+ * label c.  Per frame f with label map L:
+ *   selected    a pixel is selected when bit L[y, x] of the mask is set; the others belong to no region and connect nothing.
+ *   regions     a region is a maximal set of selected pixels of equal label connected through 4-neighbours (connectivity 4) or
+ *               8-neighbours (connectivity 8).
+ *   seed        the smallest linear index y * w + x of a region's pixels: its first pixel in raster order.
+ *   statistics  exact integers: area, min_x, min_y, max_x, max_y.
+ *   score       without `conf` 1.0f.  With conf (one entry per frame, every one with data, fp32 per pixel and its own
+ *               pitch) each pixel gives q = (uint32) rintf(fminf(fmaxf(c, 0.0f), 1.0f) * 65535.0f), a NaN
+ *               gives 0; S is the sum of q over the region in a 64-bit integer; score = (float)((double) S / ((double) area * 65535.0)).
+ *               No floating-point atomic anywhere: two calls give the same bits.
+ *   filter      the regions with area >= min_area (>= 1) are the frame's candidates; total[f] is their number, always written.
+ *   order       area descending, then seed ascending -- a strict total order; the 64-bit key of csrc/lds_sort.h,
+ *               ((0xFFFFFFFF - area) << 32) | seed.
+ *   row         [(float) min_x, (float) min_y, (float)(max_x + 1), (float)(max_y + 1), score, (float) label].
+ *   outputs     rows (frames, max_det, 6), zero past the count; counts[f] = min(total[f], max_det); areas and seeds (frames, max_det)
+ *               int32, -1 past the count.  region_maps (optional table, optional per frame): the row index of the pixel's region, -1 for
+ *               unselected pixels and for regions that were filtered or cut by max_det.  clean_maps (optional table, optional per frame):
+ *               L with every selected pixel of a region below min_area replaced by `fill` (0 .. 255); written whatever the capacity says.
+ *   capacity    8192 candidates per frame (the in-LDS sort of cvx_det_merge_tiles): beyond it counts[f] = -1, the frame's rows are zero,
+ *               its region map is all -1 and *overflow (1 int32, device, cleared by the caller) grows by 1 -- flagged, never truncated;
+ *               total[f] still says how far over it was.  The other frames of the batch are unaffected.
+ *   bad frames  h <= 0, w <= 0, h * w >= 2^31, h > max_h or w > max_w: a no-op with count 0 and total 0 that adds 1 to *overflow.
+ * 1 <= max_det <= 8192.  workspace: cvx_seg_regions_workspace_bytes(frames, max_h, max_w) bytes of device memory, 8-byte aligned: 28 bytes
+ * per pixel of a max_h x max_w plane per frame (parent 4, area 4, q sum 8, min_x 4, max_x 4, max_y 4) plus 33 KB per frame; 0 for sizes
+ * the entry refuses (max_h * max_w >= 2^31). */
+int64_t cvx_seg_regions_workspace_bytes(int32_t frames, int32_t max_h, int32_t max_w);
+int cvx_seg_regions(const cvx_seg_map* label_maps, const int32_t* frame_hw, int32_t frames, int32_t max_h, int32_t max_w,
+                    const uint32_t* class_mask_host, int32_t connectivity, int32_t min_area, int32_t max_det, int32_t fill,
+                    const cvx_seg_plane* conf, const cvx_seg_imap* region_maps, const cvx_seg_map* clean_maps, float* rows, int32_t* counts,
+                    int32_t* total, int32_t* areas, int32_t* seeds, int32_t* overflow, void* workspace, int64_t workspace_bytes,
+                    void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 

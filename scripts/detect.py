@@ -18,13 +18,17 @@ def detect_frames(algorithm, model, frames, batch_size, tiled=None, track=None, 
     return algorithm.detect_frames(model, frames, batch_size, tiled=tiled, track=track, tta=tta)
 
 
-def segment_frames(algorithm, model, frames, batch_size, **tiled):
+def segment_frames(algorithm, model, frames, batch_size, regions=None, track=None, **tiled):
     """``detect_frames`` for sliding-window segmentation: ``algorithm`` is the DeepLab algorithm object, each batch is its
     ``segment_tiled(..., draw=True, sync=False, **tiled)`` -- tiles at network size, logits stitched on the device, the class colours
-    blended into the frames in place."""
+    blended into the frames in place.  ``regions``: a ``seg_regions.SegRegions`` -- the connected regions of the label maps are boxed on
+    the device and painted over the overlay; ``track``: a ``track.Tracker`` or a dict of its parameters -- the regions keep an identity
+    from frame to frame.  With both None nothing changes."""
     if not hasattr(algorithm, "segment_frames"):
         raise CvxError(f"{type(algorithm).__name__} has no sliding-window segmentation")
-    return algorithm.segment_frames(model, frames, batch_size, **tiled)
+    if regions is None and track is None:
+        return algorithm.segment_frames(model, frames, batch_size, **tiled)
+    return algorithm.segment_frames(model, frames, batch_size, regions=regions, track=track, **tiled)
 
 
 def _run_video(src_video_path, dst_video_path, device, batches_of):
@@ -68,12 +72,12 @@ def detect_video(model, src_video_path, dst_video_path, decode_fn, batch_size=8,
                lambda frames: detect_frames(algorithm, model, frames, batch_size, tiled=tiled, track=track, tta=tta))
 
 
-def segment_video(model, src_video_path, dst_video_path, decode_fn, batch_size=2, **tiled):
+def segment_video(model, src_video_path, dst_video_path, decode_fn, batch_size=2, regions=None, track=None, **tiled):
     """``detect_video`` for full-resolution segmentation: every frame goes through ``segment_tiled`` (``tiled``: its keywords ``overlap``,
     ``weight``, ``bgr``; ``batch_size`` is the frames per call, the slots per forward stay at its default) instead of being stretched to
-    the network input."""
+    the network input.  ``regions`` and ``track`` as in ``segment_frames``."""
     algorithm = getattr(decode_fn, "__self__", decode_fn)
     if not hasattr(algorithm, "segment_frames"):
         raise CvxError("segment_video: decode_fn is the DeepLab algorithm object or its bound predict method")
     _run_video(src_video_path, dst_video_path, torch.device(algorithm.device),
-               lambda frames: segment_frames(algorithm, model, frames, batch_size, **tiled))
+               lambda frames: segment_frames(algorithm, model, frames, batch_size, regions=regions, track=track, **tiled))
