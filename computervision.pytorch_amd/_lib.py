@@ -281,6 +281,18 @@ def ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+_workspaces = {}
+
+
+def workspace(name: str, device, need: int):
+    """The grow-only uint8 workspace of the entry ``name`` on ``device``: a tensor of at least ``need`` bytes, kept between calls."""
+    import torch
+    ws = _workspaces.get((name, device))
+    if ws is None or ws.numel() < need:
+        ws = _workspaces[(name, device)] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 def stream_ptr(device=None):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

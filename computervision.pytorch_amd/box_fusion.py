@@ -65,7 +65,6 @@ class WBF:
                         self.rescale, self.class_agnostic, self.max_det if max_det is None else max_det, overflow)
 
 
-_wbf_ws = {}
 _weights_on = {}          # (device, weights) -> (the pinned host tensor the copy reads, the device tensor)
 
 
@@ -131,10 +130,7 @@ def fuse_wbf(rows: torch.Tensor, counts: torch.Tensor, view_map: torch.Tensor, f
     if overflow is None:
         overflow = torch.zeros(1, dtype=torch.int32, device=rows.device)
     lib = L.load()
-    need = int(lib.cvx_det_wbf_workspace_bytes(B))
-    ws = _wbf_ws.get(rows.device)
-    if ws is None or ws.numel() < need:
-        ws = _wbf_ws[rows.device] = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    ws = L.workspace("det_fuse_wbf", rows.device, int(lib.cvx_det_wbf_workspace_bytes(B)))
     with torch.cuda.device(rows.device):
         w = _device_weights(weights, S, rows.device)
         L.check(lib.cvx_det_fuse_wbf(L.ptr(rows), L.ptr(counts), K, L.ptr(view_map), L.ptr(frame_hw), B, S, L.ptr(w), float(iou), float(skip_score),

@@ -20,6 +20,7 @@
 // keys.  Every fp32 step is one rounded operation: the file is compiled with contraction off, and tests/box_fusion_restatement.py holds
 // the kernel to the bit.
 #include "box_overlap.h"
+#include "det_rows.h"
 #include "lds_sort.h"
 #include "view_box.h"
 #include "../../include/cvx_engine.h"
@@ -52,15 +53,6 @@ struct WbfWs {
   int* cnt;        // ... the members (0: the slot holds no cluster) and the meta word of the first member
   int* first;
 };
-
-__device__ __forceinline__ void zero_rows(float* orow, int* osrc, int* omem, int from, int max_det) {
-  for (int r = from + threadIdx.x; r < max_det; r += WBF_THREADS) {
-    float* o = orow + (long long)r * 6;
-    o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.f;
-    osrc[r] = -1;
-    omem[r] = 0;
-  }
-}
 
 __global__ __launch_bounds__(WBF_THREADS) void wbf_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int max_det_in,
                                                           const float* __restrict__ view_map, const int* __restrict__ frame_hw, int frames, int sources,
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(WBF_THREADS) void wbf_kernel(const float* __restric
   __syncthreads();
   const int n_raw = s_pre[sources];
   if (n_raw > WBF_CAP) {  // more than the in-LDS sort holds: flagged, never truncated
-    zero_rows(orow, osrc, omem, 0, max_det);
+    zero_rows<WBF_THREADS>(orow, 0, max_det, osrc, -1, omem, 0);
     if (tid == 0) {
       out_counts[f] = -1;
       atomicAdd(overflow, 1);
@@ -121,7 +113,7 @@ __global__ __launch_bounds__(WBF_THREADS) void wbf_kernel(const float* __restric
   __syncthreads();
   const int n = s_fill;
   if (n == 0) {
-    zero_rows(orow, osrc, omem, 0, max_det);
+    zero_rows<WBF_THREADS>(orow, 0, max_det, osrc, -1, omem, 0);
     if (tid == 0) out_counts[f] = 0;
     return;
   }
@@ -268,30 +260,42 @@ __global__ __launch_bounds__(WBF_THREADS) void wbf_kernel(const float* __restric
     const int slot = (int)(keys[r] & (WBF_CAP - 1));
     const float4 b = fusedg[slot];
     const int meta = first[slot], k = meta >> 16;
-    float* o = orow + (long long)r * 6;
-    o[0] = b.x;
-    o[1] = b.y;
-    o[2] = b.z;
-    o[3] = b.w;
-    o[4] = score[slot];
-    o[5] = ccls[slot];
+    store_row(orow + (long long)r * 6, b, score[slot], ccls[slot]);
     osrc[r] = (k * frames + f) * max_det_in + ((meta & 0xFFFF) - s_pre[k]);
     omem[r] = cnt[slot];
   }
-  zero_rows(orow, osrc, omem, nk, max_det);
+  zero_rows<WBF_THREADS>(orow, nk, max_det, osrc, -1, omem, 0);
   if (tid == 0) out_counts[f] = nk;
 }
 
-long long al256(long long x) { return (x + 255) & ~255LL; }
-
-// bytes per frame: two candidate tables of 28 bytes an entry, the cluster slots of 56
-constexpr long long WBF_WS_PER_FRAME = (long long)WBF_CAP * (2 * 28 + 56);
+// per frame: two candidate tables of 28 bytes an entry, the cluster slots of 56
+WbfWs wbf_layout(cvx_carver& c, long long frames) {
+  const long long n = frames * WBF_CAP;
+  WbfWs ws;
+  for (WbfCand* t : {&ws.a, &ws.b}) {
+    t->box = c.take<float4>(n);
+    t->s = c.take<float>(n);
+    t->cls = c.take<float>(n);
+    t->meta = c.take<int>(n);
+  }
+  ws.sx = c.take<float4>(n);
+  ws.fused = c.take<float4>(n);
+  ws.sw = c.take<float>(n);
+  ws.smax = c.take<float>(n);
+  ws.ccls = c.take<float>(n);
+  ws.score = c.take<float>(n);
+  ws.cnt = c.take<int>(n);
+  ws.first = c.take<int>(n);
+  return ws;
+}
 
 }  // namespace
 
 extern "C" int64_t cvx_det_wbf_workspace_bytes(int32_t frames) {
   if (frames <= 0) return 0;
-  return (int64_t)frames * WBF_WS_PER_FRAME + 16 * 256 + 256;   // 16 arrays, each aligned to 256 bytes, and the base
+  cvx_carver c(nullptr);
+  wbf_layout(c, frames);
+  return c.total();
 }
 
 extern "C" int cvx_det_fuse_wbf(const float* rows, const int32_t* counts, int32_t max_det_in, const float* view_map, const int32_t* frame_hw,
@@ -308,29 +312,8 @@ extern "C" int cvx_det_fuse_wbf(const float* rows, const int32_t* counts, int32_
   CVX_CHECK(rescale == 0 || rescale == 1, "rescale: 0 or 1");
   CVX_CHECK(max_det_out >= 1 && max_det_out <= WBF_CAP, "max_det_out must lie in [1,8192]");
   CVX_CHECK(workspace_bytes >= cvx_det_wbf_workspace_bytes(frames), "workspace too small");
-  const long long F = frames;
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  long long off = 0;
-  auto take = [&](long long bytes_each) {
-    char* p = base + off;
-    off += al256(F * WBF_CAP * bytes_each);
-    return p;
-  };
-  WbfWs ws;
-  for (WbfCand* c : {&ws.a, &ws.b}) {
-    c->box = (float4*)take(16);
-    c->s = (float*)take(4);
-    c->cls = (float*)take(4);
-    c->meta = (int*)take(4);
-  }
-  ws.sx = (float4*)take(16);
-  ws.fused = (float4*)take(16);
-  ws.sw = (float*)take(4);
-  ws.smax = (float*)take(4);
-  ws.ccls = (float*)take(4);
-  ws.score = (float*)take(4);
-  ws.cnt = (int*)take(4);
-  ws.first = (int*)take(4);
+  cvx_carver carver(workspace);
+  const WbfWs ws = wbf_layout(carver, frames);
   static unsigned long long optin = 0;  // 128 KB of fused boxes + 16 KB of segment starts: beyond the default dynamic LDS limit
   CVX_TRY(cvx_lds_optin((const void*)wbf_kernel, WBF_LDS_BYTES, &optin));
   hipLaunchKernelGGL(wbf_kernel, dim3(frames), dim3(WBF_THREADS), (size_t)WBF_LDS_BYTES, (hipStream_t)hip_stream, rows, counts, max_det_in, view_map,

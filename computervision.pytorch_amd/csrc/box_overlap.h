@@ -1,4 +1,5 @@
-// The overlap arithmetic the suite pins bit for bit, shared by the NMS (nms.hip), the tile merge (tiles.hip) and the tracker (track.hip):
+// The overlap arithmetic the suite pins bit for bit, shared by the NMS (nms.hip), Soft-NMS (soft_nms.hip), the tile merge (tiles.hip), the
+// two fusions of views (det_tta.hip, box_fusion.hip) and the tracker (track.hip):
 // plain operators with contraction switched off in each helper, every operation rounded on its own (the pragma does not reach into the
 // _rn intrinsics' own bodies, so they are not used here).  Each translation unit gets its own copy (anonymous namespace).
 #pragma once

@@ -328,8 +328,23 @@ static int slices_for(int K) {  // slices per image whose K-lists fit the merge 
   return S;
 }
 
+namespace {
+struct DecodeWs {
+  float* scores;                  // [B][H * W * nc] peak scores, 0 where suppressed
+  unsigned long long* slice_top;  // [B][S * K] the slices' sorted top-K keys; S * K <= CAND_CAP
+};
+DecodeWs decode_layout(cvx_carver& c, long long B, long long n_per_image) {
+  DecodeWs ws;
+  ws.scores = c.take<float>(B * n_per_image);
+  ws.slice_top = c.take<unsigned long long>(B * CAND_CAP);
+  return ws;
+}
+}  // namespace
+
 extern "C" int64_t cvx_centernet_decode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nc) {
-  return ((int64_t)B * H * W * nc + 64) * 4 + (int64_t)B * CAND_CAP * 8 + 512;
+  cvx_carver c(nullptr);
+  decode_layout(c, B, (long long)H * W * nc);
+  return c.total();
 }
 
 extern "C" int cvx_centernet_decode(const float* pred, int32_t pred_ld, int32_t B, int32_t H, int32_t W, int32_t nc, int32_t reg_col,
@@ -342,15 +357,15 @@ extern "C" int cvx_centernet_decode(const float* pred, int32_t pred_ld, int32_t 
   CVX_CHECK(pred_ld >= nc && reg_col >= 0 && reg_col + 2 <= pred_ld && wh_col >= 0 && wh_col + 2 <= pred_ld, "column offsets");
   CVX_CHECK(workspace_bytes >= cvx_centernet_decode_workspace_bytes(B, H, W, nc), "workspace too small");
   hipStream_t st = (hipStream_t)hip_stream;
-  float* ws = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  cvx_carver carver(workspace);
+  const DecodeWs ws = decode_layout(carver, B, (long long)H * W * nc);
   const long long n = (long long)B * H * W * nc;
-  hipLaunchKernelGGL(peak_scores_kernel, dim3(cvx_cdiv(n, 256)), dim3(256), 0, st, pred, pred_ld, B, H, W, nc, ws);
+  hipLaunchKernelGGL(peak_scores_kernel, dim3(cvx_cdiv(n, 256)), dim3(256), 0, st, pred, pred_ld, B, H, W, nc, ws.scores);
   DecodeOut o{boxes, scores, classes, topk_index, keep, counts};
   const int S = slices_for(K);
-  unsigned long long* slice_top = reinterpret_cast<unsigned long long*>(ws + ((n + 63) & ~63LL));
-  hipLaunchKernelGGL(select_slice_kernel, dim3(B, S), dim3(SEL_THREADS), 0, st, ws, (long long)H * W * nc, S, K, slice_top);
-  hipLaunchKernelGGL(finish_kernel, dim3(B), dim3(SEL_THREADS), 0, st, pred, pred_ld, H, W, nc, reg_col, wh_col, ws, slice_top, S, K, conf, nms_thr,
-                     use_nms, o);
+  hipLaunchKernelGGL(select_slice_kernel, dim3(B, S), dim3(SEL_THREADS), 0, st, ws.scores, (long long)H * W * nc, S, K, ws.slice_top);
+  hipLaunchKernelGGL(finish_kernel, dim3(B), dim3(SEL_THREADS), 0, st, pred, pred_ld, H, W, nc, reg_col, wh_col, ws.scores, ws.slice_top, S, K, conf,
+                     nms_thr, use_nms, o);
   CVX_HIP(hipGetLastError());
   return 0;
 }

@@ -66,6 +66,22 @@ inline int cvx_lds_optin(const void* kernel, int bytes, unsigned long long* done
   return 0;
 }
 
+// One statement of a workspace, for its size and for its placement.  A file's layout function fills its struct of pointers through a
+// carver; `*_workspace_bytes` runs it on null and returns total(), the launcher runs it on the caller's pointer.  Every array starts on
+// a 256-byte boundary: the base is rounded up to one here and nowhere else, and total() carries the 256 bytes that may cost.
+struct cvx_carver {
+  char* base;  // null: measuring
+  long long off = 0;
+  explicit cvx_carver(const void* workspace) : base(workspace ? (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr) {}
+  template <typename T>
+  T* take(long long count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += (count * (long long)sizeof(T) + 255) & ~255LL;
+    return p;
+  }
+  long long total() const { return off + 256; }
+};
+
 // ---- small device helpers ---------------------------------------------------------------------
 // v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the ~10-instruction IEEE division: the elementwise BN/SiLU passes are
 // VALU-limited on the big layers, and every consumer rounds the result to fp16 anyway.

@@ -20,8 +20,9 @@
 // tests/det_tta_restatement.py holds both kernels to the bit.
 #include "bilinear.h"
 #include "box_overlap.h"
-#include "lds_sort.h"
+#include "det_rows.h"
 #include "mask_nms.h"
+#include "merge_rows.h"
 #include "view_box.h"
 #include "../../include/cvx_engine.h"
 
@@ -121,60 +122,30 @@ __global__ __launch_bounds__(IN_THREADS) void det_tta_inputs_kernel(const float*
 }
 
 // ---- fusion ---------------------------------------------------------------------------------------------------------------------------
-constexpr int FUSE_CAP = 8192;  // candidates per frame the LDS sort holds: cvx_det_merge_tiles's, whose workspace layout this kernel shares
+constexpr int FUSE_CAP = MERGE_CAP;  // candidates per frame: cvx_det_merge_tiles's, whose workspace (MergeWs of merge_rows.h) this kernel shares
 constexpr int FUSE_THREADS = 1024;
-
-struct FuseWs {
-  float4* box;              // [frames][FUSE_CAP] sorted boxes in picture coordinates
-  float* score;             // [frames][FUSE_CAP]
-  float* cls;               // [frames][FUSE_CAP]
-  int* ord;                 // [frames][FUSE_CAP]
-  unsigned long long* mat;  // [frames][FUSE_CAP][FUSE_CAP / 64]
-};
 
 __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int max_det_in,
                                                             const float* __restrict__ view_map, const int* __restrict__ frame_hw, int frames, int views,
-                                                            float threshold, int class_agnostic, int mode, int score_mode, int max_det, FuseWs ws,
+                                                            float threshold, int class_agnostic, int mode, int score_mode, int max_det, MergeWs ws,
                                                             float* __restrict__ out_rows, int* __restrict__ out_counts, int* out_source,
                                                             int* __restrict__ out_members, int* overflow) {
   extern __shared__ unsigned long long keys[];  // cap2 entries (power of two >= candidates)
-  __shared__ int s_n, s_fill;
   __shared__ unsigned long long s_removed[FUSE_CAP / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   float* orow = out_rows + (long long)f * max_det * 6;
   int* osrc = out_source + (long long)f * max_det;
   int* omem = out_members + (long long)f * max_det;
-  if (tid == 0) s_n = s_fill = 0;
-  __syncthreads();
-  // ---- 1. how many candidates: the counts of this frame's slots k * frames + f; a count outside [0, max_det_in] contributes nothing ----
-  for (int k = tid; k < views; k += FUSE_THREADS) {
-    const int c = counts[k * frames + f];
-    if (c < 0 || c > max_det_in) atomicAdd(overflow, 1);
-    else if (c > 0) atomicAdd(&s_n, c);
-  }
-  __syncthreads();
-  const int n = s_n;
-  if (n > FUSE_CAP) {  // more than the in-LDS sort holds: flagged, never truncated
-    for (int i = tid; i < max_det * 6; i += FUSE_THREADS) orow[i] = 0.f;
-    for (int i = tid; i < max_det; i += FUSE_THREADS) osrc[i] = -1, omem[i] = 0;
+  // ---- 1-2. the rows of this frame's slots k * frames + f, counted, keyed by (score desc, ordinal asc) and sorted (merge_rows.h) ----
+  const int n = merge_rows_front<FUSE_THREADS>(rows, counts, views, max_det_in, keys, overflow, [&](int k) { return k * frames + f; });
+  if (n < 0) {  // more than the in-LDS sort holds: flagged, never truncated
+    zero_rows<FUSE_THREADS>(orow, 0, max_det, osrc, -1, omem, 0);
     if (tid == 0) {
       out_counts[f] = -1;
       atomicAdd(overflow, 1);
     }
     return;
   }
-  // ---- 2. keys: (score desc, ordinal asc), the ordinal s * max_det_in + r in the low word; then the sort ----
-  const int cells = views * max_det_in;   // of this frame: <= slots * max_det_in < 2^31
-  for (int e = tid; e < cells; e += FUSE_THREADS) {
-    const int k = e / max_det_in, r = e - k * max_det_in;
-    const int s = k * frames + f;
-    const int c = counts[s];
-    if (c < 0 || c > max_det_in || r >= c) continue;
-    const long long o = (long long)s * max_det_in + r;
-    const int at = atomicAdd(&s_fill, 1);
-    keys[at] = score_key(rows[o * 6 + 4], (unsigned)o);
-  }
-  lds_sort_keys<FUSE_THREADS>(keys, n);
   // ---- 3. gather the sorted candidates in picture coordinates ----
   float4* box = ws.box + (long long)f * FUSE_CAP;
   float* score = ws.score + (long long)f * FUSE_CAP;
@@ -263,16 +234,9 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(const float* __restr
       omem[r] = members;
     }
   }
-  for (int r = nk + tid; r < max_det; r += FUSE_THREADS) {
-    float* o = orow + (long long)r * 6;
-    o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.f;
-    osrc[r] = -1;
-    omem[r] = 0;
-  }
+  zero_rows<FUSE_THREADS>(orow, nk, max_det, osrc, -1, omem, 0);
   if (tid == 0) out_counts[f] = nk;
 }
-
-long long al256(long long x) { return (x + 255) & ~255LL; }
 
 }  // namespace
 
@@ -315,19 +279,8 @@ extern "C" int cvx_det_fuse_views(const float* rows, const int32_t* counts, int3
   CVX_CHECK(score_mode == 0 || score_mode == 1, "score_mode: 0 max, 1 views");
   CVX_CHECK(max_det_out >= 1 && max_det_out <= FUSE_CAP, "max_det_out must lie in [1,8192]");
   CVX_CHECK(workspace_bytes >= cvx_det_merge_workspace_bytes(frames), "workspace too small");
-  const long long F = frames;
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  FuseWs ws;
-  long long off = 0;
-  ws.box = (float4*)(base + off);
-  off += al256(F * FUSE_CAP * 16);
-  ws.score = (float*)(base + off);
-  off += al256(F * FUSE_CAP * 4);
-  ws.cls = (float*)(base + off);
-  off += al256(F * FUSE_CAP * 4);
-  ws.ord = (int*)(base + off);
-  off += al256(F * FUSE_CAP * 4);
-  ws.mat = (unsigned long long*)(base + off);
+  cvx_carver carver(workspace);
+  const MergeWs ws = merge_layout(carver, frames);
   static unsigned long long optin = 0;  // 64 KB of keys + the static words: beyond the default dynamic LDS limit
   CVX_TRY(cvx_lds_optin((const void*)fuse_kernel, FUSE_CAP * 8, &optin));
   hipLaunchKernelGGL(fuse_kernel, dim3(frames), dim3(FUSE_THREADS), (size_t)FUSE_CAP * 8, (hipStream_t)hip_stream, rows, counts, max_det_in, view_map,

@@ -1,6 +1,7 @@
 // The (score desc, index asc) key and the in-LDS bitonic sort of 64-bit keys, shared by every kernel that orders candidates: nms_kernel
-// (nms.hip), merge_kernel (tiles.hip), topk_sorted / finish_kernel (centernet_decode.hip), coco_match_kernel (coco_eval.hip, the sort)
-// and det_match_kernel (det_eval.hip, the key).  The suite pins the tie order and the padding key bit for bit, so they live in one
+// (nms.hip), soft_nms_kernel (soft_nms.hip), merge_kernel and fuse_kernel (tiles.hip, det_tta.hip, through merge_rows.h), wbf_kernel
+// (box_fusion.hip), regions_emit_kernel (seg_regions.hip), topk_sorted / finish_kernel (centernet_decode.hip), coco_match_kernel
+// (coco_eval.hip, the sort) and det_match_kernel (det_eval.hip, the key).  The suite pins the tie order and the padding key bit for bit, so they live in one
 // place.  Each translation unit gets its own copy (anonymous namespace).
 #pragma once
 #include "cvx_common.h"

@@ -494,15 +494,10 @@ struct Ws {
   uint8_t* mask;
 };
 
-long long align_up(long long x) { return (x + 255) & ~255LL; }
-
-long long carve(char* base, int B, int A, int N, Ws* w) {
-  long long off = 0;
-  auto take = [&](long long bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes);
-    return p;
-  };
+// the one statement of the workspace: the size query runs it on null, the entries on the caller's pointer (cvx_carver)
+long long carve(const void* workspace, int B, int A, int N, Ws* w) {
+  cvx_carver c(workspace);
+  auto take = [&](long long bytes) { return c.take<char>(bytes); };
   const long long BA = (long long)B * A;
   const int Nn = N > 0 ? N : 1;
   Ws t;
@@ -524,14 +519,14 @@ long long carve(char* base, int B, int A, int N, Ws* w) {
   t.loss_part = (float*)take(((BA + 15) / 16) * 12);
   t.aux = (float*)take(64);
   if (w) *w = t;
-  return off;
+  return c.total();
 }
 
 }  // namespace
 
 extern "C" int64_t cvx_loss_v8_workspace_bytes(int32_t batch, int32_t anchors, int32_t nc, int32_t max_targets) {
   (void)nc;
-  return carve(nullptr, batch, anchors, max_targets, nullptr) + 256;
+  return carve(nullptr, batch, anchors, max_targets, nullptr);
 }
 
 extern "C" int cvx_loss_v8(const float* pred, int32_t B, int32_t A, int32_t nc, const float* targets, int32_t N, int32_t max_targets,
@@ -566,9 +561,8 @@ extern "C" int cvx_loss_v8_strided(const float* pred, int32_t pred_ld, int32_t B
   L.a_off[n_levels] = off;
   CVX_CHECK(off == A, "level sizes do not add up to the anchor count");
   const float img_h = level_hw[0] * strides[0], img_w = level_hw[1] * strides[0];  // yolo_v8.py:87
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   Ws w;
-  carve(base, B, A, max_targets, &w);
+  carve(workspace, B, A, max_targets, &w);
   const long long BA = (long long)B * A;
   const int n_tss = (int)((BA + 255) / 256);
   const int n_lb = (int)((BA + 15) / 16);
@@ -608,9 +602,8 @@ extern "C" int cvx_loss_v8_strided(const float* pred, int32_t pred_ld, int32_t B
 extern "C" int cvx_loss_v8_assignment(const void* workspace, int32_t B, int32_t A, int32_t max_targets, int32_t* gt_index, float* norm_score,
                                       void* hip_stream) {
   CVX_CHECK(workspace && gt_index && norm_score && B > 0 && A > 0, "bad arguments");
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   Ws w;
-  carve(base, B, A, max_targets, &w);
+  carve(workspace, B, A, max_targets, &w);
   hipStream_t st = (hipStream_t)hip_stream;
   CVX_HIP(hipMemcpyAsync(gt_index, w.gt_idx, (size_t)B * A * 4, hipMemcpyDeviceToDevice, st));
   CVX_HIP(hipMemcpyAsync(norm_score, w.norm, (size_t)B * A * 4, hipMemcpyDeviceToDevice, st));

@@ -1,5 +1,6 @@
-// The greedy walk over a suppression bit matrix, shared by nms_kernel (nms.hip) and merge_kernel (tiles.hip): they differ in where the
-// keep list is parked, nothing else.  The suite pins the result bit for bit, so the fences live in one place.  Each kernel builds the
+// The greedy walk over a suppression bit matrix, shared by nms_kernel (nms.hip), merge_kernel (tiles.hip) and fuse_kernel (det_tta.hip):
+// they differ in where the keep list is parked, nothing else.  (soft_nms_kernel and wbf_kernel have no matrix: their picks depend on
+// scores and boxes that change as they go.)  The suite pins the result bit for bit, so the fences live in one place.  Each kernel builds the
 // matrix itself -- row i, word wj, bit j - 64 wj set when j > i and its pair test holds: behind a shared row builder that takes the test
 // as a functor merge_kernel measured 3.6 % slower (profiles/eval_tail_refactor_ab.txt).  Each translation unit gets its own copy.
 #pragma once

@@ -22,13 +22,13 @@
 #include "cvx_common.h"
 #include "lds_sort.h"
 #include "mask_nms.h"
+#include "nms_common.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
 
 constexpr int REG = 16;
 constexpr int MAXLV = 4;
-constexpr int NMS_CAP = 16384;  // candidates per image the LDS sort holds
 constexpr int NMS_THREADS = 1024;
 
 struct Levels {
@@ -151,14 +151,7 @@ __global__ void decode_rows_kernel(const float* pred, int B, int A, int no, int 
   for (int c = 0; c < nc; ++c) o[(long long)(4 + c) * A] = cvx_sigmoid(p[4 * REG + c]);
 }
 
-// The arithmetic the suite pins bit for bit: plain operators with contraction switched off in each helper, as ema_mix in misc_ops.hip
-// (the pragma does not reach into the _rn intrinsics' own bodies, so they are not used here).
-// (cx, cy, w, h) -> corners, ultralytics_ops.py:360-375
-__device__ __forceinline__ float4 box_corners(float cx, float cy, float w, float h) {
-#pragma clang fp contract(off)
-  const float hw = w * 0.5f, hh = h * 0.5f;
-  return make_float4(cx - hw, cy - hh, cx + hw, cy + hh);
-}
+// box_corners is nms_common.h's.  The arithmetic the suite pins bit for bit: plain operators with contraction switched off, as there.
 // box + cls * (boxes.max() + 1): _batched_nms_coordinate_trick
 __device__ __forceinline__ float4 class_shift(const float4& bx, int cls, float unit) {
 #pragma clang fp contract(off)
@@ -296,12 +289,16 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* y, int A,
   if (tid == 0) counts[b] = nk;
 }
 
-int cap_for(int A) {
-  int c = 64;
-  while (c < A && c < NMS_CAP) c <<= 1;
-  return c;
+NmsWs nms_layout(cvx_carver& c, long long B, long long cap) {
+  NmsWs ws;
+  ws.box = c.take<float4>(B * cap);
+  ws.boxs = c.take<float4>(B * cap);
+  ws.score = c.take<float>(B * cap);
+  ws.cls = c.take<int>(B * cap);
+  ws.aidx = c.take<int>(B * cap);
+  ws.mat = c.take<unsigned long long>(B * cap * (cap / 64));
+  return ws;
 }
-long long al(long long x) { return (x + 255) & ~255LL; }
 
 }  // namespace
 
@@ -339,8 +336,9 @@ extern "C" int cvx_decode_strided(const float* pred, int32_t pred_ld, int32_t B,
 }
 
 extern "C" int64_t cvx_nms_workspace_bytes(int32_t B, int32_t A) {
-  long long cap = cap_for(A);
-  return 2 * al(B * cap * 16) + 3 * al(B * cap * 4) + al((long long)B * cap * (cap / 64) * 8) + 1024;
+  cvx_carver c(nullptr);
+  nms_layout(c, B, nms_cap_for(A));
+  return c.total();
 }
 
 extern "C" int cvx_nms(const float* y, int32_t B, int32_t A, int32_t nc, float conf_thres, float iou_thres, int32_t max_det, float* out_rows,
@@ -358,28 +356,13 @@ extern "C" int cvx_nms_variant(const float* y, int32_t B, int32_t A, int32_t nc,
   CVX_CHECK(conf_thres >= 0.f && conf_thres <= 1.f && iou_thres >= 0.f && iou_thres <= 1.f, "thresholds must lie in [0,1]");
   CVX_CHECK(max_det >= 1 && max_det <= NMS_CAP, "max_det must lie in [1,16384]");
   CVX_CHECK(workspace_bytes >= cvx_nms_workspace_bytes(B, A), "workspace too small");
-  const long long cap = cap_for(A);
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  NmsWs ws;
-  long long off = 0;
-  ws.box = (float4*)(base + off);
-  off += al(B * cap * 16);
-  ws.boxs = (float4*)(base + off);
-  off += al(B * cap * 16);
-  ws.score = (float*)(base + off);
-  off += al(B * cap * 4);
-  ws.cls = (int*)(base + off);
-  off += al(B * cap * 4);
-  ws.aidx = (int*)(base + off);
-  off += al(B * cap * 4);
-  ws.mat = (unsigned long long*)(base + off);
-  static bool attr_set = false;
-  if (!attr_set) {
-    CVX_HIP(hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NMS_CAP * 8));
-    attr_set = true;
-  }
+  const int cap = nms_cap_for(A);
+  cvx_carver carver(workspace);
+  const NmsWs ws = nms_layout(carver, B, cap);
+  static unsigned long long optin = 0;  // 128 KB of keys at capacity: beyond the default dynamic LDS limit
+  CVX_TRY(cvx_lds_optin((const void*)nms_kernel, NMS_CAP * 8, &optin));
   hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(NMS_THREADS), (size_t)cap * 8, (hipStream_t)hip_stream, y, A, nc, conf_thres, iou_thres, max_det,
-                     (int)cap, (int)variant, ws, out_rows, out_index, counts);
+                     cap, (int)variant, ws, out_rows, out_index, counts);
   CVX_HIP(hipGetLastError());
   return 0;
 }

@@ -378,14 +378,27 @@ __global__ __launch_bounds__(TILE_THREADS) void regions_map_kernel(const cvx_seg
   }
 }
 
-inline long long al256(long long n) { return (n + 255) & ~255ll; }
+Planes regions_layout(cvx_carver& c, long long frames, long long plane_px) {
+  const long long px = frames * plane_px;
+  Planes ws;
+  ws.qsum = c.take<unsigned long long>(px);
+  ws.parent = c.take<int>(px);
+  ws.area = c.take<unsigned>(px);
+  ws.min_x = c.take<int>(px);
+  ws.max_x = c.take<int>(px);
+  ws.max_y = c.take<int>(px);
+  ws.head = c.take<int>(frames * (FRAME_HEAD + REGION_CAP));
+  ws.plane_px = plane_px;
+  return ws;
+}
 
 }  // namespace
 
 extern "C" int64_t cvx_seg_regions_workspace_bytes(int32_t frames, int32_t max_h, int32_t max_w) {
   if (frames <= 0 || max_h <= 0 || max_w <= 0 || (long long)max_h * max_w >= (1ll << 31)) return 0;
-  const long long px = (long long)frames * max_h * max_w;
-  return al256(px * 8) + 5 * al256(px * 4) + al256((long long)frames * (FRAME_HEAD + REGION_CAP) * 4) + 256;
+  cvx_carver c(nullptr);
+  regions_layout(c, frames, (long long)max_h * max_w);
+  return c.total();
 }
 
 extern "C" int cvx_seg_regions(const cvx_seg_map* label_maps, const int32_t* frame_hw, int32_t frames, int32_t max_h, int32_t max_w,
@@ -404,24 +417,8 @@ extern "C" int cvx_seg_regions(const cvx_seg_map* label_maps, const int32_t* fra
   CVX_CHECK((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "workspace: 8-byte aligned");
   ClassMask mask;
   for (int i = 0; i < 8; ++i) mask.w[i] = class_mask_host[i];
-  const long long px = (long long)frames * max_h * max_w;
-  Planes ws;
-  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
-  long long off = 0;
-  ws.qsum = reinterpret_cast<unsigned long long*>(base + off);
-  off += al256(px * 8);
-  ws.parent = reinterpret_cast<int*>(base + off);
-  off += al256(px * 4);
-  ws.area = reinterpret_cast<unsigned*>(base + off);
-  off += al256(px * 4);
-  ws.min_x = reinterpret_cast<int*>(base + off);
-  off += al256(px * 4);
-  ws.max_x = reinterpret_cast<int*>(base + off);
-  off += al256(px * 4);
-  ws.max_y = reinterpret_cast<int*>(base + off);
-  off += al256(px * 4);
-  ws.head = reinterpret_cast<int*>(base + off);
-  ws.plane_px = (long long)max_h * max_w;
+  cvx_carver carver(workspace);
+  const Planes ws = regions_layout(carver, frames, (long long)max_h * max_w);
   const hipStream_t s = (hipStream_t)hip_stream;
   const dim3 grid((unsigned)cvx_cdiv(max_w, TW), (unsigned)cvx_cdiv(max_h, TH), (unsigned)frames);
   const int conn8 = connectivity == 8, with_q = conf != nullptr;

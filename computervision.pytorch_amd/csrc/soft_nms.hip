@@ -5,11 +5,11 @@
 // The decay makes the pick order depend on the scores as they change, so the suppression bit matrix and the single greedy walk of
 // mask_nms.h do not apply.  One 1024-thread workgroup per block of the batch:
 //     1. candidates (best class score > conf) into the LDS key array, 2. lds_sort_keys by (score desc, anchor asc), 3. gather of the
-//        sorted candidates into the workspace -- the front end of nms_kernel, copied (moving it to a header would have recompiled
-//        nms.hip's kernel around it; its arithmetic is box_corners alone).
-//     4. a second in-LDS sort by (class, position) gives the segments (box_fusion.hip's construction: a ballot per 64 positions, a prefix
-//        over the mask words).  The key array is dead after it: its 8 bytes per candidate become the live score s (fp32) and the
-//        position (int32), both in segment order.  The segment-ordered boxes go to the workspace.
+//        sorted candidates into the workspace -- the front end of nms_kernel, in line in both: behind one helper both kernels measured
+//        slower (nms_common.h holds what they state once; profiles/suppress_refactor_ab.txt has the figures).
+//     4. a second in-LDS sort by (class, position) gives the segments (box_fusion.hip's construction, in line in both for the same
+//        reason: a ballot per 64 positions, a prefix over the mask words).  The key array is dead after it: its 8 bytes per candidate
+//        become the live score s (fp32) and the position (int32), both in segment order.  The segment-ordered boxes go to the workspace.
 //     5. the walk: the 16 waves take the segments round-robin.  Candidate a + l + 64 q of a segment that starts at a belongs to lane l,
 //        which alone reads and writes its s: there is no cross-lane traffic through LDS, so no fence inside a segment.  One sweep per
 //        pick applies M's decay to the lane's live candidates and tracks the lane's (largest s, lowest position); six shuffles reduce
@@ -21,12 +21,14 @@
 // bits.  Vector stores only.
 #include "box_overlap.h"
 #include "cvx_common.h"
+#include "det_rows.h"
 #include "lds_sort.h"
+#include "nms_common.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
 
-constexpr int SNMS_CAP = 16384;  // candidates per block the LDS sort holds
+constexpr int SNMS_CAP = NMS_CAP;  // candidates per block the LDS sort holds (nms_common.h)
 constexpr int SNMS_THREADS = 1024;
 constexpr int SNMS_WAVES = SNMS_THREADS / 64;
 constexpr int SNMS_PER_THREAD = SNMS_CAP / SNMS_THREADS;
@@ -34,13 +36,6 @@ constexpr unsigned SNMS_EMITTED = 0x80000000u;
 #ifndef SNMS_FLY
 #define SNMS_FLY 4  // candidates a lane has in flight per trip of the sweep
 #endif
-
-// (cx, cy, w, h) -> corners: nms.hip's box_corners, the same operations
-__device__ __forceinline__ float4 snms_box_corners(float cx, float cy, float w, float h) {
-#pragma clang fp contract(off)
-  const float hw = w * 0.5f, hh = h * 0.5f;
-  return make_float4(cx - hw, cy - hh, cx + hw, cy + hh);
-}
 
 // E(x) = exp(-x) as a fixed sequence of fp32 operations, each rounded on its own: k = rint(-x log2 e), a two-constant Cody-Waite
 // reduction (k * 0.693359375 is exact for |k| < 2^15), the degree-6 Taylor polynomial in Horner form without fma, an exact scaling by
@@ -92,14 +87,6 @@ __device__ __forceinline__ int snms_seg_start(const unsigned long long* mask, co
   return lo * 64 + __ffsll((long long)m) - 1;
 }
 
-__device__ __forceinline__ void snms_zero_rows(float* orow, int* oidx, int from, int max_det) {
-  for (int r = from + (int)threadIdx.x; r < max_det; r += SNMS_THREADS) {
-    float* o = orow + (long long)r * 6;
-    o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.f;
-    oidx[r] = 0;
-  }
-}
-
 __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __restrict__ y, int A, int nc, float conf_thres, float iou_thres,
                                                                 int max_det, int cap, int method, float sigma, float min_score, int flags,
                                                                 SnmsWs ws, float* __restrict__ out_rows, int* __restrict__ out_index,
@@ -130,13 +117,13 @@ __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __r
   }
   __syncthreads();
   if (s_n > cap) {  // more candidates than the in-LDS sort holds: signalled, never truncated
-    snms_zero_rows(orow, oidx, 0, max_det);
+    zero_rows<SNMS_THREADS>(orow, 0, max_det, oidx, 0);
     if (tid == 0) counts[b] = -1;
     return;
   }
   const int n = s_n;
   if (n == 0) {
-    snms_zero_rows(orow, oidx, 0, max_det);
+    zero_rows<SNMS_THREADS>(orow, 0, max_det, oidx, 0);
     if (tid == 0) counts[b] = 0;
     return;
   }
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __r
   for (int i = tid; i < n; i += SNMS_THREADS) {
     const int a = (int)(keys[i] & 0xFFFFFFFFu);
     const float cx = yb[a], cy = yb[(long long)A + a], w = yb[2LL * A + a], h = yb[3LL * A + a];
-    box[i] = xyxy ? make_float4(cx, cy, w, h) : snms_box_corners(cx, cy, w, h);
+    box[i] = xyxy ? make_float4(cx, cy, w, h) : box_corners(cx, cy, w, h);
     float best = -1.f;
     int bc = 0;
     for (int c = 0; c < nc; ++c) {
@@ -190,7 +177,7 @@ __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __r
     }
   }
   __syncthreads();
-  // segment starts: a change of class (box_fusion.hip, step 3)
+  // segment starts: a change of class (the construction of box_fusion.hip, step 3)
   for (int p0 = 0; p0 < n; p0 += SNMS_THREADS) {
     const int p = p0 + tid;
     const bool start = p < n && (p == 0 || (!agnostic && cls[s_pos[p]] != cls[s_pos[p - 1]]));
@@ -318,23 +305,27 @@ __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __r
     o[5] = (float)cls[p];
     oidx[r] = aidx[p];
   }
-  snms_zero_rows(orow, oidx, nk, max_det);
+  zero_rows<SNMS_THREADS>(orow, nk, max_det, oidx, 0);
   if (tid == 0) counts[b] = nk;
 }
 
-int snms_cap_for(int A) {
-  int c = 64;
-  while (c < A && c < SNMS_CAP) c <<= 1;
-  return c;
+SnmsWs snms_layout(cvx_carver& c, long long B, long long cap) {
+  SnmsWs ws;
+  ws.box = c.take<float4>(B * cap);
+  ws.bseg = c.take<float4>(B * cap);
+  ws.score = c.take<float>(B * cap);
+  ws.cls = c.take<int>(B * cap);
+  ws.aidx = c.take<int>(B * cap);
+  return ws;
 }
-long long snms_al(long long x) { return (x + 255) & ~255LL; }
 
 }  // namespace
 
 extern "C" int64_t cvx_soft_nms_workspace_bytes(int32_t B, int32_t A) {
   if (B <= 0 || A <= 0) return 0;
-  const long long cap = snms_cap_for(A);
-  return 2 * snms_al(B * cap * 16) + 3 * snms_al(B * cap * 4) + 1024;
+  cvx_carver c(nullptr);
+  snms_layout(c, B, nms_cap_for(A));
+  return c.total();
 }
 
 extern "C" int cvx_soft_nms(const float* y, int32_t B, int32_t A, int32_t nc, float conf_thres, float iou_thres, int32_t max_det, int32_t method,
@@ -349,23 +340,13 @@ extern "C" int cvx_soft_nms(const float* y, int32_t B, int32_t A, int32_t nc, fl
   CVX_CHECK(min_score >= 0.f && min_score < 1.f, "min_score must lie in [0,1)");
   CVX_CHECK(max_det >= 1 && max_det <= SNMS_CAP, "max_det must lie in [1,16384]");
   CVX_CHECK(workspace_bytes >= cvx_soft_nms_workspace_bytes(B, A), "workspace too small");
-  const long long cap = snms_cap_for(A);
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  SnmsWs ws;
-  long long off = 0;
-  ws.box = (float4*)(base + off);
-  off += snms_al(B * cap * 16);
-  ws.bseg = (float4*)(base + off);
-  off += snms_al(B * cap * 16);
-  ws.score = (float*)(base + off);
-  off += snms_al(B * cap * 4);
-  ws.cls = (int*)(base + off);
-  off += snms_al(B * cap * 4);
-  ws.aidx = (int*)(base + off);
+  const int cap = nms_cap_for(A);
+  cvx_carver carver(workspace);
+  const SnmsWs ws = snms_layout(carver, B, cap);
   static unsigned long long optin = 0;  // 128 KB of keys at capacity: beyond the default dynamic LDS limit
   CVX_TRY(cvx_lds_optin((const void*)soft_nms_kernel, SNMS_CAP * 8, &optin));
   hipLaunchKernelGGL(soft_nms_kernel, dim3(B), dim3(SNMS_THREADS), (size_t)cap * 8, (hipStream_t)hip_stream, y, A, nc, conf_thres, iou_thres, max_det,
-                     (int)cap, (int)method, sigma, min_score, (int)flags, ws, out_rows, out_index, counts);
+                     cap, (int)method, sigma, min_score, (int)flags, ws, out_rows, out_index, counts);
   CVX_HIP(hipGetLastError());
   return 0;
 }

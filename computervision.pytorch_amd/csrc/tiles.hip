@@ -13,8 +13,9 @@
 //                         row masks in the workspace by all 16 waves, and one wave walks it (greedy_walk of mask_nms.h).  The overlap test is
 //                         iou_gt or ios_gt of box_overlap.h.
 #include "box_overlap.h"
-#include "lds_sort.h"
+#include "det_rows.h"
 #include "mask_nms.h"
+#include "merge_rows.h"
 #include "../../include/cvx_engine.h"
 
 namespace {
@@ -61,16 +62,7 @@ __global__ __launch_bounds__(TILE_THREADS) void tiles_kernel(const cvx_tile_job*
 }
 
 // ---- merge ----------------------------------------------------------------------------------------------------------------------------
-constexpr int MERGE_CAP = 8192;  // candidates per frame the LDS sort holds
-constexpr int MERGE_THREADS = 1024;
-
-struct MergeWs {
-  float4* box;              // [frames][MERGE_CAP] sorted boxes in frame coordinates
-  float* score;             // [frames][MERGE_CAP]
-  float* cls;               // [frames][MERGE_CAP]
-  int* ord;                 // [frames][MERGE_CAP]
-  unsigned long long* mat;  // [frames][MERGE_CAP][MERGE_CAP / 64]
-};
+constexpr int MERGE_THREADS = 1024;  // MERGE_CAP, MergeWs and its layout: merge_rows.h
 
 // slot pixels -> frame pixels: one fp32 add, then the clamp to the frame
 __device__ __forceinline__ float to_frame(float v, int off, int size) {
@@ -85,42 +77,20 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const float* __res
                                                               float* __restrict__ out_rows, int* __restrict__ out_counts, int* out_source,
                                                               int* overflow) {
   extern __shared__ unsigned long long keys[];  // cap2 entries (power of two >= candidates)
-  __shared__ int s_n, s_fill;
   __shared__ unsigned long long s_removed[MERGE_CAP / 64];
   const int f = blockIdx.x, tid = threadIdx.x;
   float* orow = out_rows + (long long)f * max_det * 6;
   int* osrc = out_source + (long long)f * max_det;
-  if (tid == 0) s_n = s_fill = 0;
-  __syncthreads();
-  // ---- 1. how many candidates: the counts of this frame's slots; a count outside [0, max_det_in] contributes nothing and is flagged ----
-  for (int s = tid; s < slots; s += MERGE_THREADS) {
-    if (slot_map[4 * s] != f) continue;
-    const int c = counts[s];
-    if (c < 0 || c > max_det_in) atomicAdd(overflow, 1);
-    else if (c > 0) atomicAdd(&s_n, c);
-  }
-  __syncthreads();
-  const int n = s_n;
-  if (n > MERGE_CAP) {  // more than the in-LDS sort holds: flagged, never truncated
-    for (int i = tid; i < max_det * 6; i += MERGE_THREADS) orow[i] = 0.f;
-    for (int i = tid; i < max_det; i += MERGE_THREADS) osrc[i] = -1;
+  // ---- 1-2. the rows of this frame's slots, counted, keyed by (score desc, ordinal asc) and sorted (merge_rows.h) ----
+  const int n = merge_rows_front<MERGE_THREADS>(rows, counts, slots, max_det_in, keys, overflow, [&](int s) { return slot_map[4 * s] == f ? s : -1; });
+  if (n < 0) {  // more than the in-LDS sort holds: flagged, never truncated
+    zero_rows<MERGE_THREADS>(orow, 0, max_det, osrc, -1);
     if (tid == 0) {
       out_counts[f] = -1;
       atomicAdd(overflow, 1);
     }
     return;
   }
-  // ---- 2. keys: (score desc, ordinal asc), the ordinal s * max_det_in + r in the low word; then the sort ----
-  const long long cells = (long long)slots * max_det_in;
-  for (long long e = tid; e < cells; e += MERGE_THREADS) {
-    const int s = (int)(e / max_det_in), r = (int)(e - (long long)s * max_det_in);
-    if (slot_map[4 * s] != f) continue;
-    const int c = counts[s];
-    if (c < 0 || c > max_det_in || r >= c) continue;
-    const int at = atomicAdd(&s_fill, 1);
-    keys[at] = score_key(rows[e * 6 + 4], (unsigned)e);
-  }
-  lds_sort_keys<MERGE_THREADS>(keys, n);
   // ---- 3. gather the sorted candidates in frame coordinates ----
   float4* box = ws.box + (long long)f * MERGE_CAP;
   float* score = ws.score + (long long)f * MERGE_CAP;
@@ -162,27 +132,14 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const float* __res
   // ---- 5. greedy walk by wave 0 (mask_nms.h): the keep list lives in the source column until step 6 ----
   const int nk = greedy_walk<MERGE_THREADS>(mat, s_removed, n, max_det, osrc);
   // ---- 6. emit: the kept rows in order, zero rows and source -1 past the count ----
-  for (int r = tid; r < max_det; r += MERGE_THREADS) {
-    float* o = orow + (long long)r * 6;
-    if (r < nk) {
-      const int i = osrc[r];  // (each thread reads and rewrites only its own slots)
-      const float4 bx = box[i];
-      o[0] = bx.x;
-      o[1] = bx.y;
-      o[2] = bx.z;
-      o[3] = bx.w;
-      o[4] = score[i];
-      o[5] = cls[i];
-      osrc[r] = ord[i];
-    } else {
-      o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.f;
-      osrc[r] = -1;
-    }
+  for (int r = tid; r < nk; r += MERGE_THREADS) {
+    const int i = osrc[r];  // (each thread reads and rewrites only its own slots)
+    store_row(orow + (long long)r * 6, box[i], score[i], cls[i]);
+    osrc[r] = ord[i];
   }
+  zero_rows<MERGE_THREADS>(orow, nk, max_det, osrc, -1);
   if (tid == 0) out_counts[f] = nk;
 }
-
-long long al256(long long x) { return (x + 255) & ~255LL; }
 
 }  // namespace
 
@@ -204,8 +161,9 @@ extern "C" int cvx_tiles_u8_to_nchw(const cvx_tile_job* jobs, int32_t n_jobs, in
 }
 
 extern "C" int64_t cvx_det_merge_workspace_bytes(int32_t frames) {
-  const long long F = frames > 0 ? frames : 0;
-  return al256(F * MERGE_CAP * 16) + 3 * al256(F * MERGE_CAP * 4) + al256(F * MERGE_CAP * (MERGE_CAP / 64) * 8) + 256;
+  cvx_carver c(nullptr);
+  merge_layout(c, frames > 0 ? frames : 0);
+  return c.total();
 }
 
 extern "C" int cvx_det_merge_tiles(const float* rows, const int32_t* counts, int32_t slots, int32_t max_det_in, const int32_t* slot_map,
@@ -218,19 +176,8 @@ extern "C" int cvx_det_merge_tiles(const float* rows, const int32_t* counts, int
   CVX_CHECK(threshold >= 0.f && threshold <= 1.f, "the threshold must lie in [0,1]");
   CVX_CHECK(max_det_out >= 1 && max_det_out <= MERGE_CAP, "max_det_out must lie in [1,8192]");
   CVX_CHECK(workspace_bytes >= cvx_det_merge_workspace_bytes(frames), "workspace too small");
-  const long long F = frames;
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  MergeWs ws;
-  long long off = 0;
-  ws.box = (float4*)(base + off);
-  off += al256(F * MERGE_CAP * 16);
-  ws.score = (float*)(base + off);
-  off += al256(F * MERGE_CAP * 4);
-  ws.cls = (float*)(base + off);
-  off += al256(F * MERGE_CAP * 4);
-  ws.ord = (int*)(base + off);
-  off += al256(F * MERGE_CAP * 4);
-  ws.mat = (unsigned long long*)(base + off);
+  cvx_carver carver(workspace);
+  const MergeWs ws = merge_layout(carver, frames);
   static unsigned long long optin = 0;  // 64 KB of keys + the static words: beyond the default dynamic LDS limit
   CVX_TRY(cvx_lds_optin((const void*)merge_kernel, MERGE_CAP * 8, &optin));
   hipLaunchKernelGGL(merge_kernel, dim3(frames), dim3(MERGE_THREADS), (size_t)MERGE_CAP * 8, (hipStream_t)hip_stream, rows, counts, slots, max_det_in,

@@ -1,5 +1,6 @@
 // A row's box brought to the picture through its slot's affine map, the arithmetic the suite pins bit for bit, shared by the two fusions
-// of several reports per frame: fuse_kernel (det_tta.hip) and wbf_kernel (box_fusion.hip).  Plain operators with contraction switched off
+// of several reports per frame: fuse_kernel (det_tta.hip) and wbf_kernel (box_fusion.hip).  (merge_kernel's map is an add and a clamp,
+// to_frame of tiles.hip; the rows front end the two matrix kernels share is merge_rows.h.)  Plain operators with contraction switched off
 // in each helper, every operation rounded on its own.  Each translation unit gets its own copy (anonymous namespace).
 #pragma once
 #include "cvx_common.h"

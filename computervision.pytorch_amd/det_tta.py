@@ -101,9 +101,6 @@ def pad_blocks(parts, device):
     return slot_rows, torch.cat([c for _, c in parts])
 
 
-_fuse_ws = {}
-
-
 def fuse_views(rows: torch.Tensor, counts: torch.Tensor, view_map: torch.Tensor, frame_hw: torch.Tensor, threshold: float = 0.5,
                class_agnostic: bool = False, fuse: str = "vote", score: str = "max", max_det: int = 300, overflow: Optional[torch.Tensor] = None):
     """``cvx_det_fuse_views``: rows (V * B, K, 6) fp32 and counts (V * B) int32 as ``det_to_image`` leaves them, slot ``k * B + b``;
@@ -147,10 +144,7 @@ def fuse_views(rows: torch.Tensor, counts: torch.Tensor, view_map: torch.Tensor,
     if overflow is None:
         overflow = torch.zeros(1, dtype=torch.int32, device=rows.device)
     lib = L.load()
-    need = int(lib.cvx_det_merge_workspace_bytes(B))
-    ws = _fuse_ws.get(rows.device)
-    if ws is None or ws.numel() < need:
-        ws = _fuse_ws[rows.device] = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    ws = L.workspace("det_fuse_views", rows.device, int(lib.cvx_det_merge_workspace_bytes(B)))
     with torch.cuda.device(rows.device):
         L.check(lib.cvx_det_fuse_views(L.ptr(rows), L.ptr(counts), K, L.ptr(view_map), L.ptr(frame_hw), B, S // B, float(threshold),
                                        int(bool(class_agnostic)), FUSE_MODES[fuse], SCORE_MODES[score], int(max_det), L.ptr(out_rows),

@@ -366,9 +366,6 @@ def decode(pred: torch.Tensor, nc: int, level_hw, strides) -> torch.Tensor:
     return y
 
 
-_nms_ws = {}
-
-
 NMS_VARIANTS = {"tv0141_cuda": 0, "tv0141_cpu": 1, "offset": 2, "vanilla": 3}
 
 
@@ -388,10 +385,7 @@ def nms(y: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300
     y = y.contiguous().float()
     B, ch, A = y.shape
     nc = ch - 4
-    need = int(lib.cvx_nms_workspace_bytes(B, A))
-    ws = _nms_ws.get(y.device)
-    if ws is None or ws.numel() < need:
-        ws = _nms_ws[y.device] = torch.empty(need, dtype=torch.uint8, device=y.device)
+    ws = L.workspace("nms", y.device, int(lib.cvx_nms_workspace_bytes(B, A)))
     rows = torch.zeros(B, max_det, 6, dtype=torch.float32, device=y.device)
     index = torch.zeros(B, max_det, dtype=torch.int32, device=y.device)
     counts = torch.zeros(B, dtype=torch.int32, device=y.device)
@@ -433,9 +427,6 @@ def ssd_decode(loc: torch.Tensor, conf: torch.Tensor, priors: torch.Tensor, vari
     return (boxes, prob, cmax) if with_class_max else (boxes, prob)
 
 
-_cn_ws = {}
-
-
 def centernet_decode(pred: torch.Tensor, h: int, w: int, nc: int, reg_col: int, wh_col: int, k: int = 100, conf: float = 0.1,
                      nms_thr: float = 0.5, use_nms: bool = True):
     """pred (B, h*w, ld) fp32 head tensor -> dict(boxes (B,k,4) xyxy in [0,1], scores, classes, topk_index, keep, counts), on device
@@ -445,10 +436,7 @@ def centernet_decode(pred: torch.Tensor, h: int, w: int, nc: int, reg_col: int, 
     pred = pred.contiguous().float()
     B, hw, ld = pred.shape
     assert hw == h * w
-    need = int(lib.cvx_centernet_decode_workspace_bytes(B, h, w, nc))
-    ws = _cn_ws.get(pred.device)
-    if ws is None or ws.numel() < need:
-        ws = _cn_ws[pred.device] = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    ws = L.workspace("centernet_decode", pred.device, int(lib.cvx_centernet_decode_workspace_bytes(B, h, w, nc)))
     dev = pred.device
     out = dict(boxes=torch.zeros(B, k, 4, device=dev), scores=torch.zeros(B, k, device=dev),
                classes=torch.zeros(B, k, dtype=torch.int32, device=dev), topk_index=torch.zeros(B, k, dtype=torch.int32, device=dev),

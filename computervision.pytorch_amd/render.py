@@ -347,9 +347,6 @@ class TileBatch:
         return out
 
 
-_merge_ws = {}
-
-
 def merge_tiles(rows: torch.Tensor, counts: torch.Tensor, slot_map: torch.Tensor, frame_hw: torch.Tensor, metric: str = "ios",
                 threshold: float = 0.5, class_agnostic: bool = False, max_det: int = 300, overflow: Optional[torch.Tensor] = None):
     """``cvx_det_merge_tiles``: rows (slots, K, 6) fp32 and counts (slots) int32 as ``det_to_image`` leaves them, boxes in each slot's own
@@ -386,10 +383,7 @@ def merge_tiles(rows: torch.Tensor, counts: torch.Tensor, slot_map: torch.Tensor
     if overflow is None:
         overflow = torch.zeros(1, dtype=torch.int32, device=rows.device)
     lib = L.load()
-    need = int(lib.cvx_det_merge_workspace_bytes(F))
-    ws = _merge_ws.get(rows.device)
-    if ws is None or ws.numel() < need:
-        ws = _merge_ws[rows.device] = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    ws = L.workspace("det_merge_tiles", rows.device, int(lib.cvx_det_merge_workspace_bytes(F)))
     with torch.cuda.device(rows.device):
         L.check(lib.cvx_det_merge_tiles(L.ptr(rows), L.ptr(counts), S, K, L.ptr(slot_map), L.ptr(frame_hw), F, MERGE_METRICS[metric], float(threshold),
                                         int(bool(class_agnostic)), int(max_det), L.ptr(out_rows), L.ptr(out_counts), L.ptr(out_source),

@@ -83,9 +83,6 @@ class RegionBatch:
         return render.read_detections(self.rows, self.counts, self.overflow, self.ids)
 
 
-_regions_ws = {}
-
-
 def _per_frame(flag, n, what) -> List[bool]:
     if isinstance(flag, (bool, np.bool_)):
         return [bool(flag)] * n
@@ -180,9 +177,7 @@ def label_regions(labels, regions: Optional[SegRegions] = None, conf=None, regio
     need = int(lib.cvx_seg_regions_workspace_bytes(F, max_h, max_w))
     if need <= 0:
         raise ValueError(f"labels: the largest frame ({max_h} x {max_w}) has 2^31 pixels or more")
-    ws = _regions_ws.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _regions_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = L.workspace("seg_regions", dev, need)
     words = (L.C.c_uint32 * 8)(*[int(v) for v in regions.mask_words])
 
     def launch():

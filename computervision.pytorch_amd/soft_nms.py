@@ -61,9 +61,6 @@ def configured(cfg) -> Optional[SoftNMS]:
     return SoftNMS.of(getattr(getattr(cfg, "decode", None), "soft_nms", None))
 
 
-_ws = {}
-
-
 def soft_nms(y: torch.Tensor, conf_thres: float, soft: SoftNMS, iou_thres: float, max_det: int = 300, boxes_xyxy: bool = False):
     """The bare ``cvx_soft_nms`` launch: y (B, 4+nc, A) fp32 -> (rows (B, max_det, 6) [x1, y1, x2, y2, final score, cls], anchor_index
     (B, max_det) int32, counts (B,) int32), all on the device, exactly like ``engine.nms``.  ``iou_thres`` stands in where ``soft.iou`` is
@@ -82,10 +79,7 @@ def soft_nms(y: torch.Tensor, conf_thres: float, soft: SoftNMS, iou_thres: float
     lib = L.load()
     y = y.contiguous().float()
     B, ch, A = y.shape
-    need = int(lib.cvx_soft_nms_workspace_bytes(B, A))
-    ws = _ws.get(y.device)
-    if ws is None or ws.numel() < need:
-        ws = _ws[y.device] = torch.empty(need, dtype=torch.uint8, device=y.device)
+    ws = L.workspace("soft_nms", y.device, int(lib.cvx_soft_nms_workspace_bytes(B, A)))
     rows = torch.empty(B, int(max_det), 6, dtype=torch.float32, device=y.device)
     index = torch.empty(B, int(max_det), dtype=torch.int32, device=y.device)
     counts = torch.empty(B, dtype=torch.int32, device=y.device)

@@ -60,8 +60,10 @@ def main():
              f"{'file':22s} {'kernel':44s} " + " ".join(f"{s:>13s}" for _, s in FIELDS) + "  note"]
     bad = 0
     for f in args.files:
-        old, new = resources(os.path.join(args.parent, f)), resources(os.path.join(CSRC, f))
-        names = demangle(sorted(set(old) | set(new)))
+        # keyed by the kernel's own name and template integers: a renamed argument type changes the mangled name, not the kernel
+        old, new = ({name: v for name, v in ((demangle([k])[k], v) for k, v in resources(path).items())}
+                    for path in (os.path.join(args.parent, f), os.path.join(CSRC, f)))
+        names = {k: k for k in set(old) | set(new)}
         for k in sorted(names):
             a, b = old.get(k), new.get(k)
             if a is None or b is None:
