@@ -155,6 +155,8 @@ PROTOTYPES = {
     "cvx_seg_stitch": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_seg_regions_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "cvx_seg_regions": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "cvx_seg_boundary_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "cvx_seg_boundary": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _I64, _P]),
     "cvx_seg_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "cvx_seg_fuse": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "cvx_det_tta_inputs": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _F, _P, _P]),

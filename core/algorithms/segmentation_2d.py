@@ -135,7 +135,7 @@ class DeeplabV3PlusA(FramePredictor):
         return rows
 
     def segment_tiled(self, model, frames, overlap=0.2, weight="linear", batch_size=16, draw=True, bgr=False, targets=None, metrics=None,
-                      sync=False):
+                      sync=False, boundary=None):
         """Sliding-window segmentation for frames much larger than the network input, where ``predict_batch``'s stretch loses the thin
         structures and the aspect ratio: every frame is cut into tiles of ``cfg.arch.input_size`` that overlap by
         ``overlap`` (``render.tile_grid``; zoom 1, no whole-picture slot), one ``cvx_tiles_u8_to_nchw`` launch builds all slots (/ 255, no
@@ -144,14 +144,23 @@ class DeeplabV3PlusA(FramePredictor):
         ``"linear"``, the distance to the tile's borders, or ``"mean"``), takes the arg max and, with ``draw``, blends the class colours
         50/50 into the frames in place (``bgr`` as in ``predict_batch``).  ``targets`` (one (h, w) uint8 device map per frame; values
         >= num_classes are ignored) with ``metrics`` (a ``SegmentationMetrics``) adds the exact confusion counts to ``metrics.counts``;
-        ``fold()`` / ``get_results()`` then work as after ``add_rows``.  Returns the list of (h, w) uint8 label maps on the device;
+        ``fold()`` / ``get_results()`` then work as after ``add_rows``.  ``boundary`` (a ``seg_boundary.BoundaryMetrics``, DESIGN.md section
+        7z) needs ``targets`` too -- ``metrics`` may then be None -- and adds, after the stitch, the boundary counts of the returned label
+        maps against ``targets`` to its tables (one ``cvx_seg_boundary`` call).  Returns the list of (h, w) uint8 label maps on the device;
         nothing waits on the host unless ``sync``."""
         from computervision.pytorch_amd import render
         self._need_gpu("segment_tiled")
         if int(batch_size) <= 0:
             raise ValueError("batch_size is positive")
-        if (targets is None) != (metrics is None):
-            raise ValueError("targets and metrics come together")
+        if boundary is None:
+            if (targets is None) != (metrics is None):
+                raise ValueError("targets and metrics come together")
+        else:
+            from computervision.pytorch_amd.seg_boundary import BoundaryMetrics
+            if not isinstance(boundary, BoundaryMetrics):
+                raise ValueError(f"boundary: a seg_boundary.BoundaryMetrics, got {type(boundary).__name__}")
+            if targets is None:
+                raise ValueError("boundary needs targets")
         frames = list(frames)
         net_hw = tuple(int(v) for v in self.cfg.arch.input_size[1:])
         batch = render.TileBatch(frames, net_hw, overlap, full_frame=False)
@@ -169,7 +178,10 @@ class DeeplabV3PlusA(FramePredictor):
                 block[c0:c0 + rows.shape[0]].copy_(rows)
         counts = metrics.add_labels_counts(block.device) if metrics is not None else None
         labels = render.stitch_segmentation(frames, block, self.num_classes, model._last_engine.graph.level_hw[0], net_hw, batch, weight=weight,
-                                            labels=True, draw=draw, bgr=bgr, targets=targets, counts=counts)
+                                            labels=True, draw=draw, bgr=bgr, targets=targets if metrics is not None else None,
+                                            counts=counts)
+        if boundary is not None:
+            boundary.add_labels(labels, list(targets))
         if sync:
             torch.cuda.synchronize(block.device)
         return labels
@@ -247,25 +259,33 @@ class DeeplabV3PlusA(FramePredictor):
 
         return batches()
 
-    def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None, scales=None, flip=False, fuse="prob"):
+    def evaluate_on_voc(self, model, results_out_root, subset="val", dataloader=None, scales=None, flip=False, fuse="prob", boundary=None):
         """Reference :115-166: the validation metrics of ``model`` over VOC-``subset``, printed and written to
         ``results_out_root/DeepLabV3Plus/DeepLabV3Plus_<dataset>_<time>.txt`` as four lines (Overall Acc, Mean Acc, FreqW Acc, Mean IoU).
         Reading VOC from disk is outside the hot path: ``dataloader`` is a ``DeviceSegLoader`` over the pictures with
         ``DeviceSegAugmenter(crop_hw=cfg.arch.crop_size, base_size=max(cfg.arch.input_size[1:]), colormap=voc_colormap(), train=False)``.
         Each batch is one engine forward and one ``cvx_seg_criterion_eval`` launch; the host waits once, at the end.  ``scales`` / ``flip`` /
         ``fuse`` select test-time augmentation (``predict_labels``): each batch is then one forward per scale and
-        one ``cvx_seg_fuse`` launch, still with one host wait at the end.  Returns the path written."""
-        from core.trainer.segmentation_trainer import SegmentationMetrics, fused_evaluation, fused_evaluation_tta
+        one ``cvx_seg_fuse`` launch, still with one host wait at the end.  ``boundary`` (a ``seg_boundary.SegBoundary``)
+        adds the boundary metrics: after the four lines the report gains three per width, ``Trimap mIoU@d``, ``Boundary IoU@d`` and
+        ``BF@d``.  They need label maps and the plain pass (``cvx_seg_criterion_eval``) writes none, so ``boundary=`` without ``scales`` /
+        ``flip`` runs the label-writing path with one view, ``SegTTA((1.0,), False, fuse)``: its four accuracies are the fusion's, not the
+        criterion's.  Each batch gains one ``cvx_seg_boundary`` call; the host still waits once, at the end.  Returns the path written."""
+        from core.trainer.segmentation_trainer import SegmentationMetrics, fused_evaluation, fused_evaluation_boundary, fused_evaluation_tta
         if subset != "val":
             raise ValueError(f"不支持VOC-{subset}")
         if dataloader is None:
             raise L.CvxError("evaluate_on_voc reads no dataset from disk: pass dataloader=DeviceSegLoader(source, batch_size, "
                              "DeviceSegAugmenter(crop_hw, base_size, colormap=voc_colormap(), train=False)) over the VOC-val pictures")
         tta = None
-        if scales is not None or flip:
+        if boundary is not None:
+            from computervision.pytorch_amd.seg_boundary import BoundaryMetrics, SegBoundary, report_lines
+            if not isinstance(boundary, SegBoundary):
+                raise ValueError(f"boundary: a seg_boundary.SegBoundary, got {type(boundary).__name__}")
+        if scales is not None or flip or boundary is not None:
             from computervision.pytorch_amd.seg_tta import SegTTA
             tta = SegTTA((1.0,) if scales is None else scales, flip, fuse)
-            self._need_gpu("evaluate_on_voc with test-time augmentation")
+            self._need_gpu("evaluate_on_voc with boundary metrics" if scales is None and not flip else "evaluate_on_voc with test-time augmentation")
         model_name = "DeepLabV3Plus"
         results_out_root = os.path.join(results_out_root, model_name)
         os.makedirs(results_out_root, exist_ok=True)
@@ -273,12 +293,16 @@ class DeeplabV3PlusA(FramePredictor):
         metrics = SegmentationMetrics(num_classes=self.num_classes, device=self.device)
         if tta is None:
             r = fused_evaluation(model, self.build_loss(), metrics, dataloader, self.device)
-        else:
+        elif boundary is None:
             r = fused_evaluation_tta(model, metrics, dataloader, self.device, tta)
+        else:
+            r = fused_evaluation_boundary(model, metrics, dataloader, self.device, tta, BoundaryMetrics(self.num_classes, boundary, self.device))
         formatted = (f"Overall Acc: {r['Overall Acc']}\n"
                      f"Mean Acc: {r['Mean Acc']}\n"
                      f"FreqW Acc: {r['FreqW Acc']}\n"
                      f"Mean IoU: {r['Mean IoU']}")
+        if boundary is not None:
+            formatted = "\n".join([formatted] + report_lines(r, boundary.keys))
         print(f"结果：\n{formatted}")
         with open(results_filepath, mode="w", encoding="utf-8") as f:
             f.write(formatted)

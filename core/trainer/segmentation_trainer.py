@@ -195,11 +195,9 @@ def fused_evaluation(model, criterion, metrics: SegmentationMetrics, dataloader,
             "Mean IoU": r["Mean IoU"]}
 
 
-def fused_evaluation_tta(model, metrics: SegmentationMetrics, dataloader, device, tta) -> Dict:
-    """The validation pass under multi-scale / flip test-time augmentation (``tta``: a ``computervision.pytorch_amd.seg_tta.SegTTA``, DESIGN.md
-    section 7n): per batch ``tta.run`` (one input launch and one ``forward_rows`` per scale) and one ``cvx_seg_fuse`` launch that counts
-    into ``metrics.add_labels_counts(device)``; the host synchronises ONCE, when the matrix is read after the last batch.  Returns the
-    four accuracies; the criterion's value is not defined on this path, so there is no "Loss"."""
+def _tta_pass(model, metrics: SegmentationMetrics, dataloader, device, tta, boundary=None) -> Dict:
+    """The loop of ``fused_evaluation_tta``; with ``boundary`` (a ``seg_boundary.BoundaryMetrics``) the fusion also writes its label maps and
+    one ``cvx_seg_boundary`` call per batch counts them against the targets."""
     model.eval()
     metrics.reset()
     counts = metrics.add_labels_counts(device)
@@ -207,6 +205,28 @@ def fused_evaluation_tta(model, metrics: SegmentationMetrics, dataloader, device
         for images, targets in dataloader:
             images = images.to(device, non_blocking=True)
             views = tta.run(model, images)
-            tta.fuse(views, metrics.num_classes, model.layout.nc_pad, images.shape[2:], targets=targets, counts=counts, labels=False)
+            labels = tta.fuse(views, metrics.num_classes, model.layout.nc_pad, images.shape[2:], targets=targets, counts=counts,
+                              labels=boundary is not None)
+            if boundary is not None:
+                boundary.add_labels(labels, targets.to(device, non_blocking=True))
     r = metrics.get_results()
     return {"Overall Acc": r["Overall Acc"], "Mean Acc": r["Mean Acc"], "FreqW Acc": r["FreqW Acc"], "Mean IoU": r["Mean IoU"]}
+
+
+def fused_evaluation_tta(model, metrics: SegmentationMetrics, dataloader, device, tta) -> Dict:
+    """The validation pass under multi-scale / flip test-time augmentation (``tta``: a ``computervision.pytorch_amd.seg_tta.SegTTA``, DESIGN.md
+    section 7n): per batch ``tta.run`` (one input launch and one ``forward_rows`` per scale) and one ``cvx_seg_fuse`` launch that counts
+    into ``metrics.add_labels_counts(device)``; the host synchronises ONCE, when the matrix is read after the last batch.  Returns the
+    four accuracies; the criterion's value is not defined on this path, so there is no "Loss"."""
+    return _tta_pass(model, metrics, dataloader, device, tta)
+
+
+def fused_evaluation_boundary(model, metrics: SegmentationMetrics, dataloader, device, tta, boundary) -> Dict:
+    """``fused_evaluation_tta`` with the boundary metrics: ``boundary`` is a ``seg_boundary.BoundaryMetrics`` (reset
+    here); every batch's fused label maps go through one ``cvx_seg_boundary`` call against the targets (values outside ``[0,
+    num_classes)`` are void).  Nothing waits on the host inside the loop; the confusion matrix and the boundary tables are read after the
+    last batch.  Returns the four accuracies and the dicts of ``boundary.get_results()``."""
+    boundary.reset()
+    r = _tta_pass(model, metrics, dataloader, device, tta, boundary)
+    r.update(boundary.get_results())
+    return r

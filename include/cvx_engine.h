@@ -1325,6 +1325,43 @@ int cvx_seg_regions(const cvx_seg_map* label_maps, const int32_t* frame_hw, int3
                     int32_t* total, int32_t* areas, int32_t* seeds, int32_t* overflow, void* workspace, int64_t workspace_bytes,
                     void* hip_stream);
 
+/* ---- boundary metrics of label maps (csrc/seg_boundary.hip) --------------------------------------------------------------
+ * The counts behind trimap mIoU (the DeepLab papers' band around the target's label changes), Boundary IoU (Cheng et al., CVPR 2021) and the
+ * boundary F-score BF (Csurka et al. 2013, DAVIS) of predicted label maps against target label maps.  All frames of a batch run together:
+ * three launches whatever the maps hold, asynchronous on hip_stream, tables in device memory, nothing read back.  The reference has no
+ * counterpart: the rules are the project's own, restated in numpy in tests/seg_boundary_restatement.py, and the kernels are held to the
+ * restatement bit for bit -- every quantity is an integer.  Additive: CVX_ABI_VERSION stays 6 (no existing entry or struct changes).
+ * pred_maps / target_maps (frames) cvx_seg_map, read in place, and frame_hw (frames, 2) int32 [h, w] on the device; (max_h, max_w): the
+ * largest frame (the grid and the workspace planes).  widths (frames, K) int32 on the device, 1 <= K <= 8, every width d_k in 1 .. 64;
+ * dmax is the largest width of the frame.  1 <= nc <= 255.  Per frame with prediction P and target G:
+ *   void        G'[p] = G[p] if G[p] < nc, else VOID; P'[p] = P[p] if G[p] < nc and P[p] < nc, else VOID.  VOID differs from every class; a
+ *               VOID pixel takes part in no count and its planes hold 0.
+ *   distance    for a map M and a pixel p of class c, D_M^e(p) is the smallest d >= 1 such that the square of Chebyshev radius d around p
+ *               holds a pixel q with M[q] != c or, with e = edge, reaches outside the picture; dmax + 1 if no d <= dmax does.  With
+ *               e = noedge the picture border does not count.
+ *   contour     K_M = { p : M[p] is a class and D_M^noedge(p) = 1 }.
+ *   nearest     for p in K_A of class c, N_{A->B}(p) is the smallest Chebyshev distance from p to a q in K_B with B[q] = c (0 allowed);
+ *               dmax + 1 if there is none within dmax.
+ *   trimap      (K, nc, nc) int64: trimap[k][G'[p]][P'[p]] += 1 for every p with both labels classes and D_G^noedge(p) <= d_k.
+ *   biou        (K, nc, 3) int64 (I, Gb, Pb): Gb counts G'[p] = c and D_G^edge(p) <= d_k, Pb counts P'[p] = c and D_P^edge(p) <= d_k, I
+ *               the pixels where both hold.  The band of class c equals mask & ~erode(mask, 3 x 3 ones, d_k iterations, zero border).
+ *   bf          (K, nc, 4) int64 (mp, cp, mg, cg): cp = |{p in K_P : P'[p] = c}|, mp those of them with N_{P->G}(p) <= d_k; cg and mg the
+ *               same with the roles swapped.
+ *   planes      optional (NULL: none): (frames, 6, max_h, max_w) uint8, of frame f the (h, w) corner of each plane -- D_G^edge,
+ *               D_G^noedge, D_P^edge, D_P^noedge (1 .. dmax + 1), then N_{P->G} + 1 and N_{G->P} + 1 on the contour (1 .. dmax + 2) and 0 off it.
+ * The three tables are added to, never cleared.  A frame whose entry in either table has data NULL is skipped; so is a frame with
+ * h <= 0, w <= 0, h > max_h, w > max_w or a width outside 1 .. 64 (the widths live on the device: the host side of the call cannot see
+ * them, computervision.pytorch_amd/seg_boundary.py refuses them before the upload).  Refused with a message and without a launch: nc outside 1 .. 255, K outside
+ * 1 .. 8, max_h * max_w >= 2^31, a short workspace.  workspace: cvx_seg_boundary_workspace_bytes(frames, max_h, max_w) bytes of device
+ * memory: 6 bytes per pixel of a max_h x max_w plane per frame (G', P', the two run radii, the two contour planes); 0 for sizes the entry
+ * refuses. */
+#define CVX_SEG_BOUNDARY_MAX_WIDTH 64
+#define CVX_SEG_BOUNDARY_MAX_WIDTHS 8
+int64_t cvx_seg_boundary_workspace_bytes(int32_t frames, int32_t max_h, int32_t max_w);
+int cvx_seg_boundary(const cvx_seg_map* pred_maps, const cvx_seg_map* target_maps, const int32_t* frame_hw, int32_t frames, int32_t max_h,
+                     int32_t max_w, int32_t nc, const int32_t* widths, int32_t K, int64_t* trimap, int64_t* biou, int64_t* bf, uint8_t* planes,
+                     void* workspace, int64_t workspace_bytes, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 
