@@ -189,6 +189,8 @@ PROTOTYPES = {
     "cvx_seg_criterion_lovasz_view": (_I32, [C.POINTER(SegDims), C.POINTER(SegCriterion), C.POINTER(_I64)]),
     "cvx_det_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_det_ap": (_I32, [_P, _P, _P, _P, _I32, C.c_double, _I32, _P, _P, _P, _P]),
+    "cvx_det_confusion": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _I32, _P, _P, _P, _P]),
+    "cvx_det_conf_curves": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "cvx_coco_match": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "cvx_coco_accumulate": (_I32, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "cvx_coco_summarize": (_I32, [_P, _P, _I32, _P, _P]),

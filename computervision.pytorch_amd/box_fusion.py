@@ -251,9 +251,9 @@ class DetEnsemble:
             m.eval()
         return self.rows_of(min(self.eval_max_det, FUSE_CAP), evaluation=True)
 
-    def evaluate_on_voc(self, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False):
+    def evaluate_on_voc(self, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False, diagnostics=None):
         """``Detector.evaluate_on_voc`` on the ensemble's fused rows (at most ``min(eval_max_det, 8192)`` per image); the dataloader and the
-        result are those of the detectors' method.  All members must share ``_predict_input()``."""
+        result are those of the detectors' method, ``diagnostics`` included.  All members must share ``_predict_input()``."""
         if subset not in ("val", "test"):
             raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
         if dataloader is None:
@@ -262,7 +262,7 @@ class DetEnsemble:
         from . import det_eval
         from configs.dataset_cfg import VOC_CFG
         return det_eval.evaluate_detector(self._evaluation_tails("evaluate_on_voc"), dataloader, self.num_classes, self.device, map_out_root,
-                                          det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric)
+                                          det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric, diagnostics)
 
     def evaluate_on_coco(self, map_out_root, subset="val", dataloader=None, capacity=None):
         """``Detector.evaluate_on_coco`` on the ensemble's fused rows; see ``evaluate_on_voc``"""

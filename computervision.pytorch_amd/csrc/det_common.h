@@ -1,5 +1,6 @@
-// What the VOC (det_eval.hip) and COCO (coco_eval.hip) evaluation kernels share: the record cursor, the score text rule, the box map and
-// the workgroup scan.  Each translation unit gets its own copy of the kernels here (anonymous namespace).
+// What the VOC (det_eval.hip), COCO (coco_eval.hip) and diagnostics (det_diag.hip) evaluation kernels share: the record cursor, the score
+// text and threshold rules, the box map, the size limits and the workgroup scan.  Each translation unit gets its own copy of the kernels
+// here (anonymous namespace).
 #pragma once
 #include "cvx_common.h"
 
@@ -18,6 +19,18 @@ __device__ __forceinline__ float det_quantize(float x) {
 }
 
 __device__ __forceinline__ int det_count(int c, int max_det) { return (c < 0 || c > max_det) ? 0 : c; }
+
+// what the per-image VOC kernels (det_eval.hip, det_diag.hip) hold in LDS at most, and the flag of a record
+constexpr int DET_MAX_ROWS = 16384;       // what cvx_nms can return per image
+constexpr int DET_MAX_GT = 1024;
+constexpr int DET_MAX_LDS = 160 * 1024;
+enum { FLAG_FP = 0, FLAG_TP = 1, FLAG_NEITHER = 2 };
+
+__host__ __device__ inline int det_gt_slots(int G) { return (G + 1) & ~1; }
+
+__device__ __forceinline__ bool det_score_reaches(float s, double threshold, int quantize) {
+  return (quantize ? rint((double)s * 1e4) / 1e4 : (double)s) >= threshold;  // float("0.xxxx") >= score_threshold
+}
 
 __global__ __launch_bounds__(DET_THREADS) void det_cursor_kernel(const int* __restrict__ counts, int B, int max_det, long long capacity,
                                                                  unsigned long long* state) {

@@ -26,12 +26,6 @@
 
 namespace {
 
-constexpr int DET_MAX_ROWS = 16384;       // what cvx_nms can return per image
-constexpr int DET_MAX_GT = 1024;
-constexpr int DET_MAX_LDS = 160 * 1024;
-enum { FLAG_FP = 0, FLAG_TP = 1, FLAG_NEITHER = 2 };
-
-__host__ __device__ inline int det_gt_slots(int G) { return (G + 1) & ~1; }
 __host__ __device__ inline int det_row_slots(int max_det) { return (max_det + 3) & ~3; }
 inline size_t det_match_lds(int max_det, int G) { return 32 + (size_t)32 * det_gt_slots(G) + (size_t)8 * det_row_slots(max_det); }
 
@@ -150,10 +144,6 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __r
   }
   if (bad_class) atomicAdd(&state[ST_BAD_CLASS], bad_class);
   if (low_score) atomicAdd(&state[ST_LOW_SCORE], low_score);
-}
-
-__device__ __forceinline__ bool det_score_reaches(float s, double threshold, int quantize) {
-  return (quantize ? rint((double)s * 1e4) / 1e4 : (double)s) >= threshold;  // float("0.xxxx") >= score_threshold
 }
 
 __global__ __launch_bounds__(DET_THREADS) void det_ap_kernel(const float* __restrict__ score, const int* __restrict__ flag,

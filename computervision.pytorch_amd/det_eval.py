@@ -11,7 +11,8 @@ keeps that order among equal scores.  ``add_batch`` keeps (call order, image ord
 ORDER to reproduce the reference's tie-breaks.
 
 Not reproduced: scores below 1e-4 (the reference's text is scientific notation there; ``results()`` raises if one was seen -- the
-writers use ``conf_threshold=0.001``), the plots, ``images-optional`` and the log-average miss rate.
+writers use ``conf_threshold=0.001``), the plots and ``images-optional``.  The log-average miss rate is in ``det_diag.py``, with the
+confusion matrix and the confidence curves (``evaluate_detector(diagnostics=)``).
 """
 import os
 
@@ -106,6 +107,25 @@ def pack_rows(per_image, device):
     return rows, torch.tensor(n, dtype=torch.int32, device=device)
 
 
+def check_batch(rows, counts, gt, gt_counts, box_map, max_det, device):
+    """The argument checks of ``DetectionEvaluator.add_batch`` and ``det_diag.DetectionDiagnostics.add_batch``; returns the five
+    arguments contiguous."""
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    G = int(gt.shape[1])
+    if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or not (0 < K <= max_det):
+        raise ValueError(f"rows: (B, K <= {max_det}, 6) float32, got {tuple(rows.shape)} {rows.dtype}")
+    if gt.dim() != 3 or gt.shape[0] != B or (G and gt.shape[2] != 6) or gt.dtype != torch.int32 or G > MAX_GT:
+        raise ValueError(f"gt: (B, G <= {MAX_GT}, 6) int32, got {tuple(gt.shape)} {gt.dtype}")
+    if counts.dtype != torch.int32 or gt_counts.dtype != torch.int32 or counts.numel() != B or gt_counts.numel() != B:
+        raise ValueError("counts and gt_counts: (B) int32")
+    if box_map is not None and (box_map.dtype != torch.float32 or tuple(box_map.shape) != (B, 4)):
+        raise ValueError("box_map: (B, 4) float32 [px, py, gx, gy]")
+    for t in (rows, counts, gt, gt_counts, box_map):
+        if t is not None and t.device != device:
+            raise ValueError("add_batch: every tensor lives on the evaluator's device")
+    return rows.contiguous(), counts.contiguous(), gt.contiguous(), gt_counts.contiguous(), None if box_map is None else box_map.contiguous()
+
+
 class DetectionEvaluator:
     """Device-side ``get_map``.  ``max_det``: the most rows per image a batch may carry; ``capacity``: the records the whole evaluation may
     append (images x rows).  ``quantize_scores=True`` is the reference's ``str(score)[:6]``."""
@@ -148,21 +168,8 @@ class DetectionEvaluator:
         [cls, l, t, r, b, difficult] and gt_counts (B) int32; ``box_map`` None: the boxes are final (mode 0), or (B, 4) float32
         [px, py, gx, gy] (mode 1, ``letterbox_box_map``).  One launch pair, no host read."""
         self._buffers()
-        B, K = int(rows.shape[0]), int(rows.shape[1])
-        G = int(gt.shape[1])
-        if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or not (0 < K <= self.max_det):
-            raise ValueError(f"rows: (B, K <= {self.max_det}, 6) float32, got {tuple(rows.shape)} {rows.dtype}")
-        if gt.dim() != 3 or gt.shape[0] != B or (G and gt.shape[2] != 6) or gt.dtype != torch.int32 or G > MAX_GT:
-            raise ValueError(f"gt: (B, G <= {MAX_GT}, 6) int32, got {tuple(gt.shape)} {gt.dtype}")
-        if counts.dtype != torch.int32 or gt_counts.dtype != torch.int32 or counts.numel() != B or gt_counts.numel() != B:
-            raise ValueError("counts and gt_counts: (B) int32")
-        if box_map is not None and (box_map.dtype != torch.float32 or tuple(box_map.shape) != (B, 4)):
-            raise ValueError("box_map: (B, 4) float32 [px, py, gx, gy]")
-        for t in (rows, counts, gt, gt_counts, box_map):
-            if t is not None and t.device != self.rec_score.device:
-                raise ValueError("add_batch: every tensor lives on the evaluator's device")
-        rows, counts, gt, gt_counts = rows.contiguous(), counts.contiguous(), gt.contiguous(), gt_counts.contiguous()
-        box_map = None if box_map is None else box_map.contiguous()
+        rows, counts, gt, gt_counts, box_map = check_batch(rows, counts, gt, gt_counts, box_map, self.max_det, self.rec_score.device)
+        B, K, G = int(rows.shape[0]), int(rows.shape[1]), int(gt.shape[1])
         self._cache = None
         L.check(L.load().cvx_det_match(L.ptr(rows), L.ptr(counts), B, K, 0 if box_map is None else 1, L.ptr(box_map), L.ptr(gt) if G else None,
                                        L.ptr(gt_counts), G, self.num_classes, self.min_overlap, int(self.quantize), L.ptr(self.rec_score),
@@ -209,6 +216,13 @@ class DetectionEvaluator:
                 "ap": s[:, 0].copy(), "precision": s[:, 1].copy(), "recall": s[:, 2].copy(), "f1": s[:, 3].copy(),
                 "tp": s[:, 4].astype(np.int64), "n_det": s[:, 5].astype(np.int64), "n_gt": s[:, 6].astype(np.int64)})
         return self._cache["res"]
+
+    def device_records(self):
+        """What ``_reduce`` left on the device, after ``results()`` has checked the counters: ``score`` / ``flag`` / ``prec`` / ``rec`` per
+        record in get_map's order (class ascending, score descending, stable), ``seg_off`` (nc + 1) the first record of each class,
+        ``order`` / ``cls`` / ``stats``.  No host read of its own; ``det_diag.DetectionDiagnostics.results`` reads its curves from these."""
+        self.results()
+        return self._cache["device"]
 
     def curves(self):
         """Per class (prec, rec) float64 arrays, one entry per detection in get_map's order (a second host read, for the report)."""
@@ -269,13 +283,20 @@ def class_names(dataset_cfg, num_classes):
     return names if len(names) == num_classes else [str(c) for c in range(num_classes)]
 
 
-def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_root, class_names, max_det, capacity=None, coco_metric=False):
+def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_root, class_names, max_det, capacity=None, coco_metric=False,
+                      diagnostics=None):
     """The loop the four ``evaluate_on_voc`` methods share.  ``evaluator_rows(images, meta)`` -> (rows, counts, box_map or None) on the
     device.  ``capacity`` defaults to batches x batch size x min(max_det, 1024) records.  Writes ``<map_out_root>/results/results.txt`` and
     returns the ``results()`` dict.  ``coco_metric``: the same pass also feeds a ``CocoEvaluator`` what ``get_coco_map`` (mAP.py:930-959)
     reads from the writers' text files -- truncated boxes, cut scores, the ground truth as ``preprocess_gt`` converts it; its results are
-    the ``"coco"`` entry and its twelve lines go to ``<map_out_root>/coco_results.txt``."""
-    ev = coco = None
+    the ``"coco"`` entry and its twelve lines go to ``<map_out_root>/coco_results.txt``.  ``diagnostics``: a ``det_diag.DetDiagnostics`` --
+    the same rows also feed a ``DetectionDiagnostics`` (one more launch per batch); its results are the ``"diagnostics"`` entry and its
+    three files go to ``<map_out_root>/results/``.  With None nothing of it is allocated or launched."""
+    if diagnostics is not None:
+        from . import det_diag
+        if not isinstance(diagnostics, det_diag.DetDiagnostics):
+            raise ValueError(f"diagnostics: a det_diag.DetDiagnostics or None, got {type(diagnostics).__name__}")
+    ev = coco = diag = None
     for images, meta in dataloader:
         rows, counts, box_map = evaluator_rows(images, meta)
         if ev is None:
@@ -286,7 +307,11 @@ def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_r
             ev = DetectionEvaluator(num_classes, max_det, capacity, rows.device)
             if coco_metric:
                 coco = coco_eval.CocoEvaluator(num_classes, max_det, capacity, rows.device, truncate_boxes=True, quantize_scores=True)
+            if diagnostics is not None:
+                diag = det_diag.DetectionDiagnostics(num_classes, max_det, rows.device, diagnostics)
         ev.add_batch(rows, counts, meta["gt"], meta["gt_counts"], box_map)
+        if diag is not None:
+            diag.add_batch(rows, counts, meta["gt"], meta["gt_counts"], box_map)
         if coco is not None:
             coco.add_batch(rows, counts, coco_eval.voc_gt_to_coco(meta["gt"]), meta["gt_counts"], box_map)
     if ev is None:
@@ -297,4 +322,8 @@ def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_r
     if coco is not None:
         res = dict(res, coco=coco.results())
         coco_eval.write_summary(coco, map_out_root)
+    if diag is not None:
+        res = dict(res, diagnostics=diag.results(ev))
+        diag.write_report(os.path.join(map_out_root, "results"), class_names)
+        print("recommended conf_threshold = {0:.4f}".format(res["diagnostics"]["best_conf"]))
     return res

@@ -202,7 +202,7 @@ class Detector(FramePredictor):
             return render.read_detections(rows, counts, overflow)
         return rows, counts
 
-    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False, tta=None):
+    def evaluate_on_voc(self, model, map_out_root, subset="val", dataloader=None, capacity=None, coco_metric=False, tta=None, diagnostics=None):
         """The reference's ``evaluate_on_voc``: VOC mAP (``get_map`` at IoU 0.5) of ``model`` at ``conf_threshold=0.001``, written to
         ``map_out_root/results/results.txt``.  Reading VOC from disk is outside the hot path: ``dataloader`` yields ``(images, meta)`` with
         images (B, 3, H, W) already through the validation transform and meta = dict(image_hw (B, 2) original sizes, gt (B, G, 6) int32
@@ -214,7 +214,10 @@ class Detector(FramePredictor):
         ``coco_metric=True`` adds the COCO metric ``get_coco_map`` ends the reference's method with, from the same pass: the ``"coco"``
         entry of the result.
         ``tta``: a ``det_tta.DetTTA`` -- every batch is evaluated on its views and fused (``DetTTA.wrap`` around ``_evaluation_rows``, at
-        most ``min(eval_max_det, 8192)`` rows per image); everything behind the rows is unchanged."""
+        most ``min(eval_max_det, 8192)`` rows per image); everything behind the rows is unchanged.
+        ``diagnostics``: a ``det_diag.DetDiagnostics`` -- the same rows feed one ``cvx_det_confusion`` launch per batch; the confusion
+        matrix, the confidence curves with the recommended ``conf_threshold`` and the log-average miss rates are the ``"diagnostics"``
+        entry of the result and three files beside ``results.txt``.  None: nothing of it is allocated or launched."""
         if subset not in ("val", "test"):
             raise ValueError(f"sub_set must be one of 'test' and 'val', but got {subset}")
         if dataloader is None:
@@ -224,7 +227,8 @@ class Detector(FramePredictor):
         from configs.dataset_cfg import VOC_CFG
         model.eval()
         return det_eval.evaluate_detector(self._augmented(model, tta, min(self.eval_max_det, 8192)), dataloader, self.num_classes, self.device,
-                                          map_out_root, det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric)
+                                          map_out_root, det_eval.class_names(VOC_CFG, self.num_classes), self.eval_max_det, capacity, coco_metric,
+                                          diagnostics)
 
     def evaluate_on_coco(self, model, map_out_root, subset="val", dataloader=None, capacity=None, tta=None):
         """The reference's ``evaluate_on_coco``: the COCO metric (``COCOeval`` on boxes) of ``model`` at ``conf_threshold=0.001``, boxes and

@@ -681,6 +681,44 @@ int cvx_det_match(const float* rows, const int32_t* counts, int32_t batch, int32
                   void* hip_stream);
 int cvx_det_ap(const float* score, const int32_t* flag, const int64_t* seg_off, const int64_t* gt_per_class, int32_t nc,
                double score_threshold, int32_t quantize, double* prec, double* rec, double* stats, void* hip_stream);
+/* Diagnostics of a detector beside its VOC mAP (csrc/det_diag.hip).  Additive: CVX_ABI_VERSION stays 6.
+ * cvx_det_confusion, once per batch, one launch: rows, counts, box_mode, box_map, gt, gt_counts, nc and quantize exactly as cvx_det_match
+ * takes them (max_det <= 16384, max_gt <= 1024), conf in [0, 1] and iou in [0, 1).  The rule is the project's statement of Ultralytics'
+ * ConfusionMatrix.process_batch with the ties decided, per image:
+ *   take part   a detection whose class lies in [0, nc) and whose score reaches conf: rint(s * 1e4) / 1e4 >= conf in fp64 on the cut score
+ *               with quantize, s >= conf without (cvx_det_ap's threshold rule).  The others count nowhere.
+ *   overlap     cvx_det_match's, on the boxes mapped and truncated as there (integers, +1 pixel convention, one fp64 division), between a
+ *               detection and a ground truth of ANY class; a candidate pair has overlap > iou (strict).
+ *   choice      each detection picks its candidate of largest overlap, the lowest ground-truth index on a tie; difficult ground truths are
+ *               candidates.  A detection that chose a difficult ground truth counts nowhere.
+ *   winner      each non-difficult ground truth keeps, of the detections that chose it, the one of largest overlap, the lowest row on a
+ *               tie: confusion[class of the detection][class of the ground truth] += 1.
+ *   the rest    every other detection that takes part: confusion[its class][nc] += 1 -- one that lost its ground truth is NOT tried on
+ *               its second choice; every non-difficult ground truth without a winner: confusion[nc][its class] += 1.
+ * confusion (nc + 1, nc + 1) int64 indexed [predicted][true], nc = background; images_per_class (nc) int64: the images that hold a
+ * non-difficult ground truth of the class (the reference's counter_images_per_class); state (4) int64 [images seen, images skipped
+ * (a count below 0 or above max_det, a gt_count outside [0, max_gt]: the image contributes nothing), class indices outside [0, nc) of
+ * detections or ground truths (the box takes part in nothing), unused].  All three are device memory, zeroed by the caller before the
+ * first batch and added to with integer atomics: the same bytes on every run.  No host read; asynchronous on hip_stream.
+ * cvx_det_conf_curves, once per evaluation, two launches: score, prec, rec, flag and seg_off as cvx_det_ap takes and leaves them
+ * (class ascending, score descending), gt_per_class (nc) of cvx_det_match, images_per_class (nc) of cvx_det_confusion, 2 <= points <= 4096,
+ * window odd in 1 .. 65535, ref_points: the nine doubles of numpy's logspace(-2, 0, 9) on the device.  With P = points and x_k =
+ * (double)k / (double)(P - 1): n_k = the records of the class that reach x_k (the threshold rule above); precision, recall = prec, rec at
+ * record n_k - 1 and F1 = R * P * 2 / (P + R == 0 ? 1 : P + R), or (1, 0, 0) when n_k = 0 -- the operating point at conf_threshold = x_k.
+ * mean F1: the sum over the classes with gt_per_class > 0 in ascending class, divided by their number (0 without one).  smooth(y)[i] =
+ * (sum over j = 0 .. window - 1, ascending, of y[clamp(i - window / 2 + j, 0, P - 1)]) / window, applied to the mean and to every class's
+ * F1; best index = the first maximum of a smoothed curve.  Miss rates: fppi_j = (double)(FP flags among records 0 .. j) / (double)
+ * images_per_class; per reference point the last record j with fppi_j <= the point gives 1 - rec[j], 1.0 when there is none or
+ * images_per_class is 0 (log_average_miss_rate, core/metrics/mAP.py:34-70, up to its final exp(mean(log(max(1e-10, .)))), the host's).
+ * fp64 without contraction throughout.  out: out_words >= 3 * nc * P + 2 * P + 10 * nc + 1 words of 8 bytes: precision (nc, P), recall
+ * (nc, P), f1 (nc, P), mean f1 (P), smoothed mean f1 (P), miss rates (nc, 9) as doubles, then the best indices (nc + 1) as int64, the mean
+ * curve's last.  No host read; asynchronous on hip_stream. */
+int cvx_det_confusion(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, int32_t box_mode, const float* box_map,
+                      const int32_t* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc, double conf, double iou, int32_t quantize,
+                      int64_t* confusion, int64_t* images_per_class, int64_t* state, void* hip_stream);
+int cvx_det_conf_curves(const float* score, const double* prec, const double* rec, const int32_t* flag, const int64_t* seg_off,
+                        const int64_t* gt_per_class, const int64_t* images_per_class, int32_t nc, int32_t quantize, int32_t points,
+                        int32_t window, const double* ref_points, double* out, int64_t out_words, void* hip_stream);
 /* COCO detection metric of a detector (pycocotools' COCOeval(gt, dt, 'bbox'): iouThrs linspace(.5, .95, 10), recThrs linspace(0, 1, 101),
  * maxDets 1 / 10 / 100, areas all / small / medium / large, useCats), accumulated on the device batch by batch.
  * cvx_coco_match, once per batch: rows, counts, box_mode and box_map as cvx_det_match takes them.  truncate != 0: the mapped corners are
