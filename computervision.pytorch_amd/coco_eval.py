@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .det_records import MAX_GT, MAX_ROWS, RecordEvaluator, check_batch, default_capacity, record_order  # noqa: F401 (old import paths)
 
-MAX_ROWS, MAX_GT = 16384, 1024
 IOU_THRS = np.linspace(.5, .95, 10)         # the doubles as numpy makes them: not exact multiples of 0.05
 REC_THRS = np.linspace(0, 1, 101)
 MAX_DETS = (1, 10, 100)
@@ -48,68 +48,38 @@ def voc_gt_to_coco(gt: torch.Tensor) -> torch.Tensor:
     return torch.stack((g[..., 0], g[..., 1], g[..., 2], w, h, w * h - 10.0, g[..., 5]), -1).contiguous()
 
 
-class CocoEvaluator:
+class CocoEvaluator(RecordEvaluator):
     """Device-side ``COCOeval``.  ``max_det``: the most rows per image a batch may carry; ``capacity``: the records the whole evaluation
     may append (images x rows).  ``truncate_boxes`` / ``quantize_scores``: the VOC writers' ``int()`` and ``str(score)[:6]``, for the
     metric ``get_coco_map`` computes from their text files."""
+    _ENTRIES = ("cvx_coco_match", "cvx_coco_accumulate")
+    _low_score_message = ("unusable scores: below 1e-4 with quantize_scores (the reference writes them in scientific notation and reads back "
+                          "their first 6 characters), negative or NaN without")
 
     def __init__(self, num_classes, max_det, capacity, device, truncate_boxes=False, quantize_scores=False):
-        if not (0 < int(max_det) <= MAX_ROWS):
-            raise ValueError(f"max_det {max_det}: cvx_coco_match holds 1 .. {MAX_ROWS} rows per image")
-        if int(num_classes) <= 0 or int(capacity) <= 0:
-            raise ValueError("num_classes and capacity are positive")
-        self.num_classes, self.max_det, self.capacity = int(num_classes), int(max_det), int(capacity)
-        self.device = torch.device(device)
+        super().__init__(num_classes, max_det, capacity, device)
         self.truncate, self.quantize = bool(truncate_boxes), bool(quantize_scores)
-        self._alloc = False
-        self._cache = None
 
-    def _buffers(self):
-        if self.device.type != "cuda":
-            raise L.CvxError("CocoEvaluator runs on an MI355X only (cvx_coco_match / cvx_coco_accumulate): there is no CPU path")
-        if not self._alloc:
-            dev, cap, nc = self.device, self.capacity, self.num_classes
-            self.rec_score = torch.zeros(cap, dtype=torch.float32, device=dev)
-            self.rec_class = torch.empty(cap, dtype=torch.int32, device=dev)
-            self.rec_rank = torch.zeros(cap, dtype=torch.int32, device=dev)
-            self.rec_matched = torch.zeros(cap, dtype=torch.int64, device=dev)
-            self.rec_ignored = torch.zeros(cap, dtype=torch.int64, device=dev)
-            self.state = torch.zeros(4, dtype=torch.int64, device=dev)
-            self.npig = torch.zeros(nc, 4, dtype=torch.int64, device=dev)
-            # pinned and kept: the two copies do not wait on the host (the first batch of an evaluation allocates here)
-            self._thrs_host = (torch.from_numpy(IOU_THRS).pin_memory(), torch.from_numpy(REC_THRS).pin_memory())
-            self.iou_thrs = self._thrs_host[0].to(dev, non_blocking=True)
-            self.rec_thrs = self._thrs_host[1].to(dev, non_blocking=True)
-            self._alloc = True
-            self.reset()
-
-    def reset(self):
-        self._cache = None
-        if self._alloc:
-            self.rec_class.fill_(self.num_classes)       # unwritten slots sort behind every class
-            for t in (self.rec_score, self.rec_rank, self.rec_matched, self.rec_ignored, self.state, self.npig):
-                t.zero_()
+    def _columns(self):
+        dev, cap = self.device, self.capacity
+        self.rec_rank = torch.zeros(cap, dtype=torch.int32, device=dev)
+        self.rec_matched = torch.zeros(cap, dtype=torch.int64, device=dev)
+        self.rec_ignored = torch.zeros(cap, dtype=torch.int64, device=dev)
+        self.npig = torch.zeros(self.num_classes, 4, dtype=torch.int64, device=dev)
+        # pinned and kept: the two copies do not wait on the host (the first batch of an evaluation allocates here)
+        self._thrs_host = (torch.from_numpy(IOU_THRS).pin_memory(), torch.from_numpy(REC_THRS).pin_memory())
+        self.iou_thrs = self._thrs_host[0].to(dev, non_blocking=True)
+        self.rec_thrs = self._thrs_host[1].to(dev, non_blocking=True)
+        return self.rec_rank, self.rec_matched, self.rec_ignored, self.npig
 
     def add_batch(self, rows, counts, gt, gt_counts, box_map=None):
         """rows (B, K, 6) float32 and counts (B) int32 as ``engine.nms`` returns them (K <= max_det); gt (B, G, 7) float64
         [cls, x, y, w, h, area, iscrowd] and gt_counts (B) int32; ``box_map`` None: the boxes are final (mode 0), or (B, 4) float32
         [px, py, gx, gy] (mode 1, ``det_eval.letterbox_box_map``).  One launch pair, no host read."""
         self._buffers()
-        if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or not (0 < int(rows.shape[1]) <= self.max_det):
-            raise ValueError(f"rows: (B, K <= {self.max_det}, 6) float32, got {tuple(rows.shape)} {rows.dtype}")
-        B, K = int(rows.shape[0]), int(rows.shape[1])
-        G = int(gt.shape[1]) if gt.dim() == 3 else -1
-        if G < 0 or gt.shape[0] != B or (G and gt.shape[2] != 7) or gt.dtype != torch.float64 or G > MAX_GT:
-            raise ValueError(f"gt: (B, G <= {MAX_GT}, 7) float64, got {tuple(gt.shape)} {gt.dtype}")
-        if counts.dtype != torch.int32 or gt_counts.dtype != torch.int32 or counts.numel() != B or gt_counts.numel() != B:
-            raise ValueError("counts and gt_counts: (B) int32")
-        if box_map is not None and (box_map.dtype != torch.float32 or tuple(box_map.shape) != (B, 4)):
-            raise ValueError("box_map: (B, 4) float32 [px, py, gx, gy]")
-        for t in (rows, counts, gt, gt_counts, box_map):
-            if t is not None and t.device != self.rec_score.device:
-                raise ValueError("add_batch: every tensor lives on the evaluator's device")
-        rows, counts, gt, gt_counts = rows.contiguous(), counts.contiguous(), gt.contiguous(), gt_counts.contiguous()
-        box_map = None if box_map is None else box_map.contiguous()
+        rows, counts, gt, gt_counts, box_map = check_batch(rows, counts, gt, gt_counts, box_map, self.max_det, self.rec_score.device,
+                                                           torch.float64, 7)
+        B, K, G = int(rows.shape[0]), int(rows.shape[1]), int(gt.shape[1])
         self._cache = None
         L.check(L.load().cvx_coco_match(L.ptr(rows), L.ptr(counts), B, K, 0 if box_map is None else 1, L.ptr(box_map), int(self.truncate),
                                         int(self.quantize), L.ptr(gt) if G else None, L.ptr(gt_counts), G, self.num_classes,
@@ -121,10 +91,7 @@ class CocoEvaluator:
         """Order the records as COCOeval.accumulate does, run cvx_coco_accumulate and cvx_coco_summarize; everything stays on the device."""
         self._buffers()
         nc, dev = self.num_classes, self.device
-        # class in the high bits, the inverted score bits below: ascending = class ascending, score descending; stable keeps (image, row)
-        key = (self.rec_class.to(torch.int64) << 32) | (0xFFFFFFFF - self.rec_score.view(torch.int32).to(torch.int64))
-        key, order = torch.sort(key, stable=True)
-        seg_off = torch.searchsorted((key >> 32).contiguous(), torch.arange(nc + 1, dtype=torch.int64, device=dev)).contiguous()
+        order, _, seg_off = record_order(self.rec_class, self.rec_score, nc)
         rank, matched, ignored = self.rec_rank[order].contiguous(), self.rec_matched[order].contiguous(), self.rec_ignored[order].contiguous()
         precision = torch.empty(10, 101, nc, 4, 3, dtype=torch.float64, device=dev)
         recall = torch.empty(10, nc, 4, 3, dtype=torch.float64, device=dev)
@@ -144,15 +111,7 @@ class CocoEvaluator:
             nc = self.num_classes
             host = torch.cat((self.state.to(torch.float64), self.npig.reshape(-1).to(torch.float64), stats, recall.reshape(-1),
                               precision.reshape(-1))).cpu().numpy()                              # counters < 2^53: exact as doubles
-            cursor, overflow, low, bad = (int(v) for v in host[:4])
-            if overflow:
-                raise L.CvxError(f"CocoEvaluator: {overflow} image(s) dropped: an NMS count of -1 (more candidates than cvx_nms sorts), a "
-                                 f"count past its block, or more than capacity={self.capacity} records")
-            if bad:
-                raise L.CvxError(f"CocoEvaluator: {bad} class indices outside [0, {nc})")
-            if low:
-                raise L.CvxError(f"CocoEvaluator: {low} unusable scores: below 1e-4 with quantize_scores (the reference writes them in scientific "
-                                 "notation and reads back their first 6 characters), negative or NaN without")
+            cursor = self._check_counters(host)
             o = 4
             npig = host[o:o + nc * 4].astype(np.int64).reshape(nc, 4)
             o += nc * 4
@@ -171,13 +130,6 @@ class CocoEvaluator:
     def summary_text(self):
         """The twelve lines of COCOeval.summarize, newline-terminated"""
         return "".join(line + "\n" for line in summary_lines(self.results()["stats"]))
-
-
-def default_capacity(dataloader, batch, max_det, who):
-    """batches x batch size x min(max_det, 1024) records"""
-    if not hasattr(dataloader, "__len__"):
-        raise L.CvxError(f"{who}: a dataloader without len() needs capacity= (the records of the whole evaluation)")
-    return len(dataloader) * int(batch) * min(int(max_det), 1024)
 
 
 def evaluate_detector_coco(evaluator_rows, dataloader, num_classes, map_out_root, max_det, capacity=None):

@@ -24,9 +24,6 @@
 
 namespace {
 
-constexpr int COCO_MAX_ROWS = 16384;
-constexpr int COCO_MAX_GT = 1024;
-constexpr int COCO_MAX_LDS = 160 * 1024;
 constexpr int COCO_TOP = 100;             // maxDets[-1]
 constexpr int COCO_T = 10, COCO_A = 4, COCO_M = 3, COCO_R = 101;
 constexpr int COCO_WALKS = COCO_T * COCO_A;
@@ -51,7 +48,7 @@ __host__ __device__ inline CocoLds coco_lds(int P, int G, int nc) {
   l.P = P;
   l.S = ((P < nc ? P : nc) + 1) & ~1;
   l.W = (G + 31) / 32 + ((G + 31) / 32 == 0);
-  const int Gs = (G + 1) & ~1;
+  const int Gs = det_gt_slots(G);
   l.keys = 48;  // 4 wave partials, the segment counter
   l.gbox = l.keys + (size_t)8 * P;
   l.gcls = l.gbox + (size_t)40 * Gs;
@@ -110,22 +107,10 @@ __global__ __launch_bounds__(DET_THREADS) void coco_match_kernel(const float* __
   unsigned* gmask = reinterpret_cast<unsigned*>(smem + L.gmask);            // per wave and walk: ground truths matched so far
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-  // records of the images before this one in the batch
-  long long before = 0;
-  for (int i = tid; i < b; i += DET_THREADS) before += det_count(counts[i], max_det);
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
-  if (lane == 0) red[wave] = before;
-  if (tid == 0) *nseg = 0;
-  __syncthreads();
-  const long long base = (long long)state[ST_CURSOR] + red[0] + red[1] + red[2] + red[3];
-
-  const int n_raw = counts[b], ng_raw = gt_counts[b];
-  const bool bad_image = n_raw < 0 || n_raw > max_det || ng_raw < 0 || ng_raw > G || base + det_count(n_raw, max_det) > capacity;
-  if (bad_image) {  // NMS overflow (-1), a count past its block, or no room left: counted, and the image contributes nothing
-    if (tid == 0) atomicAdd(&state[ST_OVERFLOW], 1ull);
-    return;
-  }
-  const int n = n_raw, ng = ng_raw;
+  if (tid == 0) *nseg = 0;  // ahead of det_record_base: its barrier publishes this store
+  const long long base = det_record_base(counts, b, max_det, state, red);
+  const int n = counts[b], ng = gt_counts[b];
+  if (det_image_refused(n, max_det, ng, G, &state[ST_OVERFLOW], base, capacity)) return;
   unsigned long long bad_class = 0, low_score = 0;
 
   for (int g = tid; g < ng; g += DET_THREADS) {
@@ -184,13 +169,7 @@ __global__ __launch_bounds__(DET_THREADS) void coco_match_kernel(const float* __
   }
   __syncthreads();
 
-  float px = 0.f, py = 0.f, gx = 1.f, gy = 1.f;
-  if (box_mode == 1) {
-    px = box_map[b * 4 + 0];
-    py = box_map[b * 4 + 1];
-    gx = box_map[b * 4 + 2];
-    gy = box_map[b * 4 + 3];
-  }
+  const det_box_map map = det_load_box_map(box_mode, box_map, b);
   const int segments = *nseg;
   double* my_dbox = dbox + (size_t)wave * COCO_TOP * 5;
   unsigned char* my_dflag = dflag + (size_t)wave * COCO_TOP * COCO_WALKS;
@@ -207,7 +186,7 @@ __global__ __launch_bounds__(DET_THREADS) void coco_match_kernel(const float* __
       const int r = (int)(keys[s0 + dl] & ((1u << KEY_ROW_BITS) - 1));
       const float* row = rows + ((long long)b * max_det + r) * 6;
       float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
-      if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, px, py, gx, gy);
+      if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, map);
       if (truncate) {  // the VOC writers' int(): towards zero
         x1 = truncf(x1);
         y1 = truncf(y1);
@@ -299,24 +278,20 @@ __global__ __launch_bounds__(DET_THREADS) void coco_accumulate_kernel(const int*
   for (int i = tid; i < COCO_R; i += DET_THREADS) rthr[i] = rec_thrs[i];
   __syncthreads();  // the zeros above are in place before another thread writes a precision over one of them
 
-  const unsigned long long field = (1ull << 20) - 1;
   const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
   const long long chunks = (n + DET_THREADS - 1) / DET_THREADS;
   for (int t = 0; t < COCO_T; ++t) {
     const int bit = a * COCO_T + t;
-    // what record i adds: tp | fp << 20 | kept << 40
+    // what record i adds: tp, fp and kept, the packed fields of det_common.h
     const auto term = [&](long long i) -> unsigned long long {
       if (i >= hi || rank[i] >= max_det) return 0ull;
       const unsigned long long mt = (matched[i] >> bit) & 1ull, ig = (ignored[i] >> bit) & 1ull;
-      return (mt & ~ig & 1ull) | ((~mt & ~ig & 1ull) << 20) | (1ull << 40);
+      return det_pack3(mt & ~ig & 1ull, ~mt & ~ig & 1ull, 1ull);
     };
     long long tp_all = 0, fp_all = 0, kept_all = 0;
     for (long long start = lo; start < hi; start += DET_THREADS) {
       det_block_scan(term(start + tid), sbuf, tid, false, add);
-      const unsigned long long chunk = sbuf[DET_THREADS - 1];
-      tp_all += (long long)(chunk & field);
-      fp_all += (long long)((chunk >> 20) & field);
-      kept_all += (long long)((chunk >> 40) & field);
+      det_add3(sbuf[DET_THREADS - 1], tp_all, fp_all, kept_all);
       __syncthreads();  // sbuf is rewritten by the next chunk
     }
     if (tid == 0) recall[r_at(t)] = kept_all ? (double)tp_all / (double)npig : 0.0;
@@ -326,14 +301,14 @@ __global__ __launch_bounds__(DET_THREADS) void coco_accumulate_kernel(const int*
     for (long long c = chunks - 1; c >= 0; --c) {
       const long long i = lo + c * DET_THREADS + tid;
       const unsigned long long v = term(i);
-      const bool valid = (v >> 40) != 0;
-      const long long tpb = (long long)(v & 1ull);
+      const bool valid = det_field(v, 2) != 0;
+      const long long tpb = det_field(v, 0);
       const unsigned long long sfx = det_block_scan(v, sbuf, tid, true, add);  // this record and the later ones of the chunk
       const unsigned long long chunk = sbuf[DET_THREADS - 1];                  // the backward scan's last slot is thread 0's
       __syncthreads();
-      const long long tp = tp_all - tp_after - ((long long)(sfx & field) - tpb);
-      const long long fp = fp_all - fp_after - ((long long)((sfx >> 20) & field) - (long long)((v >> 20) & 1ull));
-      const long long kept = kept_all - kept_after - ((long long)((sfx >> 40) & field) - 1);
+      const long long tp = tp_all - tp_after - (det_field(sfx, 0) - tpb);
+      const long long fp = fp_all - fp_after - (det_field(sfx, 1) - det_field(v, 1));
+      const long long kept = kept_all - kept_after - (det_field(sfx, 2) - 1);
       const double pr = valid ? (double)tp / (((double)fp + (double)tp) + 0x1p-52) : 0.0;  // np.spacing(1)
       double env = det_block_scan(pr, dbuf, tid, true, [](double x, double y) { return x > y ? x : y; });
       const double chunk_max = dbuf[DET_THREADS - 1];
@@ -346,9 +321,7 @@ __global__ __launch_bounds__(DET_THREADS) void coco_accumulate_kernel(const int*
         for (ri = ri < 0 ? 0 : ri; ri < COCO_R && rthr[ri] <= rc; ++ri)
           if (first || rthr[ri] > rc_prev) precision[p_at(t, ri)] = env;
       }
-      tp_after += (long long)(chunk & field);
-      fp_after += (long long)((chunk >> 20) & field);
-      kept_after += (long long)((chunk >> 40) & field);
+      det_add3(chunk, tp_after, fp_after, kept_after);
       later_max = later_max > chunk_max ? later_max : chunk_max;
     }
   }
@@ -400,21 +373,15 @@ extern "C" int cvx_coco_match(const float* rows, const int32_t* counts, int32_t 
                               int32_t truncate, int32_t quantize, const double* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc,
                               const double* iou_thrs, float* rec_score, int32_t* rec_class, int32_t* rec_rank, int64_t* rec_matched,
                               int64_t* rec_ignored, int64_t capacity, int64_t* state, int64_t* npig, void* hip_stream) {
-  CVX_CHECK(rows && counts && gt_counts && iou_thrs && rec_score && rec_class && rec_rank && rec_matched && rec_ignored && state && npig,
-            "null arguments");
-  CVX_CHECK(batch > 0 && max_det > 0 && max_det <= COCO_MAX_ROWS && max_gt >= 0 && max_gt <= COCO_MAX_GT && nc > 0 && nc <= COCO_MAX_NC &&
-                capacity > 0,
-            "bad sizes");
-  CVX_CHECK(max_gt == 0 || gt, "null ground truth");
-  CVX_CHECK(box_mode == 0 || (box_mode == 1 && box_map), "box_mode: 0 final boxes, 1 (x - px) * gx with box_map (batch, 4)");
+  CVX_TRY(det_check_batch(rows, counts, gt_counts, iou_thrs && rec_score && rec_class && rec_rank && rec_matched && rec_ignored && state && npig,
+                          batch, max_det, box_mode, box_map, gt, max_gt, nc));
+  CVX_CHECK(nc <= COCO_MAX_NC && capacity > 0, "bad sizes");
   const int P = coco_pow2(max_det);
-  const size_t lds = coco_lds(P, max_gt, nc).total;
-  CVX_CHECK(lds <= (size_t)COCO_MAX_LDS, "max_det and max_gt do not fit the LDS");
-  if (lds > 65536) CVX_TRY(cvx_lds_optin((const void*)coco_match_kernel, COCO_MAX_LDS, &g_coco_optin));
   hipStream_t st = (hipStream_t)hip_stream;
-  hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)batch), dim3(DET_THREADS), lds, st, rows, counts, batch, max_det, P, box_mode, box_map, truncate,
-                     quantize, gt, gt_counts, max_gt, nc, iou_thrs, rec_score, rec_class, rec_rank, (unsigned long long*)rec_matched,
-                     (unsigned long long*)rec_ignored, (long long)capacity, (unsigned long long*)state, (unsigned long long*)npig);
+  CVX_TRY(det_launch_lds(coco_match_kernel, &g_coco_optin, coco_lds(P, max_gt, nc).total, batch, st, rows, counts, batch, max_det, P, box_mode,
+                         box_map, truncate, quantize, gt, gt_counts, max_gt, nc, iou_thrs, rec_score, rec_class, rec_rank,
+                         (unsigned long long*)rec_matched, (unsigned long long*)rec_ignored, (long long)capacity, (unsigned long long*)state,
+                         (unsigned long long*)npig));
   hipLaunchKernelGGL(det_cursor_kernel, dim3(1), dim3(DET_THREADS), 0, st, counts, batch, max_det, (long long)capacity, (unsigned long long*)state);
   CVX_HIP(hipGetLastError());
   return 0;

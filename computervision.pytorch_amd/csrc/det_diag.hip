@@ -33,75 +33,32 @@ constexpr int DIAG_REF_POINTS = 9;
 enum { DG_SEEN = 0, DG_SKIPPED = 1, DG_BAD_CLASS = 2 };
 enum { CH_NONE = -1, CH_DIFFICULT = -2, CH_OUT = -3 };  // a detection's choice: no candidate, a difficult ground truth, takes no part
 
-inline size_t det_confusion_lds(int max_det, int G) { return (size_t)36 * det_gt_slots(G) + (size_t)4 * max_det; }
-
-struct det_ibox {
-  long long l, t, r, b;
-};
-
-// the box of a row as det_match_kernel reads it: mode 1 (x - px) * gx uncontracted, then int() towards zero
-__device__ __forceinline__ det_ibox det_row_box(const float* row, int box_mode, float px, float py, float gx, float gy) {
-  float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
-  if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, px, py, gx, gy);
-  return {(long long)__float2int_rz(x1), (long long)__float2int_rz(y1), (long long)__float2int_rz(x2), (long long)__float2int_rz(y2)};
-}
-
-// det_match_kernel's overlap: +1 pixel convention, integer products below 2^53 and one fp64 division; 0 when the boxes do not meet
-__device__ __forceinline__ double det_int_overlap(const det_ibox& d, const int* g) {
-  const long long gl = g[1], gt = g[2], gr = g[3], gb = g[4];
-  const long long iw = min(d.r, gr) - max(d.l, gl) + 1, ih = min(d.b, gb) - max(d.t, gt) + 1;
-  if (iw <= 0 || ih <= 0) return 0.0;
-  const long long inter = iw * ih;
-  const long long ua = (d.r - d.l + 1) * (d.b - d.t + 1) + (gr - gl + 1) * (gb - gt + 1) - inter;
-  return (double)inter / (double)ua;
-}
-
 __global__ __launch_bounds__(DET_THREADS) void det_confusion_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int max_det,
                                                                     int box_mode, const float* __restrict__ box_map, const int* __restrict__ gt,
                                                                     const int* __restrict__ gt_counts, int G, int nc, double conf, double iou,
                                                                     int quantize, unsigned long long* confusion, unsigned long long* images_per_class,
                                                                     unsigned long long* state) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int slots = det_gt_slots(G);
-  unsigned long long* top = reinterpret_cast<unsigned long long*>(smem);  // per ground truth: the bits of the largest overlap that chose it
-  int* gbox = reinterpret_cast<int*>(smem + 8 * slots);                   // [cls (-1: outside [0, nc)), l, t, r, b, difficult]
-  int* winner = reinterpret_cast<int*>(smem + 32 * slots);                // the lowest row among the detections that reach `top`
-  int* choice = reinterpret_cast<int*>(smem + 36 * slots);                // per detection: its ground truth or a CH_ value
+  const det_confusion_layout L = det_confusion_layout_of(max_det, G);
+  unsigned long long* top = reinterpret_cast<unsigned long long*>(smem + L.top);
+  int* gbox = reinterpret_cast<int*>(smem + L.gbox);
+  int* winner = reinterpret_cast<int*>(smem + L.winner);
+  int* choice = reinterpret_cast<int*>(smem + L.choice);
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = counts[b], ng = gt_counts[b];
-  if (n < 0 || n > max_det || ng < 0 || ng > G) {  // the whole workgroup leaves, before any barrier
-    if (tid == 0) atomicAdd(&state[DG_SKIPPED], 1ull);
-    return;
-  }
+  if (det_image_refused(n, max_det, ng, G, &state[DG_SKIPPED])) return;
   if (tid == 0) atomicAdd(&state[DG_SEEN], 1ull);
   const long long stride = (long long)nc + 1;
   unsigned long long bad_class = 0;
 
   for (int g = tid; g < ng; g += DET_THREADS) {
-    const int* src = gt + ((long long)b * G + g) * 6;
-    int cls = src[0];
-    if (cls < 0 || cls >= nc) {
-      ++bad_class;
-      cls = -1;  // takes part in nothing
-    }
-    gbox[g * 6 + 0] = cls;
-    gbox[g * 6 + 1] = src[1];
-    gbox[g * 6 + 2] = src[2];
-    gbox[g * 6 + 3] = src[3];
-    gbox[g * 6 + 4] = src[4];
-    gbox[g * 6 + 5] = src[5] != 0;
+    det_stage_gt(gt + ((long long)b * G + g) * 6, nc, gbox + g * 6, bad_class);
     top[g] = 0ull;
     winner[g] = 0x7fffffff;
   }
   __syncthreads();
 
-  float px = 0.f, py = 0.f, gx = 1.f, gy = 1.f;
-  if (box_mode == 1) {
-    px = box_map[b * 4 + 0];
-    py = box_map[b * 4 + 1];
-    gx = box_map[b * 4 + 2];
-    gy = box_map[b * 4 + 3];
-  }
+  const det_box_map map = det_load_box_map(box_mode, box_map, b);
   // pass 1: the choice
   for (int r = tid; r < n; r += DET_THREADS) {
     const float* row = rows + ((long long)b * max_det + r) * 6;
@@ -111,16 +68,17 @@ __global__ __launch_bounds__(DET_THREADS) void det_confusion_kernel(const float*
     if (cls < 0 || cls >= nc) {
       ++bad_class;
     } else if (det_score_reaches(quantize ? det_quantize(score) : score, conf, quantize)) {
-      const det_ibox box = det_row_box(row, box_mode, px, py, gx, gy);
+      const det_ibox box = det_row_box(row, box_mode, map);
       double ovmax = iou;
       m = CH_NONE;
       for (int g = 0; g < ng; ++g) {
         if (gbox[g * 6] < 0) continue;
-        const double ov = det_int_overlap(box, gbox + g * 6);
-        if (ov > ovmax) {  // strict: above the threshold, and the lowest index keeps a tie
-          ovmax = ov;
-          m = g;
-        }
+        det_int_overlap(box, gbox + g * 6, [&](double ov) {
+          if (ov > ovmax) {  // strict: above the threshold, and the lowest index keeps a tie
+            ovmax = ov;
+            m = g;
+          }
+        });
       }
       if (m >= 0) {
         if (gbox[m * 6 + 5])
@@ -136,8 +94,10 @@ __global__ __launch_bounds__(DET_THREADS) void det_confusion_kernel(const float*
   for (int r = tid; r < n; r += DET_THREADS) {
     const int m = choice[r];
     if (m < 0) continue;
-    const det_ibox box = det_row_box(rows + ((long long)b * max_det + r) * 6, box_mode, px, py, gx, gy);
-    if ((unsigned long long)__double_as_longlong(det_int_overlap(box, gbox + m * 6)) == top[m]) atomicMin(&winner[m], r);
+    const det_ibox box = det_row_box(rows + ((long long)b * max_det + r) * 6, box_mode, map);
+    det_int_overlap(box, gbox + m * 6, [&](double ov) {
+      if ((unsigned long long)__double_as_longlong(ov) == top[m]) atomicMin(&winner[m], r);
+    });
   }
   __syncthreads();
   // pass 3: the counts
@@ -300,17 +260,11 @@ unsigned long long g_confusion_optin = 0;
 extern "C" int cvx_det_confusion(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, int32_t box_mode, const float* box_map,
                                  const int32_t* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc, double conf, double iou,
                                  int32_t quantize, int64_t* confusion, int64_t* images_per_class, int64_t* state, void* hip_stream) {
-  CVX_CHECK(rows && counts && gt_counts && confusion && images_per_class && state, "null arguments");
-  CVX_CHECK(batch > 0 && max_det > 0 && max_det <= DET_MAX_ROWS && max_gt >= 0 && max_gt <= DET_MAX_GT && nc > 0, "bad sizes");
-  CVX_CHECK(max_gt == 0 || gt, "null ground truth");
-  CVX_CHECK(box_mode == 0 || (box_mode == 1 && box_map), "box_mode: 0 final boxes, 1 (x - px) * gx with box_map (batch, 4)");
+  CVX_TRY(det_check_batch(rows, counts, gt_counts, confusion && images_per_class && state, batch, max_det, box_mode, box_map, gt, max_gt, nc));
   CVX_CHECK(conf >= 0.0 && conf <= 1.0 && iou >= 0.0 && iou < 1.0, "conf in [0, 1], iou in [0, 1)");
-  const size_t lds = det_confusion_lds(max_det, max_gt);
-  CVX_CHECK(lds <= (size_t)DET_MAX_LDS, "max_det and max_gt do not fit the LDS");
-  if (lds > 65536) CVX_TRY(cvx_lds_optin((const void*)det_confusion_kernel, DET_MAX_LDS, &g_confusion_optin));
-  hipLaunchKernelGGL(det_confusion_kernel, dim3((unsigned)batch), dim3(DET_THREADS), lds, (hipStream_t)hip_stream, rows, counts, max_det, box_mode,
-                     box_map, gt, gt_counts, max_gt, nc, conf, iou, quantize, (unsigned long long*)confusion, (unsigned long long*)images_per_class,
-                     (unsigned long long*)state);
+  CVX_TRY(det_launch_lds(det_confusion_kernel, &g_confusion_optin, det_confusion_layout_of(max_det, max_gt).total, batch, (hipStream_t)hip_stream,
+                         rows, counts, max_det, box_mode, box_map, gt, gt_counts, max_gt, nc, conf, iou, quantize, (unsigned long long*)confusion,
+                         (unsigned long long*)images_per_class, (unsigned long long*)state));
   CVX_HIP(hipGetLastError());
   return 0;
 }

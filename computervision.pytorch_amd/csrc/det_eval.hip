@@ -26,73 +26,38 @@
 
 namespace {
 
-__host__ __device__ inline int det_row_slots(int max_det) { return (max_det + 3) & ~3; }
-inline size_t det_match_lds(int max_det, int G) { return 32 + (size_t)32 * det_gt_slots(G) + (size_t)8 * det_row_slots(max_det); }
-
 __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __restrict__ rows, const int* __restrict__ counts, int B, int max_det,
                                                                 int box_mode, const float* __restrict__ box_map, const int* __restrict__ gt,
                                                                 const int* __restrict__ gt_counts, int G, int nc, double min_overlap, int quantize,
                                                                 float* __restrict__ rec_score, int* __restrict__ rec_class, int* __restrict__ rec_flag,
                                                                 long long capacity, unsigned long long* state, unsigned long long* gt_per_class) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  long long* red = reinterpret_cast<long long*>(smem);                                   // 4 wave partials
-  unsigned long long* best = reinterpret_cast<unsigned long long*>(smem + 32);           // rank key of the TP per ground truth
-  int* gbox = reinterpret_cast<int*>(smem + 32 + 8 * det_gt_slots(G));                   // [cls, l, t, r, b, difficult] per ground truth
-  int* match = reinterpret_cast<int*>(smem + 32 + 32 * det_gt_slots(G));                 // per detection: ground truth, -1 FP, -2 neither
-  float* qscore = reinterpret_cast<float*>(smem + 32 + 32 * det_gt_slots(G) + 4 * det_row_slots(max_det));
+  const det_match_layout L = det_match_layout_of(max_det, G);
+  long long* red = reinterpret_cast<long long*>(smem);  // 4 wave partials
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(smem + L.best);
+  int* gbox = reinterpret_cast<int*>(smem + L.gbox);
+  int* match = reinterpret_cast<int*>(smem + L.match);
+  float* qscore = reinterpret_cast<float*>(smem + L.qscore);
   const int b = blockIdx.x, tid = threadIdx.x;
 
-  // records of the images before this one in the batch
-  long long before = 0;
-  for (int i = tid; i < b; i += DET_THREADS) before += det_count(counts[i], max_det);
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
-  if ((tid & 63) == 0) red[tid >> 6] = before;
-  __syncthreads();
-  const long long base = (long long)state[ST_CURSOR] + red[0] + red[1] + red[2] + red[3];
-
-  const int n_raw = counts[b], ng_raw = gt_counts[b];
-  const bool bad_image = n_raw < 0 || n_raw > max_det || ng_raw < 0 || ng_raw > G || base + det_count(n_raw, max_det) > capacity;
-  if (bad_image) {  // NMS overflow (-1), a count past its block, or no room left: counted, and the image contributes nothing
-    if (tid == 0) atomicAdd(&state[ST_OVERFLOW], 1ull);
-    return;
-  }
-  const int n = n_raw, ng = ng_raw;
+  const long long base = det_record_base(counts, b, max_det, state, red);
+  const int n = counts[b], ng = gt_counts[b];
+  if (det_image_refused(n, max_det, ng, G, &state[ST_OVERFLOW], base, capacity)) return;
   unsigned long long bad_class = 0, low_score = 0;
 
   for (int g = tid; g < ng; g += DET_THREADS) {
-    const int* src = gt + ((long long)b * G + g) * 6;
-    int cls = src[0];
-    const int difficult = src[5] != 0;
-    if (cls < 0 || cls >= nc) {
-      ++bad_class;
-      cls = -1;  // matches no detection
-    } else if (!difficult) {
-      atomicAdd(&gt_per_class[cls], 1ull);
-    }
-    gbox[g * 6 + 0] = cls;
-    gbox[g * 6 + 1] = src[1];
-    gbox[g * 6 + 2] = src[2];
-    gbox[g * 6 + 3] = src[3];
-    gbox[g * 6 + 4] = src[4];
-    gbox[g * 6 + 5] = difficult;
+    const int cls = det_stage_gt(gt + ((long long)b * G + g) * 6, nc, gbox + g * 6, bad_class);
+    if (cls >= 0 && !gbox[g * 6 + 5]) atomicAdd(&gt_per_class[cls], 1ull);
     best[g] = ~0ull;
   }
   __syncthreads();
 
-  float px = 0.f, py = 0.f, gx = 1.f, gy = 1.f;
-  if (box_mode == 1) {
-    px = box_map[b * 4 + 0];
-    py = box_map[b * 4 + 1];
-    gx = box_map[b * 4 + 2];
-    gy = box_map[b * 4 + 3];
-  }
+  const det_box_map map = det_load_box_map(box_mode, box_map, b);
   for (int r = tid; r < n; r += DET_THREADS) {
     const float* row = rows + ((long long)b * max_det + r) * 6;
-    float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
     const float score = row[4];
     int cls = __float2int_rz(row[5]);
-    if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, px, py, gx, gy);
-    const long long l = __float2int_rz(x1), t = __float2int_rz(y1), rr = __float2int_rz(x2), bb = __float2int_rz(y2);  // int(): towards zero
+    const det_ibox box = det_row_box(row, box_mode, map);
     if (!(score >= 1e-4f)) ++low_score;  // the reference prints these in scientific notation: rejected at the end, not emulated
     const float q = quantize ? det_quantize(score) : score;
     if (cls < 0 || cls >= nc) {
@@ -101,20 +66,14 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(const float* __r
     }
     double ovmax = -1.0;
     int m = -1;
-    const long long area = (rr - l + 1) * (bb - t + 1);
     for (int g = 0; g < ng; ++g) {
       if (gbox[g * 6] != cls) continue;
-      const long long gl = gbox[g * 6 + 1], gtp = gbox[g * 6 + 2], gr = gbox[g * 6 + 3], gb = gbox[g * 6 + 4];
-      const long long iw = min(rr, gr) - max(l, gl) + 1, ih = min(bb, gb) - max(t, gtp) + 1;
-      if (iw > 0 && ih > 0) {
-        const long long inter = iw * ih;
-        const long long ua = area + (gr - gl + 1) * (gb - gtp + 1) - inter;
-        const double ov = (double)inter / (double)ua;  // integers below 2^53: the one rounding Python's iw * ih / ua has
+      det_int_overlap(box, gbox + g * 6, [&](double ov) {  // boxes that do not meet are no candidate, whatever min_overlap is
         if (ov > ovmax) {
           ovmax = ov;
           m = g;
         }
-      }
+      });
     }
     const unsigned long long key = score_key(q, (unsigned)r);
     if (m >= 0 && ovmax >= min_overlap) {
@@ -156,28 +115,22 @@ __global__ __launch_bounds__(DET_THREADS) void det_ap_kernel(const float* __rest
   const long long n_gt = (long long)gt_per_class[c];
   const double gt_div = (double)(n_gt > 1 ? n_gt : 1);  // np.maximum(gt_counter_per_class, 1)
 
-  // forward sweep: TP, FP and "score >= threshold" counts, packed 20 bits apart inside a chunk (each field adds at most 256 there) and
-  // carried unpacked from chunk to chunk
-  const unsigned long long field = (1ull << 20) - 1;
+  // forward sweep: TP, FP and "score >= threshold" counts, the packed fields of det_common.h
   long long tp_before = 0, fp_before = 0, reach = 0;
   for (long long start = lo; start < hi; start += DET_THREADS) {
     const long long i = start + tid;
     unsigned long long v = 0;
     if (i < hi) {
       const int f = flag[i];
-      v = (f == FLAG_TP ? 1ull : 0ull) | (f == FLAG_FP ? 1ull << 20 : 0ull) |
-          (det_score_reaches(score[i], score_threshold, quantize) ? 1ull << 40 : 0ull);
+      v = det_pack3(f == FLAG_TP, f == FLAG_FP, det_score_reaches(score[i], score_threshold, quantize));
     }
     v = det_block_scan(v, sbuf, tid, false, [](unsigned long long a, unsigned long long x) { return a + x; });
     if (i < hi) {
-      const long long tp = tp_before + (long long)(v & field), fp = fp_before + (long long)((v >> 20) & field);
+      const long long tp = tp_before + det_field(v, 0), fp = fp_before + det_field(v, 1);
       rec[i] = (double)tp / gt_div;
       prec[i] = (double)tp / (double)(tp + fp > 1 ? tp + fp : 1);
     }
-    const unsigned long long chunk = sbuf[DET_THREADS - 1];
-    tp_before += (long long)(chunk & field);
-    fp_before += (long long)((chunk >> 20) & field);
-    reach += (long long)((chunk >> 40) & field);
+    det_add3(sbuf[DET_THREADS - 1], tp_before, fp_before, reach);
     __syncthreads();  // sbuf is rewritten by the next chunk
   }
   __threadfence_block();
@@ -254,17 +207,13 @@ extern "C" int cvx_det_match(const float* rows, const int32_t* counts, int32_t b
                              const int32_t* gt, const int32_t* gt_counts, int32_t max_gt, int32_t nc, double min_overlap, int32_t quantize,
                              float* rec_score, int32_t* rec_class, int32_t* rec_flag, int64_t capacity, int64_t* state, int64_t* gt_per_class,
                              void* hip_stream) {
-  CVX_CHECK(rows && counts && gt_counts && rec_score && rec_class && rec_flag && state && gt_per_class, "null arguments");
-  CVX_CHECK(batch > 0 && max_det > 0 && max_det <= DET_MAX_ROWS && max_gt >= 0 && max_gt <= DET_MAX_GT && nc > 0 && capacity > 0, "bad sizes");
-  CVX_CHECK(max_gt == 0 || gt, "null ground truth");
-  CVX_CHECK(box_mode == 0 || (box_mode == 1 && box_map), "box_mode: 0 final boxes, 1 (x - px) * gx with box_map (batch, 4)");
-  const size_t lds = det_match_lds(max_det, max_gt);
-  CVX_CHECK(lds <= (size_t)DET_MAX_LDS, "max_det and max_gt do not fit the LDS");
-  if (lds > 65536) CVX_TRY(cvx_lds_optin((const void*)det_match_kernel, DET_MAX_LDS, &g_match_optin));
+  CVX_TRY(det_check_batch(rows, counts, gt_counts, rec_score && rec_class && rec_flag && state && gt_per_class, batch, max_det, box_mode, box_map, gt,
+                          max_gt, nc));
+  CVX_CHECK(capacity > 0, "bad sizes");
   hipStream_t st = (hipStream_t)hip_stream;
-  hipLaunchKernelGGL(det_match_kernel, dim3((unsigned)batch), dim3(DET_THREADS), lds, st, rows, counts, batch, max_det, box_mode, box_map, gt, gt_counts,
-                     max_gt, nc, min_overlap, quantize, rec_score, rec_class, rec_flag, (long long)capacity, (unsigned long long*)state,
-                     (unsigned long long*)gt_per_class);
+  CVX_TRY(det_launch_lds(det_match_kernel, &g_match_optin, det_match_layout_of(max_det, max_gt).total, batch, st, rows, counts, batch, max_det,
+                         box_mode, box_map, gt, gt_counts, max_gt, nc, min_overlap, quantize, rec_score, rec_class, rec_flag, (long long)capacity,
+                         (unsigned long long*)state, (unsigned long long*)gt_per_class));
   hipLaunchKernelGGL(det_cursor_kernel, dim3(1), dim3(DET_THREADS), 0, st, counts, batch, max_det, (long long)capacity, (unsigned long long*)state);
   CVX_HIP(hipGetLastError());
   return 0;

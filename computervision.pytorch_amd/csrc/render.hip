@@ -63,7 +63,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_to_image_kernel(const float* 
   float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, score = 0.f, cls = 0.f;
   if (r < n) {
     x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3], score = row[4], cls = row[5];
-    if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, box_map[b * 4 + 0], box_map[b * 4 + 1], box_map[b * 4 + 2], box_map[b * 4 + 3]);
+    if (box_mode == 1) det_undo_letterbox(x1, y1, x2, y2, det_load_box_map(box_mode, box_map, b));
   }
   o[0] = x1;
   o[1] = y1;

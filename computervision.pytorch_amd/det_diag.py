@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .det_eval import MAX_ROWS, check_batch
+from .det_records import MAX_ROWS, check_batch
 
 MAX_POINTS, MAX_WINDOW = 4096, 65535
 REF_POINTS = np.logspace(-2.0, 0.0, num=9)       # the reference's nine FPPI points, computed by numpy: no pow on the device

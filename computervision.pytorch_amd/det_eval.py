@@ -21,9 +21,9 @@ import torch
 
 from . import _lib as L
 from . import coco_eval
+from .det_records import MAX_GT, MAX_ROWS, RecordEvaluator, check_batch, default_capacity, record_order  # noqa: F401 (old import paths)
 
 FLAG_FP, FLAG_TP, FLAG_NEITHER = 0, 1, 2
-MAX_ROWS, MAX_GT = 16384, 1024
 
 
 def quantize_scores(x):
@@ -107,61 +107,21 @@ def pack_rows(per_image, device):
     return rows, torch.tensor(n, dtype=torch.int32, device=device)
 
 
-def check_batch(rows, counts, gt, gt_counts, box_map, max_det, device):
-    """The argument checks of ``DetectionEvaluator.add_batch`` and ``det_diag.DetectionDiagnostics.add_batch``; returns the five
-    arguments contiguous."""
-    B, K = int(rows.shape[0]), int(rows.shape[1])
-    G = int(gt.shape[1])
-    if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or not (0 < K <= max_det):
-        raise ValueError(f"rows: (B, K <= {max_det}, 6) float32, got {tuple(rows.shape)} {rows.dtype}")
-    if gt.dim() != 3 or gt.shape[0] != B or (G and gt.shape[2] != 6) or gt.dtype != torch.int32 or G > MAX_GT:
-        raise ValueError(f"gt: (B, G <= {MAX_GT}, 6) int32, got {tuple(gt.shape)} {gt.dtype}")
-    if counts.dtype != torch.int32 or gt_counts.dtype != torch.int32 or counts.numel() != B or gt_counts.numel() != B:
-        raise ValueError("counts and gt_counts: (B) int32")
-    if box_map is not None and (box_map.dtype != torch.float32 or tuple(box_map.shape) != (B, 4)):
-        raise ValueError("box_map: (B, 4) float32 [px, py, gx, gy]")
-    for t in (rows, counts, gt, gt_counts, box_map):
-        if t is not None and t.device != device:
-            raise ValueError("add_batch: every tensor lives on the evaluator's device")
-    return rows.contiguous(), counts.contiguous(), gt.contiguous(), gt_counts.contiguous(), None if box_map is None else box_map.contiguous()
-
-
-class DetectionEvaluator:
+class DetectionEvaluator(RecordEvaluator):
     """Device-side ``get_map``.  ``max_det``: the most rows per image a batch may carry; ``capacity``: the records the whole evaluation may
     append (images x rows).  ``quantize_scores=True`` is the reference's ``str(score)[:6]``."""
+    _ENTRIES = ("cvx_det_match", "cvx_det_ap")
+    _low_score_message = ("scores below 1e-4: the reference writes them in scientific notation and reads back their first 6 characters, "
+                          "which is not reproduced; evaluate with conf_threshold >= 0.001")
 
     def __init__(self, num_classes, max_det, capacity, device, min_overlap=0.5, score_threshold=0.5, quantize_scores=True):
-        if not (0 < int(max_det) <= MAX_ROWS):
-            raise ValueError(f"max_det {max_det}: cvx_det_match holds 1 .. {MAX_ROWS} rows per image")
-        if int(num_classes) <= 0 or int(capacity) <= 0:
-            raise ValueError("num_classes and capacity are positive")
-        self.num_classes, self.max_det, self.capacity = int(num_classes), int(max_det), int(capacity)
-        self.device = torch.device(device)
+        super().__init__(num_classes, max_det, capacity, device)
         self.min_overlap, self.score_threshold, self.quantize = float(min_overlap), float(score_threshold), bool(quantize_scores)
-        self._alloc = False
-        self._cache = None
 
-    def _buffers(self):
-        if self.device.type != "cuda":
-            raise L.CvxError("DetectionEvaluator runs on an MI355X only (cvx_det_match / cvx_det_ap): there is no CPU path")
-        if not self._alloc:
-            dev, cap, nc = self.device, self.capacity, self.num_classes
-            self.rec_score = torch.zeros(cap, dtype=torch.float32, device=dev)
-            self.rec_class = torch.empty(cap, dtype=torch.int32, device=dev)
-            self.rec_flag = torch.zeros(cap, dtype=torch.int32, device=dev)
-            self.state = torch.zeros(4, dtype=torch.int64, device=dev)
-            self.gt_per_class = torch.zeros(nc, dtype=torch.int64, device=dev)
-            self._alloc = True
-            self.reset()
-
-    def reset(self):
-        self._cache = None
-        if self._alloc:
-            self.rec_class.fill_(self.num_classes)       # unwritten slots sort behind every class
-            self.rec_score.zero_()
-            self.rec_flag.zero_()
-            self.state.zero_()
-            self.gt_per_class.zero_()
+    def _columns(self):
+        self.rec_flag = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+        self.gt_per_class = torch.zeros(self.num_classes, dtype=torch.int64, device=self.device)
+        return self.rec_flag, self.gt_per_class
 
     def add_batch(self, rows, counts, gt, gt_counts, box_map=None):
         """rows (B, K, 6) float32 and counts (B) int32 as ``engine.nms`` returns them (K <= max_det); gt (B, G, 6) int32
@@ -180,11 +140,7 @@ class DetectionEvaluator:
         """Order the records as get_map does, run cvx_det_ap; everything stays on the device."""
         self._buffers()
         nc, cap, dev = self.num_classes, self.capacity, self.device
-        # class in the high bits, the inverted score bits below: ascending = class ascending, score descending; stable keeps (image, row)
-        key = (self.rec_class.to(torch.int64) << 32) | (0xFFFFFFFF - self.rec_score.view(torch.int32).to(torch.int64))
-        key, order = torch.sort(key, stable=True)
-        cls = (key >> 32).contiguous()
-        seg_off = torch.searchsorted(cls, torch.arange(nc + 1, dtype=torch.int64, device=dev)).contiguous()
+        order, cls, seg_off = record_order(self.rec_class, self.rec_score, nc)
         score, flag = self.rec_score[order].contiguous(), self.rec_flag[order].contiguous()
         prec = torch.zeros(cap, dtype=torch.float64, device=dev)
         rec = torch.zeros(cap, dtype=torch.float64, device=dev)
@@ -201,15 +157,7 @@ class DetectionEvaluator:
             dev = self._reduce()
             nc = self.num_classes
             host = torch.cat((self.state.to(torch.float64), dev["stats"])).cpu().numpy()        # counters < 2^53: exact as doubles
-            cursor, overflow, low, bad = (int(v) for v in host[:4])
-            if overflow:
-                raise L.CvxError(f"DetectionEvaluator: {overflow} image(s) dropped: an NMS count of -1 (more candidates than cvx_nms sorts), a "
-                                 f"count past its block, or more than capacity={self.capacity} records")
-            if bad:
-                raise L.CvxError(f"DetectionEvaluator: {bad} class indices outside [0, {nc})")
-            if low:
-                raise L.CvxError(f"DetectionEvaluator: {low} scores below 1e-4: the reference writes them in scientific notation and reads "
-                                 "back their first 6 characters, which is not reproduced; evaluate with conf_threshold >= 0.001")
+            cursor = self._check_counters(host)
             s = host[4:4 + nc * 8].reshape(nc, 8)
             self._cache = dict(device=dev, n_records=cursor, res={
                 "mAP": float(host[4 + nc * 8]), "n_classes": int(host[4 + nc * 8 + 1]),
@@ -301,9 +249,7 @@ def evaluate_detector(evaluator_rows, dataloader, num_classes, device, map_out_r
         rows, counts, box_map = evaluator_rows(images, meta)
         if ev is None:
             if capacity is None:
-                if not hasattr(dataloader, "__len__"):
-                    raise L.CvxError("evaluate_on_voc: a dataloader without len() needs capacity= (the records of the whole evaluation)")
-                capacity = len(dataloader) * int(rows.shape[0]) * min(int(max_det), 1024)
+                capacity = default_capacity(dataloader, rows.shape[0], max_det, "evaluate_on_voc")
             ev = DetectionEvaluator(num_classes, max_det, capacity, rows.device)
             if coco_metric:
                 coco = coco_eval.CocoEvaluator(num_classes, max_det, capacity, rows.device, truncate_boxes=True, quantize_scores=True)
