@@ -152,6 +152,10 @@ PROTOTYPES = {
     "cvx_track_state_bytes": (_I64, [_I32]),
     "cvx_track_update": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "cvx_draw_tracks": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _P]),
+    "cvx_mot_state_bytes": (_I64, [_I32, _I32, _I32]),
+    "cvx_mot_workspace_bytes": (_I64, [_I32]),
+    "cvx_mot_frames": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P, _I64, _P]),
+    "cvx_mot_summary": (_I32, [_P, _I32, _I32, _I32, _P, _P]),
     "cvx_seg_stitch": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_seg_regions_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "cvx_seg_regions": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),

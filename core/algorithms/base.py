@@ -87,6 +87,56 @@ class FramePredictor:
 
         return batches()
 
+    def evaluate_tracking(self, model, sequence, out_root, tracker=None, batch_size=8, tiled=None):
+        """Scores the tracker on a sequence with ground-truth identities (the four detectors): ``sequence`` is an iterable of ``(frame, gt)``
+        in time order, frame a uint8 HWC RGB device tensor and gt (n <= 1024, 6) float32 ``[x1, y1, x2, y2, cls, identity]`` in the
+        frame's pixels, on the device.  Every batch of ``batch_size`` frames is one ``predict_batch(..., tracker=, sync=False)`` -- or, with
+        ``tiled`` (a dict of ``predict_tiled`` keywords), one ``predict_tiled`` -- and one ``cvx_mot_frames`` launch
+        (``track_eval.TrackingEvaluator``, default parameters); nothing inside the loop waits on the host.  ``tracker``: a
+        ``track.Tracker``, a dict of its parameters, or None for the defaults.  One host read at the end: writes
+        ``out_root/results/tracking.txt`` and returns ``TrackingEvaluator.get_results()``."""
+        if not isinstance(self, Detector):
+            raise L.CvxError(f"{type(self).__name__} has no detections to track")
+        self._need_gpu("evaluate_tracking")
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size is positive")
+        import os
+
+        import torch
+        from computervision.pytorch_amd.track import Tracker
+        from computervision.pytorch_amd.track_eval import TrackingEvaluator
+        if not isinstance(tracker, Tracker):
+            tracker = Tracker(self.device, **dict(tracker or {}))
+        if tiled is not None and {"draw", "sync", "tracker"} & set(tiled):
+            raise ValueError("evaluate_tracking neither draws nor waits and brings its tracker: tiled= takes none of draw, sync, tracker")
+        evaluator = TrackingEvaluator(self.device)
+
+        def flush(frames, truths):
+            if tiled is None:
+                rows, counts, ids = self.predict_batch(model, frames, sync=False, tracker=tracker)
+            else:
+                rows, counts, ids = self.predict_tiled(model, frames, sync=False, tracker=tracker, **dict(tiled))
+            gt = torch.zeros(len(frames), max(1, max(int(t.shape[0]) for t in truths)), 6, dtype=torch.float32, device=rows.device)
+            for b, t in enumerate(truths):
+                gt[b, :t.shape[0]] = t
+            gt_counts = torch.tensor([int(t.shape[0]) for t in truths], dtype=torch.int32).to(rows.device, non_blocking=True)
+            evaluator.add_frames(rows, counts, ids, gt, gt_counts)
+
+        frames, truths = [], []
+        for frame, gt in sequence:
+            if not (torch.is_tensor(gt) and gt.dim() == 2 and gt.shape[1] == 6 and gt.dtype == torch.float32 and gt.is_cuda):
+                raise ValueError("evaluate_tracking: gt is (n, 6) float32 [x1, y1, x2, y2, cls, identity] on the device")
+            frames.append(frame)
+            truths.append(gt)
+            if len(frames) == int(batch_size):
+                flush(frames, truths)
+                frames, truths = [], []
+        if frames:
+            flush(frames, truths)
+        results = evaluator.get_results()
+        evaluator.write_report(os.path.join(out_root, "results", "tracking.txt"))
+        return results
+
 
 class Detector(FramePredictor):
     """Needs ``num_classes``, ``device``, ``eval_max_det`` (the most rows per image ``_evaluation_rows`` returns) and

@@ -1400,6 +1400,73 @@ int cvx_seg_boundary(const cvx_seg_map* pred_maps, const cvx_seg_map* target_map
                      int32_t max_w, int32_t nc, const int32_t* widths, int32_t K, int64_t* trimap, int64_t* biou, int64_t* bf, uint8_t* planes,
                      void* workspace, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- tracking evaluation: CLEAR-MOT and the identity measures (csrc/track_eval.hip) -----------------------------------
+ * Scores the ids of cvx_track_update against ground-truth identities: MOTA, MOTP and their counts (Bernardin & Stiefelhagen 2008), IDF1,
+ * IDP, IDR (Ristani et al. 2016).  The rules are the project's own, with every tie decided; on inputs without ties they are
+ * py-motmetrics' and the MOTChallenge devkit's.  They are restated in numpy in tests/track_eval_restatement.py and the kernels are held
+ * to the restatement bit for bit: behind the quantisation of the IoU everything is an integer.  Additive: CVX_ABI_VERSION stays 6.
+ *
+ * cvx_mot_frames: rows (batch, max_det, 6), counts (batch) and ids (batch, max_det) as cvx_track_update takes and leaves them;
+ * gt (batch, max_gt <= 1024, 6) fp32 [x1, y1, x2, y2, cls, identity] and gt_counts (batch); frame_stream as in cvx_track_update.  One
+ * workgroup per stream walks its frames in batch order; asynchronous on hip_stream, nothing read back.  state:
+ * cvx_mot_state_bytes(streams, max_gt_ids, max_track_ids) bytes of device memory carried from call to call, per stream (rounded up to 8 bytes)
+ *   cvx_mot_stream_header, then int32 arrays of max_gt_ids entries each -- mem (1 + the track of the identity's last match, 0: none), last (the
+ *   stream's frame number of that match, frames counted from 1), present, matched (frames), gap (1: unmatched in its last present frame) --
+ *   then c (max_gt_ids, max_track_ids) int32.  All zero means "nothing seen": creating or resetting an evaluator is a memset.
+ * workspace: cvx_mot_workspace_bytes(streams) bytes (a 1024 x 1024 int32 cost matrix per stream, used when a frame's matrix has more than
+ * 16384 cells; smaller ones live in LDS).
+ * Per frame of a stream, in order:
+ *   hypotheses  the rows d < count with ids[d] >= 0, in row order; beyond 1024 of them the rest are skipped (flag excess).  Skipped and
+ *               flagged one by one: a box with a NaN (flag nan), an id >= max_track_ids (flag track), a row whose id an earlier row
+ *               that passed these two checks carries (flag dup_row).
+ *   truths      the gt rows g < gt_count; skipped and flagged: a box with a NaN (nan), an identity that is not an integer in
+ *               [0, max_gt_ids) (identity), an identity an earlier row that passed these checks carries (dup_gt).
+ *   frame       a count outside [0, max_det], a gt_count outside [0, max_gt] or a stream outside [0, streams) skips the whole frame (flag
+ *               frame; a bad stream is flagged in stream 0).  Otherwise the stream's frame number grows by 1.
+ *   gate        a pair (truth, hypothesis) is allowed when iou_value(truth, hypothesis) >= iou (box_overlap.h, the IoU of cvx_nms; a NaN
+ *               never passes) and the classes are equal or class_agnostic.  Its cost is rint((1 - iou_value) * 65536) as an integer, every
+ *               fp32 operation rounded on its own.  c[identity, id] grows by 1 for every allowed pair, matched or not.
+ *   1 keep      an identity with mem > 0 and last == frame - 1 keeps that track when the track is among the hypotheses and the pair is
+ *               allowed: a match, never a switch.
+ *   2 assign    the remaining truths and hypotheses, each in order: the assignment with the maximal number of allowed pairs and, among
+ *               those, the minimal sum of costs, as the solver below finds it.  A new pair is a switch when mem > 0 and mem - 1 is
+ *               another track, however old.  Every match sets mem and last.
+ *   3 count     objects += truths, hypotheses += hypotheses, matches, cost += the costs of the matches, misses = truths - matches,
+ *               false positives = hypotheses - matches.
+ *   4 identity  present += 1; matched += 1 on a match.  A match with gap == 1 and matched > 0 before it is a fragmentation.  gap becomes
+ *               0 on a match and 1 otherwise.
+ *   solver      rows: the smaller side (the truths when both are equal), columns: the other; a forbidden cell costs 2^27.  Rows are
+ *               inserted in order by shortest augmenting paths with 64-bit potentials (the classical O(n^2 m) method: from the new row,
+ *               repeatedly relax the slacks of the unvisited columns through the row of the column visited last, take the unvisited
+ *               column of minimal slack -- the lowest index on a tie --, lower the potentials by that slack, until a free column is
+ *               reached; then flip the path).  The pairs on forbidden cells are dropped.
+ * cvx_mot_summary: one launch per stream's table row and one that sums them, after the last frame (it changes no state and may be
+ * called again later).  table (streams + 1, CVX_MOT_TABLE_WORDS) int64 on the device, the last row the sum over the streams:
+ *   0 frames, 1 objects, 2 hypotheses, 3 matches, 4 misses, 5 false positives, 6 switches, 7 fragmentations, 8 cost, 9 mostly tracked
+ *   (5 * matched >= 4 * present), 10 partly tracked, 11 mostly lost (5 * matched < present), 12 IDTP, 13 .. 19 the flags nan, dup_row, dup_gt,
+ *   identity, track, frame, excess, 20 identities seen, 21 tracks with a non-zero column of c, 22 .. 23 zero.
+ * IDTP is the maximum of sum c[o, h] over the partial one-to-one matchings of identities to tracks: the solver on the non-empty rows and
+ * columns of c with cost -c (a zero cell is as good as no pair).  This equals Ristani's minimum of FN + FP on the graph with dummy nodes,
+ * whose total is sum n_o + sum n_h - 2 IDTP.  IDFN = objects - IDTP, IDFP = hypotheses - IDTP; the scores follow in double on the host. */
+#define CVX_MOT_FRAME_CAP 1024
+#define CVX_MOT_MAX_GT_IDS 1024
+#define CVX_MOT_MAX_TRACK_IDS 4096
+#define CVX_MOT_HEADER_WORDS 16
+#define CVX_MOT_TABLE_WORDS 24
+typedef struct cvx_mot_stream_header {
+  int64_t v[CVX_MOT_HEADER_WORDS]; /* the table's words 0 .. 8, then the seven flags */
+} cvx_mot_stream_header;
+typedef struct cvx_mot_params {
+  float iou;
+  int32_t class_agnostic, max_gt_ids, max_track_ids, reserved[2];
+} cvx_mot_params;
+int64_t cvx_mot_state_bytes(int32_t streams, int32_t max_gt_ids, int32_t max_track_ids);
+int64_t cvx_mot_workspace_bytes(int32_t streams);
+int cvx_mot_frames(const float* rows, const int32_t* counts, const int32_t* ids, int32_t batch, int32_t max_det, const float* gt,
+                   const int32_t* gt_counts, int32_t max_gt, const int32_t* frame_stream, int32_t streams, const cvx_mot_params* params, void* state,
+                   void* workspace, int64_t workspace_bytes, void* hip_stream);
+int cvx_mot_summary(void* state, int32_t streams, int32_t max_gt_ids, int32_t max_track_ids, int64_t* table, void* hip_stream);
+
 /* (The tile-resident chain kernel's unit entry points -- cvx_chain_pair_unit / _conv_unit / _detect_unit, csrc/conv_chain.hip -- live in
  * include/cvx_engine_experimental.h: the kernel measured slower than the per-layer launches and is built into the tuning library only.) */
 
