@@ -151,6 +151,8 @@ PROTOTYPES = {
     "cvx_det_merge_tiles": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _I32, _F, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
     "cvx_track_state_bytes": (_I64, [_I32]),
     "cvx_track_update": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "cvx_track_ext_bytes": (_I64, [_I32]),
+    "cvx_track_update_model": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "cvx_draw_tracks": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _P]),
     "cvx_mot_state_bytes": (_I64, [_I32, _I32, _I32]),
     "cvx_mot_workspace_bytes": (_I64, [_I32]),

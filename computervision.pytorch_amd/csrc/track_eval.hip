@@ -9,17 +9,16 @@
 //   counts c[o, h] also fills the cost matrix of the identities and hypotheses that continuity left over, in LDS when it has at most
 //   MAT_LDS cells and in the caller's workspace otherwise -- two instantiations of the frame's body, so the first reads it with LDS
 //   instructions.
-//   The assignment (solve) is the shortest-augmenting-path method with potentials, rows inserted in order: one lane per column keeps
+//   The assignment (assign_solver.h:solve) is the shortest-augmenting-path method with potentials, rows inserted in order: one lane per column keeps
 //   the column's slack, potential and visited bit in registers, a workgroup reduction takes the arg min (lowest column on a tie), and
 //   there is one barrier per step of a path.  Forbidden cells cost BIG = 2^27 > 1024 * 65536, so a minimum-cost assignment of the smaller
 //   side has the maximal number of allowed pairs and, among those, the minimal sum; the potentials reach 1024 * BIG and are 64-bit.
 //   cvx_mot_summary: one workgroup per stream classifies the identities, compacts the non-empty rows and columns of c and solves the
 //   maximum-weight assignment with the same solver (cost -c, up to four columns per lane); a second one-workgroup launch sums the table.
 // Only a stream's workgroup touches its state: no floating-point atomics, nothing read across workgroups within a launch.
+#include "assign_solver.h"
 #include "box_overlap.h"
 #include "../../include/cvx_engine.h"
-
-#include <limits.h>
 
 #pragma clang fp contract(off)
 
@@ -31,8 +30,7 @@ constexpr int CAP = CVX_MOT_FRAME_CAP;        // identities, and hypotheses, of 
 constexpr int MAX_GT = CVX_MOT_MAX_GT_IDS;    // bounds of max_gt_ids / max_track_ids: the summary's maps are LDS arrays
 constexpr int MAX_TR = CVX_MOT_MAX_TRACK_IDS;
 constexpr int MAT_LDS = 16384;                // cells of a cost matrix kept in LDS (128 x 128)
-constexpr long long BIG = 1ll << 27;          // a forbidden cell
-constexpr long long INF = LLONG_MAX / 4;
+static_assert(THREADS == SOLVE_THREADS, "the solver's workgroup (assign_solver.h: Red, red_min, Solver, solve, BIG, INF)");
 static_assert(THREADS == CAP, "thread t owns identity t / column t of a frame");
 static_assert(MAX_TR == 4 * THREADS, "the summary gives a lane four columns");
 
@@ -40,11 +38,6 @@ static_assert(MAX_TR == 4 * THREADS, "the summary gives a lane four columns");
 enum { H_FRAMES, H_OBJECTS, H_HYPS, H_MATCHES, H_MISSES, H_FP, H_SWITCHES, H_FRAGS, H_COST, H_FLAG_NAN, H_FLAG_DUP_ROW, H_FLAG_DUP_GT,
        H_FLAG_IDENTITY, H_FLAG_TRACK, H_FLAG_FRAME, H_FLAG_EXCESS, H_WORDS };
 static_assert(H_WORDS == CVX_MOT_HEADER_WORDS, "the header track_eval.py reads");
-
-struct Red {
-  long long v;
-  int j, pad;
-};
 
 struct State {   // one stream's block
   long long* head;
@@ -86,100 +79,6 @@ __device__ __forceinline__ long long block_sum(long long v, long long* wave_sum)
   for (int k = 0; k < WAVES; ++k) s += wave_sum[k];
   __syncthreads();
   return s;
-}
-
-__device__ __forceinline__ void red_min(long long& v, int& j, long long ov, int oj) {
-  if (ov < v || (ov == v && oj < j)) v = ov, j = oj;
-}
-
-struct Solver {   // LDS of the assignment
-  long long* u;   // row potentials [n]
-  int* p;         // the row of each column, -1 free [m]
-  int* way;       // the previous column on the path [m]
-  Red* red;       // 2 * WAVES: the partial arg mins of the waves, two steps deep
-};
-
-// Minimum-cost assignment of the n rows to n of the m >= n columns (n <= THREADS, m <= CPT * THREADS); cost(i, j) is a 64-bit integer.
-// Rows are inserted in order; in every arg min the lowest column wins a tie.  Lane t owns the columns t, t + THREADS, ...: slack, column
-// potential and visited bit in registers.  Leaves s.p; every thread must call it.
-template <int CPT, class Cost>
-__device__ __forceinline__ void solve(const Solver& s, const Cost& cost, int n, int m) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long v[CPT], minv[CPT];
-  bool used[CPT];
-#pragma unroll
-  for (int k = 0; k < CPT; ++k) {
-    v[k] = 0;
-    const int j = tid + k * THREADS;
-    if (j < m) s.p[j] = -1;
-  }
-  for (int i = tid; i < n; i += THREADS) s.u[i] = 0;
-  __syncthreads();
-  int par = 0;
-  for (int i = 0; i < n; ++i) {
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) minv[k] = INF, used[k] = false;
-    int j0 = -1, i0 = i;
-    for (;;) {
-      const long long ui = s.u[i0];
-      long long bv = INF;
-      int bj = INT_MAX;
-#pragma unroll
-      for (int k = 0; k < CPT; ++k) {
-        const int j = tid + k * THREADS;
-        if (j < m && !used[k]) {
-          const long long cur = cost(i0, j) - ui - v[k];
-          if (cur < minv[k]) {
-            minv[k] = cur;
-            s.way[j] = j0;
-          }
-          red_min(bv, bj, minv[k], j);
-        }
-      }
-      for (int o = 1; o < 64; o <<= 1) {
-        const long long ov = __shfl_xor(bv, o);
-        const int oj = __shfl_xor(bj, o);
-        red_min(bv, bj, ov, oj);
-      }
-      if (lane == 0) s.red[par * WAVES + wave] = {bv, bj, 0};
-      __syncthreads();
-      bv = INF, bj = INT_MAX;
-      for (int k = 0; k < WAVES; ++k) {
-        const Red r = s.red[par * WAVES + k];
-        red_min(bv, bj, r.v, r.j);
-      }
-      par ^= 1;
-      const long long delta = bv;
-      const int j1 = bj;   // m >= n: a free column always remains, so j1 is a column
-#pragma unroll
-      for (int k = 0; k < CPT; ++k) {
-        const int j = tid + k * THREADS;
-        if (j < m) {
-          if (used[k]) {
-            s.u[s.p[j]] += delta;   // the rows of the visited columns are distinct, and none is row i
-            v[k] -= delta;
-          } else {
-            minv[k] -= delta;
-          }
-          if (j == j1) used[k] = true;
-        }
-      }
-      if (tid == 0) s.u[i] += delta;
-      j0 = j1;
-      const int r = s.p[j0];   // p changes only between the barriers below
-      if (r < 0) break;
-      i0 = r;                  // its potential was not touched in this step: column j1 was not visited
-    }
-    __syncthreads();
-    if (tid == 0) {
-      while (j0 >= 0) {
-        const int jp = s.way[j0];
-        s.p[j0] = jp < 0 ? i : s.p[jp];
-        j0 = jp;
-      }
-    }
-    __syncthreads();
-  }
 }
 
 struct Side {   // the hypotheses or the ground truths of a frame, compacted in row order

@@ -1199,6 +1199,46 @@ typedef struct cvx_track_params {
 int64_t cvx_track_state_bytes(int32_t streams);
 int cvx_track_update(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, const int32_t* frame_stream, int32_t streams,
                      const cvx_track_params* params, void* state, int32_t* out_ids, int32_t* overflow, void* hip_stream);
+/* ---- a Kalman motion model and a minimum-cost association for the tracker, both optional (csrc/track.hip) ----------
+ * cvx_track_update with two choices more: the same arguments, state, flags and frame rules, except for what `model` replaces.  The rules
+ * are restated in numpy in tests/track_model_restatement.py and the kernel is held to the restatement bit for bit.  With motion alpha-beta
+ * and assign greedy every byte is cvx_track_update's.  Additive: CVX_ABI_VERSION stays 6 (no existing entry or struct changes).
+ * Replaces: nothing, the reference has no counterpart.
+ * ext: cvx_track_ext_bytes(streams) bytes of device memory, 16-byte aligned, carried from call to call with state: per stream
+ * float cov[CVX_TRACK_CAP][4], the covariance (Pxx, Pxv, Pvv, reserved 0) of the track in the same slot of cvx_track_stream.  All zero means
+ * "nothing seen"; it is read and written under the Kalman motion only, by the stream's workgroup.
+ *
+ * motion = CVX_TRACK_MOTION_KALMAN: a constant-velocity Kalman filter per coordinate (the four corners stay the state).  The four
+ *   coordinates share one noise scale s = max(y2 - y1, min_scale) of the track's box (fmaxf: min_scale for a NaN), and the covariance
+ *   recurrence does not see the measurements, so one symmetric 2 x 2 covariance per track serves all four.  alpha and beta are ignored.
+ *   Every line is one rounded fp32 operation per operator, in the order written; the division is correctly rounded:
+ *   8 births    v = 0; a = init_pos * r_pos; a = a * s; Pxx = a * a; Pxv = 0; b = init_vel * q_vel; b = b * s; Pvv = b * b, s of the row's box.
+ *   2 predict   s of the box before the move; p = p + v; a = Pxv + Pxv; a = a + Pvv; b = q_pos * s; b = b * b; a = a + b; Pxx = Pxx + a;
+ *               Pxv = Pxv + Pvv (the old Pvv); c = q_vel * s; c = c * c; Pvv = Pvv + c.  Every live track in every frame of its stream.
+ *   6 update    s of the predicted box; e = r_pos * s; e = e * e; e = Pxx + e; kx = Pxx / e; kv = Pxv / e; per coordinate r = z - p;
+ *               p = p + kx * r; v = v + kv * r (mul, then add); then Pvv = Pvv - kv * Pxv; Pxv = Pxv - kx * Pxv; Pxx = Pxx - kx * Pxx.
+ * assign = CVX_TRACK_ASSIGN_OPTIMAL: stages 1 and 2 as a minimum-cost assignment over the same candidate tracks and rows.  A pair is
+ *   allowed when iou(p, box) > the stage's threshold (a NaN never passes) and the classes agree unless class_agnostic; its cost is the
+ *   integer rint((1 - iou) * 65536) of cvx_mot_frames.  (a) An allowed pair that is the only allowed pair of its track and of its row is
+ *   taken.  (b) Candidates without an allowed pair are set aside.  (c) The remaining tracks in ascending id and the remaining rows in
+ *   ascending row index are assigned by the solver of cvx_mot_frames (csrc/assign_solver.h): the number of pairs is maximal and among those
+ *   the cost sum minimal; the smaller side drives, the tracks when the sides are equal; a forbidden cell costs 2^27 and a pair on one is
+ *   dropped; rows inserted in order, the lowest column wins a tie.  max_det <= CVX_TRACK_OPTIMAL_MAX_DET.
+ * Host memory, read during the call.  Defaults: alpha-beta, greedy, q_pos 1/20, q_vel 1/160, r_pos 1/20, init_pos 2, init_vel 10,
+ * min_scale 1.  The five weights are finite and >= 0, min_scale is finite and > 0. */
+#define CVX_TRACK_MOTION_ALPHA_BETA 0
+#define CVX_TRACK_MOTION_KALMAN 1
+#define CVX_TRACK_ASSIGN_GREEDY 0
+#define CVX_TRACK_ASSIGN_OPTIMAL 1
+#define CVX_TRACK_OPTIMAL_MAX_DET 4096
+typedef struct cvx_track_model {
+  int32_t motion, assign;
+  float q_pos, q_vel, r_pos, init_pos, init_vel, min_scale;
+} cvx_track_model;
+int64_t cvx_track_ext_bytes(int32_t streams);
+int cvx_track_update_model(const float* rows, const int32_t* counts, int32_t batch, int32_t max_det, const int32_t* frame_stream, int32_t streams,
+                           const cvx_track_params* params, const cvx_track_model* model, void* state, void* ext, int32_t* out_ids,
+                           int32_t* overflow, void* hip_stream);
 /* cvx_draw_detections for tracked rows: ids (batch, max_det) int32 as cvx_track_update leaves them.  A row whose id is negative paints
  * nothing.  The label is "{id % 1000000}:{cls}" and the outline colour entry (id + 1) mod lut_entries, so an object keeps its colour
  * while it keeps its id; tag and text colours follow from it by cvx_draw_detections's rules, and geometry, painter's order and the

@@ -2,6 +2,11 @@
 section 7ac) on seeded SYNTHETIC scenes, at the default parameters and on a small grid of ``alpha``, ``beta`` and ``iou_high``.
 
     python tools/track_quality.py [--frames 80] [--out profiles/track_quality.txt]
+    python tools/track_quality.py --models [--frames 80] [--out profiles/track_model_quality.txt]
+
+``--models`` scores instead the four combinations of ``track.TrackModel`` -- the alpha-beta or the Kalman motion
+model, the greedy or the minimum-cost association -- at ``track.DEFAULTS`` and the model's default weights on the same scenes: MOTA,
+IDF1, identity switches and fragmentations per scene and over all of them.
 
 The scenes are boxes drawn by a random generator, not footage: constant velocities with a slow sway, detections jittered by up to 2 px,
 3 % of them dropped, scores from 0.6 .. 0.95 unless the scene says otherwise, 3 false detections per frame.  They say how the rules
@@ -76,14 +81,17 @@ def scene(np, name, frames, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=80)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "track_quality.txt"))
+    ap.add_argument("--models", action="store_true", help="score the four (motion, assign) combinations of TrackModel at the defaults")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "track_model_quality.txt" if args.models else "track_quality.txt")
 
     import numpy as np
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("track_quality.py runs the tracker and its evaluation on the MI355X: no device found (there is no CPU path)")
-    from computervision.pytorch_amd.track import DEFAULTS, Tracker
+    from computervision.pytorch_amd.track import ASSIGNS, DEFAULTS, MOTIONS, Tracker, TrackModel
     from computervision.pytorch_amd.track_eval import TrackingEvaluator
 
     dev = torch.device("cuda", 0)
@@ -92,8 +100,8 @@ def main():
         arrays = scene(np, name, args.frames, seed=100 + s)
         data.append([torch.from_numpy(a).to(dev) for a in arrays] + [torch.full((args.frames,), s, dtype=torch.int32, device=dev)])
 
-    def score(**params):
-        tracker = Tracker(dev, streams=len(SCENES), **params)
+    def score(model=None, **params):
+        tracker = Tracker(dev, streams=len(SCENES), model=model, **params)
         evaluator = TrackingEvaluator(dev, streams=len(SCENES), max_gt_ids=512)
         for rows, counts, gt, gt_counts, stream in data:
             for f in range(0, args.frames, 8):                 # batches of 8 frames, as the video path feeds them
@@ -106,6 +114,39 @@ def main():
     def line(label, res):
         per = "  ".join(f"{r['mota']:6.3f} {r['idf1']:6.3f} {r['num_switches']:4d}" for r in res["streams"] + [res["overall"]])
         return f"{label:34s} {per}"
+
+    def finish(lines):
+        text = "\n".join(lines) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+        print(text, end="")
+
+    if args.models:
+        names = SCENES + ("overall",)
+        lines = [f"tracking quality of the four TrackModel combinations on SYNTHETIC seeded scenes ({args.frames} frames each; tools/track_quality.py says",
+                 "what they are): MOTA, IDF1, identity switches and fragmentations per scene and over all of them, the evaluation's gate at IoU 0.5.",
+                 "Boxes from a random generator: this says nothing about real footage.  The parameters are track.DEFAULTS and the model's default",
+                 "weights; model=None stays the tracker's default, and this table moves nothing.  The first line is the tracker without a model",
+                 "(cvx_track_update); the second is the same rules through cvx_track_update_model and must equal it.", "",
+                 f"{'motion / assign':26s} " + "  ".join(f"{name:>23s}" for name in names),
+                 f"{'':26s} " + "  ".join(f"{'MOTA':>6s} {'IDF1':>6s} {'IDSW':>4s} {'FRAG':>4s}" for _ in names)]
+
+        def model_line(label, res):
+            per = "  ".join(f"{r['mota']:6.3f} {r['idf1']:6.3f} {r['num_switches']:4d} {r['num_fragmentations']:4d}" for r in res["streams"] + [res["overall"]])
+            return f"{label:26s} {per}"
+
+        plain = score()
+        lines.append(model_line("no model", plain))
+        for motion in MOTIONS:
+            for assign in ASSIGNS:
+                res = score(model=TrackModel(motion=motion, assign=assign))
+                lines.append(model_line(f"{motion} / {assign}", res))
+                if (motion, assign) == ("alpha_beta", "greedy"):
+                    counted = ("num_matches", "num_misses", "num_false_positives", "num_switches", "num_fragmentations", "idtp")
+                    assert all(res["overall"][k] == plain["overall"][k] for k in counted), "TrackModel() does not score as the tracker without a model"
+        finish(lines)
+        return
 
     head = f"{'alpha beta iou_high':34s} " + "  ".join(f"{name:>18s}" for name in SCENES + ("overall",))
     sub = f"{'':34s} " + "  ".join(f"{'MOTA':>6s} {'IDF1':>6s} {'IDSW':>4s}" for _ in range(len(SCENES) + 1))
@@ -128,11 +169,7 @@ def main():
               f"best overall MOTA of the grid: alpha {by_mota[0][0]}, beta {by_mota[0][1]}, iou_high {by_mota[0][2]}: MOTA "
               f"{by_mota[1]['overall']['mota']:.4f}, IDF1 {by_mota[1]['overall']['idf1']:.4f}, {by_mota[1]['overall']['num_switches']} switches",
               "Whether to move a default on the strength of generated boxes is left to a later change."]
-    text = "\n".join(lines) + "\n"
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text)
-    print(text, end="")
+    finish(lines)
 
 
 if __name__ == "__main__":
