@@ -95,6 +95,8 @@ PROTOTYPES = {
                                        C.POINTER(_I64)]),
     "cvx_debug_clock_buffer": (_I32, [_P]),
     "cvx_debug_conv_tile_plan": (_I32, [_I32, _I32, _I32, _I32, _I32, _P]),
+    "cvx_debug_conv_tile_ring": (_I32, [_I32, _I32, _I32, _I32, _I32, _P]),
+    "cvx_debug_conv_tile_force": (_I32, [_I32, _I32]),
     "cvx_debug_conv_dma_plan": (_I32, [_I64, _I32, _I32, _I32, _P]),
     "cvx_debug_conv_halo_plan": (_I32, [_I32, _I32, _I32, _I32, _I32, _P]),
     "cvx_debug_conv_pw_plan": (_I32, [_I64, _I32, _I32, _P]),

@@ -3,7 +3,7 @@
 //
 //   * tile = TR full rows x W columns of one image; the pixels of the tile are enumerated row-major and cut into groups of 16 (the MFMA
 //     pixel dimension), so a 40- or 20-wide map wastes nothing on 16-column tiles (conv_halo.hip: 48 / 32 columns computed for 40 / 20);
-//     4 waves, wave w owns groups [w * MT, (w + 1) * MT) and ALL 16 * NTW output channels of the workgroup; the launcher picks
+//     8 waves (kTileWaves: two per SIMD), wave w owns groups [w * MT, (w + 1) * MT) and ALL 16 * NTW output channels of the workgroup; the launcher picks
 //     (TR, channel block) so that tiles x channel blocks fills the chip in ONE round where the layer is small enough (cvx_conv_tile_plan);
 //   * the (TR + 2) x (W + 2) x Cin halo patch is DMA'd into LDS once (`buffer_load ... lds`, hardware zero fill outside the image);
 //     16-byte units [pixel][Cin / 8], the unit index XOR-swizzled by the patch COLUMN (applied on the global side) so that the 16 pixels
@@ -11,13 +11,14 @@
 //   * the weights arrive PRE-PACKED in LDS image order ([channel block][K-step][16 * NTW rows][32 k], cvx_conv_tile_pack_jobs: one
 //     launch per forward for all layers), so a K-chunk is ONE contiguous block: a wave issues 1-KiB pieces at base + lane * 16 with a
 //     scalar offset -- no per-lane address arithmetic (conv_halo.hip spent 1.7 us of a 12-us launch issuing its weight DMAs);
-//     they stream through a 3-slot ring of chunks (chunk c + 2 is issued when chunk c's last K-step begins), so the first MFMA waits
-//     for the patch and ONE chunk, and layers whose weights exceed the LDS (128 -> 144 at 40 x 40: 332 KB) need no channel split that
-//     re-reads the patch;
+//     where they fit beside the patch they are ONE chunk, requested whole before the K loop (R = 2: no refill, no barrier in the loop);
+//     else they stream through a ring of R = 3 or 4 slots of chunks (KSC K-steps each: a whole tap, or a divisor of a tap's steps; chunk
+//     c + R - 1 is issued when the load cursor leaves chunk c), so the first MFMA waits for the patch and ONE chunk, and layers whose
+//     weights exceed the LDS (128 -> 144 at 40 x 40: 332 KB) need no channel split that re-reads the patch;
 //   * K loop: ROLLED, one K-step (tap, 32 channels) per iteration, everything but (MT, NTW) at run time (any Cin % 8 == 0, >= 32);
 //     v_mfma_f32_16x16x32_f16, weights as the A operand; ROLLING fragment refill: the pixel fragment of group i is re-requested for the
 //     NEXT K-step right behind the MFMAs that consumed it, the next step's weight fragments at the top of the step, so every LDS latency
-//     hides behind MT * NTW MFMAs of the wave itself (one wave per SIMD: nobody else would hide it);
+//     hides behind MT * NTW MFMAs of the wave itself and of the SIMD's other wave;
 //   * epilogues: the shared ones of conv_tile_common.h (raw fp32 + statistics / folded BN + activation / bias / plain-accumulate).
 // Roofline: latency (dispatch, DMA landing, K loop, stores); measured phases: profiles/r04_conv_floor.txt.  Reference: the arithmetic of
 // nn.Conv2d in core/models/yolov8/modules.py:19-33 (Conv), :124-135 (Bottleneck), :407-455 (Detect) and its autograd data gradient.
@@ -90,13 +91,20 @@ struct Plan {
   int MT, NTW, TR, NB, KSC, NCH, R, SPT, lds, ntiles, tpi, PP, units, CB, wring_off, stat_off;
   double cost;
 };
+// 1-KiB DMA pieces of one weight chunk, and of n pieces per wave (the launch and cvx_debug_conv_tile_ring read the same two)
+int chunk_pieces(const Plan& pl) { return pl.KSC * pl.NTW; }
+int pieces_per_wave(int n) { return (n + kTileWaves - 1) / kTileWaves; }
+
+// test handle (cvx_debug_conv_tile_force): rows per tile / channel tiles per workgroup every plan must have; 0 = the cost model's choice
+int g_force_tr = 0, g_force_ntw = 0;
 
 // estimated launch time (us) of one candidate; calibrated on the phase stamps of tools/conv_clock.py (profiles/r04_conv_floor.txt)
 bool plan_tile(const ConvParams& p, Plan* best) {
   const int H = p.IH, W = p.IW, Cin = p.Cin;
   const int P = Cin / 8, SPT = (Cin + 31) / 32, NSTEPS = 9 * SPT;
   const int ctiles = (p.Cout + 15) / 16;
-  static const int force_tr = cvx_tune_int("CVX_TILE_TR", 0), force_ntw = cvx_tune_int("CVX_TILE_NTW", 0);
+  static const int env_tr = cvx_tune_int("CVX_TILE_TR", 0), env_ntw = cvx_tune_int("CVX_TILE_NTW", 0);  // (tuning build)
+  const int force_tr = g_force_tr ? g_force_tr : env_tr, force_ntw = g_force_ntw ? g_force_ntw : env_ntw;
   bool found = false;
   for (int NTW : kNtwMenu) {
     if (force_ntw && NTW != force_ntw) continue;
@@ -281,10 +289,10 @@ int cvx_conv_tile_launch(const ConvParams& p, hipStream_t stream) {
   a.KSC = pl.KSC;
   a.NCH = pl.NCH;
   a.R = pl.R;
-  a.CP = pl.KSC * pl.NTW;
-  a.PW = (a.CP + kTileWaves - 1) / kTileWaves;
+  a.CP = chunk_pieces(pl);
+  a.PW = pieces_per_wave(a.CP);
   a.PP = pl.PP;
-  a.PPW = (pl.PP + kTileWaves - 1) / kTileWaves;
+  a.PPW = pieces_per_wave(pl.PP);
   a.units = pl.units;
   a.Wp = p.IW + 2;
   a.magic_wp = magic_of(a.Wp);
@@ -307,8 +315,9 @@ int cvx_conv_tile_launch(const ConvParams& p, hipStream_t stream) {
   return 0;
 }
 
-extern "C" int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out8) {
-  CVX_CHECK(out8 && batch > 0 && h > 0 && w > 0, "bad arguments");
+namespace {
+// the dense 3x3 / stride 1 / pad 1 launch of a batch x h x w map the two query functions below describe -> its plan, or false
+bool debug_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, Plan* pl) {
   ConvParams p;
   memset(&p, 0, sizeof(p));
   static half_t dummy_zero[8];
@@ -321,10 +330,15 @@ extern "C" int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int
   p.IW = p.OW2 = p.OWr = w;
   p.Cin = p.in_ld = cin;
   p.in_bstride = (long long)h * w * cin;
-  p.Cout = cout;
-  if (!cvx_conv_tile_shape_ok(p)) return -1;
+  p.Cout = p.out_ld = cout;
+  return cvx_conv_tile_shape_ok(p) && plan_tile(p, pl);
+}
+}  // namespace
+
+extern "C" int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out8) {
+  CVX_CHECK(out8 && batch > 0 && h > 0 && w > 0, "bad arguments");
   Plan pl;
-  if (!plan_tile(p, &pl)) return -1;
+  if (!debug_plan(batch, h, w, cin, cout, &pl)) return -1;
   out8[0] = pl.TR;
   out8[1] = pl.MT;
   out8[2] = pl.NTW;
@@ -334,6 +348,31 @@ extern "C" int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int
   out8[6] = pl.lds;
   out8[7] = (int)(pl.cost * 100.0);
   return 0;
+}
+
+extern "C" int cvx_debug_conv_tile_ring(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out8) {
+  CVX_CHECK(out8 && batch > 0 && h > 0 && w > 0, "bad arguments");
+  Plan pl;
+  if (!debug_plan(batch, h, w, cin, cout, &pl)) return -1;
+  out8[0] = pl.KSC;
+  out8[1] = pl.NCH;
+  out8[2] = pl.R;
+  out8[3] = pl.SPT;
+  out8[4] = pieces_per_wave(chunk_pieces(pl));  // PW
+  out8[5] = pl.PP;
+  out8[6] = pl.MT;                              // the plan the ring belongs to: CP = KSC * NTW pieces per chunk
+  out8[7] = pl.NTW;
+  return 0;
+}
+
+extern "C" int cvx_debug_conv_tile_force(int32_t tr, int32_t ntw) {
+  bool ntw_ok = ntw == 0;
+  for (int q : kNtwMenu) ntw_ok |= q == ntw;
+  CVX_CHECK(tr >= 0 && tr <= 4000 && ntw_ok, "rows per tile 0 .. 4000 and channel tiles 0, 1, 2, 3, 4, 5, 6 or 9 (0: the cost model's choice)");
+  const int prev = (g_force_tr << 8) | g_force_ntw;
+  g_force_tr = tr;
+  g_force_ntw = ntw;
+  return prev;
 }
 
 void cvx_conv_tile_release() {

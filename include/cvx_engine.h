@@ -194,6 +194,16 @@ int cvx_debug_clock_buffer(void* buf);
  * workgroups, K-steps per weight chunk, LDS bytes, estimated microseconds x 100.  Returns 0, or -1 when the kernel does not take the
  * shape.  (No reference counterpart: the reference leaves the choice of algorithm to cuDNN behind nn.Conv2d, core/models/yolov8/modules.py:19-33.) */
 int cvx_debug_conv_tile_plan(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out8);
+/* Test hooks of the same kernel.  cvx_debug_conv_tile_ring reports the weight ring of that plan -- out[0..7] = K-steps per chunk (KSC),
+ * chunks (NCH), ring slots (R: 2 = one chunk, requested whole; 3 or 4 = a ring), K-steps per tap (SPT), 1-KiB DMA pieces per wave and chunk
+ * (PW), pieces of the halo patch (PP), MT and NTW of the plan (a chunk has KSC * NTW pieces).  Returns 0, or -1 when the kernel does not take the shape.
+ * cvx_debug_conv_tile_force(tr, ntw) makes every plan of the process use tr rows per tile and / or ntw 16-channel tiles per workgroup
+ * (0: the cost model's choice; ntw one of 1, 2, 3, 4, 5, 6, 9), so that a small map runs the instantiations the cost model picks at batch
+ * 16 .. 32 only; a shape the forced pair has no plan for is one the kernel does not take (cvx_debug_conv_tile_plan returns -1,
+ * cvx_conv2d_nhwc(mode | 0x2000) is an error and launches nothing, the dispatcher passes the shape on).  Returns the previous pair as
+ * (tr << 8) | ntw, or -1 for other arguments (nothing changes).  Process-wide: restore (0, 0).  (No reference counterpart, as above.) */
+int cvx_debug_conv_tile_ring(int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t* out8);
+int cvx_debug_conv_tile_force(int32_t tr, int32_t ntw);
 /* Test hook: which of its compiled tile configurations the LDS-DMA ring convolution kernel (csrc/conv_igemm_dma.hip) runs for a launch of
  * `pixels` output pixels (of the largest phase class for a merged data gradient), cin gathered and cout produced channels and ntaps taps --
  * out[0..3] = tile rows (128, 64 or 32), channel tiles per workgroup (16-channel tiles for 128 / 64 rows: 1..6 or 8; 32-channel pairs for
