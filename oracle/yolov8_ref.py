@@ -351,23 +351,25 @@ def ciou(box1: torch.Tensor, box2: torch.Tensor, eps: float = 1e-7) -> torch.Ten
     return iou - (rho2 / c2 + v * alpha)
 
 
-def build_targets(batch: dict, batch_size: int, img_h: float, img_w: float):
-    """Loss.preprocess (yolo_v8.py:51-65): flat (N,6) labels -> (B,Gmax,5) [cls, xyxy pixels]."""
-    bi = batch["batch_idx"].view(-1).float()
-    cls = batch["cls"].view(-1).float()
-    boxes = batch["bboxes"].view(-1, 4).float()
+def build_targets(batch: dict, batch_size: int, img_h: float, img_w: float, dtype=torch.float32):
+    """Loss.preprocess (yolo_v8.py:51-65): flat (N,6) labels -> (B,Gmax,5) [cls, xyxy pixels].
+
+    ``dtype``: the precision of the arithmetic (float32: the reference's; float64: the yardstick of the kernel sweeps)."""
+    bi = batch["batch_idx"].view(-1).to(dtype)
+    cls = batch["cls"].view(-1).to(dtype)
+    boxes = batch["bboxes"].view(-1, 4).to(dtype)
     if bi.numel() == 0:
-        return torch.zeros(batch_size, 0, 5)
+        return torch.zeros(batch_size, 0, 5, dtype=dtype)
     counts = [(bi == j).sum().item() for j in range(batch_size)]
     gmax = int(max(counts))
-    out = torch.zeros(batch_size, gmax, 5)
+    out = torch.zeros(batch_size, gmax, 5, dtype=dtype)
     for j in range(batch_size):
         sel = bi == j
         n = int(sel.sum())
         if n:
             out[j, :n, 0] = cls[sel]
             out[j, :n, 1:] = boxes[sel]
-    scale = torch.tensor([img_w, img_h, img_w, img_h])
+    scale = torch.tensor([img_w, img_h, img_w, img_h], dtype=dtype)
     cxcywh = out[..., 1:5] * scale
     xy, wh = cxcywh[..., :2], cxcywh[..., 2:]
     out[..., 1:5] = torch.cat((xy - wh / 2, xy + wh / 2), -1)
@@ -376,12 +378,13 @@ def build_targets(batch: dict, batch_size: int, img_h: float, img_w: float):
 
 @torch.no_grad()
 def task_aligned_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt,
-                        topk: int = 10, alpha: float = 0.5, beta: float = 6.0, eps: float = 1e-9):
+                        topk: int = 10, alpha: float = 0.5, beta: float = 6.0, eps: float = 1e-9, dtype=torch.float32):
     """TaskAlignedAssigner.forward (bboxes.py:299-345).
 
     pd_scores (B,A,nc) sigmoid scores, pd_bboxes (B,A,4) xyxy px, anc_points (A,2) px,
     gt_labels (B,G,1), gt_bboxes (B,G,4) xyxy px, mask_gt (B,G,1) in {0,1}.
     Returns target_bboxes (B,A,4), target_scores (B,A,nc), fg_mask (B,A) bool, target_gt_idx (B,A).
+    ``dtype`` is the precision of the inputs and of the masks multiplied with them.
     """
     B, A, nc = pd_scores.shape
     G = gt_bboxes.shape[1]
@@ -391,7 +394,7 @@ def task_aligned_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, 
     # anchors strictly inside a gt (bboxes.py:231-246)
     lt = anc_points.view(1, 1, A, 2) - gt_bboxes[:, :, None, :2]
     rb = gt_bboxes[:, :, None, 2:] - anc_points.view(1, 1, A, 2)
-    in_gt = (torch.cat((lt, rb), -1).amin(-1) > eps).float()            # (B,G,A)
+    in_gt = (torch.cat((lt, rb), -1).amin(-1) > eps).to(dtype)          # (B,G,A)
     valid = (in_gt * mask_gt).bool()                                    # (B,G,A)
     # metric = score^alpha * CIoU^beta on the valid (gt, anchor) pairs (bboxes.py:369-396)
     lab = gt_labels.long().squeeze(-1).clamp(0, nc - 1)                 # (B,G)
@@ -404,13 +407,13 @@ def task_aligned_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, 
     _, top_idx = torch.topk(metric, topk, dim=-1)
     top_idx = torch.where(mask_gt.bool().expand(B, G, topk), top_idx, torch.zeros_like(top_idx))
     hits = torch.zeros(B, G, A, dtype=torch.long).scatter_add_(2, top_idx, torch.ones_like(top_idx))
-    in_topk = torch.where(hits > 1, torch.zeros_like(hits), hits).float()
+    in_topk = torch.where(hits > 1, torch.zeros_like(hits), hits).to(dtype)
     mask_pos = in_topk * in_gt * mask_gt
     # an anchor claimed by several gts keeps the one with the largest overlap (bboxes.py:249-272)
     fg = mask_pos.sum(1)
     if fg.max() > 1:
         multi = (fg.unsqueeze(1) > 1).expand(B, G, A)
-        best = F.one_hot(overlaps.argmax(1), G).permute(0, 2, 1).float()
+        best = F.one_hot(overlaps.argmax(1), G).permute(0, 2, 1).to(dtype)
         mask_pos = torch.where(multi, best, mask_pos)
         fg = mask_pos.sum(1)
     gt_idx = mask_pos.argmax(1)                                         # (B,A)
@@ -418,7 +421,7 @@ def task_aligned_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, 
     flat_idx = gt_idx + torch.arange(B).view(B, 1) * G
     t_labels = gt_labels.long().flatten()[flat_idx]
     t_boxes = gt_bboxes.reshape(-1, 4)[flat_idx]
-    t_scores = F.one_hot(t_labels.clamp(0), nc).float() * (fg > 0).unsqueeze(-1)
+    t_scores = F.one_hot(t_labels.clamp(0), nc).to(dtype) * (fg > 0).unsqueeze(-1)
     # rescale by the normalised alignment metric (bboxes.py:338-343)
     metric = metric * mask_pos
     pos_metric = metric.amax(-1, keepdim=True)
@@ -428,36 +431,37 @@ def task_aligned_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, 
 
 
 def v8_loss(feats: List[torch.Tensor], batch: dict, nc: int = 80, strides=(8.0, 16.0, 32.0),
-            gains=(7.5, 0.5, 1.5), aux: dict | None = None):
-    """Loss.__call__ (yolo_v8.py:75-124): returns (sum(box,cls,dfl) * B, detached (3,) items)."""
+            gains=(7.5, 0.5, 1.5), aux: dict | None = None, dtype=torch.float32):
+    """Loss.__call__ (yolo_v8.py:75-124): returns (sum(box,cls,dfl) * B, detached (3,) items).
+
+    ``dtype``: float32 is the reference's arithmetic; float64 runs every step of the same algorithm in double."""
     B = feats[0].shape[0]
     no = nc + 4 * REG_MAX
-    cat = torch.cat([f.reshape(B, no, -1) for f in feats], 2)
+    cat = torch.cat([f.reshape(B, no, -1) for f in feats], 2).to(dtype)
     pred_dist, pred_scores = cat.split((4 * REG_MAX, nc), 1)
     pred_scores = pred_scores.permute(0, 2, 1).contiguous()            # (B,A,nc)
     pred_dist = pred_dist.permute(0, 2, 1).contiguous()                # (B,A,64)
     img_h, img_w = feats[0].shape[2] * strides[0], feats[0].shape[3] * strides[0]
-    anchors, stride_t = make_anchors([f.shape[2:] for f in feats], strides)
+    anchors, stride_t = (t.to(dtype) for t in make_anchors([f.shape[2:] for f in feats], strides))
 
-    targets = build_targets(batch, B, img_h, img_w)
+    targets = build_targets(batch, B, img_h, img_w, dtype)
     gt_labels, gt_bboxes = targets.split((1, 4), 2)
-    mask_gt = (gt_bboxes.sum(2, keepdim=True) > 0).float()
+    mask_gt = (gt_bboxes.sum(2, keepdim=True) > 0).to(dtype)
 
     # expectation over the 16 DFL bins -> ltrb -> xyxy in grid units (yolo_v8.py:67-73)
     A = pred_dist.shape[1]
-    ltrb = pred_dist.view(B, A, 4, REG_MAX).softmax(3).matmul(torch.arange(REG_MAX, dtype=torch.float32))
+    ltrb = pred_dist.view(B, A, 4, REG_MAX).softmax(3).matmul(torch.arange(REG_MAX, dtype=dtype))
     pred_boxes = torch.cat((anchors - ltrb[..., :2], anchors + ltrb[..., 2:]), -1)
 
     t_boxes, t_scores, fg, gt_idx = task_aligned_assign(
         pred_scores.detach().sigmoid(), pred_boxes.detach() * stride_t, anchors * stride_t,
-        gt_labels, gt_bboxes, mask_gt)
+        gt_labels, gt_bboxes, mask_gt, dtype=dtype)
     t_boxes = t_boxes / stride_t
     score_sum = max(t_scores.sum(), 1)
 
-    loss = torch.zeros(3)
     loss_cls = F.binary_cross_entropy_with_logits(pred_scores, t_scores, reduction="none").sum() / score_sum
-    loss_box = torch.zeros(())
-    loss_dfl = torch.zeros(())
+    loss_box = torch.zeros((), dtype=dtype)
+    loss_dfl = torch.zeros((), dtype=dtype)
     if fg.sum():
         w = t_scores.sum(-1)[fg].unsqueeze(-1)
         iou = ciou(pred_boxes[fg], t_boxes[fg]).unsqueeze(-1)
